@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of salt's single-end alignment hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload grch38|grch38_tenth|chr21|grch38_mini|mini|tiny]
+    python bench.py --gpus N --steps K --warmup W [--workload grch38|grch38_tenth|chr21|grch38_mini|mini|tiny] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, ms_per_step, the per-kernel times of
+the timed region).  --full adds everything else listed below (serialized steps, counters and roofline, CPU baseline and parity,
+the paired-end leg, the end-to-end legs).  --dump-outputs DIR writes the result rows of the last timed step as DIR/<field>.npy
+(a fixed, seeded sample of the batch's reads; entries past their counts zeroed).
 
 Workload (default `grch38` = BASELINE.json configs[2] restated as seeded synthetic data): a 3.1e9-base genome in 24
 contigs with 14.8 M SNPs, generated on the GPU, indexed on the GPU by the product's own salt-idx (device suffix sorter), k = 21;
@@ -14,6 +19,7 @@ data path).
 
 Prints ONE JSON line (rank 0) with the metric of BASELINE.json plus
   "stages_s":     what the run spent before the timed region (generate / index / load / attach / broadcast / reads)
+and, with --full,
   "roofline":     the dominant single kernel: device-layout algorithmic bytes per launch (kernel counters) / its HIP-event time
                   vs 8 TB/s, PMC traffic and the issue-rate bound from profiles/ when they hold this workload
   "cpu_baseline": the CPU oracle (bit-exact restatement of the reference) on a bounded sample of the same reads on this box's
@@ -87,6 +93,37 @@ def device_bytes(ctr, n_reads, L, spr):
     return b
 
 
+DUMP_READS = 30000             # --dump-outputs: rows written per run (1 828 bytes of .npy each: 55 MB, under the 64 MB a dump may take)
+DUMP_SEED = 20261016           # --dump-outputs: the fixed sample of reads whose rows are written
+
+
+def dump_rows(d, rows, np, suffix="", world=1):
+    """--dump-outputs: the result rows of the last timed step (salt_amd.RESULT_DTYPE), what a caller of salt_gpu_align_se_resident
+    receives, one DIR/<field><suffix>.npy per field.  A fixed, seeded sample of DUMP_READS / world of the batch's reads (read_index.npy);
+    float64 for the 32-bit fields, float32 for the 8- and 16-bit ones (both exact); entries past their counts (hits[s][j >= n_hits[s]],
+    cigar[k >= n_cigar], hit_n_cigar / hit_cigar past the live hits and their op counts) are zeroed, so that two builds compare on what
+    the rows say and not on what a workspace held before.  `pad` is not written."""
+    os.makedirs(d, exist_ok=True)
+    wide = lambda t: np.float64 if t.itemsize >= 4 else np.float32
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(len(rows), size=min(len(rows), DUMP_READS // world), replace=False))
+    r = rows[sel]
+    out = {"read_index": sel.astype(np.float64)}
+    for name in ("pos", "strand", "n_diff", "is_gap", "mapq", "b0", "b1", "seq_start", "seq_end", "n_hits", "n_cigar", "skipped"):
+        out[name] = r[name].astype(wide(r[name].dtype))
+    live = np.arange(r["hits"].shape[2])[None, None, :] < r["n_hits"][:, :, None]              # [read, strand, j]
+    for f in r["hits"].dtype.names:
+        out["hits_" + f] = np.where(live, r["hits"][f], 0).astype(wide(r["hits"][f].dtype))
+    n_live = r["n_hits"].astype(np.int64).sum(axis=1)                                          # hit_cigar[h]: strand-0 hits, then strand-1
+    hlive = np.arange(r["hit_n_cigar"].shape[1])[None, :] < n_live[:, None]
+    hnc = np.where(hlive, r["hit_n_cigar"], 0)
+    out["hit_n_cigar"] = hnc.astype(np.float32)
+    ops = np.arange(r["cigar"].shape[1])
+    out["cigar"] = np.where(ops[None, :] < r["n_cigar"][:, None], r["cigar"], 0).astype(np.float32)
+    out["hit_cigar"] = np.where(ops[None, None, :] < hnc[:, :, None], r["hit_cigar"], 0).astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -107,7 +144,12 @@ def main():
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU per step (experiments; default: the workload's own batch)")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("SALT_BENCH_STREAMS", "4")),
                     help="workspaces / HIP streams per GPU the steps are dealt to round-robin (salt runs 2-4 align workers per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: serialized per-kernel steps, access counters + roofline, CPU baseline + parity, the paired-end and end-to-end legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the result rows of the last timed step as DIR/<field>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.mode == "pe":
         args.steps, args.warmup, args.batches, args.e2e_reads, args.e2e_pairs = max(1, args.streams), 1, 1, 0, 0
@@ -228,16 +270,19 @@ def main():
     for i in range(max(args.warmup, 0)):
         step(i)
     torch.cuda.synchronize()
-    # serialized steps first (one workspace, one stream, every batch once): per-kernel durations of a kernel that has the GPU to
-    # itself -- what a roofline fraction is about; in the timed region a kernel shares the GPU with the other batches' kernels
+    # the timed region runs with the per-kernel HIP events on (kernel_ms), whether or not --full
     for a in alns:
         a.timing(True)
-    n_serial = max(3, n_batches)
-    for i in range(n_serial):
-        step(i, 0)
-    torch.cuda.synchronize()
-    serial_kms, serial_calls = aln.kernel_ms()
-    serial_kms = {k: v / max(serial_calls, 1) for k, v in serial_kms.items()}
+    serial_kms, n_serial = {}, 0
+    if args.full:
+        # serialized steps first (one workspace, one stream, every batch once): per-kernel durations of a kernel that has the GPU to
+        # itself -- what a roofline fraction is about; in the timed region a kernel shares the GPU with the other batches' kernels
+        n_serial = max(3, n_batches)
+        for i in range(n_serial):
+            step(i, 0)
+        torch.cuda.synchronize()
+        serial_kms, serial_calls = aln.kernel_ms()
+        serial_kms = {k: v / max(serial_calls, 1) for k, v in serial_kms.items()}
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     if world > 1:
         dist.barrier()
@@ -254,8 +299,10 @@ def main():
     dt = time.perf_counter() - t0
     # the rows the LAST timed step left behind (its batch, its workspace): what the parity leg compares with the oracle
     last = args.steps - 1
-    timed_rows = d_ress[last % n_streams].clone() if args.steps > 0 else None
+    timed_rows = d_ress[last % n_streams].clone()
     timed_batch = last % n_batches
+    if args.dump_outputs:
+        dump_rows(args.dump_outputs, timed_rows.cpu().numpy().view(salt_amd.RESULT_DTYPE), np, "" if world == 1 else ".rank%d" % rank, world)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -288,10 +335,11 @@ def main():
                                       "steps dealt round-robin to %d workspace(s)/HIP stream(s) per GPU" % (world, n_streams),
                        "streams_per_gpu": n_streams},
             "stages_s": stages,
-            "step_ms": spread([step_ev[0].elapsed_time(e) for e in step_ev[1:]]) if args.steps > 0 else None,
+            "step_ms": spread([step_ev[0].elapsed_time(e) for e in step_ev[1:]]),
             "kernel_ms": {k: round(v, 3) for k, v in kms.items() if v},
-            "kernel_ms_serialized": {k: round(v, 3) for k, v in serial_kms.items() if v},
         }
+    if rank == 0 and args.full:
+        out["kernel_ms_serialized"] = {k: round(v, 3) for k, v in serial_kms.items() if v}
         # ---- one more serialized step of batch 0 with the access counters on (k_light instead of k_light2: same accesses; its rows are NOT
         # the ones compared with the oracle -- those are timed_rows, taken above) ----
         copt = salt_amd.AlnOpt(l_seed=cfg["k"], collect_counters=0 if args.no_counters else 1)
@@ -467,14 +515,14 @@ def main():
         del d_ress, batches, timed_rows
         torch.cuda.empty_cache()
         # ---- end to end: the drop-in binary, FASTQ text -> SAM text, wall clock (SURVEY 8d's metric; never `value`) ----
-        if args.e2e_reads > 0:
+        if args.full and args.e2e_reads > 0:
             try:
                 out["e2e"] = e2e_leg(args, cfg, w, genome, site, workload, torch, np, log, 1 if os.environ.get("SALT_BENCH_SAME_GPU") else world)
             except Exception as ex:                                    # the leg is a report, not a gate
                 out["e2e"] = {"error": str(ex)[:300]}
-        if args.e2e_pairs > 0 and args.e2e_reads > 0 and world > 1 and "error" in out.get("e2e", {}):
+        if args.full and args.e2e_pairs > 0 and args.e2e_reads > 0 and world > 1 and "error" in out.get("e2e", {}):
             out["e2e_pe"] = {"error": "skipped: the single-end `salt --gpus %d` run did not finish (see e2e.error)" % world}     # not another wait of minutes on the same cause
-        elif args.e2e_pairs > 0 and args.e2e_reads > 0:
+        elif args.full and args.e2e_pairs > 0 and args.e2e_reads > 0:
             try:
                 out["e2e_pe"] = e2e_pe_leg(args, w, genome, site, workload, torch, np, log, 1 if os.environ.get("SALT_BENCH_SAME_GPU") else world)
             except Exception as ex:

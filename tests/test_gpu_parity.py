@@ -722,13 +722,13 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
 
 
 def test_bench_line_keeps_its_contract_on_the_mini_workload(tmp_path):
-    """bench.py at N = 1 on the small workload: ONE JSON line with the driver's keys, the roofline and cpu_baseline objects, the
+    """bench.py --full at N = 1 on the small workload: ONE JSON line with the driver's keys, the roofline and cpu_baseline objects, the
     paired-end leg, both end-to-end legs (each also with its stream on /dev/null) and parity on a timed step."""
     import json
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SALT_BENCH_WORKLOAD="mini", SALT_GPU_LKT_LEN="14", SALT_BENCH_CACHE=str(tmp_path))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--cpu-sample", "5000", "--e2e-reads", "40000",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--cpu-sample", "5000", "--e2e-reads", "40000",
                           "--e2e-pairs", "10000", "--pe-pairs", "5000", "--pe-steps", "4", "--pe-batches", "2", "--pe-check", "1000"],
                          capture_output=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-800:]
@@ -746,6 +746,40 @@ def test_bench_line_keeps_its_contract_on_the_mini_workload(tmp_path):
     assert d["parity"]["path"] == "timed step" and d["parity"]["mismatching_reads"] == 0
     assert d["pe"]["value"] > 0 and d["pe"]["parity"]["mismatching_mates"] == 0 and "roofline" in d["pe"]
     assert d["e2e"]["value"] > 0 and d["e2e"]["value_devnull"] > 0 and d["e2e_pe"]["value"] > 0 and d["e2e_pe"]["value_devnull"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_rows_twice(tmp_path):
+    """bench.py without --full: the headline line only (no serialized, counter, CPU, paired-end or end-to-end legs), --steps timed
+    steps, and --dump-outputs writes the last timed step's rows as float32 / float64 .npy files within 64 MB -- the same files from
+    two runs with the same arguments."""
+    import json
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SALT_BENCH_WORKLOAD="mini", SALT_GPU_LKT_LEN="14", SALT_BENCH_CACHE=str(tmp_path / "cache"))
+    dumps = []
+    for run in range(2):
+        dd = tmp_path / ("dump%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(dd)],
+                             capture_output=True, env=env, timeout=600)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mreads/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "u32" and d["metric"]
+        for k in ("roofline", "cpu_baseline", "parity", "pe", "e2e", "e2e_pe", "kernel_ms_serialized", "queue_counts"):
+            assert k not in d, k
+        files = sorted(os.listdir(dd))
+        assert "pos.npy" in files and "cigar.npy" in files and "read_index.npy" in files
+        assert sum(os.path.getsize(dd / f) for f in files) <= 64 * 10**6
+        arrs = {f: np.load(dd / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert (arrs["pos.npy"] != 0xFFFFFFFF).mean() > 0.9
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 @pytest.fixture(scope="module")

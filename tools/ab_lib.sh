@@ -7,7 +7,7 @@ for spec in "$@"; do
   envs=""; tag="$spec"
   while [[ "$tag" == *=*:* ]]; do envs="$envs ${tag%%:*}"; tag="${tag#*:}"; done
   if [ "$tag" = "release" ] || [ -z "$tag" ]; then cp /tmp/libsalt_gpu_release.so salt_amd/lib/libsalt_gpu.so; else cp "salt_amd/lib/libsalt_gpu_${tag}.so" salt_amd/lib/libsalt_gpu.so; fi
-  out=$(env $envs python3 bench.py $ARGS 2>/dev/null | tail -1)
+  out=$(env $envs python3 bench.py --full $ARGS 2>/dev/null | tail -1)
   echo "== $spec :: $(echo "$out" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["kernel_ms_serialized"], "parity", d.get("parity",{}).get("mismatching_reads"), "| pe", d.get("pe",{}).get("value"), d.get("pe",{}).get("kernel_ms_serialized"))')"
 done
 cp /tmp/libsalt_gpu_release.so salt_amd/lib/libsalt_gpu.so

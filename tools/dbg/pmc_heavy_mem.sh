@@ -1,7 +1,7 @@
 #!/bin/bash
 # what k_heavy waits for at 8 and 12 one-wave blocks per CU: L1 -> L2 read latency, translation misses, address-unit stalls, scalar memory
 R=$PWD; OUT=$R/gpurun_out/heavy_mem; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-Q="--workload grch38 --no-cpu --no-counters --e2e-reads 0 --streams 1 --steps 4 --warmup 2 --batches 4 --mode se"
+Q="--full --workload grch38 --no-cpu --no-counters --e2e-reads 0 --streams 1 --steps 4 --warmup 2 --batches 4 --mode se"
 for n in 8 12; do
  for pass in "a1:TCP_TCC_READ_REQ_LATENCY TCP_TCC_READ_REQ TCP_PENDING_STALL_CYCLES GRBM_GUI_ACTIVE" "a2:TCP_UTCL1_TRANSLATION_MISS TCP_UTCL1_REQUEST TCP_TOTAL_CACHE_ACCESSES TCP_CACHE_MISS" "a3:TA_ADDR_STALLED_BY_TC_CYCLES TA_TA_BUSY TCP_TCR_TCP_STALL_CYCLES TCP_TCP_LATENCY" "b:SQ_INSTS_SMEM SQ_INST_CYCLES_SMEM SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES" "c:TCP_UTCL1_STALL_UTCL2_REQ_OUT_OF_CREDITS TCP_UTCL1_STALL_INFLIGHT_MAX TCP_UTCL1_STALL_MULTI_MISS TCP_READ_TAGCONFLICT_STALL_CYCLES"; do
   name=${pass%%:*}; ctrs=${pass#*:}

@@ -5,7 +5,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 CTRS=$1; shift
 OUT=$ROOT/gpurun_out/pmc_one; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CTRS --output-format csv -d "$OUT" -o pmc -- python3 "$ROOT/bench.py" --no-cpu --e2e-reads 0 --streams 1 --steps 4 --warmup 2 --batches 4 "$@" > /dev/null 2> "$OUT/err.log"
+rocprofv3 --pmc $CTRS --output-format csv -d "$OUT" -o pmc -- python3 "$ROOT/bench.py" --full --no-cpu --e2e-reads 0 --streams 1 --steps 4 --warmup 2 --batches 4 "$@" > /dev/null 2> "$OUT/err.log"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 from collections import defaultdict

@@ -10,13 +10,13 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
 if [ "${SALT_PROFILE_MODE:-se}" != pe ]; then
-python3 bench.py --workload "$WL" "$@" > "$OUT/bench_${WL}_1gpu.json" 2> "$OUT/bench.log"
+python3 bench.py --full --workload "$WL" "$@" > "$OUT/bench_${WL}_1gpu.json" 2> "$OUT/bench.log"
 tail -1 "$OUT/bench_${WL}_1gpu.json" | cut -c1-300
 fi
 cd /tmp && export TMPDIR=/tmp
 MODE=${SALT_PROFILE_MODE:-se}
 SUF=""; PRE=""; [ "$MODE" = pe ] && SUF="_pe" && PRE="pe_"
-Q="--workload $WL --no-cpu --no-counters --e2e-reads 0 --mode $MODE"
+Q="--full --workload $WL --no-cpu --no-counters --e2e-reads 0 --mode $MODE"
 # kernel-trace stats twice: --streams 1 (every kernel alone on the GPU: what the roofline block of the bench line is built from)
 # and the default command (batches overlapping on 4 streams: what "kernel_ms" of the bench line shows)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 "$ROOT/bench.py" $Q --streams 1 "$@" > "$OUT/bench_under_rocprofv3${SUF}_${WL}.json" 2>> "$OUT/bench.log"
