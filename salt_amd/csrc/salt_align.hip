@@ -1514,7 +1514,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
             // duplicates included -- rule_unsorted needs neither).  Strand 1's rows are still in `loci` (unless the context table
             // thinned them: the gapped pass needs every row); strand 0's are located again.  (Single end and paired end alike.)
             uint32_t slot = 0;
-            if (lane == 0) slot = atomicAdd(&g.gctl[QC(2)], 1u);
+            if (lane == 0) slot = atomicAdd(&g.gctl->gap_slots, 1u);
             slot = (uint32_t)__shfl((int)slot, 0);
             if (slot < g.cap) {
                 uint32_t ns[2], off[2];
@@ -1531,7 +1531,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
                     }
                     if (n > 1024u * LLV_N) { ok = false; break; }        // a work item names its chunk in 10 bits; PE lists can be longer
                     uint32_t o = 0;
-                    if (lane == 0) o = atomicAdd(&g.gctl[QC(8)], n);
+                    if (lane == 0) o = atomicAdd(&g.gctl->pool_used, n);
                     o = (uint32_t)__shfl((int)o, 0);
                     ok = (uint64_t)o + n <= g.pool;
                     if (ok) for (uint32_t i = lane; i < n; i += 64) g.gloci[o + i] = loci[i];
@@ -1539,7 +1539,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
                 }
                 const uint32_t ch0 = ok ? (ns[0] + LLV_N - 1) / LLV_N : 0, ch1 = ok ? (ns[1] + LLV_N - 1) / LLV_N : 0;
                 uint32_t base = 0;
-                if (ok && lane == 0) base = atomicAdd(&g.gctl[QC(5)], ch0 + ch1);
+                if (ok && lane == 0) base = atomicAdd(&g.gctl->gap_items, ch0 + ch1);
                 base = (uint32_t)__shfl((int)base, 0);
                 ok = ok && (uint64_t)base + ch0 + ch1 <= g.items_cap;
                 if (lane == 0) {
@@ -1571,7 +1571,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
             // ... which takes the lane-LV scratch this block does not carry: the read goes to the overflow queue and the pass behind
             // this kernel (the same code in a block that has it) starts it again.  Nothing of it has been written yet.
             if (lanes_fit && n_cand_nogap > 0) {
-                if (lane == 0) g.ovq[atomicAdd(&g.gctl[QC(9)], 1u)] = r;
+                if (lane == 0) g.ovq[atomicAdd(&g.gctl->ovq_count, 1u)] = r;
                 return;
             }
         }
@@ -1706,25 +1706,21 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
 }
 
 // ---------------------------------------------------------------------------------------------
-// Persistent kernels: one-wave blocks pull work items through counters in qctl[] until the head passes the count (control word k lives
-// at qctl[QC(k)], a cache line of its own; k_heavy, k_gap and k_gapfin take their items through ranged heads instead: pop_ranged)
-//   qctl[0] reads queued by k_light    qctl[1] (was k_heavy's head)
-//   qctl[2] gapped reads (slots)       qctl[3] k_gap head        qctl[4] k_gapfin head
-//   qctl[5] k_gap items                qctl[6] CIGAR items       qctl[7] k_cigar head      qctl[8] pool entries used
 // ---------------------------------------------------------------------------------------------
-static constexpr uint32_t HEAVY_HEADS = 64, HEAVY_HEAD_STRIDE = 64;          // ranges of the queue with a head of their own; words between the heads
-// Thread 0 of a persistent one-wave block: the next item of a queue of n_items cut into HEAVY_HEADS ranges (heads[range * HEAVY_HEAD_STRIDE],
-// zero at launch); 0xFFFFFFFF once every range is empty.  seg / tried: where this block is (start at blockIdx % HEAVY_HEADS, 0).
-__device__ __forceinline__ uint32_t pop_ranged(uint32_t *heads, const uint32_t n_items, uint32_t &seg, uint32_t &tried)
+// Persistent kernels: one-wave blocks pull work items until the queue is empty (k_heavy, k_gap, k_gapfin: pop_ranged; k_cigar: sw_pull)
+// ---------------------------------------------------------------------------------------------
+// Thread 0 of a persistent one-wave block: the next item of a queue of n_items cut into QUEUE_RANGES ranges (ranges[range].heads[which],
+// zero at launch); 0xFFFFFFFF once every range is empty.  seg / tried: where this block is (start at blockIdx % QUEUE_RANGES, 0).
+__device__ __forceinline__ uint32_t pop_ranged(QueueRange *ranges, const uint32_t which, const uint32_t n_items, uint32_t &seg, uint32_t &tried)
 {
-    while (tried < HEAVY_HEADS) {
-        const uint32_t lo = (uint32_t)((uint64_t)n_items * seg / HEAVY_HEADS), hi = (uint32_t)((uint64_t)n_items * (seg + 1u) / HEAVY_HEADS);
-        uint32_t *h = heads + seg * HEAVY_HEAD_STRIDE;
+    while (tried < QUEUE_RANGES) {
+        const uint32_t lo = (uint32_t)((uint64_t)n_items * seg / QUEUE_RANGES), hi = (uint32_t)((uint64_t)n_items * (seg + 1u) / QUEUE_RANGES);
+        uint32_t *h = &ranges[seg].heads[which];
         if (lo < hi && __hip_atomic_load(h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < hi - lo) {      // (a look first: late waves do not queue up on an empty range's counter)
             const uint32_t k = atomicAdd(h, 1u);
             if (k < hi - lo) return lo + k;
         }
-        seg = (seg + 1u) & (HEAVY_HEADS - 1u); ++tried;
+        seg = (seg + 1u) & (QUEUE_RANGES - 1u); ++tried;
     }
     return 0xFFFFFFFFu;
 }
@@ -1742,18 +1738,18 @@ __device__ __forceinline__ void heavy_body(const IndexView &ix, const AlignParam
     if (ctr) { for (int i = threadIdx.x; i < SALT_CTR_N; i += 64) s_phase[i] = 0; }
     WSYNC();
     // the usual pass takes the reads k_light queued (or all of them); the overflow pass the ones a block without the lane-LV scratch left
-    const uint32_t n_items = overflow_pass ? g.gctl[QC(9)] : ap.all_heavy ? ap.n_reads : g.gctl[QC(0)];
+    const uint32_t n_items = overflow_pass ? g.gctl->ovq_count : ap.all_heavy ? ap.n_reads : g.gctl->light_queued;
     // One read per pop.  The pops of all waves on ONE counter are served one after the other, ~14 ns each whatever the waves do in between
     // (75 700 queued reads: 1.09 of the kernel's 1.165 ms, the same at 8, 12 and 16 blocks per CU; time = 0.08 ms + 14.4 ns x reads from
-    // 9 000 to 150 000 reads, profiles/r03/heavy_vs_batch.log).  So the queue is cut into HEAVY_HEADS ranges with a head each, 256 bytes
-    // apart; a wave starts at range blockIdx % HEAVY_HEADS and moves on to the next when one is empty (pop_ranged).  k_gap and k_gapfin
-    // take their items the same way (heads + 1, + 2); the counters k_heavy's gapped reads push through are a cache line apart each (QC()).
-    uint32_t seg = blockIdx.x & (HEAVY_HEADS - 1u), tried = 0;
+    // 9 000 to 150 000 reads, profiles/r03/heavy_vs_batch.log).  So the queue is cut into QUEUE_RANGES ranges with a head each, 256 bytes
+    // apart; a wave starts at range blockIdx % QUEUE_RANGES and moves on to the next when one is empty (pop_ranged).  k_gap and k_gapfin
+    // take their items the same way; the counters k_heavy's gapped reads push through are a cache line apart each (SeCtl).
+    uint32_t seg = blockIdx.x & (QUEUE_RANGES - 1u), tried = 0;
     for (;;) {
         if (threadIdx.x == 0) {
             uint32_t got = 0xFFFFFFFFu;
-            if (overflow_pass) { got = atomicAdd(&g.gctl[QC(10)], 1u); if (got >= n_items) got = 0xFFFFFFFFu; }
-            else got = pop_ranged(g.qheads, n_items, seg, tried);
+            if (overflow_pass) { got = atomicAdd(&g.gctl->ovq_head, 1u); if (got >= n_items) got = 0xFFFFFFFFu; }
+            else got = pop_ranged(g.ranges, QueueRange::HEAVY, n_items, seg, tried);
             s_item = got;
         }
         WSYNC();
@@ -1807,10 +1803,10 @@ k_gap(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, GapBufs g)
     __shared__ GapLds s;
     __shared__ uint32_t s_item;
     const uint32_t lane = lane_id();
-    const uint32_t n_items = g.gctl[QC(5)] < g.items_cap ? g.gctl[QC(5)] : g.items_cap;
-    uint32_t seg = blockIdx.x & (HEAVY_HEADS - 1u), tried = 0;
+    const uint32_t n_items = g.gctl->gap_items < g.items_cap ? g.gctl->gap_items : g.items_cap;
+    uint32_t seg = blockIdx.x & (QUEUE_RANGES - 1u), tried = 0;
     for (;;) {
-        if (threadIdx.x == 0) s_item = pop_ranged(g.qheads + 1, n_items, seg, tried);
+        if (threadIdx.x == 0) s_item = pop_ranged(g.ranges, QueueRange::GAP, n_items, seg, tried);
         WSYNC();
         const uint32_t it = s_item;
         WSYNC();
@@ -1847,10 +1843,10 @@ k_gapfin(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, salt_res
     __shared__ uint32_t s_item;
     const uint32_t lane = lane_id();
     const uint64_t lt = (1ull << lane) - 1ull;
-    const uint32_t n_items = g.gctl[QC(2)] < g.cap ? g.gctl[QC(2)] : g.cap;
-    uint32_t seg = blockIdx.x & (HEAVY_HEADS - 1u), tried = 0;
+    const uint32_t n_items = g.gctl->gap_slots < g.cap ? g.gctl->gap_slots : g.cap;
+    uint32_t seg = blockIdx.x & (QUEUE_RANGES - 1u), tried = 0;
     for (;;) {
-        if (threadIdx.x == 0) s_item = pop_ranged(g.qheads + 2, n_items, seg, tried);
+        if (threadIdx.x == 0) s_item = pop_ranged(g.ranges, QueueRange::GAPFIN, n_items, seg, tried);
         WSYNC();
         const uint32_t slot = s_item;
         WSYNC();
@@ -1905,7 +1901,7 @@ k_gapfin(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, salt_res
                     out->hits[s][j].is_gap = 1; out->hits[s][j].strand = (uint16_t)s;
                 }
             if (n_cig_items > first_cig) {                                // main hit (which = 0) and every alternative hit (1 + index)
-                const uint32_t base = atomicAdd(&g.gctl[QC(6)], n_cig_items - first_cig);
+                const uint32_t base = atomicAdd(&g.gctl->cigar_items, n_cig_items - first_cig);
                 for (uint32_t c = first_cig; c < n_cig_items; ++c) g.cq[base + c - first_cig] = (r << 3) | c;
             }
             if (ctr) atomicMax(ctr + SALT_CTR_MAX_GAPFIN, ((unsigned long long)(__builtin_amdgcn_s_memrealtime() - rt0) << 32) | r);
@@ -1928,11 +1924,7 @@ k_cigar(IndexView ix, PackGeom pg, const uint32_t *__restrict__ pm, salt_result_
     struct { PackGeom pg; } ap = { pg };
     bool first = true;
     for (;;) {
-        // the block's own index first, then what the counter hands out behind those -- after a look at it (a plain load): the pops of a
-        // launch on one counter are served one after the other, ~14 ns each, also the ones that only find the queue empty
-        if (threadIdx.x == 0)
-            s_item = first ? blockIdx.x
-                   : (gridDim.x >= n_items || gridDim.x + __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_items) ? 0xFFFFFFFFu : gridDim.x + atomicAdd(head, 1u);
+        if (threadIdx.x == 0) s_item = first ? blockIdx.x : sw_pull(head, 1u, gridDim.x, n_items);      // the block's own index first
         first = false;
         WSYNC();
         const uint32_t it = s_item;
@@ -1970,24 +1962,23 @@ k_cigar(IndexView ix, PackGeom pg, const uint32_t *__restrict__ pm, salt_result_
 // ---------------------------------------------------------------------------------------------
 // The queue of reads for k_heavy.  One counter for all of them was what k_light2 waited for: an atomic on ONE address is served every
 // ~11 ns however many waves ask (75 700 queued reads: 0.83 of its 0.87 ms).  The reads of workgroup-sized groups of four go to one
-// of QSEG segments, each with a counter 256 bytes from the next and room for every read that can map to it; k_queue_pack then
-// lays the segments end to end (the order of the queue does not matter) and leaves the count where k_heavy reads it.
-static constexpr uint32_t QSEG = 64, QSEG_STRIDE = 64;                      // segments; words between their counters
-__host__ __device__ __forceinline__ uint32_t qseg_cap(uint32_t n_reads) { return n_reads / QSEG + 8u; }
-__device__ __forceinline__ void queue_push(uint32_t *__restrict__ qseg, uint32_t *__restrict__ qsub, uint32_t n_reads, uint32_t r)
+// of QUEUE_RANGES segments, each with a counter 256 bytes from the next (QueueRange::push) and room for every read that can map to it;
+// k_queue_pack then lays the segments end to end (the order of the queue does not matter) and leaves the count where k_heavy reads it.
+__host__ __device__ __forceinline__ uint32_t qseg_cap(uint32_t n_reads) { return n_reads / QUEUE_RANGES + 8u; }
+__device__ __forceinline__ void queue_push(uint32_t *__restrict__ qseg, QueueRange *__restrict__ ranges, uint32_t n_reads, uint32_t r)
 {
-    const uint32_t s = (r >> 2) & (QSEG - 1u);
-    qseg[(size_t)s * qseg_cap(n_reads) + atomicAdd(&qsub[s * QSEG_STRIDE], 1u)] = r;
+    const uint32_t s = (r >> 2) & (QUEUE_RANGES - 1u);
+    qseg[(size_t)s * qseg_cap(n_reads) + atomicAdd(&ranges[s].push, 1u)] = r;
 }
 __global__ void __launch_bounds__(256)
-k_queue_pack(const uint32_t *__restrict__ qseg, const uint32_t *__restrict__ qsub, uint32_t n_reads, uint32_t *__restrict__ queue, uint32_t *__restrict__ qctl)
+k_queue_pack(const uint32_t *__restrict__ qseg, const QueueRange *__restrict__ ranges, uint32_t n_reads, uint32_t *__restrict__ queue, SeCtl *__restrict__ ctl)
 {
     __shared__ uint32_t base_s, cnt_s;
     if (threadIdx.x == 0) {
         uint32_t base = 0, total = 0;
-        for (uint32_t s = 0; s < QSEG; ++s) { const uint32_t c = qsub[s * QSEG_STRIDE]; if (s < blockIdx.x) base += c; total += c; }
-        base_s = base; cnt_s = qsub[blockIdx.x * QSEG_STRIDE];
-        if (blockIdx.x == 0) qctl[QC(0)] = total;
+        for (uint32_t s = 0; s < QUEUE_RANGES; ++s) { const uint32_t c = ranges[s].push; if (s < blockIdx.x) base += c; total += c; }
+        base_s = base; cnt_s = ranges[blockIdx.x].push;
+        if (blockIdx.x == 0) ctl->light_queued = total;
     }
     __syncthreads();
     const uint32_t *src = qseg + (size_t)blockIdx.x * qseg_cap(n_reads);
@@ -2012,7 +2003,7 @@ static constexpr int LT_WAVES = 2;       // independent reads (waves) per workgr
 __global__ void __launch_bounds__(64 * LT_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
         const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
-        uint32_t *__restrict__ queue /* the segments */, uint32_t *__restrict__ qsub, unsigned long long *__restrict__ ctr)
+        uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges, unsigned long long *__restrict__ ctr)
 {
     __shared__ LightLds w_all[LT_WAVES];
     LightLds &w = w_all[threadIdx.x >> 6];
@@ -2199,7 +2190,7 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
         }
     }
     if (heavy) {
-        if (lane == 0) queue_push(queue, qsub, ap.n_reads, r);
+        if (lane == 0) queue_push(queue, ranges, ap.n_reads, r);
         return;                                                             // k_heavy does (and counts) all of it
     }
     stamp(SALT_CTR_LT_OUT);
@@ -2314,7 +2305,7 @@ template <int L2_WAVES, int LN = 4>
 __global__ void __launch_bounds__(64 * L2_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_light2(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
          const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
-         uint32_t *__restrict__ queue /* the segments */, uint32_t *__restrict__ qsub)
+         uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges)
 {
     __shared__ LightLds2 w2[2 * L2_WAVES];
     const uint32_t lane = lane_id(), hl = lane & 31u, hb = lane & 32u, half = lane >> 5;
@@ -2495,7 +2486,7 @@ k_light2(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
             }
         }
     }
-    if (heavy && hl == 0) queue_push(queue, qsub, ap.n_reads, r);            // k_heavy does all of it
+    if (heavy && hl == 0) queue_push(queue, ranges, ap.n_reads, r);            // k_heavy does all of it
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2538,11 +2529,11 @@ k_pe_final(PackGeom pg, uint32_t n_pairs, const uint32_t *__restrict__ pm,
 }
 
 void launch_pe_final(const IndexView &ix, const PackGeom &pg, uint32_t n_pairs, const uint32_t *pm, salt_result_t *res, const PePair *pairs,
-                     const PeSwRes *sw, void *lvtab, uint32_t *citems, uint32_t *cctl, uint32_t n_blocks, hipStream_t st)
+                     const PeSwRes *sw, void *lvtab, uint32_t *citems, PeCtl *ctl, uint32_t n_blocks, hipStream_t st)
 {
     if (!n_pairs) return;
-    hipLaunchKernelGGL(k_pe_final, dim3((n_pairs + 255) / 256), dim3(256), 0, st, pg, n_pairs, pm, res, pairs, sw, citems, cctl);
-    hipLaunchKernelGGL(k_cigar, dim3(n_blocks), dim3(64), 0, st, ix, pg, pm, res, citems, cctl, cctl + 1, 2 * n_pairs, static_cast<LvTables *>(lvtab));
+    hipLaunchKernelGGL(k_pe_final, dim3((n_pairs + 255) / 256), dim3(256), 0, st, pg, n_pairs, pm, res, pairs, sw, citems, &ctl->n_cigar);
+    hipLaunchKernelGGL(k_cigar, dim3(n_blocks), dim3(64), 0, st, ix, pg, pm, res, citems, &ctl->n_cigar, &ctl->cigar_head, 2 * n_pairs, static_cast<LvTables *>(lvtab));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2565,23 +2556,20 @@ void launch_seed(const IndexView &ix, const SeedParams &sp, const uint32_t *tb, 
 }
 
 void launch_light(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint8_t *, const uint32_t *, const uint4 *sai_c,
-                  const uint4 *sai_r, salt_result_t *results, uint32_t *queue, uint32_t *qctl, uint32_t *qseg, uint32_t *qsub, unsigned long long *ctr, hipStream_t st)
+                  const uint4 *sai_r, salt_result_t *results, uint32_t *queue, SeCtl *ctl, uint32_t *qseg, QueueRange *ranges, unsigned long long *ctr, hipStream_t st)
 {
     if (!ap.n_reads) return;
-    hipMemsetAsync(qsub, 0, (size_t)QSEG * QSEG_STRIDE * 4, st);
     static const bool no_half = getenv("SALT_GPU_NO_LIGHT2") && atoi(getenv("SALT_GPU_NO_LIGHT2"));
     if (!no_half && !ctr && !SALT_DIAG_VAL(ap.dbg_stop) && ap.spr <= (uint32_t)L2_SLOTS && ap.pg.nw8 <= 31) {          // reads of at most 120 / 248 bases with at most 8 seed slots: two per wave
         static const int wv = getenv("SALT_GPU_L2_WAVES") ? atoi(getenv("SALT_GPU_L2_WAVES")) : 2;
-        if (ap.pg.nw8 > 15) hipLaunchKernelGGL((k_light2<2, 8>), dim3((ap.n_reads + 3) / 4), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, qsub);
-        else if (wv == 1) hipLaunchKernelGGL(k_light2<1>, dim3((ap.n_reads + 1) / 2), dim3(64), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, qsub);
-        else hipLaunchKernelGGL(k_light2<2>, dim3((ap.n_reads + 3) / 4), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, qsub);
+        if (ap.pg.nw8 > 15) hipLaunchKernelGGL((k_light2<2, 8>), dim3((ap.n_reads + 3) / 4), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
+        else if (wv == 1) hipLaunchKernelGGL(k_light2<1>, dim3((ap.n_reads + 1) / 2), dim3(64), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
+        else hipLaunchKernelGGL(k_light2<2>, dim3((ap.n_reads + 3) / 4), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
     } else
-        hipLaunchKernelGGL(k_light, dim3((ap.n_reads + LT_WAVES - 1) / LT_WAVES), dim3(64 * LT_WAVES), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, qsub, ctr);
-    hipLaunchKernelGGL(k_queue_pack, dim3(QSEG), dim3(256), 0, st, qseg, qsub, ap.n_reads, queue, qctl);
+        hipLaunchKernelGGL(k_light, dim3((ap.n_reads + LT_WAVES - 1) / LT_WAVES), dim3(64 * LT_WAVES), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges, ctr);
+    hipLaunchKernelGGL(k_queue_pack, dim3(QUEUE_RANGES), dim3(256), 0, st, qseg, ranges, ap.n_reads, queue, ctl);
 }
-size_t queue_words(uint32_t max_reads) { return (size_t)max_reads * 2 + (size_t)QSEG * qseg_cap(max_reads); }     // flat queue | overflow queue | segments
-uint32_t queue_sub_words() { return QSEG * QSEG_STRIDE; }
-uint32_t queue_heads_offset() { static_assert(HEAVY_HEADS == QSEG && HEAVY_HEAD_STRIDE == QSEG_STRIDE, "k_heavy's heads live in the segments' counter slots"); return QSEG_STRIDE / 2; }
+size_t queue_words(uint32_t max_reads) { return (size_t)max_reads * 2 + (size_t)QUEUE_RANGES * qseg_cap(max_reads); }     // flat queue | overflow queue | segments
 
 // ---------------------------------------------------------------------------------------------
 // k_diag_rule: unit access to rule_unsorted / rule_sparse (tests only).  One wave per case; out[case] = any, best_pos,
@@ -2844,12 +2832,12 @@ uint32_t heavy_blocks_per_cu()
 
 void launch_heavy(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint4 *sai_c,
                   const uint4 *sai_r, salt_result_t *results, const uint32_t *queue, unsigned long long *ctr,
-                  uint32_t n_blocks, uint32_t gap_blocks, void *lvtab, const GapBufs &g_in, uint32_t *ovq, uint32_t *qheads, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st)
+                  uint32_t n_blocks, uint32_t gap_blocks, void *lvtab, const GapBufs &g_in, uint32_t *ovq, QueueRange *ranges, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st)
 {
     if (!ap.n_reads) { if (ev3) for (int i = 0; i < 3; ++i) hipEventRecord(ev3[i], st); return; }
     uint32_t blocks = n_blocks < ap.n_reads ? n_blocks : ap.n_reads;
     LvTables *tab = static_cast<LvTables *>(lvtab);
-    GapBufs g = g_in; g.ovq = ovq; g.qheads = qheads;
+    GapBufs g = g_in; g.ovq = ovq; g.ranges = ranges;
     // The usual shape (7.5 KB of LDS per block) when the batch fits it: at most 32 seed slots per strand and k_gap's buffers to hand gapped
     // reads to; the few reads it cannot finish (no k_gap slot left) wait in the overflow queue for the pass right behind it, which runs
     // the all-in-one shape (18.6 KB) and leaves at once when the queue is empty.  SALT_GPU_HEAVY_BIG=1: the all-in-one shape for everything.
@@ -2876,10 +2864,10 @@ void launch_heavy(const IndexView &ix, const AlignParams &ap, const uint32_t *pm
     if (ev3) hipEventRecord(ev3[1], st);
     hipLaunchKernelGGL(k_gapfin, dim3((n_blocks + 3) / 4), dim3(64), 0, st, ix, ap, pm, results, g, ctr);
     if (ev3) hipEventRecord(ev3[2], st);
-    hipLaunchKernelGGL(k_cigar, dim3((n_blocks + 1) / 2), dim3(64), 0, st, ix, ap.pg, pm, results, g.cq, g.gctl + QC(6), g.gctl + QC(7), g.cap * (1u + SALT_MAX_HITS), tab);
+    hipLaunchKernelGGL(k_cigar, dim3((n_blocks + 1) / 2), dim3(64), 0, st, ix, ap.pg, pm, results, g.cq, &g.gctl->cigar_items, &g.gctl->cigar_head, g.cap * (1u + SALT_MAX_HITS), tab);
 }
 
-GapBufs gap_bufs_layout(uint8_t *base, uint32_t cap, uint32_t *gctl, size_t *bytes)
+GapBufs gap_bufs_layout(uint8_t *base, uint32_t cap, SeCtl *gctl, size_t *bytes)
 {
     GapBufs g; size_t off = 0;
     auto take = [&](size_t n) { size_t o = off; off = (off + n + 255) & ~(size_t)255; return base ? base + o : nullptr; };

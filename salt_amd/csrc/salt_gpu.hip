@@ -22,6 +22,8 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
     return fail(SALT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+// the same in a function that frees its buffers in a lambda done(rc) on every return
+#define DONECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(SALT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_))); } while (0)
 
 struct salt_gpu_index {
     int device = 0;
@@ -44,12 +46,12 @@ struct salt_gpu_ws {
     uint32_t *d_pm = nullptr, *d_tb = nullptr; uint64_t pm_cap = 0, tb_cap = 0;     // k_pack's records (words)
     uint8_t *d_heads = nullptr, *h_heads = nullptr;          // first 128 bytes of every result row: dense device copy + pinned host staging
     unsigned long long *d_ctr = nullptr;
-    uint32_t *d_queue = nullptr, *d_qctl = nullptr;   // reads k_light hands to k_heavy; {count, head}
+    uint32_t *d_queue = nullptr; SeCtl *d_qctl = nullptr;   // reads k_light hands to k_heavy; the batch's control words
     void *d_lvtab = nullptr;                          // one LV traceback table per persistent k_heavy block
     uint8_t *d_gap = nullptr; uint32_t gcap = 0; GapBufs gap{};             // deferred gapped passes
     // paired end (allocated on first use)
     uint8_t *d_pe_scr = nullptr;                       // per persistent block: PE_LOCI_CAP loci + distances
-    PePair *d_pairs = nullptr; PeSwReq *d_req = nullptr; PeSwRes *d_swres = nullptr; uint32_t *d_pctl = nullptr;
+    PePair *d_pairs = nullptr; PeSwReq *d_req = nullptr; PeSwRes *d_swres = nullptr; PeCtl *d_pctl = nullptr;
     uint8_t *d_sw_scr = nullptr; uint64_t sw_scr_bytes = 0; uint32_t sw_blocks = 0; uint32_t pe_pairs_cap = 0;
     uint32_t *d_pcq = nullptr;                         // k_cigar items of the gapped, not rescued mates
     // FASTQ text in / SAM text out (allocated on first use, grown on demand)
@@ -60,7 +62,7 @@ struct salt_gpu_ws {
     bool h_sam_owned = true;                                                 // false: the caller's page-locked buffer (salt_gpu_ws_reserve_text)
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
     uint32_t heavy_blocks = 2048, gap_blocks = 2048;
-    uint32_t *d_qsub = nullptr;                                               // counters of the queue's segments
+    QueueRange *d_ranges = nullptr;                                           // k_heavy's queue ranges: k_light's push counters, the heads
     int all_heavy = 0;
     hipStream_t stream = nullptr;
     bool timing = false;
@@ -293,8 +295,8 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
     CHKW(hipMalloc((void **)&ws->d_results, (uint64_t)max_reads * sizeof(salt_result_t)));
     CHKW(hipMemset(ws->d_results, 0, (uint64_t)max_reads * sizeof(salt_result_t)));
     CHKW(hipMalloc((void **)&ws->d_queue, queue_words(max_reads) * 4));         // the reads k_light queues (flat, and the segments they arrive in) + k_heavy's overflow queue
-    CHKW(hipMalloc((void **)&ws->d_qsub, (size_t)queue_sub_words() * 4));
-    CHKW(hipMalloc((void **)&ws->d_qctl, (size_t)QCTL_WORDS * 4));
+    CHKW(hipMalloc((void **)&ws->d_ranges, QUEUE_RANGES * sizeof(QueueRange)));
+    CHKW(hipMalloc((void **)&ws->d_qctl, sizeof(SeCtl)));
     ws->gcap = max_reads < (1u << 20) ? max_reads : (1u << 20);         // slots for reads whose gapped pass is deferred (44 B each + their rows in the pool)
     if (const char *e3 = getenv("SALT_GPU_NO_GAP_DEFER")) if (atoi(e3)) ws->gcap = 0;
     if (const char *e3 = getenv("SALT_GPU_GAP_SLOTS")) { const int v = atoi(e3); if (v > 0 && (uint32_t)v < ws->gcap) ws->gcap = (uint32_t)v; }     // tests: the overflow pass
@@ -337,7 +339,7 @@ extern "C" void salt_gpu_ws_destroy(salt_gpu_ws_t *ws)
 {
     if (!ws) return;
     hipSetDevice(ws->ix->device);
-    hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_wq_cnt); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_qsub); hipFree(ws->d_qctl); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
+    hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_wq_cnt); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_ranges); hipFree(ws->d_qctl); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
     hipFree(ws->d_raw); hipFree(ws->d_tile); hipFree(ws->d_lines); hipFree(ws->d_rec); hipFree(ws->d_tctl); hipFree(ws->d_samoff); hipFree(ws->d_samslot); hipFree(ws->d_samseg); hipFree(ws->d_scan); hipFree(ws->d_sam); hipFree(ws->d_rg);
     if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam);
     hipFree(ws->d_pe_scr); hipFree(ws->d_pairs); hipFree(ws->d_req); hipFree(ws->d_swres); hipFree(ws->d_pctl); hipFree(ws->d_sw_scr); hipFree(ws->d_pcq);
@@ -414,7 +416,8 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     unsigned long long *ctr = o->collect_counters ? ws->d_ctr : nullptr;
     const bool timed = ws->timing && ws->n_timed < MAX_TIMED;
     hipEvent_t *ev = timed ? &ws->ev[(size_t)ws->n_timed * EV_PER_CALL] : nullptr;
-    HIPCHK(hipMemsetAsync(ws->d_qctl, 0, (size_t)QCTL_WORDS * 4, st));
+    HIPCHK(hipMemsetAsync(ws->d_qctl, 0, sizeof(SeCtl), st));
+    HIPCHK(hipMemsetAsync(ws->d_ranges, 0, QUEUE_RANGES * sizeof(QueueRange), st));
     if (timed) HIPCHK(hipEventRecord(ev[0], st));
     launch_pack(pg, n_reads, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_pm, ws->d_tb, st);
     if (timed) HIPCHK(hipEventRecord(ev[1], st));
@@ -422,12 +425,11 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     if (timed) HIPCHK(hipEventRecord(ev[2], st));
     if (!ap.all_heavy)
         launch_light(ws->ix->view, ap, ws->d_pm, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_sai_c, ws->d_sai_r,
-                     static_cast<salt_result_t *>(d_results), ws->d_queue, ws->d_qctl, ws->d_queue + 2 * (size_t)ws->max_reads, ws->d_qsub, ctr, st);
-    else HIPCHK(hipMemsetAsync(ws->d_qsub, 0, (size_t)queue_sub_words() * 4, st));          // (launch_light does it otherwise: k_heavy's queue heads live there)
+                     static_cast<salt_result_t *>(d_results), ws->d_queue, ws->d_qctl, ws->d_queue + 2 * (size_t)ws->max_reads, ws->d_ranges, ctr, st);
     if (timed) HIPCHK(hipEventRecord(ev[3], st));
     launch_heavy(ws->ix->view, ap, ws->d_pm, ws->d_sai_c, ws->d_sai_r,
                  static_cast<salt_result_t *>(d_results), ws->d_queue, ctr, ws->heavy_blocks, ws->gap_blocks, ws->d_lvtab,
-                 gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_qsub + queue_heads_offset(), glob_loci ? ws->d_pe_scr : nullptr, timed ? ev + 4 : nullptr, st);
+                 gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr : nullptr, timed ? ev + 4 : nullptr, st);
     if (timed) { HIPCHK(hipEventRecord(ev[7], st)); ws->ev_pe[ws->n_timed] = 0; ++ws->n_timed; }
     HIPCHK(hipGetLastError());
     return SALT_OK;
@@ -802,7 +804,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     uint32_t total = 0, n_over = 0; unsigned long long total64 = 0;
     HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
-    if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, ws->d_pctl + 4, 4, hipMemcpyDeviceToHost, st));
+    if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W): "
                                              "the rows of this batch would differ from the reference's");
@@ -866,20 +868,41 @@ extern "C" int salt_gpu_polish_lv(salt_gpu_polish_t *p, const uint8_t *codes, co
     uint8_t *d_codes = nullptr, *d_pool = nullptr, *d_nc = nullptr; uint32_t *d_offs = nullptr; salt_polish_item_t *d_items = nullptr; int32_t *d_dist = nullptr; uint16_t *d_cig = nullptr;
     const uint64_t bases = offs[n_reads];
     auto done = [&](int rc) { hipFree(d_codes); hipFree(d_pool); hipFree(d_nc); hipFree(d_offs); hipFree(d_items); hipFree(d_dist); hipFree(d_cig); return rc; };
-#define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(SALT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_))); } while (0)
-    PCHK(hipMalloc((void **)&d_codes, bases + 64)); PCHK(hipMemcpy(d_codes, codes, bases, hipMemcpyHostToDevice));
-    PCHK(hipMalloc((void **)&d_offs, ((uint64_t)n_reads + 1) * 4)); PCHK(hipMemcpy(d_offs, offs, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice));
-    PCHK(hipMalloc((void **)&d_items, (uint64_t)n_items * sizeof(salt_polish_item_t))); PCHK(hipMemcpy(d_items, items, (uint64_t)n_items * sizeof(salt_polish_item_t), hipMemcpyHostToDevice));
-    if (n_pool) { PCHK(hipMalloc((void **)&d_pool, (uint64_t)n_pool * pool_stride + 8)); PCHK(hipMemcpy(d_pool, pool, (uint64_t)n_pool * pool_stride, hipMemcpyHostToDevice)); }
-    PCHK(hipMalloc((void **)&d_dist, (uint64_t)n_items * 4));
-    if (want_cigar) { PCHK(hipMalloc((void **)&d_cig, (uint64_t)n_items * SALT_MAX_CIGAR_OPS * 2)); PCHK(hipMalloc((void **)&d_nc, n_items)); PCHK(hipMemset(d_nc, 0, n_items)); }
+    DONECHK(hipMalloc((void **)&d_codes, bases + 64)); DONECHK(hipMemcpy(d_codes, codes, bases, hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_offs, ((uint64_t)n_reads + 1) * 4)); DONECHK(hipMemcpy(d_offs, offs, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_items, (uint64_t)n_items * sizeof(salt_polish_item_t))); DONECHK(hipMemcpy(d_items, items, (uint64_t)n_items * sizeof(salt_polish_item_t), hipMemcpyHostToDevice));
+    if (n_pool) { DONECHK(hipMalloc((void **)&d_pool, (uint64_t)n_pool * pool_stride + 8)); DONECHK(hipMemcpy(d_pool, pool, (uint64_t)n_pool * pool_stride, hipMemcpyHostToDevice)); }
+    DONECHK(hipMalloc((void **)&d_dist, (uint64_t)n_items * 4));
+    if (want_cigar) { DONECHK(hipMalloc((void **)&d_cig, (uint64_t)n_items * SALT_MAX_CIGAR_OPS * 2)); DONECHK(hipMalloc((void **)&d_nc, n_items)); DONECHK(hipMemset(d_nc, 0, n_items)); }
     const uint32_t blocks = n_items < p->n_blocks ? n_items : p->n_blocks;
     launch_polish(p->d_pac, d_codes, d_offs, d_items, n_items, d_pool, pool_stride, want_cigar, d_dist, d_cig, d_nc, p->d_tabs, blocks, nullptr);
-    PCHK(hipGetLastError());
-    PCHK(hipDeviceSynchronize());
-    PCHK(hipMemcpy(dist, d_dist, (uint64_t)n_items * 4, hipMemcpyDeviceToHost));
-    if (want_cigar) { PCHK(hipMemcpy(cigars, d_cig, (uint64_t)n_items * SALT_MAX_CIGAR_OPS * 2, hipMemcpyDeviceToHost)); PCHK(hipMemcpy(n_cigar, d_nc, n_items, hipMemcpyDeviceToHost)); }
-#undef PCHK
+    DONECHK(hipGetLastError());
+    DONECHK(hipDeviceSynchronize());
+    DONECHK(hipMemcpy(dist, d_dist, (uint64_t)n_items * 4, hipMemcpyDeviceToHost));
+    if (want_cigar) { DONECHK(hipMemcpy(cigars, d_cig, (uint64_t)n_items * SALT_MAX_CIGAR_OPS * 2, hipMemcpyDeviceToHost)); DONECHK(hipMemcpy(n_cigar, d_nc, n_items, hipMemcpyDeviceToHost)); }
+    return done(SALT_OK);
+}
+
+// One Smith-Waterman launch outside a workspace (polish -s, the unit entry): h_req in, their rows into h_res, *overflow = the rescues
+// this build cannot finish as the reference would (PeCtl::overflow).  Frees what it allocates on every path.
+static int sw_run(const IndexView &v, const uint8_t *d_pac, const uint8_t *d_codes, const uint32_t *d_offs, const std::vector<PeSwReq> &h_req,
+                  SwGeom geom, uint32_t max_len, std::vector<PeSwRes> &h_res, uint32_t *overflow)
+{
+    const uint64_t n = h_req.size();
+    PeSwReq *d_req = nullptr; PeSwRes *d_res = nullptr; uint8_t *d_scr = nullptr; PeCtl *d_ctl = nullptr;
+    auto done = [&](int rc) { hipFree(d_req); hipFree(d_res); hipFree(d_scr); hipFree(d_ctl); return rc; };
+    DONECHK(hipMalloc((void **)&d_req, n * sizeof(PeSwReq))); DONECHK(hipMemcpy(d_req, h_req.data(), n * sizeof(PeSwReq), hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_res, n * sizeof(PeSwRes)));
+    DONECHK(hipMalloc((void **)&d_scr, sw_scratch_bytes(geom)));
+    PeCtl ctl{}; ctl.n_req = (uint32_t)n;
+    DONECHK(hipMalloc((void **)&d_ctl, sizeof ctl)); DONECHK(hipMemcpy(d_ctl, &ctl, sizeof ctl, hipMemcpyHostToDevice));
+    launch_sw(v, d_pac, d_codes, d_offs, d_req, d_ctl, d_res, d_scr, geom, max_len, nullptr);
+    DONECHK(hipGetLastError());
+    DONECHK(hipDeviceSynchronize());
+    DONECHK(hipMemcpy(&ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+    h_res.resize(n);
+    DONECHK(hipMemcpy(h_res.data(), d_res, n * sizeof(PeSwRes), hipMemcpyDeviceToHost));
+    *overflow = ctl.overflow;
     return done(SALT_OK);
 }
 
@@ -900,30 +923,18 @@ extern "C" int salt_gpu_polish_sw(salt_gpu_polish_t *p, const uint8_t *codes, co
         h_req[i] = PeSwReq{ x.offset, x.offset + x.tlen - 1u, x.read, (uint8_t)(x.strand ? 1 : 0), 2, (uint16_t)(want_cigar ? 0 : 1) };
     }
     HIPCHK(hipSetDevice(p->device));
-    uint8_t *d_codes = nullptr, *d_scr = nullptr; uint32_t *d_offs = nullptr, *d_ctl = nullptr; PeSwReq *d_req = nullptr; PeSwRes *d_res = nullptr;
+    uint8_t *d_codes = nullptr; uint32_t *d_offs = nullptr;
     const uint64_t bases = offs[n_reads];
-    auto done = [&](int rc) { hipFree(d_codes); hipFree(d_scr); hipFree(d_offs); hipFree(d_ctl); hipFree(d_req); hipFree(d_res); return rc; };
-#define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(SALT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_))); } while (0)
-    PCHK(hipMalloc((void **)&d_codes, bases + 64)); PCHK(hipMemcpy(d_codes, codes, bases, hipMemcpyHostToDevice));
-    PCHK(hipMalloc((void **)&d_offs, ((uint64_t)n_reads + 1) * 4)); PCHK(hipMemcpy(d_offs, offs, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice));
-    PCHK(hipMalloc((void **)&d_req, (uint64_t)n_items * sizeof(PeSwReq))); PCHK(hipMemcpy(d_req, h_req.data(), (uint64_t)n_items * sizeof(PeSwReq), hipMemcpyHostToDevice));
-    PCHK(hipMalloc((void **)&d_res, (uint64_t)n_items * sizeof(PeSwRes)));
+    auto done = [&](int rc) { hipFree(d_codes); hipFree(d_offs); return rc; };
+    DONECHK(hipMalloc((void **)&d_codes, bases + 64)); DONECHK(hipMemcpy(d_codes, codes, bases, hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_offs, ((uint64_t)n_reads + 1) * 4)); DONECHK(hipMemcpy(d_offs, offs, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice));
     SwGeom geom = sw_geom(max_len, max_len, p->n_blocks / 8u);
     sw_geom_limit(geom, (n_items + 7u) / 8u);
-    PCHK(hipMalloc((void **)&d_scr, sw_scratch_bytes(geom)));
-    const uint32_t ctl[9] = { n_items, 0, 0, 0, 0, 0, 0, 0, 0 };   // requests, -, overflow count, -, the four kernels' queue heads + pending count
-    PCHK(hipMalloc((void **)&d_ctl, 36)); PCHK(hipMemcpy(d_ctl, ctl, 36, hipMemcpyHostToDevice));
     IndexView v; memset(&v, 0, sizeof v);
     v.ref_len = (uint32_t)p->l_pac;                            // k_sw's range check; mode 2 reads the 2-bit genome only
-    launch_sw(v, p->d_pac, d_codes, d_offs, d_req, d_ctl, d_res, d_ctl + 4, d_ctl + 2, d_scr, geom, max_len, nullptr);
-    PCHK(hipGetLastError());
-    PCHK(hipDeviceSynchronize());
-    uint32_t h_ctl[3];
-    PCHK(hipMemcpy(h_ctl, d_ctl, 12, hipMemcpyDeviceToHost));
-    if (h_ctl[2]) return done(fail(SALT_E_INVAL, "polish -s: an alignment needs a wider band or more CIGAR operations than this build holds"));
-    std::vector<PeSwRes> h_res(n_items);
-    PCHK(hipMemcpy(h_res.data(), d_res, (uint64_t)n_items * sizeof(PeSwRes), hipMemcpyDeviceToHost));
-#undef PCHK
+    std::vector<PeSwRes> h_res; uint32_t n_over = 0;
+    if (int rc = sw_run(v, p->d_pac, d_codes, d_offs, h_req, geom, max_len, h_res, &n_over)) return done(rc);
+    if (n_over) return done(fail(SALT_E_INVAL, "polish -s: an alignment needs a wider band or more CIGAR operations than this build holds"));
     for (uint32_t i = 0; i < n_items; ++i) {
         const PeSwRes &r = h_res[i];
         score[i] = r.score1;
@@ -1087,30 +1098,22 @@ extern "C" int salt_gpu_diag_ssw(uint32_t n_cases, const uint8_t *aware, const u
         h_req[i] = PeSwReq{ ref_offs[i], ref_offs[i + 1] - 1, i, 0, (uint8_t)(aware[i] ? 1 : 0), 0 };
         if (read_offs[i + 1] - read_offs[i] > diag_max_len) diag_max_len = read_offs[i + 1] - read_offs[i];
     }
-    uint32_t *d_ref = nullptr, *d_offs = nullptr, *d_ctl = nullptr; uint8_t *d_pac = nullptr, *d_codes = nullptr, *d_scr = nullptr;
-    PeSwReq *d_req = nullptr; PeSwRes *d_res = nullptr;
-    const uint32_t blocks = n_cases / 8 + 1 < 256 ? n_cases / 8 + 1 : 256;
-    HIPCHK(hipMalloc((void **)&d_ref, h_ref.size() * 4)); HIPCHK(hipMemcpy(d_ref, h_ref.data(), h_ref.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&d_pac, h_pac.size())); HIPCHK(hipMemcpy(d_pac, h_pac.data(), h_pac.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&d_codes, n_base + 16)); HIPCHK(hipMemcpy(d_codes, codes, n_base, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&d_offs, ((uint64_t)n_cases + 1) * 4)); HIPCHK(hipMemcpy(d_offs, read_offs, ((uint64_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&d_req, (uint64_t)n_cases * sizeof(PeSwReq))); HIPCHK(hipMemcpy(d_req, h_req.data(), (uint64_t)n_cases * sizeof(PeSwReq), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&d_res, (uint64_t)n_cases * sizeof(PeSwRes)));
+    if (diag_max_len > SALT_MAX_READ_LEN) return fail(SALT_E_INVAL, "read longer than SALT_MAX_READ_LEN");
     uint64_t diag_max_win = 1;
     for (uint32_t i = 0; i < n_cases; ++i) if (ref_offs[i + 1] - ref_offs[i] > diag_max_win) diag_max_win = ref_offs[i + 1] - ref_offs[i];
-    if (diag_max_len > SALT_MAX_READ_LEN) return fail(SALT_E_INVAL, "read longer than SALT_MAX_READ_LEN");
+    uint32_t *d_ref = nullptr, *d_offs = nullptr; uint8_t *d_pac = nullptr, *d_codes = nullptr;
+    auto done = [&](int rc) { hipFree(d_ref); hipFree(d_pac); hipFree(d_codes); hipFree(d_offs); return rc; };
+    DONECHK(hipMalloc((void **)&d_ref, h_ref.size() * 4)); DONECHK(hipMemcpy(d_ref, h_ref.data(), h_ref.size() * 4, hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_pac, h_pac.size())); DONECHK(hipMemcpy(d_pac, h_pac.data(), h_pac.size(), hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_codes, n_base + 16)); DONECHK(hipMemcpy(d_codes, codes, n_base, hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_offs, ((uint64_t)n_cases + 1) * 4)); DONECHK(hipMemcpy(d_offs, read_offs, ((uint64_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
+    const uint32_t blocks = n_cases / 8 + 1 < 256 ? n_cases / 8 + 1 : 256;
     SwGeom geom = sw_geom(diag_max_len, diag_max_win, 1);
     geom.n_blocks = blocks; geom.tb_blocks = blocks;
-    HIPCHK(hipMalloc((void **)&d_scr, sw_scratch_bytes(geom)));
-    const uint32_t ctl[9] = { n_cases, 0, 0, 0, 0, 0, 0, 0, 0 };    // requests, -, overflow count, -, the four kernels' queue heads + pending count
-    HIPCHK(hipMalloc((void **)&d_ctl, 36)); HIPCHK(hipMemcpy(d_ctl, ctl, 36, hipMemcpyHostToDevice));
     IndexView v; memset(&v, 0, sizeof v);
     v.ref = d_ref; v.ref_len = (uint32_t)n_sym;
-    launch_sw(v, d_pac, d_codes, d_offs, d_req, d_ctl, d_res, d_ctl + 4, d_ctl + 2, d_scr, geom, diag_max_len, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<PeSwRes> h_res(n_cases);
-    HIPCHK(hipMemcpy(h_res.data(), d_res, (uint64_t)n_cases * sizeof(PeSwRes), hipMemcpyDeviceToHost));
+    std::vector<PeSwRes> h_res; uint32_t n_over = 0;
+    if (int rc = sw_run(v, d_pac, d_codes, d_offs, h_req, geom, diag_max_len, h_res, &n_over)) return done(rc);
     for (uint32_t i = 0; i < n_cases; ++i) {
         const PeSwRes &r = h_res[i];
         int32_t *o = out6 + 6 * (uint64_t)i;
@@ -1118,8 +1121,7 @@ extern "C" int salt_gpu_diag_ssw(uint32_t n_cases, const uint8_t *aware, const u
         n_cigar[i] = r.n_cigar;
         memcpy(cigars + (uint64_t)i * SALT_MAX_CIGAR_OPS, r.cigar, sizeof r.cigar);
     }
-    hipFree(d_ref); hipFree(d_pac); hipFree(d_codes); hipFree(d_offs); hipFree(d_req); hipFree(d_res); hipFree(d_scr); hipFree(d_ctl);
-    return SALT_OK;
+    return done(SALT_OK);
 }
 
 extern "C" int salt_gpu_buffer_alloc(int device, uint64_t bytes, void **dev_ptr)
@@ -1220,9 +1222,9 @@ extern "C" int salt_gpu_ws_queue_counts(salt_gpu_ws_t *ws, uint32_t out[8])
     if (!ws || !out) return fail(SALT_E_INVAL, "null argument");
     HIPCHK(hipSetDevice(ws->ix->device));
     HIPCHK(hipDeviceSynchronize());
-    uint32_t all[QCTL_WORDS];
-    HIPCHK(hipMemcpy(all, ws->d_qctl, sizeof all, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < 8; ++k) out[k] = all[QC(k)];
+    SeCtl c; HIPCHK(hipMemcpy(&c, ws->d_qctl, sizeof c, hipMemcpyDeviceToHost));
+    memset(out, 0, 32);
+    out[0] = c.light_queued; out[2] = c.gap_slots; out[5] = c.gap_items; out[6] = c.cigar_items; out[7] = c.cigar_head;
     return SALT_OK;
 }
 
@@ -1231,10 +1233,8 @@ extern "C" int salt_gpu_ws_heavy_reads(salt_gpu_ws_t *ws, uint32_t *ids, uint32_
     if (!ws || !n) return fail(SALT_E_INVAL, "null argument");
     HIPCHK(hipSetDevice(ws->ix->device));
     HIPCHK(hipDeviceSynchronize());
-    uint32_t ctl[1];
-    HIPCHK(hipMemcpy(ctl, ws->d_qctl + QC(0), 4, hipMemcpyDeviceToHost));
-    *n = ctl[0];
-    if (ids && cap) HIPCHK(hipMemcpy(ids, ws->d_queue, (uint64_t)(ctl[0] < cap ? ctl[0] : cap) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n, &ws->d_qctl->light_queued, 4, hipMemcpyDeviceToHost));
+    if (ids && cap) HIPCHK(hipMemcpy(ids, ws->d_queue, (uint64_t)(*n < cap ? *n : cap) * 4, hipMemcpyDeviceToHost));
     return SALT_OK;
 }
 
@@ -1269,7 +1269,7 @@ extern "C" int salt_gpu_ws_pe_overflow(salt_gpu_ws_t *ws, uint32_t *n)
     if (!ws->d_pctl) return SALT_OK;
     HIPCHK(hipSetDevice(ws->ix->device));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(n, ws->d_pctl + 4, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost));
     return SALT_OK;
 }
 
@@ -1280,7 +1280,8 @@ extern "C" int salt_gpu_ws_pe_counts(salt_gpu_ws_t *ws, uint32_t out[8])
     if (!ws->d_pctl) return SALT_OK;
     HIPCHK(hipSetDevice(ws->ix->device));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, ws->d_pctl, 32, hipMemcpyDeviceToHost));
+    PeCtl c; HIPCHK(hipMemcpy(&c, ws->d_pctl, sizeof c, hipMemcpyDeviceToHost));
+    out[0] = c.n_req; out[2] = c.n_cigar; out[3] = c.cigar_head; out[4] = c.overflow; out[5] = c.diag_cols; out[6] = c.diag_clk;
     return SALT_OK;
 }
 
@@ -1297,7 +1298,7 @@ static int pe_prepare(salt_gpu_ws_t *ws, uint32_t n_pairs, hipStream_t st)
         ws->pe_pairs_cap = n_pairs;
     }
     if (!ws->d_pctl) {
-        HIPCHK(hipMalloc((void **)&ws->d_pctl, 20 * 4));         // [0..7] see pe_resident_impl; [8..11] k_swtb's phase clocks (diagnostics build); [12..15] the queue heads of k_swf, k_swf1, k_swr, k_swtb, [16] k_swf1's request count
+        HIPCHK(hipMalloc((void **)&ws->d_pctl, sizeof(PeCtl)));
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, ws->ix->device));
         ws->sw_blocks = (uint32_t)prop.multiProcessorCount;             // CUs: k_sw runs up to SW_MAX_BLOCKS_PER_CU blocks on each
@@ -1315,7 +1316,7 @@ static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sa
     rc = align_resident_impl(ws, o, 2 * n_pairs, max_len, d_seqs, d_offs, d_results, st, 1);
     if (rc) return rc;
     hipEvent_t *ev = ws->n_timed == ti + 1 ? &ws->ev[(size_t)ti * EV_PER_CALL] : nullptr;      // the call above was timed: three more events
-    HIPCHK(hipMemsetAsync(ws->d_pctl, 0, 80, st));
+    HIPCHK(hipMemsetAsync(ws->d_pctl, 0, sizeof(PeCtl), st));
     launch_pair(n_pairs, pe->min_tlen, pe->max_tlen, (uint32_t)ws->ix->l_pac, static_cast<const uint32_t *>(d_offs), static_cast<salt_result_t *>(d_results),
                 ws->d_pairs, ws->d_req, ws->d_pctl, st);
     if (ev) HIPCHK(hipEventRecord(ev[8], st));
@@ -1335,16 +1336,16 @@ static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sa
         ws->sw_scr_bytes = need;
     }
     launch_sw(ws->ix->view, ws->ix->d_pac, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_req, ws->d_pctl, ws->d_swres,
-              ws->d_pctl + 12, ws->d_pctl + 4, ws->d_sw_scr, geom, max_len, st);   // pctl: requests, -, CIGAR items + head, overflow, (diagnostics); [12..15] the Smith-Waterman kernels' queue heads
+              ws->d_sw_scr, geom, max_len, st);
     if (ev) HIPCHK(hipEventRecord(ev[9], st));
     launch_pe_final(ws->ix->view, PackGeom::make(max_len), n_pairs, ws->d_pm, static_cast<salt_result_t *>(d_results), ws->d_pairs, ws->d_swres, ws->d_lvtab,
-                    ws->d_pcq, ws->d_pctl + 2, ws->heavy_blocks, st);
+                    ws->d_pcq, ws->d_pctl, ws->heavy_blocks, st);
     if (ev) { HIPCHK(hipEventRecord(ev[10], st)); ws->ev_pe[ti] = 1; }
 #ifdef SALT_DIAG
     if (getenv("SALT_GPU_TB_CLOCKS")) {
-        uint32_t c[16]; HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipMemcpy(c, ws->d_pctl, 64, hipMemcpyDeviceToHost));
-        if (c[11]) fprintf(stderr, "[k_swtb] %u tracebacks: operands %.1f us, band passes %.1f us, walk + write %.1f us each (s_memtime, 10 ns ticks)\n", c[11],
-                           c[8] / 100.0 / c[11], c[9] / 100.0 / c[11], c[10] / 100.0 / c[11]);
+        PeCtl c; HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipMemcpy(&c, ws->d_pctl, sizeof c, hipMemcpyDeviceToHost)); const uint32_t *t = c.tb_clk;
+        if (t[3]) fprintf(stderr, "[k_swtb] %u tracebacks: operands %.1f us, band passes %.1f us, walk + write %.1f us each (s_memtime, 10 ns ticks)\n", t[3],
+                          t[0] / 100.0 / t[3], t[1] / 100.0 / t[3], t[2] / 100.0 / t[3]);
     }
 #endif
     HIPCHK(hipGetLastError());

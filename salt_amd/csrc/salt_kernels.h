@@ -1,6 +1,7 @@
 // salt_amd/csrc/salt_kernels.h -- host-visible declarations of the kernel launchers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include "../../include/salt_gpu.h"
 #include "salt_device.h"
 
@@ -62,16 +63,40 @@ void launch_seed(const IndexView &ix, const SeedParams &sp, const uint32_t *tb, 
                  uint32_t walk_blocks, unsigned long long *ctr, hipStream_t st);
 size_t seed_wq_words(uint64_t items);
 uint32_t seed_wq_cnt_words();
+// The queues of the Smith-Waterman kernels and k_cigar.  All pulls of a launch on one counter are served one after the other (~14 ns each),
+// also when every puller asks for its first item at once, or finds the queue empty.  So the FIRST item of a puller is its own index (no
+// atomic), the counter hands out what lies behind those, and a puller looks at the counter (a plain load) before it adds to it.
+// n_first: items the static first round covers (pullers x step).  Returns the item index, >= n_items when there is none.
+__device__ __forceinline__ uint32_t sw_pull(uint32_t *head, const uint32_t step, const uint32_t n_first, const uint32_t n_items)
+{
+    if (n_first >= n_items || n_first + __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_items) return 0xFFFFFFFFu;
+    return n_first + atomicAdd(head, step);
+}
+// Control words of a single-end batch, a 128-byte line each: atomics on one line are served one after the other (~14 ns each) however
+// many waves issue them, and k_heavy's gapped reads push through three of these words.  Zeroed per batch.
+struct SeCtl {
+    alignas(128) uint32_t light_queued;     // reads k_light queued for k_heavy (k_queue_pack)
+    alignas(128) uint32_t gap_slots;        // gapped reads given a k_gap slot
+    alignas(128) uint32_t gap_items;        // k_gap items
+    alignas(128) uint32_t cigar_items;      // k_cigar items
+    alignas(128) uint32_t cigar_head;       // k_cigar's queue head
+    alignas(128) uint32_t pool_used;        // located rows in the gapped passes' pool
+    alignas(128) uint32_t ovq_count;        // reads in k_heavy's overflow queue
+    alignas(128) uint32_t ovq_head;         // its head
+};
+static_assert(sizeof(SeCtl) == 8 * 128 && alignof(SeCtl) == 128, "one control word per 128-byte line");
+// One range of k_heavy's queue, 256 bytes: the counter k_light's reads of that range are pushed through, and the heads k_heavy, k_gap and
+// k_gapfin pull the range's items from (pop_ranged), a 128-byte line apart from the counter.  QUEUE_RANGES of them, zeroed per batch.
+static const uint32_t QUEUE_RANGES = 64;
+struct QueueRange {
+    enum { HEAVY, GAP, GAPFIN };            // heads[]: k_heavy's, k_gap's, k_gapfin's
+    uint32_t push, pad0[31], heads[3], pad1[29];
+};
+static_assert(sizeof(QueueRange) == 256 && offsetof(QueueRange, push) == 0 && offsetof(QueueRange, heads) == 128, "k_light's counter, then the heads");
 void launch_light(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint8_t *seqs, const uint32_t *offs, const uint4 *sai_c,
-                  const uint4 *sai_r, salt_result_t *results, uint32_t *queue, uint32_t *qctl, uint32_t *qseg, uint32_t *qsub, unsigned long long *ctr, hipStream_t st);
+                  const uint4 *sai_r, salt_result_t *results, uint32_t *queue, SeCtl *ctl, uint32_t *qseg, QueueRange *ranges, unsigned long long *ctr, hipStream_t st);
 size_t queue_words(uint32_t max_reads);                      // d_queue: the flat queue, k_heavy's overflow queue, k_light's segments
-uint32_t queue_heads_offset();                              // k_heavy's queue heads inside the same array: word offset of head 0 (zeroed with the counters)
-uint32_t queue_sub_words();                                 // the segments' counters
-// Control word k of a workspace (qctl / GapBufs::gctl) lives at word QC(k): a cache line each.  Atomics on one line are served one after the
-// other (~14 ns each) however many waves issue them, and k_heavy's gapped reads push through three of these words.
-#define QC(k) ((k) * 32u)
-static const uint32_t QCTL_WORDS = 16 * 32;
-// Deferred gapped passes (k_heavy -> k_gap -> k_gapfin -> k_cigar), `cap` slots; gctl = the workspace's qctl
+// Deferred gapped passes (k_heavy -> k_gap -> k_gapfin -> k_cigar), `cap` slots; gctl = the workspace's control words
 struct GapBufs {
     uint32_t *gq;        // [cap] read index of the slot (0xFFFFFFFF: not used after all)
     uint32_t *gn;        // [cap][2] located rows per strand
@@ -80,15 +105,15 @@ struct GapBufs {
     uint8_t  *ge;        // [pool] their Landau-Vishkin distances (255 = none within the bound)
     uint32_t *gitems;    // k_gap items: (slot << 11) | (strand << 10) | chunk of 32 candidates
     uint32_t *cq;        // k_cigar items: (read << 3) | which (0 = the alignment, 1 + i = alternative hit i)
-    uint32_t *gctl;
+    SeCtl *gctl;
     uint32_t cap, pool, items_cap;
-    uint32_t *ovq;       // reads k_heavy's small shape could not finish (launch_heavy); count gctl[9], head gctl[10]
-    uint32_t *qheads;    // k_heavy's queue heads (launch_heavy): one per range of the queue, 256 bytes apart, zero at launch
+    uint32_t *ovq;       // reads k_heavy's small shape could not finish (launch_heavy)
+    QueueRange *ranges;  // k_heavy's queue ranges and their heads (launch_heavy)
 };
-GapBufs gap_bufs_layout(uint8_t *base, uint32_t cap, uint32_t *gctl, size_t *bytes);   // base = nullptr: size only
+GapBufs gap_bufs_layout(uint8_t *base, uint32_t cap, SeCtl *gctl, size_t *bytes);   // base = nullptr: size only
 void launch_heavy(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint4 *sai_c,
                   const uint4 *sai_r, salt_result_t *results, const uint32_t *queue, unsigned long long *ctr,
-                  uint32_t n_blocks, uint32_t gap_blocks, void *lvtab, const GapBufs &g, uint32_t *ovq, uint32_t *qheads, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st);
+                  uint32_t n_blocks, uint32_t gap_blocks, void *lvtab, const GapBufs &g, uint32_t *ovq, QueueRange *ranges, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st);
 size_t lv_table_bytes();                // per-block LV traceback table (global memory)
 
 // ---- paired end (salt_pe.hip) ----
@@ -108,19 +133,30 @@ struct PeSwReq { uint32_t start, end, mate; uint8_t strand, aware; uint16_t pad;
                                                                                             // aware: 0 plain, 1 SNP-aware, 2 polish matrix; pad bit 0: score only, bit 1: mate rescue (no CIGAR for spans under 20 bases)
 struct PeSwRes { int32_t score1, score2, ref_begin, ref_end, read_begin, read_end; uint32_t start, strand; uint16_t n_cigar, ok; uint16_t cigar[SALT_MAX_CIGAR_OPS]; };
 struct PePair { uint32_t req0; uint8_t n_req; uint8_t rescued[2]; uint8_t pad; };             // requests req0 .. req0+n_req-1, in the order tried
+// Control words of a paired-end batch, zeroed per batch.  The four Smith-Waterman queue heads share one line.
+struct PeCtl {
+    uint32_t n_req, unused1;          // Smith-Waterman requests (k_pair)
+    uint32_t n_cigar, cigar_head;     // k_cigar items of the mates k_pe_final leaves gapped, and their queue head
+    uint32_t overflow;                // rescues this build cannot finish as the reference would (launch_sw)
+    uint32_t diag_cols, diag_clk, unused7;      // diagnostics build: k_swf's phase clock or the column counts; k_swr's phase clock
+    uint32_t tb_clk[4];               // diagnostics build: k_swtb's phase clocks (operands, band passes, walk + write) and tracebacks
+    uint32_t sw_heads[4];             // the queue heads of k_swf, k_swf1, k_swr, k_swtb
+    uint32_t swf1_pending;            // the requests k_swf leaves to k_swf1
+};
+static_assert(offsetof(PeCtl, n_cigar) == 8 && offsetof(PeCtl, overflow) == 16 && offsetof(PeCtl, diag_cols) == 20 && offsetof(PeCtl, tb_clk) == 32 &&
+              offsetof(PeCtl, sw_heads) == 48 && offsetof(PeCtl, swf1_pending) == 64 && sizeof(PeCtl) == 68, "paired-end control words");
 void launch_pair(uint32_t n_pairs, uint32_t min_tlen, uint32_t max_tlen, uint32_t l_pac, const uint32_t *offs, salt_result_t *res,
-                 PePair *pairs, PeSwReq *req, uint32_t *pctl, hipStream_t st);
-// k_swf (+ k_swf1: forward pass: scores, end point), k_swr (reverse pass: begin point), k_swtb (banded traceback -> CIGAR); heads[0..3]: the
-// four kernels' queue heads, heads[4]: the number of requests k_swf leaves to k_swf1 (five words zeroed by the caller).
-// overflow: counts rescues this build cannot finish as the reference would (window beyond the scratch, band beyond SW_BAND_W, more than
-// SALT_MAX_CIGAR_OPS operations); the caller turns a non-zero count into an error instead of returning rows that differ from the reference's
-void launch_sw(const IndexView &ix, const uint8_t *pac, const uint8_t *seqs, const uint32_t *offs, const PeSwReq *req, const uint32_t *pctl,
-               PeSwRes *res, uint32_t *heads, uint32_t *overflow, uint8_t *scratch, SwGeom g, uint32_t max_len, hipStream_t st);
+                 PePair *pairs, PeSwReq *req, PeCtl *ctl, hipStream_t st);
+// k_swf (+ k_swf1: forward pass: scores, end point), k_swr (reverse pass: begin point), k_swtb (banded traceback -> CIGAR) on ctl->n_req
+// requests.  ctl->overflow: rescues this build cannot finish as the reference would (window beyond the scratch, band beyond SW_BAND_W, more
+// than SALT_MAX_CIGAR_OPS operations); the caller turns it into an error instead of returning rows that differ from the reference's
+void launch_sw(const IndexView &ix, const uint8_t *pac, const uint8_t *seqs, const uint32_t *offs, const PeSwReq *req, PeCtl *ctl,
+               PeSwRes *res, uint8_t *scratch, SwGeom g, uint32_t max_len, hipStream_t st);
 static const uint32_t SW_MAX_BLOCKS_PER_CU = 16;   // one-wave blocks per CU at most
 static const uint64_t SW_SCRATCH_TOTAL = 2ull << 30;   // k_swtb's grid shrinks before its groups' global scratch passes 2 GiB
 uint32_t sw_blocks_per_cu(uint32_t max_len);
 void launch_pe_final(const IndexView &ix, const PackGeom &pg, uint32_t n_pairs, const uint32_t *pm, salt_result_t *res, const PePair *pairs,
-                     const PeSwRes *sw, void *lvtab, uint32_t *citems, uint32_t *cctl, uint32_t n_blocks, hipStream_t st);   // cctl[0] count, cctl[1] head
+                     const PeSwRes *sw, void *lvtab, uint32_t *citems, PeCtl *ctl, uint32_t n_blocks, hipStream_t st);
 
 uint32_t heavy_blocks_per_cu();
 void launch_polish(const uint8_t *pac, const uint8_t *codes, const uint32_t *offs, const salt_polish_item_t *items, uint32_t n_items, const uint8_t *pool,

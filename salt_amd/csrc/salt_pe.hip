@@ -57,6 +57,23 @@ __host__ __device__ __forceinline__ uint32_t sw_lds_words_at(uint32_t seg, uint3
     const uint32_t rd = (8u * seg + 15u) & ~15u;
     return variant ? (fwd ? 2u : 1u) * (8u * rd + 8u * variant * 8u * 2u) : 8u * (4u * seg * 16u + rd);
 }
+// group grp's views in k_swf1's / k_swr's LDS: the stripe rows and the read (LDS variant, SEG = 0), or the read and the H-at-best rows
+template <int SEG>
+__device__ __forceinline__ SwLds sw_group_lds(uint8_t *lds, uint32_t grp, uint32_t seg)
+{
+    SwLds s;
+    if (SEG == 0) {
+        uint8_t *base = lds + (size_t)grp * sw_group_bytes(seg);
+        s.H[0] = reinterpret_cast<short *>(base); s.H[1] = s.H[0] + seg * 8; s.E = s.H[1] + seg * 8; s.Hmax = s.E + seg * 8;
+        s.read = reinterpret_cast<uint8_t *>(s.Hmax + seg * 8);
+    } else {
+        const uint32_t rd = (8u * seg + 15u) & ~15u;
+        s.H[0] = s.H[1] = s.E = nullptr;
+        s.read = lds + (size_t)grp * rd;
+        s.Hmax = reinterpret_cast<short *>(lds + 8u * rd) + (size_t)grp * (SEG ? SEG : 1) * 8;
+    }
+    return s;
+}
 
 
 __device__ __forceinline__ uint32_t ref_symbol(const IndexView &ix, const uint8_t *pac, int aware, uint32_t p)
@@ -346,15 +363,23 @@ __device__ __forceinline__ uint32_t dpp_pk_max8(uint32_t x)
     t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true); x = pk_max(x, t);
     t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xF, 0xF, true); return pk_max(x, t);
 }
-// The queues of the Smith-Waterman kernels.  All pulls of a launch on one counter are served one after the other (~14 ns each): when
-// every group of the device asks for its first item at the same moment the last one has waited a third of a millisecond, and again when
-// they all come back to find the queue empty.  So the FIRST item of a puller is its own index (no atomic), the counter hands out what
-// lies behind those, and a puller looks at the counter before it adds to it (the look is a plain load: no queue).
-// n_first: items the static first round covers (pullers x step).  Returns the item index, >= n_items when there is none.
-__device__ __forceinline__ uint32_t sw_pull(uint32_t *head, const uint32_t step, const uint32_t n_first, const uint32_t n_items)
+// The request loop of k_swf1, k_swr and k_swtb: the wave pulls eight requests at a time (its own index first, sw_pull), request
+// base + g to its 8-lane group g, body(it) runs in every group whose request exists, and the loop ends for the whole wave at once: a
+// group never leaves on its own.  (Groups pulling one request each and leaving one by one is the shape this loop first had; with hipcc
+// 7.2 k_swr then never finished once the traceback had moved out of it -- tools/dbg/sw_hang.hip reproduces that.)
+template <class Body>
+__device__ __forceinline__ void sw_for_requests(uint32_t *head, const uint32_t n_req, Body body)
 {
-    if (n_first >= n_items || n_first + __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_items) return 0xFFFFFFFFu;
-    return n_first + atomicAdd(head, step);
+    bool first = true;
+    for (;;) {
+        uint32_t base = 8u * blockIdx.x;
+        if (!first && threadIdx.x == 0) base = sw_pull(head, 8u, 8u * gridDim.x, n_req);
+        first = false;
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (base >= n_req) break;
+        const uint32_t it = base + (threadIdx.x >> 3);
+        if (it < n_req) body(it);
+    }
 }
 template <int SEG> struct Fwd2 {                                 // a pair's forward pass between two columns
     uint32_t H[SEG], E[SEG], shp[(SEG + 2) / 3];                 // shp: per stripe the 5-bit profile shifts of A and of B, three stripes per register
@@ -718,15 +743,15 @@ __device__ __forceinline__ void sw_fwd_row(PeSwRes *o, const PeSwReq &rq, bool f
 // waits for the longest window of its wave, and the last pairs of the queue spread over all SIMDs.  (Wave-sized pulls of 16 requests
 // left 2.9 wave-tasks per SIMD at 46 783 requests: SIMDs with four of them ran twice as long as those with two.)  The two requests of a
 // pair may differ in scoring (a singleton's plain rescue next to a SNP-aware one).  A pair that cannot take the packed path -- another
-// read length than request 0's, a window beyond the scratch -- leaves with ok = 3 for k_swf1.  The loop ends for the whole wave at once, when no group has work left (a uniform exit: see k_swr).
+// read length than request 0's, a window beyond the scratch -- leaves with ok = 3 for k_swf1.  The loop ends for the whole wave at once, when no group has work left (a uniform exit: see sw_for_requests).
 #ifndef SALT_SWF_WAVES
 #define SALT_SWF_WAVES 3          // 168 registers: the pair's rows, shifts and streams without spills (at 128 the packed shifts went to scratch and back every column)
 #endif
 template <int SEG>                     // stripe rows in registers, segLen <= SEG
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((SEG == 13 || SEG == 19) ? SALT_SWF_WAVES : 1, (SEG == 13 || SEG == 19) ? SALT_SWF_WAVES : 8)))
 k_swf(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
-      const PeSwReq *__restrict__ req, const uint32_t *__restrict__ pctl, PeSwRes *__restrict__ res, uint32_t *__restrict__ head,
-      uint32_t *__restrict__ overflow, uint8_t *__restrict__ scratch, uint32_t maxcol_bytes, uint32_t seg, int dbg_arg)
+      const PeSwReq *__restrict__ req, PeCtl *__restrict__ ctl, PeSwRes *__restrict__ res, uint8_t *__restrict__ scratch, uint32_t maxcol_bytes,
+      uint32_t seg, int dbg_arg)
 {
     const int dbg = SALT_DIAG_VAL(dbg_arg);                      // diagnostics build only: 2 = phase clocks, 4 = column counts, 32 / 128 = everything to k_swf1
     extern __shared__ __attribute__((aligned(16))) uint8_t sw_lds[];
@@ -735,7 +760,7 @@ k_swf(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
     uint8_t *readA = sw_lds + (size_t)grp * 2u * rd, *readB = readA + rd;
     short *hmA = reinterpret_cast<short *>(sw_lds + 16u * rd) + (size_t)grp * 2u * SEG * 8, *hmB = hmA + SEG * 8;      // 2 x [SEG][8] per group, behind the reads
     uint32_t *lw = reinterpret_cast<uint32_t *>(sw_lds + sw_lds_words_at(seg, SEG, true)) + grp * 16u;                   // 2 x 8 window words per group
-    const uint32_t n_req = pctl[0];
+    const uint32_t n_req = ctl->n_req;
     if (n_req == 0) return;
     uint16_t *mcA = reinterpret_cast<uint16_t *>(scratch + ((size_t)blockIdx.x * 8 + grp) * 2u * maxcol_bytes);
     uint16_t *mcB = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(mcA) + maxcol_bytes);
@@ -752,7 +777,7 @@ k_swf(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
     for (;;) {
         if (idle && !done) {                                        // the group's next pair (sw_pull: its own index first)
             uint32_t t = 2u * (blockIdx.x * 8u + grp);
-            if (!first && lane == 0) t = sw_pull(head, 2u, 2u * 8u * gridDim.x, n_req);
+            if (!first && lane == 0) t = sw_pull(&ctl->sw_heads[0], 2u, 2u * 8u * gridDim.x, n_req);
             first = false;
             it0 = (uint32_t)__shfl((int)t, 0, 8);
             if (it0 >= n_req) done = true;
@@ -765,7 +790,7 @@ k_swf(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
                 const bool fits1 = rq1.start < ix.ref_len && refLenB > 0 && (uint64_t)refLenB * 2u <= maxcol_bytes;
                 // (the odd last request runs as a pair with itself)
                 if (!(shape_ok && fits0 && fits1 && L0 == Lref && L1 == Lref)) {
-                    if (lane == 0) { res[it0].ok = 3; if (two) res[it0 + 1].ok = 3; atomicAdd(head + 4, two ? 2u : 1u); }      // forward pass pending (head[4]: how many)
+                    if (lane == 0) { res[it0].ok = 3; if (two) res[it0 + 1].ok = 3; atomicAdd(&ctl->swf1_pending, two ? 2u : 1u); }      // forward pass pending
                 } else {
                     if (dbg & 2) t0 = __builtin_amdgcn_s_memtime();
                     sw_load_read(seqs, off0, Lref, rq0.strand, readA, lane); sw_load_read(seqs, off1, Lref, rq1.strand, readB, lane);
@@ -790,8 +815,8 @@ k_swf(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
                 sw_fwd_row(res + it0, rq0, true, refLenA, Lref, mcA, f.maxA, f.erA, edA, lane);
                 if (two) sw_fwd_row(res + it0 + 1, rq1, true, refLenB, Lref, mcB, f.maxB, f.erB, edB, lane);
                 if (lane == 0) {
-                    if (dbg & 2) atomicAdd(overflow + 1, (uint32_t)(__builtin_amdgcn_s_memtime() - t0));       // phase clock
-                    if (dbg & 4) atomicAdd(overflow + 1, (uint32_t)nCols);
+                    if (dbg & 2) atomicAdd(&ctl->diag_cols, (uint32_t)(__builtin_amdgcn_s_memtime() - t0));       // phase clock
+                    if (dbg & 4) atomicAdd(&ctl->diag_cols, (uint32_t)nCols);
                 }
                 idle = true;
             }
@@ -804,43 +829,25 @@ k_swf(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
 template <int SEG>                     // 0: stripe rows in LDS (any read length); > 0: in registers, segLen <= SEG
 __global__ void __launch_bounds__(64) SALT_SW_WAVES(SEG)
 k_swf1(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
-       const PeSwReq *__restrict__ req, const uint32_t *__restrict__ pctl, PeSwRes *__restrict__ res, uint32_t *__restrict__ head,
-       uint32_t *__restrict__ overflow, uint8_t *__restrict__ scratch, uint32_t maxcol_bytes, uint32_t seg, int all, int dbg_arg)
+       const PeSwReq *__restrict__ req, PeCtl *__restrict__ ctl, PeSwRes *__restrict__ res, uint8_t *__restrict__ scratch, uint32_t maxcol_bytes,
+       uint32_t seg, int all, int dbg_arg)
 {
     const int dbg = SALT_DIAG_VAL(dbg_arg);                      // diagnostics build only: 4 = column counts, 32 = no pass
     extern __shared__ __attribute__((aligned(16))) uint8_t sw_lds[];
     const uint32_t grp = threadIdx.x >> 3, lane = threadIdx.x & 7u;
-    SwLds s;
-    if (SEG == 0) {
-        uint8_t *base = sw_lds + (size_t)grp * sw_group_bytes(seg);
-        s.H[0] = reinterpret_cast<short *>(base); s.H[1] = s.H[0] + seg * 8; s.E = s.H[1] + seg * 8; s.Hmax = s.E + seg * 8;
-        s.read = reinterpret_cast<uint8_t *>(s.Hmax + seg * 8);
-    } else {
-        const uint32_t rd = (8u * seg + 15u) & ~15u;
-        s.H[0] = s.H[1] = s.E = nullptr;
-        s.read = sw_lds + (size_t)grp * rd;
-        s.Hmax = reinterpret_cast<short *>(sw_lds + 8u * rd) + (size_t)grp * (SEG ? SEG : 1) * 8;
-    }
+    SwLds s = sw_group_lds<SEG>(sw_lds, grp, seg);
     uint32_t *lw = reinterpret_cast<uint32_t *>(sw_lds + sw_lds_words_at(seg, SEG, false)) + grp * 8u;
-    const uint32_t n_req = pctl[0];
-    if (!all && head[3] == 0) return;                              // (head[3]: the requests k_swf left pending, behind the four queue heads)
+    const uint32_t n_req = ctl->n_req;
+    if (!all && ctl->swf1_pending == 0) return;
     uint16_t *maxColumn = reinterpret_cast<uint16_t *>(scratch + ((size_t)blockIdx.x * 8 + grp) * 2u * maxcol_bytes);
-    bool first = true;
-    for (;;) {                                                       // eight requests per pull, a uniform exit (see k_swr)
-        uint32_t base = 8u * blockIdx.x;
-        if (!first && threadIdx.x == 0) base = sw_pull(head, 8u, 8u * gridDim.x, n_req);
-        first = false;
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (base >= n_req) break;
-        const uint32_t it = base + grp;
-        if (it >= n_req) continue;
-        if (!all && res[it].ok != 3) continue;
+    sw_for_requests(&ctl->sw_heads[1], n_req, [&](const uint32_t it) {
+        if (!all && res[it].ok != 3) return;
         const PeSwReq rq = req[it];
         const uint32_t off = offs[rq.mate], L = offs[rq.mate + 1] - off;
         const int refLen = (int)(rq.end - rq.start + 1);
         const bool sane = rq.start < ix.ref_len && refLen > 0;
         const bool fits = sane && (uint64_t)refLen * 2u <= maxcol_bytes && L <= seg * 8u && !(dbg & 32);
-        if (lane == 0 && sane && !fits && !(dbg & 32)) atomicAdd(overflow, 1u);
+        if (lane == 0 && sane && !fits && !(dbg & 32)) atomicAdd(&ctl->overflow, 1u);
         int m = 0, er = 0, ed = 0;
         if (fits) {
             sw_load_read(seqs, off, L, rq.strand, s.read, lane);
@@ -848,52 +855,29 @@ k_swf1(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict_
             auto fwd = [&](int q) -> uint32_t { return rdp[q]; };
             if (SEG == 0) sw_word_pass(ix, pac, (int)rq.aware, s, rq.start, 0, refLen, (int)L, fwd, 0xFFFF, maxColumn, m, er, ed);
             else sw_word_pass_reg<(SEG ? SEG : 1)>(ix, pac, (int)rq.aware, rq.start, 0, refLen, (int)L, fwd, 0xFFFF, maxColumn, s.Hmax, lw, m, er, ed,
-                                                   (dbg & 4) ? overflow + 1 : nullptr);
+                                                   (dbg & 4) ? &ctl->diag_cols : nullptr);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
         sw_fwd_row(res + it, rq, fits, refLen, L, maxColumn, m, er, ed, lane);
-    }
+    });
 }
 
-// k_swr: the reverse pass from the end point of every request k_swf / k_swf1 left with ok = 1, eight requests per wave in step.  (One
-// request per group pulled inside the column loop, as k_swf does for its pairs, took 0.77 ms against 0.58 ms here: a reverse pass is
-// ~120 columns, and every group's start -- request, row, offsets, bases: four dependent loads -- holds up its whole wave.)
-// The wave pulls eight requests at a time, one per group, and leaves as a whole (a uniform exit): groups that drew a number past the end
-// sit the round out.  (Groups pulling one request each and leaving one by one is the shape this loop first had; with hipcc 7.2 the kernel
-// then never finished once the traceback had moved out of it -- tools/dbg/sw_hang.hip reproduces that -- so the exit is kept uniform.)
+// k_swr: the reverse pass from the end point of every request k_swf / k_swf1 left with ok = 1, eight requests per wave in step
+// (sw_for_requests).  (One request per group pulled inside the column loop, as k_swf does for its pairs, took 0.77 ms against 0.58 ms
+// here: a reverse pass is ~120 columns, and every group's start -- request, row, offsets, bases: four dependent loads -- holds up its wave.)
 template <int SEG>
 __global__ void __launch_bounds__(64) SALT_SW_WAVES(SEG)
 k_swr(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
-      const PeSwReq *__restrict__ req, const uint32_t *__restrict__ pctl, PeSwRes *__restrict__ res, uint32_t *__restrict__ head,
-      uint32_t *__restrict__ overflow, uint32_t seg, int dbg_arg)
+      const PeSwReq *__restrict__ req, PeCtl *__restrict__ ctl, PeSwRes *__restrict__ res, uint32_t seg, int dbg_arg)
 {
     const int dbg = SALT_DIAG_VAL(dbg_arg);                      // diagnostics build only: 2 = phase clocks, 8 = column counts, 16 = no pass
     extern __shared__ __attribute__((aligned(16))) uint8_t sw_lds[];
     const uint32_t grp = threadIdx.x >> 3, lane = threadIdx.x & 7u;
-    SwLds s;
-    if (SEG == 0) {
-        uint8_t *base = sw_lds + (size_t)grp * sw_group_bytes(seg);
-        s.H[0] = reinterpret_cast<short *>(base); s.H[1] = s.H[0] + seg * 8; s.E = s.H[1] + seg * 8; s.Hmax = s.E + seg * 8;
-        s.read = reinterpret_cast<uint8_t *>(s.Hmax + seg * 8);
-    } else {
-        const uint32_t rd = (8u * seg + 15u) & ~15u;
-        s.H[0] = s.H[1] = s.E = nullptr;
-        s.read = sw_lds + (size_t)grp * rd;
-        s.Hmax = reinterpret_cast<short *>(sw_lds + 8u * rd) + (size_t)grp * (SEG ? SEG : 1) * 8;
-    }
+    SwLds s = sw_group_lds<SEG>(sw_lds, grp, seg);
     uint32_t *lw = reinterpret_cast<uint32_t *>(sw_lds + sw_lds_words_at(seg, SEG, false)) + grp * 8u;
-    const uint32_t n_req = pctl[0];
-    bool first = true;
-    for (;;) {
-        uint32_t base = 8u * blockIdx.x;
-        if (!first && threadIdx.x == 0) base = sw_pull(head, 8u, 8u * gridDim.x, n_req);
-        first = false;
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (base >= n_req) break;
-        const uint32_t it = base + grp;
-        if (it >= n_req) continue;
+    sw_for_requests(&ctl->sw_heads[2], ctl->n_req, [&](const uint32_t it) {
         PeSwRes *o = res + it;
-        if (o->ok != 1 || (dbg & 16)) continue;
+        if (o->ok != 1 || (dbg & 16)) return;
         const PeSwReq rq = req[it];
         const uint32_t off = offs[rq.mate], L = offs[rq.mate + 1] - off;
         const int max1 = o->score1, end_ref1 = o->ref_end, end_read1 = o->read_end;
@@ -904,13 +888,13 @@ k_swr(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
         auto rev = [&](int q) -> uint32_t { return rdp[end_read1 - q]; };
         if (SEG == 0) sw_word_pass(ix, pac, (int)rq.aware, s, rq.start, 1, end_ref1 + 1, end_read1 + 1, rev, max1, (uint16_t *)nullptr, max2, beg_ref, beg_read_rev);
         else sw_word_pass_reg<(SEG ? SEG : 1)>(ix, pac, (int)rq.aware, rq.start, 1, end_ref1 + 1, end_read1 + 1, rev, max1, (uint16_t *)nullptr, s.Hmax, lw,
-                                               max2, beg_ref, beg_read_rev, (dbg & 8) ? overflow + 1 : nullptr);
+                                               max2, beg_ref, beg_read_rev, (dbg & 8) ? &ctl->diag_cols : nullptr);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
         if (lane == 0) {
             o->ref_begin = beg_ref; o->read_begin = end_read1 - beg_read_rev; o->ok = 2;      // the banded traceback is k_swtb's
-            if (dbg & 2) atomicAdd(overflow + 2, (uint32_t)(__builtin_amdgcn_s_memtime() - t0));
+            if (dbg & 2) atomicAdd(&ctl->diag_clk, (uint32_t)(__builtin_amdgcn_s_memtime() - t0));
         }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -918,8 +902,8 @@ k_swr(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
 k_swtb(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
-       const PeSwReq *__restrict__ req, const uint32_t *__restrict__ pctl, PeSwRes *__restrict__ res, uint32_t *__restrict__ head,
-       uint32_t *__restrict__ overflow, uint8_t *__restrict__ scratch, uint32_t group_bytes, TbGeom tg, int dbg_arg)
+       const PeSwReq *__restrict__ req, PeCtl *__restrict__ ctl, PeSwRes *__restrict__ res, uint8_t *__restrict__ scratch, uint32_t group_bytes,
+       TbGeom tg, int dbg_arg)
 {
     const int dbg_max_bw = SALT_DIAG_VAL(dbg_arg);               // diagnostics build only: bands wider than (low 16 bits) count as overflow; bit 16: phase clocks
     extern __shared__ __attribute__((aligned(16))) uint8_t tb_lds[];
@@ -931,27 +915,18 @@ k_swtb(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict_
     int32_t *const grows = reinterpret_cast<int32_t *>(my);
     uint8_t *const gdir = my + 3u * SW_BAND_W * 4u;
     const uint64_t gdir_cap = group_bytes > 3u * SW_BAND_W * 4u ? group_bytes - 3u * SW_BAND_W * 4u : 0u;
-    const uint32_t n_req = pctl[0];
-    bool first = true;
-    for (;;) {                                                       // eight requests per pull, a uniform exit (see k_swr)
-        uint32_t base = 8u * blockIdx.x;
-        if (!first && threadIdx.x == 0) base = sw_pull(head, 8u, 8u * gridDim.x, n_req);
-        first = false;
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (base >= n_req) break;
-        const uint32_t it = base + grp;
-        if (it >= n_req) continue;
+    sw_for_requests(&ctl->sw_heads[3], ctl->n_req, [&](const uint32_t it) {
         PeSwRes *o = res + it;
-        if (o->ok != 2) continue;
+        if (o->ok != 2) return;
         const PeSwReq rq = req[it];
         const int ref_begin = o->ref_begin, ref_end = o->ref_end, read_begin = o->read_begin, read_end = o->read_end, score = o->score1;
         const int rfl = ref_end - ref_begin + 1, rdl = read_end - read_begin + 1, aware = rq.aware;
         const uint32_t off = offs[rq.mate], L = offs[rq.mate + 1] - off;
         int n_cig = 0;
-        const bool clk = (dbg_max_bw & 0x10000) != 0;                 // diagnostics build: s_memtime ticks per phase into overflow[4..7]
+        const bool clk = (dbg_max_bw & 0x10000) != 0;                 // diagnostics build: s_memtime ticks per phase into ctl->tb_clk
         const unsigned long long c0 = clk ? __builtin_amdgcn_s_memtime() : 0ull;
         unsigned long long c1 = c0, c2 = c0;
-        if ((rq.pad & 2u) && rdl < 20) { if (lane == 0) { o->n_cigar = 0; o->ok = 0; } continue; }    // a mate rescue (pad bit 1): alnpe.c:297 turns it down whatever its CIGAR
+        if ((rq.pad & 2u) && rdl < 20) { if (lane == 0) { o->n_cigar = 0; o->ok = 0; } return; }    // a mate rescue (pad bit 1): alnpe.c:297 turns it down whatever its CIGAR
         if (rfl > 0 && rdl > 0 && (uint32_t)rdl <= tg.read_b) {
             const uint32_t ref0 = rq.start + (uint32_t)ref_begin;
             // the aligned part of the mate on the requested strand and the alignment's reference symbols: 64 per trip and group (eight loads
@@ -1009,15 +984,15 @@ k_swtb(IndexView ix, const uint8_t *__restrict__ pac, const uint8_t *__restrict_
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
         } else if (rfl > 0 && rdl > 0) n_cig = -1;
         if (lane == 0) {
-            if (n_cig < 0) { atomicAdd(overflow, 1u); n_cig = 0; }
+            if (n_cig < 0) { atomicAdd(&ctl->overflow, 1u); n_cig = 0; }
             o->n_cigar = (uint16_t)n_cig;
             o->ok = (uint16_t)((n_cig > 0 && rdl >= 20) ? 1 : 0);      // alnpe.c:297 (filters = 0, filterd = 20)
             if (clk) {
                 const unsigned long long c3 = __builtin_amdgcn_s_memtime();
-                atomicAdd(overflow + 4, (uint32_t)(c1 - c0)); atomicAdd(overflow + 5, (uint32_t)(c2 - c1)); atomicAdd(overflow + 6, (uint32_t)(c3 - c2)); atomicAdd(overflow + 7, 1u);
+                atomicAdd(&ctl->tb_clk[0], (uint32_t)(c1 - c0)); atomicAdd(&ctl->tb_clk[1], (uint32_t)(c2 - c1)); atomicAdd(&ctl->tb_clk[2], (uint32_t)(c3 - c2)); atomicAdd(&ctl->tb_clk[3], 1u);
             }
         }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1032,7 +1007,7 @@ __device__ __forceinline__ int in_range(uint32_t a, uint32_t b, uint32_t small, 
 
 __global__ void __launch_bounds__(256)
 k_pair(uint32_t n_pairs, uint32_t min_tlen, uint32_t max_tlen, uint32_t l_pac, const uint32_t *__restrict__ offs,
-       salt_result_t *__restrict__ res, PePair *__restrict__ pairs, PeSwReq *__restrict__ req, uint32_t *__restrict__ pctl)
+       salt_result_t *__restrict__ res, PePair *__restrict__ pairs, PeSwReq *__restrict__ req, PeCtl *__restrict__ ctl)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_pairs) return;
@@ -1085,7 +1060,7 @@ k_pair(uint32_t n_pairs, uint32_t min_tlen, uint32_t max_tlen, uint32_t l_pac, c
         }
     }
     if (nr) {
-        const uint32_t base = atomicAdd(&pctl[0], (uint32_t)nr);
+        const uint32_t base = atomicAdd(&ctl->n_req, (uint32_t)nr);
         pr.n_req = (uint8_t)nr; pr.req0 = base;
         for (int k = 0; k < nr; ++k) { PeSwReq r; r.start = st[k]; r.end = en[k]; r.mate = 2 * p + who[k]; r.strand = str[k]; r.aware = aw[k]; r.pad = 2; req[base + k] = r; pr.rescued[k] = who[k]; }
     }
@@ -1093,9 +1068,9 @@ k_pair(uint32_t n_pairs, uint32_t min_tlen, uint32_t max_tlen, uint32_t l_pac, c
 }
 
 void launch_pair(uint32_t n_pairs, uint32_t min_tlen, uint32_t max_tlen, uint32_t l_pac, const uint32_t *offs, salt_result_t *res,
-                 PePair *pairs, PeSwReq *req, uint32_t *pctl, hipStream_t st)
+                 PePair *pairs, PeSwReq *req, PeCtl *ctl, hipStream_t st)
 {
-    if (n_pairs) hipLaunchKernelGGL(k_pair, dim3((n_pairs + 255) / 256), dim3(256), 0, st, n_pairs, min_tlen, max_tlen, l_pac, offs, res, pairs, req, pctl);
+    if (n_pairs) hipLaunchKernelGGL(k_pair, dim3((n_pairs + 255) / 256), dim3(256), 0, st, n_pairs, min_tlen, max_tlen, l_pac, offs, res, pairs, req, ctl);
 }
 
 // stripe rows in registers for reads up to 256 bases (13 / 19 / 32 stripes of 8), in LDS beyond
@@ -1157,8 +1132,8 @@ SwGeom sw_geom(uint32_t max_len, uint64_t max_window, uint32_t cus)
 void sw_geom_limit(SwGeom &g, uint32_t blocks) { if (blocks < 1) blocks = 1; if (g.n_blocks > blocks) g.n_blocks = blocks; if (g.tb_blocks > blocks) g.tb_blocks = blocks; }
 uint64_t sw_scratch_bytes(const SwGeom &g) { return (uint64_t)g.n_blocks * 16 * g.maxcol_bytes + (uint64_t)g.tb_blocks * 8 * g.tb_group_bytes; }
 
-void launch_sw(const IndexView &ix, const uint8_t *pac, const uint8_t *seqs, const uint32_t *offs, const PeSwReq *req, const uint32_t *pctl,
-               PeSwRes *res, uint32_t *heads, uint32_t *overflow, uint8_t *scratch, SwGeom g, uint32_t max_len, hipStream_t st)
+void launch_sw(const IndexView &ix, const uint8_t *pac, const uint8_t *seqs, const uint32_t *offs, const PeSwReq *req, PeCtl *ctl,
+               PeSwRes *res, uint8_t *scratch, SwGeom g, uint32_t max_len, hipStream_t st)
 {
     const uint32_t seg = (max_len + 7) / 8;
 #ifdef SALT_DIAG
@@ -1166,14 +1141,12 @@ void launch_sw(const IndexView &ix, const uint8_t *pac, const uint8_t *seqs, con
 #else
     const int dbg = 0;
 #endif
-    // heads[0..3]: the queue heads of k_swf, k_swf1, k_swr, k_swtb; heads[4]: the requests k_swf left to k_swf1
 #define SALT_LAUNCH_SW(V, ALL) do { \
-        hipLaunchKernelGGL(k_swf1<V>, dim3(g.n_blocks), dim3(64), sw_lds_bytes(max_len, false), st, ix, pac, seqs, offs, req, pctl, res, heads + 1, \
-                           overflow, scratch, g.maxcol_bytes, seg, ALL, dbg); \
-        hipLaunchKernelGGL(k_swr<V>, dim3(g.n_blocks), dim3(64), sw_lds_bytes(max_len, false), st, ix, pac, seqs, offs, req, pctl, res, heads + 2, \
-                           overflow, seg, dbg); } while (0)
-#define SALT_LAUNCH_SWF(V) hipLaunchKernelGGL(k_swf<V>, dim3(g.n_blocks), dim3(64), sw_lds_bytes(max_len, true), st, ix, pac, seqs, offs, req, pctl, res, heads, \
-                                              overflow, scratch, g.maxcol_bytes, seg, dbg)
+        hipLaunchKernelGGL(k_swf1<V>, dim3(g.n_blocks), dim3(64), sw_lds_bytes(max_len, false), st, ix, pac, seqs, offs, req, ctl, res, \
+                           scratch, g.maxcol_bytes, seg, ALL, dbg); \
+        hipLaunchKernelGGL(k_swr<V>, dim3(g.n_blocks), dim3(64), sw_lds_bytes(max_len, false), st, ix, pac, seqs, offs, req, ctl, res, seg, dbg); } while (0)
+#define SALT_LAUNCH_SWF(V) hipLaunchKernelGGL(k_swf<V>, dim3(g.n_blocks), dim3(64), sw_lds_bytes(max_len, true), st, ix, pac, seqs, offs, req, ctl, res, \
+                                              scratch, g.maxcol_bytes, seg, dbg)
     switch (sw_seg_variant(max_len)) {
     case 13: SALT_LAUNCH_SWF(13); SALT_LAUNCH_SW(13, 0); break;
     case 19: SALT_LAUNCH_SWF(19); SALT_LAUNCH_SW(19, 0); break;
@@ -1189,7 +1162,7 @@ void launch_sw(const IndexView &ix, const uint8_t *pac, const uint8_t *seqs, con
     if (getenv("SALT_GPU_TB_MAXBW")) tb_dbg = atoi(getenv("SALT_GPU_TB_MAXBW"));
     if (getenv("SALT_GPU_TB_CLOCKS")) tb_dbg |= 0x10000;
 #endif
-    hipLaunchKernelGGL(k_swtb, dim3(g.tb_blocks), dim3(64), 8u * tg.group_b, st, ix, pac, seqs, offs, req, pctl, res, heads + 3, overflow,
+    hipLaunchKernelGGL(k_swtb, dim3(g.tb_blocks), dim3(64), 8u * tg.group_b, st, ix, pac, seqs, offs, req, ctl, res,
                        scratch + (uint64_t)g.n_blocks * 16 * g.maxcol_bytes, g.tb_group_bytes, tg, tb_dbg);
 }
 
