@@ -262,7 +262,9 @@ int  salt_gpu_diag_lv(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_ca
 /* Unit entry of the Smith-Waterman mate-rescue kernel (ssw_init + ssw_align as snpaln_sw[_snpaware] call them,
  * alnpe.c:260-393; ssw.c): case i aligns codes[read_offs[i]..read_offs[i+1]) against reference symbols
  * ref_syms[ref_offs[i]..ref_offs[i+1]) -- 4-bit allele masks when aware[i], bases 0..3 otherwise.
- * out6[6i..]: score1, score2, ref_begin1, ref_end1, read_begin1, read_end1; cigars[i][SALT_MAX_CIGAR_OPS], n_cigar[i]. */
+ * out6[6i..]: score1, score2, ref_begin1, ref_end1, read_begin1, read_end1; cigars[i][SALT_MAX_CIGAR_OPS], n_cigar[i].
+ * Cases whose CIGAR needs more than SALT_MAX_CIGAR_OPS operations (or a band beyond the build's) keep their six numbers, get
+ * n_cigar 0, and make the call return SALT_E_CAPACITY after every row is written. */
 int  salt_gpu_diag_ssw(uint32_t n_cases, const uint8_t *aware, const uint8_t *ref_syms, const uint32_t *ref_offs,
                        const uint8_t *codes, const uint32_t *read_offs, int32_t *out6, uint16_t *cigars, uint16_t *n_cigar);
 

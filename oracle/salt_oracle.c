@@ -1321,7 +1321,7 @@ lazy_done:
 
 /* banded_sw (ssw.c:549-727): returns ops (len<<4|op) in out, count as return value (0 on traceback error) */
 static int ssw_banded(const int8_t *ref, const int8_t *read, int refLen, int readLen, int score, int go, int ge, int band_width,
-                      const int8_t *mat, int n, uint32_t *out, int out_cap)
+                      const int8_t *mat, int n, uint32_t *out, int out_cap, int *bw_out)
 {
 #define SET_U(u, w, i, j) { int x_ = (i) - (w); x_ = x_ > 0 ? x_ : 0; (u) = (j) - x_ + 1; }
 #define SET_D(u, w, i, j, p) { int x_ = (i) - (w); x_ = x_ > 0 ? x_ : 0; x_ = (j) - x_; (u) = x_ * 3 + p; }
@@ -1367,6 +1367,7 @@ static int ssw_banded(const int8_t *ref, const int8_t *read, int refLen, int rea
         band_width *= 2;
     } while (max < score);
     band_width /= 2;
+    if (bw_out) *bw_out = band_width;                         /* the half-width the doubling stopped at: the traceback's band */
     i = readLen - 1; j = refLen - 1; e = 0; l = 0; f = max = 0; temp2 = 2;
     direction_line = direction + width_d * (readLen - 1) * 3;
     while (i > 0) {
@@ -1390,7 +1391,7 @@ static int ssw_banded(const int8_t *ref, const int8_t *read, int refLen, int rea
     return l;
 }
 
-typedef struct { int score1, score2, ref_begin1, ref_end1, read_begin1, read_end1, n_cigar; uint32_t cigar[256]; } so_ssw_t;
+typedef struct { int score1, score2, ref_begin1, ref_end1, read_begin1, read_end1, n_cigar, band; uint32_t cigar[256]; } so_ssw_t;
 
 /* ssw_align with flag = 2, filters = 0 (ssw.c:771-856) */
 static void ssw_align2(const int8_t *read, int readLen, const int8_t *mat, int n, const int8_t *ref, int refLen, int go, int ge,
@@ -1415,7 +1416,7 @@ static void ssw_align2(const int8_t *read, int readLen, const int8_t *mat, int n
     {
         int rfl = r->ref_end1 - r->ref_begin1 + 1, rdl = r->read_end1 - r->read_begin1 + 1;
         int bw = abs(rfl - rdl) + 1;
-        r->n_cigar = ssw_banded(ref + r->ref_begin1, read + r->read_begin1, rfl, rdl, r->score1, go, ge, bw, mat, n, r->cigar, 256);
+        r->n_cigar = ssw_banded(ref + r->ref_begin1, read + r->read_begin1, rfl, rdl, r->score1, go, ge, bw, mat, n, r->cigar, 256, &r->band);
     }
 }
 
@@ -1677,8 +1678,14 @@ int so_sam_pe(const so_index_t *ix, const so_opt_t *o, uint32_t min_tlen, uint32
     return s.ovf ? -1 : (int)s.l;
 }
 
-/* unit entry for tests/golden/ssw_vectors.txt: ssw_init + ssw_align as snpaln_sw[_snpaware] call them */
+/* unit entry for tests/golden/ssw_vectors*.txt: ssw_init + ssw_align as snpaln_sw[_snpaware] call them */
 int so_ssw_unit(int aware, const uint8_t *ref_syms, int refLen, const uint8_t *codes, int L, int out6[6], char *cigar, int cap)
+{
+    return so_ssw_unit_band(aware, ref_syms, refLen, codes, L, out6, cigar, cap, NULL);
+}
+
+/* so_ssw_unit, and the band half-width banded_sw's doubling stopped at (*band; 0 when there was no traceback) */
+int so_ssw_unit_band(int aware, const uint8_t *ref_syms, int refLen, const uint8_t *codes, int L, int out6[6], char *cigar, int cap, int *band)
 {
     so_ssw_t res; int i, j; char *o = cigar;
     int8_t *ref = xcalloc((size_t)refLen + 1, 1), *read = xcalloc((size_t)L + 1, 1);
@@ -1687,6 +1694,7 @@ int so_ssw_unit(int aware, const uint8_t *ref_syms, int refLen, const uint8_t *c
     for (i = 0; i < L; ++i) read[i] = aware ? (int8_t)(1 << codes[i]) : (int8_t)codes[i];
     ssw_align2(read, L, aware ? SCORE_MAT2 : SCORE_MAT, aware ? 16 : 5, ref, refLen, 3, 1, L / 2, &res);
     out6[0] = res.score1; out6[1] = res.score2; out6[2] = res.ref_begin1; out6[3] = res.ref_end1; out6[4] = res.read_begin1; out6[5] = res.read_end1;
+    if (band) *band = res.band;
     cigar[0] = 0;
     for (j = 0; j < res.n_cigar; ++j) { int w = snprintf(o, (size_t)cap, "%u%c", res.cigar[j] >> 4, "MID"[res.cigar[j] & 15]); if (w >= cap) break; o += w; cap -= w; }
     free(ref); free(read);

@@ -806,8 +806,8 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
     if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W): "
-                                             "the rows of this batch would differ from the reference's");
+    if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W) "
+                                             "or a CIGAR of more than SALT_MAX_CIGAR_OPS operations: the rows of this batch would differ from the reference's");
     if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
     if ((uint64_t)total + 64 > ws->sam_cap) {
         hipFree(ws->d_sam); ws->d_sam = nullptr; if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam); ws->h_sam = nullptr; ws->sam_cap = 0; ws->h_sam_owned = true;
@@ -1078,7 +1078,9 @@ extern "C" int salt_gpu_diag_lv(const uint32_t *ref_words, uint32_t ref_len, uin
 
 // Unit entry of the Smith-Waterman rescue kernel: case i aligns read codes[read_offs[i]..) against the reference symbols
 // ref_syms[ref_offs[i]..) (4-bit allele masks when aware[i], bases 0..3 otherwise), the way snpaln_sw_snpaware / snpaln_sw
-// call ssw_init + ssw_align (alnpe.c:260-393).  out6: score1, score2, ref_begin, ref_end, read_begin, read_end.
+// call ssw_init + ssw_align (alnpe.c:260-393).  out6: score1, score2, ref_begin, ref_end, read_begin, read_end.  Every row is filled; when
+// cases overflow (ctl.overflow: band beyond SW_BAND_W, more than SALT_MAX_CIGAR_OPS operations) their n_cigar is 0 and the call returns
+// SALT_E_CAPACITY with their count in the message.
 extern "C" int salt_gpu_diag_ssw(uint32_t n_cases, const uint8_t *aware, const uint8_t *ref_syms, const uint32_t *ref_offs,
                                  const uint8_t *codes, const uint32_t *read_offs, int32_t *out6, uint16_t *cigars, uint16_t *n_cigar)
 {
@@ -1121,6 +1123,8 @@ extern "C" int salt_gpu_diag_ssw(uint32_t n_cases, const uint8_t *aware, const u
         n_cigar[i] = r.n_cigar;
         memcpy(cigars + (uint64_t)i * SALT_MAX_CIGAR_OPS, r.cigar, sizeof r.cigar);
     }
+    if (n_over) return done(fail(SALT_E_CAPACITY, std::to_string(n_over) + " case(s) need a band wider than SW_BAND_W or a CIGAR of more than "
+                                 "SALT_MAX_CIGAR_OPS operations: their rows hold the scores and end points, and no CIGAR"));
     return done(SALT_OK);
 }
 
@@ -1391,8 +1395,8 @@ extern "C" int salt_gpu_align_pe(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, con
     uint32_t n_over = 0;
     rc = salt_gpu_ws_pe_overflow(ws, &n_over);
     if (rc) return rc;
-    if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W): "
-                                             "the rows of this batch would differ from the reference's");
+    if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W) "
+                                             "or a CIGAR of more than SALT_MAX_CIGAR_OPS operations: the rows of this batch would differ from the reference's");
     return SALT_OK;
 }
 

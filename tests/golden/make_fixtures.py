@@ -11,9 +11,11 @@ Outputs: tests/golden/lambda/{genome.fa,snps.txt,reads_se.fq,reads_pe_[12].fq}
                                                which tests rebuild from .C.pac)
          tests/golden/lambda/expect_*.sam     (@PG line stripped)
          tests/golden/lv_vectors.txt          (LV / mismatch unit vectors from the reference units)
+         tests/golden/ssw_vectors_shapes.txt.gz  (ssw.c known answers of the shape sweep; alone: make_fixtures.py --ssw-shapes)
 
 Nothing here is needed at test time except the files it wrote.
 """
+import gzip
 import os
 import random
 import shutil
@@ -211,7 +213,22 @@ PE_CASES = {
 }
 
 
+SSW_SHAPES = (1000, 1)          # sswharness --shapes N SEED
+
+
+def write_ssw_shapes():
+    """oracle/_ref/sswharness --shapes 1000 1, gzipped without a time stamp (tests/ssw_sweep.py reads it)."""
+    cmd = [os.path.join(REF_BIN, "sswharness"), "--shapes"] + [str(x) for x in SSW_SHAPES]
+    print("+", " ".join(cmd), file=sys.stderr)
+    text = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout
+    with open(os.path.join(HERE, "ssw_vectors_shapes.txt.gz"), "wb") as f:
+        f.write(gzip.compress(text, compresslevel=9, mtime=0))
+
+
 def main():
+    if sys.argv[1:] == ["--ssw-shapes"]:
+        write_ssw_shapes()
+        return
     rng = random.Random(20261004)
     if os.path.isdir(OUT):
         shutil.rmtree(OUT)
@@ -250,6 +267,7 @@ def main():
     with open(os.path.join(OUT, "cases.txt"), "w") as f:
         for name, args in list(SE_CASES.items()) + list(PE_CASES.items()):
             f.write("%s\t%s\n" % (name, " ".join(args)))
+    write_ssw_shapes()
 
 
 if __name__ == "__main__":

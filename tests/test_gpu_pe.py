@@ -2,10 +2,13 @@
 rescue, alnpe_sam), through the C ABI: against the reference's own SAM output and its ssw.c known answers."""
 import ctypes
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
+import ssw_sweep
 from conftest import GOLDEN, LAMBDA, read_cases
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +96,78 @@ def test_gpu_ssw_unit_matches_reference_vectors():
         assert [int(x) for x in out6[i]] == w6, (i, out6[i], w6)
         got = "".join("%d%s" % (int(x) >> 4, "MID"[int(x) & 3]) for x in cig[i, :int(ncig[i])]) or "-"
         assert got == wc, (i, got, wc)
+
+
+@pytest.mark.parametrize("lds", [False, True], ids=["registers", "lds_only"])
+def test_gpu_ssw_shape_sweep_matches_reference(lds, tmp_path):
+    """k_swf (packed pairs), k_swf1, k_swr and k_swtb against the answers the reference's ssw.c printed for the shape sweep
+    (tests/golden/ssw_vectors_shapes.txt.gz): one launch per stripe variant (reads up to 104 / 152 / 256 / 512 bases), each
+    opening with pairs of its longest read length and mixing windows of ~20 to ~3000 columns; once with the variant sw_seg_variant
+    picks and once with SALT_GPU_SW_LDS=1 (rows in LDS at every length).  Each leg is a fresh process: the switch is read once.
+    Vectors whose CIGAR has more than SALT_MAX_CIGAR_OPS operations keep their six numbers, come back without a CIGAR, and make
+    the launch return SALT_E_CAPACITY with their count."""
+    env = dict(os.environ)
+    env.pop("SALT_GPU_SW_LDS", None)
+    if lds:
+        env["SALT_GPU_SW_LDS"] = "1"
+    out = str(tmp_path / "sweep.npz")
+    try:
+        p = subprocess.run([sys.executable, ssw_sweep.__file__, out], env=env, capture_output=True, text=True, timeout=300)
+    except subprocess.TimeoutExpired as e:
+        pytest.fail("the sweep child did not finish in %ds" % e.timeout)
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
+    vecs = ssw_sweep.load()
+    got = np.load(out)
+    plan = ssw_sweep.launches(vecs)
+    assert [e for e, _ in plan] == list(ssw_sweep.CLASS_EDGES)
+    assert any(len(order) % 2 == 1 and len(vecs[order[-1]].codes) == len(vecs[order[0]].codes) for e, order in plan if e <= 256)
+    n_checked = n_over = 0
+    for edge, order in plan:
+        assert got["order_%d" % edge].tolist() == order
+        out6, ncig, cigar = got["out6_%d" % edge], got["ncig_%d" % edge], got["cigar_%d" % edge]
+        over = [k for k, i in enumerate(order) if vecs[i].n_ops > ssw_sweep.MAX_CIGAR_OPS]
+        rc, err = int(got["rc_%d" % edge][0]), str(got["err_%d" % edge][0])
+        if over:
+            assert rc == ssw_sweep.SALT_E_CAPACITY and err.startswith("%d case(s) " % len(over)), (edge, rc, err)
+        else:
+            assert rc == 0, (edge, rc, err)
+        for k, i in enumerate(order):
+            v = vecs[i]
+            assert out6[k].tolist() == v.want6, (edge, k, i, out6[k].tolist(), v.want6)
+            if v.n_ops > ssw_sweep.MAX_CIGAR_OPS:
+                assert int(ncig[k]) == 0, (edge, k, i, str(cigar[k]))
+                n_over += 1
+            else:
+                assert str(cigar[k]) == v.cigar, (edge, k, i, str(cigar[k]), v.cigar)
+                n_checked += 1
+    assert n_checked + n_over == len(vecs) and n_over >= 8
+
+
+def test_gpu_pe_rescue_beyond_cigar_cap_raises(tiny_pe):
+    """A pair whose unmapped mate is found by the rescue only with a 1-base insertion every 7 bases (~140 CIGAR operations, more
+    than SALT_MAX_CIGAR_OPS): alnpe_core1 raises instead of returning rows that differ from the reference's."""
+    import salt_amd
+    w, _, _ = tiny_pe
+    g = w["genome"]
+    L, isz, n_pairs = 500, 1750, 8
+    rng = np.random.default_rng(3)
+    reads = []
+    for start in rng.integers(1000, len(g) - 4000, size=n_pairs):
+        m1 = g[start:start + L]
+        src = g[start + isz - L:start + isz]
+        m2f = np.insert(src, np.arange(7, L, 7), rng.integers(0, 4, size=len(range(7, L, 7))).astype(np.uint8))[:L]
+        reads += [m1, (3 - m2f[::-1])]
+    seqs = np.concatenate(reads).astype(np.uint8)
+    offs = (np.arange(2 * n_pairs + 1) * L).astype(np.uint32)
+    idx = salt_amd.Index.reload(w["prefix"])
+    opt, _ = salt_amd.AlnOpt.from_argv(["-p", "-a", "1000", "-b", "2400"], idx.l_seed)
+    aln = salt_amd.GpuAligner(idx, device=0, max_reads=len(offs) - 1, max_bases=int(offs[-1]) + 64)
+    try:
+        with pytest.raises(salt_amd.SaltError, match="SALT_MAX_CIGAR_OPS"):
+            aln.alnpe_core1(opt, idx, seqs, offs)
+    finally:
+        aln.close()
+        idx.destroy()
 
 
 def test_gpu_pe_needs_even_mates_and_pac(lam_pe):

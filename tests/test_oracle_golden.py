@@ -109,3 +109,57 @@ def test_oracle_ssw_matches_reference_vectors(oracle_lib):
         assert (buf.value.decode() or "-") == cig, (n, buf.value, cig)
         n += 1
     assert n == 600
+
+
+def test_oracle_ssw_matches_reference_shape_sweep(oracle_lib):
+    """The same restatement against ssw.c's answers for the shape sweep (oracle/ref_harness_ssw.c --shapes: reads of 16-512 bases,
+    windows up to ~3000 columns, indel runs up to 60 bases, copies of the target around the second-best mask, CIGARs beyond 64
+    operations).  With the half-width at which the band doubling stopped, each vector is classed by the k_swtb pass its traceback
+    reads in the GPU launch of its length class (tests/ssw_sweep.py); every class keeps a minimum count, so no fixture edit can drop
+    a code path of the GPU tests unnoticed."""
+    import collections
+    import re
+    import ssw_sweep
+    lib = oracle_lib
+    vecs = ssw_sweep.load()
+    assert len(vecs) == 1000
+    band = []
+    for n, v in enumerate(vecs):
+        out6 = (ctypes.c_int * 6)()
+        buf = ctypes.create_string_buffer(4096)
+        bw = ctypes.c_int(0)
+        codes = np.ascontiguousarray(v.codes)
+        lib.so_ssw_unit_band(v.aware, v.ref.ctypes.data_as(ctypes.c_void_p), len(v.ref), codes.ctypes.data_as(ctypes.c_void_p), len(codes),
+                             out6, buf, 4096, ctypes.byref(bw))
+        assert list(out6) == v.want6, (n, list(out6), v.want6)
+        assert (buf.value.decode() or "-") == v.cigar, (n, buf.value, v.cigar)
+        band.append(bw.value)
+    total = collections.Counter()
+    for edge, order in ssw_sweep.launches(vecs):
+        max_len = ssw_sweep.launch_max_len(vecs, order)
+        c = collections.Counter()
+        for i in order:
+            v = vecs[i]
+            c[ssw_sweep.tb_pass(v, band[i], max_len)] += 1
+            rfl, rdl = v.want6[3] - v.want6[2] + 1, v.want6[5] - v.want6[4] + 1
+            if band[i] > abs(rfl - rdl) + 1:
+                c["doubled"] += 1
+            if v.n_ops > ssw_sweep.MAX_CIGAR_OPS:
+                c["over_ops"] += 1
+        for k in ("reg", "lds", "rows_lds", "global", "doubled"):
+            assert c[k] >= 5, (edge, k, dict(c))
+        assert c["over"] == 0 and c[None] == 0, (edge, dict(c))          # no band beyond SW_BAND_W; every vector has a traceback
+        total.update(c)
+    want = {"reg": 400, "lds": 50, "rows_lds": 50, "dir_lds": 10, "global": 100, "doubled": 80, "over_ops": 8}
+    assert all(total[k] >= m for k, m in want.items()), dict(total)
+    # the other shapes the sweep is for
+    lens = collections.Counter(len(v.codes) for v in vecs)
+    assert all(lens[L] >= 10 for L in (104, 105, 152, 153, 256, 257, 512)), lens
+    assert sum(lens[L] for L in range(16, 30)) >= 20                                  # maskLen < 15: no second best
+    assert sum(1 for v in vecs if len(v.codes) in (30, 31) and v.want6[1] > 0) >= 5    # maskLen == 15: second best
+    assert max(len(v.ref) for v in vecs) >= 2500 and sum(len(v.ref) < len(v.codes) for v in vecs) >= 20
+    assert sum(v.want6[0] == v.want6[1] and v.want6[0] >= 50 for v in vecs) >= 10     # ties at real alignment scores
+    gap = [max([int(x) for x in re.findall(r"(\d+)[ID]", v.cigar)] or [0]) for v in vecs]
+    assert sum(g >= 30 for g in gap) >= 10
+    assert sum((v.codes == 4).sum() >= 5 for v in vecs) >= 20
+    assert sum(v.aware and (v.ref == 0).sum() >= 5 for v in vecs) >= 20
