@@ -196,6 +196,16 @@ int  salt_gpu_ws_reserve_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, uint
                               uint64_t est_sam_bytes, void *host_sam, uint64_t host_sam_bytes);
 int  salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_text_opt_t *topt, const char *fastq, uint64_t n_bytes,
                             const char **sam, uint64_t *sam_bytes, uint32_t *n_reads);
+/* BGZF output (`salt --bgzf`): after salt_gpu_ws_set_sam_bgzf(ws, 1) the two text entry points deflate the SAM block on the device, right
+ * behind the kernel that wrote it, and return whole BGZF blocks in *sam / *sam_bytes (htslib's blocked gzip: independent gzip members with
+ * a 'BC' extra field, each holding at most 32 640 bytes of the text; no end-of-file block -- that one is the caller's, after its last
+ * block).  Only the compressed bytes cross to the host.  A block of text that does not compress leaves as a stored block, 31 bytes larger
+ * than its text; the workspace's buffers (and what it takes from the host_sam of salt_gpu_ws_reserve_text) allow for that. */
+int  salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on);
+/* The same kernels on their own, host buffers in and out: text[0 .. n_bytes) -> ceil(n_bytes / 32640) BGZF blocks in out, *out_bytes of them
+ * (0 for an empty text; no end-of-file block).  The same text gives the same bytes on every run.  SALT_E_CAPACITY when out_cap is too
+ * small: n_bytes + 31 bytes per block is the exact bound, 65 536 bytes per block always suffice. */
+int  salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes);
 int  salt_gpu_host_alloc(uint64_t bytes, void **ptr);      /* page-locked host memory for the text buffers */
 void salt_gpu_host_free(void *ptr);
 /* Multi-GPU drivers (`salt --gpus N`, which stands where alnse_core's pthread fan-out is, alnse.c:1419-1429): the host NUMA node of a device

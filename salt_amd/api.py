@@ -361,6 +361,23 @@ def suffix_array(text, bits, gpu_device=None):
     return sa
 
 
+BGZF_CUT = 32640        # text bytes per BGZF block (salt_amd/csrc/salt_bgzf_block.h)
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_deflate(data, device=0):
+    """data -> BGZF blocks (blocked gzip, one block per BGZF_CUT bytes) by the device kernels behind `salt --bgzf`.
+    No end-of-file block: append BGZF_EOF after the last piece of a stream."""
+    g = gpu_lib()
+    g.salt_gpu_bgzf_deflate.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    data = bytes(data)
+    cap = len(data) + 31 * ((len(data) + BGZF_CUT - 1) // BGZF_CUT)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n = ctypes.c_uint64(0)
+    _gpu_check(g.salt_gpu_bgzf_deflate(int(device), data, len(data), out, cap, ctypes.byref(n)))
+    return out.raw[:n.value]
+
+
 KERNELS = ("k_pack", "k_seed", "k_light", "k_heavy", "k_gap", "k_gapfin", "k_cigar", "k_pair", "k_sw", "k_pe_final")
 
 

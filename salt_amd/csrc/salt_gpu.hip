@@ -60,6 +60,10 @@ struct salt_gpu_ws {
     char *d_sam = nullptr, *h_sam = nullptr; uint64_t sam_cap = 0; char *d_rg = nullptr; std::string rg;
     char *d_samslot = nullptr; SamSeg *d_samseg = nullptr;      // [max_reads]: the records' formatted heads and tails between k_sam_len and k_sam_write
     bool h_sam_owned = true;                                                 // false: the caller's page-locked buffer (salt_gpu_ws_reserve_text)
+    // salt_gpu_ws_set_sam_bgzf: the SAM block leaves as BGZF blocks (allocated on first use, grown on demand)
+    bool sam_bgzf = false;
+    uint32_t *d_bz_slots = nullptr, *d_bz_sizes = nullptr; unsigned long long *d_bz_offs = nullptr; uint8_t *d_bz_out = nullptr; uint64_t bz_blocks_cap = 0;
+    char *h_bz = nullptr; uint64_t h_bz_cap = 0;                             // page-locked, only for a compressed block that outgrows h_sam
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
     uint32_t heavy_blocks = 2048, gap_blocks = 2048;
     QueueRange *d_ranges = nullptr;                                           // k_heavy's queue ranges: k_light's push counters, the heads
@@ -342,6 +346,7 @@ extern "C" void salt_gpu_ws_destroy(salt_gpu_ws_t *ws)
     hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_wq_cnt); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_ranges); hipFree(ws->d_qctl); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
     hipFree(ws->d_raw); hipFree(ws->d_tile); hipFree(ws->d_lines); hipFree(ws->d_rec); hipFree(ws->d_tctl); hipFree(ws->d_samoff); hipFree(ws->d_samslot); hipFree(ws->d_samseg); hipFree(ws->d_scan); hipFree(ws->d_sam); hipFree(ws->d_rg);
     if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam);
+    hipFree(ws->d_bz_slots); hipFree(ws->d_bz_sizes); hipFree(ws->d_bz_offs); hipFree(ws->d_bz_out); if (ws->h_bz) hipHostFree(ws->h_bz);
     hipFree(ws->d_pe_scr); hipFree(ws->d_pairs); hipFree(ws->d_req); hipFree(ws->d_swres); hipFree(ws->d_pctl); hipFree(ws->d_sw_scr); hipFree(ws->d_pcq);
     if (ws->stream) hipStreamDestroy(ws->stream);
     for (auto &e : ws->ev) if (e) hipEventDestroy(e);
@@ -606,6 +611,85 @@ extern "C" int salt_gpu_ws_reserve_text(salt_gpu_ws_t *ws, const salt_aln_opt_t 
     return SALT_OK;
 }
 
+// ---- BGZF: the SAM block deflated on the device, behind k_sam_write on the same stream ----
+struct BgzfBufs { uint32_t *slots = nullptr, *sizes = nullptr; unsigned long long *offs = nullptr; uint8_t *out = nullptr; };
+static int bgzf_alloc(uint64_t n_blocks, BgzfBufs &b)
+{
+    HIPCHK(hipMalloc((void **)&b.slots, n_blocks * BGZF_SLOT_BYTES));
+    HIPCHK(hipMalloc((void **)&b.sizes, n_blocks * 4));
+    HIPCHK(hipMalloc((void **)&b.offs, (n_blocks + 1) * 8));
+    HIPCHK(hipMalloc((void **)&b.out, n_blocks * (BGZF_CUT_BYTES + 31)));      // bgzf_bound of n_blocks full blocks
+    return SALT_OK;
+}
+static void bgzf_free(BgzfBufs &b) { hipFree(b.slots); hipFree(b.sizes); hipFree(b.offs); hipFree(b.out); b = BgzfBufs(); }
+
+// ws->d_sam[0 .. total) -> whole BGZF blocks in page-locked host memory (*sam, *sam_bytes); no end-of-file block
+static int ws_sam_bgzf(salt_gpu_ws_t *ws, uint64_t total, hipStream_t st, const char **sam, uint64_t *sam_bytes)
+{
+    const uint64_t n_blocks = bgzf_blocks(total);
+    if (n_blocks > ws->bz_blocks_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        BgzfBufs b; b.slots = ws->d_bz_slots; b.sizes = ws->d_bz_sizes; b.offs = ws->d_bz_offs; b.out = ws->d_bz_out;
+        bgzf_free(b); ws->d_bz_slots = ws->d_bz_sizes = nullptr; ws->d_bz_offs = nullptr; ws->d_bz_out = nullptr; ws->bz_blocks_cap = 0;
+        const uint64_t want = n_blocks + n_blocks / 4 + 1;
+        const int rc = bgzf_alloc(want, b);
+        ws->d_bz_slots = b.slots; ws->d_bz_sizes = b.sizes; ws->d_bz_offs = b.offs; ws->d_bz_out = b.out;
+        if (rc) return rc;
+        ws->bz_blocks_cap = want;
+    }
+    HIPCHK(launch_bgzf_deflate(reinterpret_cast<const uint8_t *>(ws->d_sam), total, ws->d_bz_slots, ws->d_bz_sizes, ws->d_bz_offs, ws->d_bz_out, st));
+    unsigned long long bytes = 0;
+    HIPCHK(hipMemcpyAsync(&bytes, ws->d_bz_offs + n_blocks, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bytes > bgzf_bound(total)) return fail(SALT_E_HIP, "BGZF blocks larger than their bound");
+    char *dst = ws->h_sam;
+    if (bytes > ws->sam_cap) {                               // incompressible text: up to 31 bytes per block more than the text the SAM buffers were sized for
+        if (bytes > ws->h_bz_cap) {
+            if (ws->h_bz) hipHostFree(ws->h_bz);
+            ws->h_bz = nullptr; ws->h_bz_cap = 0;
+            HIPCHK(hipHostMalloc((void **)&ws->h_bz, bytes + bytes / 4, hipHostMallocDefault));
+            ws->h_bz_cap = bytes + bytes / 4;
+        }
+        dst = ws->h_bz;
+    }
+    HIPCHK(hipMemcpyAsync(dst, ws->d_bz_out, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *sam = dst; *sam_bytes = bytes;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    ws->sam_bgzf = on != 0;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!out_bytes || (n_bytes && (!text || !out))) return fail(SALT_E_INVAL, "null argument");
+    *out_bytes = 0;
+    if (n_bytes == 0) return SALT_OK;
+    int n_dev = 0;
+    HIPCHK(hipGetDeviceCount(&n_dev));
+    if (n_dev <= 0) return fail(SALT_E_HIP, "no HIP device visible: the BGZF kernels cannot run (there is no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    const uint64_t n_blocks = bgzf_blocks(n_bytes);
+    BgzfBufs b; uint8_t *d_text = nullptr;
+    auto done = [&](int rc) { bgzf_free(b); hipFree(d_text); return rc; };
+    if (int rc = bgzf_alloc(n_blocks, b)) return done(rc);
+    DONECHK(hipMalloc((void **)&d_text, n_bytes + 64));
+    DONECHK(hipMemcpy(d_text, text, n_bytes, hipMemcpyHostToDevice));
+    DONECHK(launch_bgzf_deflate(d_text, n_bytes, b.slots, b.sizes, b.offs, b.out, nullptr));
+    unsigned long long bytes = 0;
+    DONECHK(hipMemcpy(&bytes, b.offs + n_blocks, 8, hipMemcpyDeviceToHost));
+    if (bytes > bgzf_bound(n_bytes)) return done(fail(SALT_E_HIP, "BGZF blocks larger than their bound"));
+    if (bytes > out_cap) return done(fail(SALT_E_CAPACITY, "output buffer smaller than the BGZF blocks (" + std::to_string(bytes) + " bytes; 65536 per block always suffice)"));
+    DONECHK(hipMemcpy(out, b.out, bytes, hipMemcpyDeviceToHost));
+    *out_bytes = bytes;
+    return done(SALT_OK);
+}
+
 extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, uint64_t n_bytes,
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
 {
@@ -703,14 +787,18 @@ extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     }
     mark();
     HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
-    HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
+    if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
+    else {
+        HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
     mark();
     if (trace && n_tm == 8)
         fprintf(stderr, "[salt_gpu] first text call (ms): raw buffers %.1f, copy in + count %.1f, lines/parse/codes %.1f, align launch (+ its buffers) %.1f, "
                         "kernels + SAM lengths %.1f, SAM buffers %.1f, write + copy out %.1f\n", (tm[1] - tm[0]) * 1e3, (tm[2] - tm[1]) * 1e3, (tm[3] - tm[2]) * 1e3,
                 (tm[4] - tm[3]) * 1e3, (tm[5] - tm[4]) * 1e3, (tm[6] - tm[5]) * 1e3, (tm[7] - tm[6]) * 1e3);
-    *sam = ws->h_sam; *sam_bytes = total; *n_reads = n_rec;
+    *sam = host_sam; *sam_bytes = host_bytes; *n_reads = n_rec;
     return SALT_OK;
 }
 
@@ -817,9 +905,13 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
         ws->sam_cap = want;
     }
     HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
-    HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    *sam = ws->h_sam; *sam_bytes = total; *n_pairs = n;
+    const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
+    if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
+    else {
+        HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    *sam = host_sam; *sam_bytes = host_bytes; *n_pairs = n;
     return SALT_OK;
 }
 #undef REGROW

@@ -201,6 +201,14 @@ hipError_t launch_sam_len(const SamDev &d, uint32_t n, uint32_t *off, unsigned l
 hipError_t launch_sam_write(const SamDev &d, uint32_t n, const uint32_t *off, char *out, hipStream_t st);
 static const uint32_t FQ_TILE = 1024;                                          // bytes per newline-count tile (k_fq_count)
 
+// ---- BGZF output (salt_bgzf.hip) ----
+// text[0 .. n) (readable up to the next multiple of 4) -> out: ceil(n / BGZF_CUT_BYTES) BGZF blocks, contiguous and in order, bgzf_bound(n) bytes at
+// most; offs[b] = where block b starts, offs[n_blocks] = all bytes.  slots: n_blocks x BGZF_SLOT_BYTES, sizes: n_blocks words, offs: n_blocks + 1.
+static const uint32_t BGZF_CUT_BYTES = 32640, BGZF_SLOT_BYTES = 32768;
+inline uint64_t bgzf_blocks(uint64_t n) { return (n + BGZF_CUT_BYTES - 1) / BGZF_CUT_BYTES; }
+inline uint64_t bgzf_bound(uint64_t n) { return n + 31 * bgzf_blocks(n); }       // a stored block: 18 + 5 + text + 8
+hipError_t launch_bgzf_deflate(const uint8_t *text, uint64_t n, uint32_t *slots, uint32_t *sizes, unsigned long long *offs, uint8_t *out, hipStream_t st);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

@@ -6,7 +6,8 @@
 //   one worker per GPU : salt_gpu_align_se on its batch                     (stands where alnse_core1 ran)
 //   formatter threads (-t) : SAM text per read                              (aln_samse, sam.c:87-182)
 //   writer : records in input order                                         (the puts() loop, alnse.c:1433-1439)
-// Extra long options (not in the reference): --gpus N (default 1).
+// Extra long options (not in the reference): --gpus N (default 1); --bgzf: everything written to stdout is one BGZF stream (blocked gzip,
+// htslib's .sam.gz container), the SAM blocks deflated on the device before they cross to the host.
 // Flags the reference parses but ignores stay ignored (-n -e -M -O -E -l -X).  -p <mate1> <mate2>: paired end
 // (alnpe_core, Align_src/alnpe.c:530-661) through salt_gpu_align_pe.
 #include "../../include/salt_host.h"
@@ -32,6 +33,10 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+// Taken weakly: `salt` also links and runs against a libsalt_gpu without the device compressor (an older build, the tests' stub), and
+// --bgzf then deflates on the host.
+extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on) __attribute__((weak));
 
 namespace {
 
@@ -323,6 +328,109 @@ void pin_to_device_node(int device)
     if (any) sched_setaffinity(0, sizeof set, &set);
 }
 
+// ---------------------------------------------------------------------------------------------
+// --bgzf: the header, every SAM block in input order and htslib's empty end-of-file block, as independent gzip members of at most
+// BGZF_CUT text bytes each.  On the text path the device deflates the SAM block behind the kernel that wrote it
+// (salt_gpu_ws_set_sam_bgzf); everything else -- the header, the host pipeline, a libsalt_gpu without that entry point, and the text
+// path under SALT_BGZF_HOST=1 -- goes through zlib level 1 here, on the worker that produced the text.  The writers do not change:
+// whole blocks concatenate in order.
+// ---------------------------------------------------------------------------------------------
+const size_t BGZF_CUT = 32640;                               // the device's cut (salt_bgzf_block.h): both compressors cut the text the same way
+const unsigned char BGZF_EOF[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+struct BgzfRun {
+    bool on = false, device = false;                         // device: the text path's workspaces deflate
+    std::atomic<bool> host_blocks{ false };                  // SAM blocks (not only the header) went through zlib
+    std::atomic<uint64_t> text_bytes{ 0 }, file_bytes{ 0 };
+} g_bgzf;
+
+// text[0 .. n) -> BGZF blocks appended to out
+bool bgzf_deflate_host(const char *text, size_t n, std::string &out)
+{
+    z_stream z; memset(&z, 0, sizeof z);
+    if (deflateInit2(&z, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+    bool ok = true;
+    for (size_t at = 0; at < n && ok; at += BGZF_CUT) {
+        const size_t len = std::min(BGZF_CUT, n - at), base = out.size(), bound = deflateBound(&z, (uLong)len);
+        out.resize(base + 18 + bound + 8);
+        unsigned char *o = reinterpret_cast<unsigned char *>(&out[base]);
+        deflateReset(&z);
+        z.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(text + at)); z.avail_in = (uInt)len;
+        z.next_out = o + 18; z.avail_out = (uInt)bound;
+        ok = deflate(&z, Z_FINISH) == Z_STREAM_END && 18 + z.total_out + 8 <= 65536;
+        if (!ok) break;
+        const size_t clen = z.total_out, bsize = 18 + clen + 8 - 1;
+        memcpy(o, BGZF_EOF, 16); o[16] = (unsigned char)bsize; o[17] = (unsigned char)(bsize >> 8);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), reinterpret_cast<const Bytef *>(text + at), (uInt)len), isize = (uint32_t)len;
+        for (int i = 0; i < 4; ++i) { o[18 + clen + i] = (unsigned char)(crc >> (8 * i)); o[18 + clen + 4 + i] = (unsigned char)(isize >> (8 * i)); }
+        out.resize(base + 18 + clen + 8);
+    }
+    deflateEnd(&z);
+    return ok;
+}
+
+// the text bytes a run of whole BGZF blocks holds (the ISIZE fields, found by the BSIZE fields)
+uint64_t bgzf_text_bytes(const char *blocks, uint64_t n)
+{
+    const unsigned char *b = reinterpret_cast<const unsigned char *>(blocks);
+    uint64_t text = 0;
+    for (uint64_t at = 0; at + 26 <= n; ) {
+        const uint64_t bsize = (uint64_t)(b[at + 16] | (b[at + 17] << 8)) + 1;
+        if (at + bsize > n) break;
+        const unsigned char *t = b + at + bsize - 4;
+        text += t[0] | (t[1] << 8) | (t[2] << 16) | ((uint64_t)t[3] << 24);
+        at += bsize;
+    }
+    return text;
+}
+
+// a batch of the host pipeline: its SAM pieces become BGZF blocks, cut over the whole batch and deflated by the worker's helper threads
+bool bgzf_batch(std::vector<std::string> &pieces, Pool &pool)
+{
+    std::string all;
+    size_t n = 0;
+    for (const std::string &p : pieces) n += p.size();
+    all.reserve(n);
+    for (const std::string &p : pieces) all += p;
+    const size_t n_blocks = (n + BGZF_CUT - 1) / BGZF_CUT, n_threads = (size_t)pool.n;
+    std::vector<std::string> out(n_threads);
+    std::atomic<bool> ok{ true };
+    pool.parallel([&](int t) {
+        const size_t lo = n_blocks * (size_t)t / n_threads * BGZF_CUT, hi = std::min(n, n_blocks * ((size_t)t + 1) / n_threads * BGZF_CUT);
+        if (lo < hi && !bgzf_deflate_host(all.data() + lo, hi - lo, out[(size_t)t])) ok = false;
+    });
+    size_t bytes = 0;
+    for (const std::string &o : out) bytes += o.size();
+    g_bgzf.text_bytes += n; g_bgzf.file_bytes += bytes; g_bgzf.host_blocks = true;
+    pieces.swap(out);
+    return ok;
+}
+
+// a block of the text path, before it is written: from the device it is BGZF already; otherwise it becomes BGZF here (zbuf: the worker's own)
+bool bgzf_text_block(const char *&sam, uint64_t &sam_bytes, std::string &zbuf)
+{
+    if (g_bgzf.device) g_bgzf.text_bytes += bgzf_text_bytes(sam, sam_bytes);
+    else {
+        zbuf.clear();
+        if (!bgzf_deflate_host(sam, (size_t)sam_bytes, zbuf)) return false;
+        g_bgzf.text_bytes += sam_bytes; g_bgzf.host_blocks = true;
+        sam = zbuf.data(); sam_bytes = zbuf.size();
+    }
+    g_bgzf.file_bytes += sam_bytes;
+    return true;
+}
+
+// after the last SAM block of a run that succeeded: the end-of-file block, and the line that says which compressor ran
+void bgzf_finish()
+{
+    if (!g_bgzf.on) return;
+    fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout);
+    fflush(stdout);
+    g_bgzf.file_bytes += sizeof BGZF_EOF;
+    const bool dev = g_bgzf.device, host = g_bgzf.host_blocks;
+    fprintf(stderr, "[salt] BGZF output: %s deflate%s, %llu -> %llu bytes\n", dev ? "device" : "host", dev && host ? " (host deflate behind the hand-over)" : "",
+            (unsigned long long)g_bgzf.text_bytes.load(), (unsigned long long)g_bgzf.file_bytes.load());
+}
+
 double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + ts.tv_nsec * 1e-9; }
 
 int usage()
@@ -342,6 +450,7 @@ int usage()
             "           -a, --min_tlen      <int>    min template length [250]\n"
             "           -b, --max_tlen      <int>    max template length [550]\n"
             "               --gpus          <int>    GPUs to shard batches over [1]\n"
+            "               --bgzf                   write the SAM stream as BGZF blocks (.sam.gz), deflated on the GPU [False]\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -586,7 +695,8 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
             const bool trace = getenv("SALT_TEXT_TRACE") != nullptr;      // per-worker timeline on stderr
             const double tw_start = now(); int n_calls = 0; double t_first = 0, t_rest = 0;
             uint32_t ws_reads = max_reads;
-            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) ||
+            std::string zbuf;                                             // --bgzf with the host compressor: this worker's blocks
+            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) ||
                 (head_read_len && salt_gpu_ws_reserve_text(ws, &ao, R.chunk + TEXT_SLACK, (uint32_t)(ws_reads / 1.3), head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
                 fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
             }
@@ -656,6 +766,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                     if (trace) fprintf(stderr, "[salt] worker %d: chunk %llu holds more than %u reads, workspace re-created for %u\n", wk, (unsigned long long)k, ws_reads, worst_reads);
                     salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = worst_reads;
                     grc = salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws);
+                    if (!grc && g_bgzf.device) grc = salt_gpu_ws_set_sam_bgzf(ws, 1);
                     if (!grc) grc = salt_gpu_align_se_text(ws, &ao, &to, buf + beg2, end - beg2, &sam, &sam_bytes, &n_reads);
                 }
                 if (grc == SALT_E_INVAL) {
@@ -673,6 +784,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 t_gpu = t_gpu + (now() - tg0);
                 if (n_calls++ == 0) t_first = now() - tg0; else t_rest += now() - tg0;
+                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] zlib failed on a SAM block\n"); set_failed(); break; }
                 // block k is written when block k - 1 has been
                 {
                     std::unique_lock<std::mutex> lk(R.mu);
@@ -860,7 +972,8 @@ static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const
         workers.emplace_back([&, wk]() {
             salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk];
             pin_to_device_node(wk / P.wpg);
-            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) ||
+            std::string zbuf;
+            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) ||
                 (P.head_read_len && salt_gpu_ws_reserve_text(ws, &ao, P.in_cap, P.max_reads, P.head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
                 fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
             }
@@ -900,6 +1013,7 @@ static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const
                 if (grc == SALT_E_INVAL) { fall_back(k, salt_gpu_last_error()); break; }
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 t_gpu = t_gpu + (now() - tg0);
+                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] zlib failed on a SAM block\n"); set_failed(); break; }
                 {
                     std::unique_lock<std::mutex> lk(wmu);
                     wcv.wait(lk, [&] { return failed.load() || fallback.load() || written == k; });
@@ -951,7 +1065,7 @@ int main(int argc, char **argv)
         { "threads", 1, 0, 't' }, { "num", 1, 0, 'n' }, { "help", 0, 0, 'h' }, { "pe", 0, 0, 'p' }, { "min_tlen", 1, 0, 'a' },
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
-        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { 0, 0, 0, 0 } };
+        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { 0, 0, 0, 0 } };
     int c;
     while ((c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0) {
         switch (c) {
@@ -967,6 +1081,7 @@ int main(int argc, char **argv)
         case 'a': po.min_tlen = (uint32_t)atoi(optarg); break;
         case 'b': po.max_tlen = (uint32_t)atoi(optarg); break;
         case 1000: n_gpus = atoi(optarg); break;
+        case 1001: g_bgzf.on = true; break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -976,6 +1091,8 @@ int main(int argc, char **argv)
     if (n_threads < 1) n_threads = 1;
     if (n_gpus < 1) n_gpus = 1;
     const char *prefix = argv[optind], *fn_reads = argv[optind + 1], *fn_mates = pe ? argv[optind + 2] : nullptr;
+    // the device compressor, unless this libsalt_gpu has none or SALT_BGZF_HOST=1 asks for zlib (A/B runs, tests)
+    g_bgzf.device = g_bgzf.on && salt_gpu_ws_set_sam_bgzf != nullptr && !(getenv("SALT_BGZF_HOST") && atoi(getenv("SALT_BGZF_HOST")));
 
     // Single end + a plain (not gzipped) strict 4-line FASTQ in a regular file: the text path -- parse, align and format on the device
     // (run_se_text).  Everything else (paired end, gzip, pipes, multi-line records) goes through the host pipeline below.
@@ -1015,9 +1132,15 @@ int main(int argc, char **argv)
         std::vector<char> hb(16 << 20);
         int w = salt_sam_header(ix, &so, hb.data(), hb.size());
         if (w < 0) { fprintf(stderr, "[salt] SAM header too large\n"); return false; }
-        fwrite(hb.data(), 1, (size_t)w, stdout);
         time_t tt = time(nullptr); struct tm *tmv = localtime(&tt);
-        printf("@PG\tID:snpaln\tPN:snpaln\tCL:\"%s\"\tDS:%d-%d-%d\tVN:0.1beta\n", cmd.c_str(), tmv->tm_year + 1900, tmv->tm_mon + 1, tmv->tm_mday);
+        std::vector<char> pg(cmd.size() + 128);
+        const int wp = snprintf(pg.data(), pg.size(), "@PG\tID:snpaln\tPN:snpaln\tCL:\"%s\"\tDS:%d-%d-%d\tVN:0.1beta\n", cmd.c_str(), tmv->tm_year + 1900, tmv->tm_mon + 1, tmv->tm_mday);
+        if (!g_bgzf.on) { fwrite(hb.data(), 1, (size_t)w, stdout); fwrite(pg.data(), 1, (size_t)wp, stdout); return true; }
+        std::string text(hb.data(), (size_t)w), z;
+        text.append(pg.data(), (size_t)wp);
+        if (!bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] zlib failed on the SAM header\n"); return false; }
+        fwrite(z.data(), 1, z.size(), stdout);
+        g_bgzf.text_bytes += text.size(); g_bgzf.file_bytes += z.size();
         return true;
     };
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
@@ -1026,6 +1149,7 @@ int main(int argc, char **argv)
         if (!print_header()) return 1;
         const int rc = run_se_text(fn_reads, ix, gix, n_gpus, plan, ao, so, now(), &resume[0]);
         if (rc != 2) {
+            if (rc == 0) bgzf_finish();
             for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]);
             salt_index_free(ix);
             return rc;
@@ -1066,6 +1190,7 @@ int main(int argc, char **argv)
         if (!print_header()) return 1;
         const int rc = run_pe_text(fn_reads, fn_mates, ix, gix, n_gpus, plan, ao, so, po, now(), resume);
         if (rc != 2) {
+            if (rc == 0) bgzf_finish();
             for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]);
             salt_index_free(ix);
             return rc;
@@ -1176,6 +1301,7 @@ int main(int argc, char **argv)
                 }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &so, &po, *b, pool); else format_batch(ix, &so, *b, pool);
+                if (g_bgzf.on && !bgzf_batch(b->sam, pool)) { fprintf(stderr, "[salt] zlib failed on a SAM block\n"); set_failed(); break; }
                 t_fmt = t_fmt + (now() - tf0);
                 std::unique_lock<std::mutex> lk(mu);
                 done.push_back(std::move(b));
@@ -1205,6 +1331,7 @@ int main(int argc, char **argv)
     }
     reader.join();
     for (auto &w : workers) w.join();
+    if (!failed) bgzf_finish();
     fflush(stdout);
     double dt = now() - t0;
     fprintf(stderr, "[alnse_core]: total %lf sec escaped\n", dt);

@@ -2,7 +2,9 @@
 """End-to-end experiments with the `salt` binary on the GRCh38-scale workload (GPU box): builds the index once, writes one FASTQ file,
 then runs `salt -d -c` for every settings string given on the command line ("ENV=VAL,ENV=VAL"; "" = defaults).
 A setting IN=bgzf / IN=gz runs on a blocked-gzip / plain-gzip copy of the FASTQ (written once, 32 processes); OUT=null sends the SAM to
-/dev/null; PROF=<dir> runs under rocprofv3 --kernel-trace --stats.
+/dev/null; ARGS=--bgzf adds arguments to the `salt` command line (several: separated by '+'), so that one invocation runs plain and
+compressed legs side by side; PROF=<dir> runs under rocprofv3 --kernel-trace --stats.  SALT_E2E_BIN in the environment names the `salt`
+binary of another build (the parent commit's, say) for the same legs on the same files.
 usage: tools/e2e_text.py <n_reads> [settings ...]"""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,11 +58,11 @@ def make_bgzf(src, dst):
 
 
 made = {}
-salt = os.path.join(ROOT, "salt_amd", "bin", "salt")
+salt = os.environ.get("SALT_E2E_BIN", os.path.join(ROOT, "salt_amd", "bin", "salt"))      # another build's binary: A/B against this tree's
 for s in settings:
     env = dict(os.environ)
     for kv in filter(None, s.split(",")):
-        a, b = kv.split("=")
+        a, b = kv.split("=", 1)
         env[a] = b
     sam = os.path.join(w["dir"], "e2e.sam")
     to_null = env.pop("OUT", "") == "null"
@@ -77,7 +79,7 @@ for s in settings:
             made[kind] = 1
             print("   (%s written in %.1f s, %.2f GB)" % (src, time.time() - tz, os.path.getsize(src) / 1e9))
     t0 = time.time()
-    cmd = [salt, "-d", "-c", "-t", env.pop("T", "64"), w["prefix"], src]
+    cmd = [salt, "-d", "-c", "-t", env.pop("T", "64")] + [a for a in env.pop("ARGS", "").split("+") if a] + [w["prefix"], src]
     prof = env.pop("PROF", "")                                  # PROF=<dir>: the run under rocprofv3 --kernel-trace --stats, summary CSV into <dir>
     if prof:
         env["TMPDIR"] = "/tmp"
@@ -85,7 +87,7 @@ for s in settings:
     with open("/dev/null" if to_null else sam, "wb") as fo:
         r = subprocess.run(cmd, stdout=fo, stderr=subprocess.PIPE, env=env, cwd="/tmp" if prof else None)
     tail = [l for l in r.stderr.decode().splitlines() if l.startswith("[salt") or l.startswith("[alnse_core]: total")]
-    print("== %s  (rc %d, process %.1f s)" % (s or "defaults", r.returncode, time.time() - t0))
+    print("== %s  (rc %d, process %.1f s%s)" % (s or "defaults", r.returncode, time.time() - t0, "" if to_null else ", %.3f GB written" % (os.path.getsize(sam) / 1e9)))
     for l in tail:
         print("   ", l)
     sys.stdout.flush()
