@@ -270,15 +270,15 @@ __device__ __forceinline__ uint32_t seed_resolve_unique(const uint32_t *__restri
         const uint32_t m = (uint32_t)it + 1u;
         const uint32_t reln = s - (nb << 5);
         const uint64_t vn = ((uint64_t)n0 << 32) | n1;
-        if (c_ctx && m <= CTX_N) {
-            // the context table's record of the row holds the suffix's position AND the 23 bases in front of it: one load instead of
-            // the suffix-array load followed by the text load (record layout: salt_device.h; side B is complete iff CTX_N <= p0 <= ctx_len)
+        if (c_ctx && m <= CTX_N_B) {
+            // the context table's record of the row holds the suffix's position AND the CTX_N_B bases in front of it: one load instead of
+            // the suffix-array load followed by the text load (salt_ctx_record.h; side B is complete iff CTX_N_B <= p0 <= ctx_len)
             const uint4 rec = c_ctx[row];
             const uint32_t p0c = rec.x == 0xFFFFFFFFu ? c_seq_len : rec.x;
-            if (p0c >= CTX_N && p0c <= ctx_len) {
+            if (p0c >= CTX_N_B && p0c <= ctx_len) {
                 n_aux += 1u << 10;
                 if (((vn >> (64 - reln - m)) & ((1ull << m) - 1ull)) != 0) return 0xFFFFFFFFu;
-                const uint64_t lo = ((uint64_t)rec.y | ((uint64_t)(rec.z & 0x3FFFu) << 32)) >> CTX_N, hi = ((uint64_t)(rec.z >> 14) | ((uint64_t)(rec.w & 0x0FFFFFFFu) << 18)) >> CTX_N;
+                const uint32_t lo = ctx_front_lo(rec), hi = ctx_front_hi(rec);
                 uint32_t rlo = 0, rhi = 0;
                 for (uint32_t u = 0; u < m; ++u) {                            // read base s + it - u faces genome base p0 - 1 - u
                     const uint32_t rel = s + (uint32_t)it - u - (wb << 4);
@@ -287,7 +287,7 @@ __device__ __forceinline__ uint32_t seed_resolve_unique(const uint32_t *__restri
                     rlo |= (code & 1u) << u; rhi |= (code >> 1) << u;
                 }
                 const uint32_t mk = (1u << m) - 1u;
-                return ((((uint32_t)lo ^ rlo) | ((uint32_t)hi ^ rhi)) & mk) == 0 ? p0c - m : 0xFFFFFFFFu;
+                return (((lo ^ rlo) | (hi ^ rhi)) & mk) == 0 ? p0c - m : 0xFFFFFFFFu;
             }
         }
         uint32_t p0 = c_sa[row];
@@ -667,17 +667,16 @@ struct CandArgs {                      // everything by value: a by-reference In
 };
 
 // The read's side of a context comparison for a seed that starts at read offset `off` (pm: the strand's one-hot words in LDS).
-// Lane t < CTX_N faces genome base s + ctx_k + t, i.e. read base off + ctx_k + t; lane CTX_N + u faces s - 1 - u, read base off - 1 - u.
+// Lane t faces the read base ctx_face gives plane bit t (salt_ctx_record.h).
 __device__ __forceinline__ CtxRead ctx_read(const uint32_t *pm, uint32_t L, uint32_t off, uint32_t ctx_k)
 {
-    const uint32_t t = lane_id();
-    const int p = t < CTX_N ? (int)(off + ctx_k + t) : (int)off - 1 - (int)(t - CTX_N);
-    const bool v = t < 2u * CTX_N && p >= 0 && p < (int)L;
+    const int p = ctx_face(lane_id(), off, ctx_a_start(ctx_k));
+    const bool v = p >= 0 && p < (int)L;
     const uint32_t nib = v ? (pm[(uint32_t)p >> 3] >> (4u * ((uint32_t)p & 7u))) & 15u : 0u;
     CtxRead rd;
-    rd.lo = __ballot(v && (nib & 0xAu) != 0);                // one-hot 1 << code: code bit 0 set for 2 and 8, bit 1 for 4 and 8
-    rd.hi = __ballot(v && (nib & 0xCu) != 0);
-    rd.use = __ballot(v && (nib == 1u || nib == 2u || nib == 4u || nib == 8u));     // N (15) matches everything: not counted
+    rd.lo = __ballot(v && ctx_nib_lo(nib));
+    rd.hi = __ballot(v && ctx_nib_hi(nib));
+    rd.use = __ballot(v && ctx_nib_use(nib));                // N (15) matches everything: not counted
     return rd;
 }
 // Not inlined (three call sites, ~1 400 instructions).  Its arguments are the same for all 64 lanes: passed by value they would be

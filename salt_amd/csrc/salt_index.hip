@@ -131,73 +131,31 @@ k_build_text(IndexView ix, uint32_t *__restrict__ out)
     }
 }
 
-// c_ctx (salt_device.h): one record per suffix-array row, from the expanded suffix array, the 2-bit text and the allele masks
-__global__ void __launch_bounds__(256)
-k_build_c_ctx(IndexView ix, uint32_t ctx_k, uint4 *__restrict__ out)
-{
-    const uint64_t n = (uint64_t)ix.c_seq_len + 1, stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t len = ix.c_seq_len < ix.ref_len ? ix.c_seq_len : ix.ref_len;      // positions both the text and the masks hold
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
-        const uint32_t sa = ix.c_sa[j];
-        const uint64_t s = sa == 0xFFFFFFFFu ? (uint64_t)ix.c_seq_len : (uint64_t)sa;
-        uint64_t lo = 0, hi = 0;
-        uint32_t ns[2] = { 0, 0 };
-        bool whole[2] = { s + ctx_k + CTX_N <= len, s >= CTX_N && s <= len };
-        for (int side = 0; side < 2; ++side) {
-            if (!whole[side]) { ns[side] = 3; continue; }
-            for (uint32_t t = 0; t < CTX_N; ++t) {
-                const uint64_t p = side == 0 ? s + ctx_k + t : s - 1 - t;
-                const uint32_t b = (ix.text[p >> 4] >> (30 - 2 * (uint32_t)(p & 15u))) & 3u;
-                const uint32_t mask = (ix.ref[p >> 3] >> (4 * (uint32_t)(p & 7u))) & 15u;
-                const uint32_t bit = side * CTX_N + t;
-                lo |= (uint64_t)(b & 1u) << bit; hi |= (uint64_t)(b >> 1) << bit;
-                ns[side] += mask != (1u << b);
-            }
-            if (ns[side] > 3) ns[side] = 3;
-        }
-        out[j] = ctx_pack(sa, lo, hi, ns[0], ns[1]);
-    }
-}
-
-// r_ctx: the same record for every row of the R index -- the genome around the position r_pos gives the row (the seed's first base): a
+// c_ctx and r_ctx (salt_ctx_record.h): one record per row of a table of genome positions -- the expanded suffix array (row 0, the empty
+// suffix, holds 0xFFFFFFFF and stands at c_seq_len) or r_pos, the position Rbwt_back_bwt_sa gives an R row (the seed's first base): a
 // paired-end mate of a repeat enumerates up to max_locate rows of every R interval too (alnse.c:538-595), and two thirds of the candidate
-// windows k_heavy_pe looked at came from there
+// windows k_heavy_pe looked at came from there.  From the table, the 2-bit text and the allele masks.
 __global__ void __launch_bounds__(256)
-k_build_r_ctx(IndexView ix, uint32_t ctx_k, uint4 *__restrict__ out)
+k_build_ctx(IndexView ix, const uint32_t *__restrict__ first, uint64_t n, uint64_t s_none, uint32_t ctx_k, uint4 *__restrict__ out)
 {
-    const uint64_t n = (uint64_t)ix.r_text_len + 1, stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t len = ix.c_seq_len < ix.ref_len ? ix.c_seq_len : ix.ref_len;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t len = ix.c_seq_len < ix.ref_len ? ix.c_seq_len : ix.ref_len;      // positions both the text and the masks hold
+    const uint32_t a_start = ctx_a_start(ctx_k);
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
-        const uint32_t rp = ix.r_pos[j];
-        const uint64_t s = rp;
-        uint64_t lo = 0, hi = 0;
-        uint32_t ns[2] = { 0, 0 };
-        bool whole[2] = { s + ctx_k + CTX_N <= len, s >= CTX_N && s <= len };
-        for (int side = 0; side < 2; ++side) {
-            if (!whole[side]) { ns[side] = 3; continue; }
-            for (uint32_t t = 0; t < CTX_N; ++t) {
-                const uint64_t p = side == 0 ? s + ctx_k + t : s - 1 - t;
-                const uint32_t b = (ix.text[p >> 4] >> (30 - 2 * (uint32_t)(p & 15u))) & 3u;
-                const uint32_t mask = (ix.ref[p >> 3] >> (4 * (uint32_t)(p & 7u))) & 15u;
-                const uint32_t bit = side * CTX_N + t;
-                lo |= (uint64_t)(b & 1u) << bit; hi |= (uint64_t)(b >> 1) << bit;
-                ns[side] += mask != (1u << b);
-            }
-            if (ns[side] > 3) ns[side] = 3;
-        }
-        out[j] = ctx_pack(rp, lo, hi, ns[0], ns[1]);
+        const uint32_t v = first[j];
+        out[j] = ctx_build(ix.text, ix.ref, len, v, v == 0xFFFFFFFFu ? s_none : (uint64_t)v, a_start);      // s_none: where a row without a position stands
     }
 }
 void launch_build_r_ctx(const IndexView &ix, uint32_t ctx_k, uint4 *out, hipStream_t st)
 {
     const uint64_t n = (uint64_t)ix.r_text_len + 1;
-    hipLaunchKernelGGL(k_build_r_ctx, dim3(stride_grid(n)), dim3(256), 0, st, ix, ctx_k, out);
+    hipLaunchKernelGGL(k_build_ctx, dim3(stride_grid(n)), dim3(256), 0, st, ix, ix.r_pos, n, (uint64_t)0xFFFFFFFFu, ctx_k, out);      // beyond the genome: bounds nothing
 }
 
 void launch_build_c_ctx(const IndexView &ix, uint32_t ctx_k, uint4 *out, hipStream_t st)
 {
     const uint64_t n = (uint64_t)ix.c_seq_len + 1;
-    hipLaunchKernelGGL(k_build_c_ctx, dim3(stride_grid(n)), dim3(256), 0, st, ix, ctx_k, out);
+    hipLaunchKernelGGL(k_build_ctx, dim3(stride_grid(n)), dim3(256), 0, st, ix, ix.c_sa, n, (uint64_t)ix.c_seq_len, ctx_k, out);
 }
 
 void launch_build_text(const IndexView &ix, uint32_t *out, hipStream_t st)
