@@ -202,6 +202,14 @@ int  salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const 
  * block).  Only the compressed bytes cross to the host.  A block of text that does not compress leaves as a stored block, 31 bytes larger
  * than its text; the workspace's buffers (and what it takes from the host_sam of salt_gpu_ws_reserve_text) allow for that. */
 int  salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on);
+/* BAM output (`salt --bam`): after salt_gpu_ws_set_sam_bam(ws, 1) the two text entry points write the block's records as BAM records (SAM
+ * specification 4.2; k_bam_len / k_bam_write) where they wrote SAM lines: one record per read or mate in input order, none for a skipped read
+ * and none for the paired-end driver's blank lines; NM in the smallest unsigned type that holds it, XV always as an array B:I; no file header
+ * (salt_bam_header of salt_host.h writes that).  The bytes equal salt_bam_from_sam of the SAM lines the same call would have returned.
+ * Whether they then pass through the device compressor is still salt_gpu_ws_set_sam_bgzf's decision: with it *sam holds BGZF blocks cut
+ * every 32 640 bytes of the record stream (records straddle blocks, as the format allows), without it the raw records.  A read name longer
+ * than 254 bytes cannot be a BAM name: the call fails with SALT_E_INVAL and a message that starts with "BAM:". */
+int  salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on);
 /* The same kernels on their own, host buffers in and out: text[0 .. n_bytes) -> ceil(n_bytes / 32640) BGZF blocks in out, *out_bytes of them
  * (0 for an empty text; no end-of-file block).  The same text gives the same bytes on every run.  SALT_E_CAPACITY when out_cap is too
  * small: n_bytes + 31 bytes per block is the exact bound, 65 536 bytes per block always suffice. */

@@ -56,6 +56,24 @@ int salt_sam_pe(const salt_index_t *ix, const salt_sam_opt_t *opt, const salt_pe
                 const uint8_t *const seq[2], const int32_t l_seq[2], const char *const qual[2],
                 const salt_result_t *q, char *buf, size_t cap);
 
+/* BAM (SAM specification 4.2), the uncompressed bytes that `salt --bam` wraps in BGZF blocks.  Written from the format definition, without
+ * any code of the device's record kernels (k_bam_len / k_bam_write): it is the model their bytes are compared with, and it encodes whatever
+ * does not come from them (the host pipeline, the blocks behind a hand-over, a libsalt_gpu without salt_gpu_ws_set_sam_bam, SALT_BAM_HOST=1).
+ *   salt_bam_header    "BAM\1", l_text, header_text as given (no NUL padding), n_ref and per sequence of the index l_name, name NUL, l_ref
+ *   salt_bam_from_sam  one record per non-empty line of this program's own SAM records (no header lines), in order.  refID from RNAME
+ *                      ('*': -1), pos = POS - 1, bin = reg2bin(pos, pos + reference length of the CIGAR, 1 without one), next_refID from
+ *                      RNEXT ('=': refID), QUAL - 33; tags in the line's order: Z verbatim, integers in the smallest unsigned type that
+ *                      holds them (C, S, I; c, s, i below zero), XV always as an array B:I of its comma-separated offsets.
+ * Both return the bytes written, SALT_BAM_E_CAP when cap is too small (SALT_BAM_BOUND(n) always suffices for salt_bam_from_sam) or
+ * SALT_BAM_E_INVAL with salt_host_last_error() set: a line that is no SAM record of this program, an RNAME the index does not hold, a read
+ * name longer than SALT_BAM_MAX_NAME bytes (l_read_name is one byte and counts the NUL).  *n_records, when given: records written. */
+#define SALT_BAM_MAX_NAME 254
+#define SALT_BAM_E_INVAL (-1)
+#define SALT_BAM_E_CAP   (-2)
+#define SALT_BAM_BOUND(n_sam_bytes) (4 * (uint64_t)(n_sam_bytes) + 64)
+int64_t salt_bam_header(const salt_index_t *ix, const char *header_text, size_t n_text, uint8_t *out, size_t cap);
+int64_t salt_bam_from_sam(const salt_index_t *ix, const char *sam, size_t n, uint8_t *out, size_t cap, uint64_t *n_records);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

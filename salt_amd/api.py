@@ -103,6 +103,12 @@ def host_lib():
                                     ctypes.c_int32, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         lib.salt_lkt_build.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
         lib.salt_cigar_text.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+        lib.salt_index_seq.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_char_p)]
+        lib.salt_bam_header.restype = ctypes.c_int64
+        lib.salt_bam_header.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        lib.salt_bam_from_sam.restype = ctypes.c_int64
+        lib.salt_bam_from_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
         _host = lib
     return _host
 
@@ -245,6 +251,16 @@ class Index:
             raise SaltError("SAM header too large")
         return buf.raw[:n]
 
+    def contigs(self):
+        """[(offset in the concatenated genome, length, name)] of <P>.C.ann: what @SQ, RNAME and BAM's reference list come from."""
+        lib = host_lib()
+        out = []
+        for i in range(lib.salt_index_n_seqs(self._h)):
+            off, ln, nm = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_char_p()
+            lib.salt_index_seq(self._h, i, ctypes.byref(off), ctypes.byref(ln), ctypes.byref(nm))
+            out.append((off.value, ln.value, nm.value))
+        return out
+
     def pac(self):
         n = ctypes.c_uint64()
         p = host_lib().salt_index_pac(self._h, ctypes.byref(n))
@@ -378,6 +394,38 @@ def bgzf_deflate(data, device=0):
     return out.raw[:n.value]
 
 
+BAM_MAX_NAME = 254      # bytes of a BAM read name (l_read_name is one byte and counts the NUL)
+
+
+def bam_header(index, header_text):
+    """The uncompressed head of a BAM file (SAM spec 4.2): magic, header_text as given, the reference list of the index's contigs."""
+    h = host_lib()
+    header_text = bytes(header_text)
+    cap = len(header_text) + 64 + sum(len(nm) + 16 for _, _, nm in index.contigs())
+    out = ctypes.create_string_buffer(cap)
+    n = h.salt_bam_header(index._h, header_text, len(header_text), out, cap)
+    if n < 0:
+        raise SaltError("BAM header: %s" % (h.salt_host_last_error().decode() if n == -1 else "buffer too small"))
+    return out.raw[:n]
+
+
+def bam_from_sam(index, sam):
+    """This program's own SAM records (no header lines) -> the BAM records `salt --bam` holds for them, by the host encoder
+    (salt_bam_from_sam): one per non-empty line.  It is also the model the device's record kernels are compared with."""
+    h = host_lib()
+    sam = bytes(sam)
+    cap = 4 * len(sam) + 64
+    out = ctypes.create_string_buffer(cap)
+    n = h.salt_bam_from_sam(index._h, sam, len(sam), out, cap, None)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode() if n == -1 else "BAM records larger than their bound")
+    return out.raw[:n]
+
+
+class _TextOpt(ctypes.Structure):
+    _fields_ = [("print_xa_cigar", ctypes.c_int32), ("print_nm_md", ctypes.c_int32), ("rg_id", ctypes.c_char_p)]
+
+
 KERNELS = ("k_pack", "k_seed", "k_light", "k_heavy", "k_gap", "k_gapfin", "k_cigar", "k_pair", "k_sw", "k_pe_final")
 
 
@@ -500,6 +548,50 @@ class GpuAligner:
             pac, l_pac = index.pac()
             _gpu_check(gpu_lib().salt_gpu_index_set_pac(self._ix, pac, l_pac))
             self._pac_set = True
+
+    def set_contigs(self, index):
+        """The contig table the text entry points print RNAME / POS from (once per device index)."""
+        cs = index.contigs()
+        offs = (ctypes.c_int64 * len(cs))(*[c[0] for c in cs])
+        names = (ctypes.c_char_p * len(cs))(*[c[2] for c in cs])
+        lib = gpu_lib()
+        lib.salt_gpu_index_set_contigs.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_index_set_contigs(self._ix, len(cs), offs, names))
+
+    def set_sam_bgzf(self, on=True):
+        """The text entry points return BGZF blocks (deflated on the device) instead of the bytes themselves."""
+        gpu_lib().salt_gpu_ws_set_sam_bgzf.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _gpu_check(gpu_lib().salt_gpu_ws_set_sam_bgzf(self._ws, 1 if on else 0))
+
+    def set_sam_bam(self, on=True):
+        """The text entry points write BAM records (k_bam_len / k_bam_write) instead of SAM lines."""
+        gpu_lib().salt_gpu_ws_set_sam_bam.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _gpu_check(gpu_lib().salt_gpu_ws_set_sam_bam(self._ws, 1 if on else 0))
+
+    def align_se_text(self, opt, fastq):
+        """One block of whole 4-line FASTQ records -> (the block's SAM lines, or what set_sam_bam / set_sam_bgzf make of them; reads)."""
+        lib = gpu_lib()
+        lib.salt_gpu_align_se_text.argtypes = [ctypes.c_void_p, ctypes.POINTER(_AlnOpt), ctypes.POINTER(_TextOpt), ctypes.c_char_p, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        fastq = bytes(fastq)
+        co, to = opt._c(), _TextOpt(opt.print_xa_cigar, opt.print_nm_md, opt.rg_id.encode() if opt.rg_id else None)
+        out, n, reads = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint32()
+        _gpu_check(lib.salt_gpu_align_se_text(self._ws, ctypes.byref(co), ctypes.byref(to), fastq, len(fastq), ctypes.byref(out), ctypes.byref(n), ctypes.byref(reads)))
+        return ctypes.string_at(out.value, n.value) if n.value else b"", reads.value
+
+    def align_pe_text(self, opt, index, fastq1, fastq2):
+        """Two blocks with the mates of the same pairs -> (both records of every pair in order; pairs)."""
+        lib = gpu_lib()
+        lib.salt_gpu_align_pe_text.argtypes = [ctypes.c_void_p, ctypes.POINTER(_AlnOpt), ctypes.POINTER(_PeOpt), ctypes.POINTER(_TextOpt), ctypes.c_char_p,
+                                               ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_uint32)]
+        self.set_pac(index)
+        fastq1, fastq2 = bytes(fastq1), bytes(fastq2)
+        co, pe, to = opt._c(), opt._pe(), _TextOpt(opt.print_xa_cigar, opt.print_nm_md, opt.rg_id.encode() if opt.rg_id else None)
+        out, n, pairs = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint32()
+        _gpu_check(lib.salt_gpu_align_pe_text(self._ws, ctypes.byref(co), ctypes.byref(pe), ctypes.byref(to), fastq1, len(fastq1), fastq2, len(fastq2),
+                                              ctypes.byref(out), ctypes.byref(n), ctypes.byref(pairs)))
+        return ctypes.string_at(out.value, n.value) if n.value else b"", pairs.value
 
     def align_pe_resident(self, opt, index, n_pairs, max_read_len, d_seqs, d_offs, d_results, stream=0):
         lib = gpu_lib()

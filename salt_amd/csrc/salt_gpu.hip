@@ -62,6 +62,8 @@ struct salt_gpu_ws {
     bool h_sam_owned = true;                                                 // false: the caller's page-locked buffer (salt_gpu_ws_reserve_text)
     // salt_gpu_ws_set_sam_bgzf: the SAM block leaves as BGZF blocks (allocated on first use, grown on demand)
     bool sam_bgzf = false;
+    // salt_gpu_ws_set_sam_bam: the text entry points write BAM records (k_bam_len / k_bam_write) where they wrote SAM lines
+    bool sam_bam = false;
     uint32_t *d_bz_slots = nullptr, *d_bz_sizes = nullptr; unsigned long long *d_bz_offs = nullptr; uint8_t *d_bz_out = nullptr; uint64_t bz_blocks_cap = 0;
     char *h_bz = nullptr; uint64_t h_bz_cap = 0;                             // page-locked, only for a compressed block that outgrows h_sam
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
@@ -575,7 +577,7 @@ extern "C" int salt_gpu_ws_reserve_text(salt_gpu_ws_t *ws, const salt_aln_opt_t 
     HIPCHK(hipSetDevice(ws->ix->device));
     hipStream_t st = ws->stream;
     REGROW(ws->d_raw, ws->raw_cap, max_block_bytes + 64, uint8_t);
-    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits
+    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
     REGROW(ws->d_tile, ws->tile_cap, ws->raw_cap / FQ_TILE + 4, uint32_t);
     {
         const size_t need = text_scan_bytes(std::max<uint64_t>(ws->tile_cap, (uint64_t)ws->max_reads + 2));
@@ -665,6 +667,15 @@ extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on)
     return SALT_OK;
 }
 
+static const char *const BAM_NAME_ERROR = "BAM: a read name in this block is longer than 254 bytes, the most a BAM record holds (its length byte counts the NUL)";
+
+extern "C" int salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    ws->sam_bam = on != 0;
+    return SALT_OK;
+}
+
 extern "C" int salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes)
 {
     if (!out_bytes || (n_bytes && (!text || !out))) return fail(SALT_E_INVAL, "null argument");
@@ -709,7 +720,7 @@ extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     // ---- the raw block and its lines ----
     REGROW(ws->d_raw, ws->raw_cap, n_bytes + 64, uint8_t);
     const uint64_t n_tiles = (n_bytes + FQ_TILE - 1) / FQ_TILE;
-    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits
+    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
     {   // tile counters + scan scratch follow the raw capacity
         const uint64_t tiles_cap = ws->raw_cap / FQ_TILE + 4;
         REGROW(ws->d_tile, ws->tile_cap, tiles_cap, uint32_t);
@@ -771,11 +782,14 @@ extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
     d.pe = 0; d.min_tlen = d.max_tlen = 0; d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(ctl[1]);
     if (to->rg_id && rg.empty()) return fail(SALT_E_INVAL, "empty read group id");
-    HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
-    uint32_t total = 0; unsigned long long total64 = 0;
+    if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
+    else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
+    uint32_t total = 0, bam_err = 0; unsigned long long total64 = 0;
     HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
+    if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (bam_err) return fail(SALT_E_INVAL, BAM_NAME_ERROR);
     if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
     mark();
     if ((uint64_t)total + 64 > ws->sam_cap) {
@@ -786,7 +800,8 @@ extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
         ws->sam_cap = want;
     }
     mark();
-    HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
     const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
     if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
     else {
@@ -825,7 +840,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     const uint64_t b2 = (n1 + 3) & ~3ull;                      // block 2 behind block 1, on a word boundary
     REGROW(ws->d_raw, ws->raw_cap, b2 + n2 + 64, uint8_t);
     const uint64_t t1 = (n1 + FQ_TILE - 1) / FQ_TILE, t2 = (n2 + FQ_TILE - 1) / FQ_TILE;
-    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits
+    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
     {
         REGROW(ws->d_tile, ws->tile_cap, ws->raw_cap / FQ_TILE + 16, uint32_t);
         const size_t need = text_scan_bytes(std::max<uint64_t>(ws->tile_cap, (uint64_t)ws->max_reads + 2));
@@ -888,14 +903,17 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     d.text = ix->view.text; d.ref = ix->view.ref; d.xa_cigar = to->print_xa_cigar; d.nm_md = to->print_nm_md;
     d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
     d.pe = 1; d.min_tlen = pe->min_tlen; d.max_tlen = pe->max_tlen; d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(ctl[1]);
-    HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
-    uint32_t total = 0, n_over = 0; unsigned long long total64 = 0;
+    if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
+    else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
+    uint32_t total = 0, n_over = 0, bam_err = 0; unsigned long long total64 = 0;
     HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
+    if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
     if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W) "
                                              "or a CIGAR of more than SALT_MAX_CIGAR_OPS operations: the rows of this batch would differ from the reference's");
+    if (bam_err) return fail(SALT_E_INVAL, BAM_NAME_ERROR);
     if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
     if ((uint64_t)total + 64 > ws->sam_cap) {
         hipFree(ws->d_sam); ws->d_sam = nullptr; if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam); ws->h_sam = nullptr; ws->sam_cap = 0; ws->h_sam_owned = true;
@@ -904,7 +922,8 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
         HIPCHK(hipHostMalloc((void **)&ws->h_sam, want, hipHostMallocDefault));
         ws->sam_cap = want;
     }
-    HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
     const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
     if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
     else {

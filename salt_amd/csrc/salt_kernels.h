@@ -199,6 +199,9 @@ hipError_t launch_text_scan(uint32_t *v, uint32_t n_plus_1, void *tmp, size_t tm
 hipError_t launch_fq_codes(const uint8_t *raw, const FqRec *rec, const uint32_t *offs, uint32_t n_rec, uint8_t *seqs, hipStream_t st);
 hipError_t launch_sam_len(const SamDev &d, uint32_t n, uint32_t *off, unsigned long long *total64, void *tmp, size_t tmp_bytes, hipStream_t st);   // *total64: all bytes, 64-bit
 hipError_t launch_sam_write(const SamDev &d, uint32_t n, const uint32_t *off, char *out, hipStream_t st);
+// the same block as BAM records (salt --bam): same slots, same scan; *err != 0: a read name longer than 254 bytes
+hipError_t launch_bam_len(const SamDev &d, uint32_t n, uint32_t *off, unsigned long long *total64, uint32_t *err, void *tmp, size_t tmp_bytes, hipStream_t st);
+hipError_t launch_bam_write(const SamDev &d, uint32_t n, const uint32_t *off, char *out, hipStream_t st);
 static const uint32_t FQ_TILE = 1024;                                          // bytes per newline-count tile (k_fq_count)
 
 // ---- BGZF output (salt_bgzf.hip) ----

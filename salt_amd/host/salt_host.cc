@@ -433,3 +433,205 @@ extern "C" int salt_sam_pe(const salt_index_t *ix, const salt_sam_opt_t *opt, co
     }
     return o.done();
 }
+
+// ---------------------------------------------------------------------------------------------
+// BAM records (SAM specification 4.2) from SAM lines: the host encoder of `salt --bam`, and the model of the device's
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct Bytes {
+    std::vector<uint8_t> b;
+    void u8(uint32_t v) { b.push_back((uint8_t)v); }
+    void u16(uint32_t v) { u8(v); u8(v >> 8); }
+    void u32(uint32_t v) { u16(v); u16(v >> 16); }
+    void text(const char *p, const char *e) { b.insert(b.end(), p, e); }
+    void set32(size_t at, uint32_t v) { for (int i = 0; i < 4; ++i) b[at + (size_t)i] = (uint8_t)(v >> (8 * i)); }
+};
+
+// the specification's bin of the half-open interval [beg, end)
+uint32_t reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+bool field_int(const char *p, const char *e, int64_t *v)
+{
+    if (p == e) return false;
+    const bool neg = *p == '-';
+    if (neg || *p == '+') ++p;
+    if (p == e || e - p > 18) return false;
+    int64_t x = 0;
+    for (; p < e; ++p) { if (*p < '0' || *p > '9') return false; x = 10 * x + (*p - '0'); }
+    *v = neg ? -x : x;
+    return true;
+}
+
+void bam_int_tag(Bytes &o, int64_t v)
+{
+    if (v >= 0) {
+        if (v <= 0xFF) { o.u8('C'); o.u8((uint32_t)v); }
+        else if (v <= 0xFFFF) { o.u8('S'); o.u16((uint32_t)v); }
+        else { o.u8('I'); o.u32((uint32_t)v); }
+    } else if (v >= -128) { o.u8('c'); o.u8((uint32_t)v); }
+    else if (v >= -32768) { o.u8('s'); o.u16((uint32_t)v); }
+    else { o.u8('i'); o.u32((uint32_t)v); }
+}
+
+struct RefIds {
+    std::vector<std::pair<std::string, int32_t>> by_name;       // sorted; the first of equal names wins, as a header's reader would take it
+    explicit RefIds(const salt_index *ix)
+    {
+        for (size_t i = 0; i < ix->anns.size(); ++i) by_name.emplace_back(ix->anns[i].name, (int32_t)i);
+        std::stable_sort(by_name.begin(), by_name.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    }
+    int32_t find(const char *p, const char *e) const
+    {
+        const std::string key(p, e);
+        auto it = std::lower_bound(by_name.begin(), by_name.end(), key, [](const auto &a, const std::string &k) { return a.first < k; });
+        return it != by_name.end() && it->first == key ? it->second : -2;
+    }
+};
+
+// one line [l, e) without its newline -> one record appended to o; false with g_err set
+bool bam_record_of_line(const RefIds &ids, const char *l, const char *e, Bytes &o)
+{
+    const char *f[12]; int nf = 0;                                 // starts of the 11 mandatory fields and of the tags
+    f[nf++] = l;
+    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
+    auto bad = [&](const char *why) { g_err = std::string("BAM: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return false; };
+    if (nf < 11) return bad("fewer than 11 fields");
+    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };      // end of field k (the tags: all of them)
+    const size_t l_name = (size_t)(fe(0) - f[0]);
+    if (l_name == 0) return bad("empty read name");
+    if (l_name > SALT_BAM_MAX_NAME) {
+        g_err = "BAM: read name of " + std::to_string(l_name) + " bytes ('" + std::string(l, 40) + "...'): a BAM read name holds at most " +
+                std::to_string(SALT_BAM_MAX_NAME) + " bytes";
+        return false;
+    }
+    int64_t flag, pos1, mapq, pnext1, tlen;
+    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || !field_int(f[7], fe(7), &pnext1) ||
+        !field_int(f[8], fe(8), &tlen) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 || pos1 < 0 || pos1 > 0x7FFFFFFF || pnext1 < 0 || pnext1 > 0x7FFFFFFF ||
+        tlen < INT32_MIN || tlen > INT32_MAX) return bad("a numeric field is no number of its range");
+    int32_t rid = -1, nrid = -1;
+    if (!(fe(2) - f[2] == 1 && *f[2] == '*') && (rid = ids.find(f[2], fe(2))) < -1) return bad("RNAME is no sequence of the index");
+    if (fe(6) - f[6] == 1 && *f[6] == '=') nrid = rid;
+    else if (!(fe(6) - f[6] == 1 && *f[6] == '*') && (nrid = ids.find(f[6], fe(6))) < -1) return bad("RNEXT is no sequence of the index");
+    // CIGAR
+    std::vector<uint32_t> cig;
+    int64_t ref_len = 0;
+    if (!(fe(5) - f[5] == 1 && *f[5] == '*')) {
+        uint64_t n = 0; bool digits = false;
+        for (const char *p = f[5]; p < fe(5); ++p) {
+            if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
+            const char *ops = "MIDNSHP=X", *w = strchr(ops, *p);
+            if (!w || !digits) return bad("malformed CIGAR");
+            const uint32_t op = (uint32_t)(w - ops);
+            cig.push_back((uint32_t)n << 4 | op);
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += (int64_t)n;
+            n = 0; digits = false;
+        }
+        if (digits || cig.empty() || cig.size() > 0xFFFF) return bad("malformed CIGAR");
+    }
+    const int64_t pos = pos1 - 1;
+    const uint32_t bin = pos < 0 ? 4680u : reg2bin(pos, pos + (ref_len > 0 ? ref_len : 1));
+    const char *seq = f[9], *qual = f[10];
+    size_t l_seq = (size_t)(fe(9) - seq);
+    if (l_seq == 1 && *seq == '*') l_seq = 0;
+    const size_t l_qual = (size_t)(fe(10) - qual);
+    const bool no_qual = l_qual == 1 && *qual == '*' && l_seq != 1;
+    if (!no_qual && l_qual != l_seq) return bad("SEQ and QUAL differ in length");
+    const size_t at = o.b.size();
+    o.u32(0);                                                      // block_size, set below
+    o.u32((uint32_t)rid); o.u32((uint32_t)(int32_t)pos);
+    o.u8((uint32_t)l_name + 1); o.u8((uint32_t)mapq); o.u16(bin);
+    o.u16((uint32_t)cig.size()); o.u16((uint32_t)flag);
+    o.u32((uint32_t)l_seq);
+    o.u32((uint32_t)nrid); o.u32((uint32_t)(int32_t)(pnext1 - 1)); o.u32((uint32_t)(int32_t)tlen);
+    o.text(f[0], fe(0)); o.u8(0);
+    for (uint32_t c : cig) o.u32(c);
+    auto code = [](char c) -> uint32_t {                           // "=ACMGRSVTWYHKDBN"
+        switch (c) { case '=': return 0; case 'A': case 'a': return 1; case 'C': case 'c': return 2; case 'M': case 'm': return 3; case 'G': case 'g': return 4;
+                     case 'R': case 'r': return 5; case 'S': case 's': return 6; case 'V': case 'v': return 7; case 'T': case 't': return 8; case 'W': case 'w': return 9;
+                     case 'Y': case 'y': return 10; case 'H': case 'h': return 11; case 'K': case 'k': return 12; case 'D': case 'd': return 13; case 'B': case 'b': return 14;
+                     default: return 15; }
+    };
+    for (size_t i = 0; i < l_seq; i += 2) o.u8(code(seq[i]) << 4 | (i + 1 < l_seq ? code(seq[i + 1]) : 0u));
+    for (size_t i = 0; i < l_seq; ++i) {
+        if (no_qual) { o.u8(0xFF); continue; }
+        if ((unsigned char)qual[i] < 33 || (unsigned char)qual[i] > 126) return bad("a quality character outside '!' .. '~'");
+        o.u8((uint32_t)((unsigned char)qual[i] - 33));
+    }
+    // tags: TAG:TYPE:VALUE
+    for (const char *t = nf > 11 ? f[11] : e; t < e; ) {
+        const char *te = (const char *)memchr(t, '\t', (size_t)(e - t));
+        if (!te) te = e;
+        if (te - t < 5 || t[2] != ':' || t[4] != ':') return bad("malformed tag");
+        const char *v = t + 5;
+        o.u8((unsigned char)t[0]); o.u8((unsigned char)t[1]);
+        if (t[0] == 'X' && t[1] == 'V' && t[3] == 'i') {           // the offsets of the listed alleles: one tag, one type, however many there are
+            std::vector<uint32_t> items;
+            for (const char *p = v; p <= te; ) {
+                const char *c = (const char *)memchr(p, ',', (size_t)(te - p));
+                if (!c) c = te;
+                int64_t x;
+                if (!field_int(p, c, &x) || x < 0 || x > 0xFFFFFFFFll) return bad("malformed XV list");
+                items.push_back((uint32_t)x);
+                p = c + 1;
+            }
+            o.u8('B'); o.u8('I'); o.u32((uint32_t)items.size());
+            for (uint32_t x : items) o.u32(x);
+        } else if (t[3] == 'Z') { o.u8('Z'); o.text(v, te); o.u8(0); }
+        else if (t[3] == 'i') {
+            int64_t x;
+            if (!field_int(v, te, &x) || x < INT32_MIN || x > 0xFFFFFFFFll) return bad("malformed integer tag");
+            bam_int_tag(o, x);
+        } else return bad("a tag type this program does not write");
+        t = te + 1;
+    }
+    o.set32(at, (uint32_t)(o.b.size() - at - 4));
+    return true;
+}
+
+} // namespace
+
+extern "C" int64_t salt_bam_header(const salt_index_t *ix, const char *header_text, size_t n_text, uint8_t *out, size_t cap)
+{
+    if (!ix || (!header_text && n_text) || n_text > 0x7FFFFFFFu) { g_err = "BAM: bad header arguments"; return SALT_BAM_E_INVAL; }
+    Bytes o;
+    o.u8('B'); o.u8('A'); o.u8('M'); o.u8(1);
+    o.u32((uint32_t)n_text); o.text(header_text, header_text + n_text);
+    o.u32((uint32_t)ix->anns.size());
+    for (const Ann &a : ix->anns) { o.u32((uint32_t)a.name.size() + 1); o.text(a.name.data(), a.name.data() + a.name.size()); o.u8(0); o.u32((uint32_t)a.len); }
+    if (o.b.size() > cap || !out) return SALT_BAM_E_CAP;
+    memcpy(out, o.b.data(), o.b.size());
+    return (int64_t)o.b.size();
+}
+
+extern "C" int64_t salt_bam_from_sam(const salt_index_t *ix, const char *sam, size_t n, uint8_t *out, size_t cap, uint64_t *n_records)
+{
+    if (n_records) *n_records = 0;
+    if (!ix || (!sam && n) || (!out && cap)) { g_err = "BAM: null argument"; return SALT_BAM_E_INVAL; }
+    const RefIds ids(ix);
+    Bytes rec;
+    size_t w = 0; uint64_t n_rec = 0;
+    for (const char *l = sam, *end = sam + n; l < end; ) {
+        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
+        if (!e) e = end;
+        if (e > l) {                                               // (a skipped read's empty line, the paired-end driver's blank lines: no record)
+            rec.b.clear();
+            if (!bam_record_of_line(ids, l, e, rec)) return SALT_BAM_E_INVAL;
+            if (w + rec.b.size() > cap) return SALT_BAM_E_CAP;
+            memcpy(out + w, rec.b.data(), rec.b.size());
+            w += rec.b.size(); ++n_rec;
+        }
+        l = e + 1;
+    }
+    if (n_records) *n_records = n_rec;
+    return (int64_t)w;
+}

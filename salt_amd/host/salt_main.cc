@@ -7,7 +7,8 @@
 //   formatter threads (-t) : SAM text per read                              (aln_samse, sam.c:87-182)
 //   writer : records in input order                                         (the puts() loop, alnse.c:1433-1439)
 // Extra long options (not in the reference): --gpus N (default 1); --bgzf: everything written to stdout is one BGZF stream (blocked gzip,
-// htslib's .sam.gz container), the SAM blocks deflated on the device before they cross to the host.
+// htslib's .sam.gz container), the SAM blocks deflated on the device before they cross to the host; --bam: the stream is a BAM file -- the same
+// container around binary records (SAM spec 4.2), which the device writes in place of the SAM text.
 // Flags the reference parses but ignores stay ignored (-n -e -M -O -E -l -X).  -p <mate1> <mate2>: paired end
 // (alnpe_core, Align_src/alnpe.c:530-661) through salt_gpu_align_pe.
 #include "../../include/salt_host.h"
@@ -37,6 +38,8 @@
 // Taken weakly: `salt` also links and runs against a libsalt_gpu without the device compressor (an older build, the tests' stub), and
 // --bgzf then deflates on the host.
 extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on) __attribute__((weak));
+// Likewise the device's BAM record kernels: without them --bam encodes the records on the host, from the SAM text (salt_bam_from_sam).
+extern "C" int salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on) __attribute__((weak));
 
 namespace {
 
@@ -383,11 +386,40 @@ uint64_t bgzf_text_bytes(const char *blocks, uint64_t n)
     return text;
 }
 
+// --bam: the records come from the device's BAM kernels on the text path (salt_gpu_ws_set_sam_bam), deflated behind them like SAM text;
+// everywhere else the SAM text of a block or batch becomes records here (salt_bam_from_sam), on the thread that deflates it next.
+struct BamRun {
+    bool on = false, device = false;                         // device: the text path's workspaces write the records
+    std::atomic<bool> host_records{ false };                 // records (not only the header) were encoded on the host
+    const salt_index_t *ix = nullptr;
+} g_bam;
+
+// SAM lines -> BAM records in `out`; false with the reason on stderr (a read name past the format's limit)
+bool bam_of_sam(const char *sam, size_t n, std::string &out)
+{
+    int64_t w = SALT_BAM_E_CAP;
+    for (size_t cap = 2 * n + 4096; w == SALT_BAM_E_CAP && cap <= SALT_BAM_BOUND(n) + 2 * n + 4096; cap *= 2) {
+        out.resize(cap);
+        w = salt_bam_from_sam(g_bam.ix, sam, n, reinterpret_cast<uint8_t *>(&out[0]), cap, nullptr);
+    }
+    if (w < 0) { fprintf(stderr, "[salt] %s\n", w == SALT_BAM_E_CAP ? "BAM: records larger than their bound" : salt_host_last_error()); return false; }
+    out.resize((size_t)w);
+    g_bam.host_records = true;
+    return true;
+}
+
 // a batch of the host pipeline: its SAM pieces become BGZF blocks, cut over the whole batch and deflated by the worker's helper threads
 bool bgzf_batch(std::vector<std::string> &pieces, Pool &pool)
 {
     std::string all;
     size_t n = 0;
+    if (g_bam.on) {                                          // every piece holds whole lines: records piece by piece, side by side
+        std::vector<std::string> rec(pieces.size());
+        std::atomic<bool> good{ true };
+        pool.parallel([&](int t) { for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)pool.n) if (!bam_of_sam(pieces[i].data(), pieces[i].size(), rec[i])) good = false; });
+        if (!good) return false;
+        pieces.swap(rec);
+    }
     for (const std::string &p : pieces) n += p.size();
     all.reserve(n);
     for (const std::string &p : pieces) all += p;
@@ -408,6 +440,11 @@ bool bgzf_batch(std::vector<std::string> &pieces, Pool &pool)
 // a block of the text path, before it is written: from the device it is BGZF already; otherwise it becomes BGZF here (zbuf: the worker's own)
 bool bgzf_text_block(const char *&sam, uint64_t &sam_bytes, std::string &zbuf)
 {
+    std::string rec;
+    if (g_bam.on && !g_bam.device) {
+        if (!bam_of_sam(sam, (size_t)sam_bytes, rec)) return false;
+        sam = rec.data(); sam_bytes = rec.size();
+    }
     if (g_bgzf.device) g_bgzf.text_bytes += bgzf_text_bytes(sam, sam_bytes);
     else {
         zbuf.clear();
@@ -429,6 +466,11 @@ void bgzf_finish()
     const bool dev = g_bgzf.device, host = g_bgzf.host_blocks;
     fprintf(stderr, "[salt] BGZF output: %s deflate%s, %llu -> %llu bytes\n", dev ? "device" : "host", dev && host ? " (host deflate behind the hand-over)" : "",
             (unsigned long long)g_bgzf.text_bytes.load(), (unsigned long long)g_bgzf.file_bytes.load());
+    if (g_bam.on) {
+        const bool bd = g_bam.device, bh = g_bam.host_records;
+        fprintf(stderr, "[salt] BAM output: %s records%s, %llu -> %llu bytes\n", bd ? "device" : "host", bd && bh ? " (host records behind the hand-over)" : "",
+                (unsigned long long)g_bgzf.text_bytes.load(), (unsigned long long)g_bgzf.file_bytes.load());
+    }
 }
 
 double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + ts.tv_nsec * 1e-9; }
@@ -451,6 +493,8 @@ int usage()
             "           -b, --max_tlen      <int>    max template length [550]\n"
             "               --gpus          <int>    GPUs to shard batches over [1]\n"
             "               --bgzf                   write the SAM stream as BGZF blocks (.sam.gz), deflated on the GPU [False]\n"
+            "               --bam                    write BAM: binary records from the GPU inside BGZF blocks (implies --bgzf;\n"
+            "                                        read names of up to 254 bytes) [False]\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -696,7 +740,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
             const double tw_start = now(); int n_calls = 0; double t_first = 0, t_rest = 0;
             uint32_t ws_reads = max_reads;
             std::string zbuf;                                             // --bgzf with the host compressor: this worker's blocks
-            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) ||
+            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) ||
                 (head_read_len && salt_gpu_ws_reserve_text(ws, &ao, R.chunk + TEXT_SLACK, (uint32_t)(ws_reads / 1.3), head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
                 fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
             }
@@ -767,8 +811,10 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                     salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = worst_reads;
                     grc = salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws);
                     if (!grc && g_bgzf.device) grc = salt_gpu_ws_set_sam_bgzf(ws, 1);
+                    if (!grc && g_bam.device) grc = salt_gpu_ws_set_sam_bam(ws, 1);
                     if (!grc) grc = salt_gpu_align_se_text(ws, &ao, &to, buf + beg2, end - beg2, &sam, &sam_bytes, &n_reads);
                 }
+                if (grc == SALT_E_INVAL && g_bam.device && strncmp(salt_gpu_last_error(), "BAM:", 4) == 0) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 if (grc == SALT_E_INVAL) {
                     // not strict 4-line FASTQ in this chunk: when the blocks before it are out, the host parser continues from its first record
                     const std::string why = salt_gpu_last_error();
@@ -784,7 +830,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 t_gpu = t_gpu + (now() - tg0);
                 if (n_calls++ == 0) t_first = now() - tg0; else t_rest += now() - tg0;
-                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] zlib failed on a SAM block\n"); set_failed(); break; }
+                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
                 // block k is written when block k - 1 has been
                 {
                     std::unique_lock<std::mutex> lk(R.mu);
@@ -973,7 +1019,7 @@ static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const
             salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk];
             pin_to_device_node(wk / P.wpg);
             std::string zbuf;
-            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) ||
+            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) ||
                 (P.head_read_len && salt_gpu_ws_reserve_text(ws, &ao, P.in_cap, P.max_reads, P.head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
                 fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
             }
@@ -1010,10 +1056,11 @@ static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const
                 const char *sam = nullptr; uint64_t sam_bytes = 0; uint32_t n_pairs = 0;
                 double tg0 = now();
                 const int grc = salt_gpu_align_pe_text(ws, &ao, &po, &to, buf, m1, buf + b2, m2, &sam, &sam_bytes, &n_pairs);
+                if (grc == SALT_E_INVAL && g_bam.device && strncmp(salt_gpu_last_error(), "BAM:", 4) == 0) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 if (grc == SALT_E_INVAL) { fall_back(k, salt_gpu_last_error()); break; }
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 t_gpu = t_gpu + (now() - tg0);
-                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] zlib failed on a SAM block\n"); set_failed(); break; }
+                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
                 {
                     std::unique_lock<std::mutex> lk(wmu);
                     wcv.wait(lk, [&] { return failed.load() || fallback.load() || written == k; });
@@ -1065,7 +1112,7 @@ int main(int argc, char **argv)
         { "threads", 1, 0, 't' }, { "num", 1, 0, 'n' }, { "help", 0, 0, 'h' }, { "pe", 0, 0, 'p' }, { "min_tlen", 1, 0, 'a' },
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
-        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { 0, 0, 0, 0 } };
+        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { 0, 0, 0, 0 } };
     int c;
     while ((c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0) {
         switch (c) {
@@ -1082,6 +1129,7 @@ int main(int argc, char **argv)
         case 'b': po.max_tlen = (uint32_t)atoi(optarg); break;
         case 1000: n_gpus = atoi(optarg); break;
         case 1001: g_bgzf.on = true; break;
+        case 1002: g_bam.on = true; g_bgzf.on = true; break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1093,6 +1141,10 @@ int main(int argc, char **argv)
     const char *prefix = argv[optind], *fn_reads = argv[optind + 1], *fn_mates = pe ? argv[optind + 2] : nullptr;
     // the device compressor, unless this libsalt_gpu has none or SALT_BGZF_HOST=1 asks for zlib (A/B runs, tests)
     g_bgzf.device = g_bgzf.on && salt_gpu_ws_set_sam_bgzf != nullptr && !(getenv("SALT_BGZF_HOST") && atoi(getenv("SALT_BGZF_HOST")));
+    // the device's record kernels, unless this libsalt_gpu has none or SALT_BAM_HOST=1 asks for the host encoder; records made on the host
+    // out of the device's SAM text are deflated there too
+    g_bam.device = g_bam.on && salt_gpu_ws_set_sam_bam != nullptr && !(getenv("SALT_BAM_HOST") && atoi(getenv("SALT_BAM_HOST")));
+    if (g_bam.on && !g_bam.device) g_bgzf.device = false;
 
     // Single end + a plain (not gzipped) strict 4-line FASTQ in a regular file: the text path -- parse, align and format on the device
     // (run_se_text).  Everything else (paired end, gzip, pipes, multi-line records) goes through the host pipeline below.
@@ -1117,6 +1169,7 @@ int main(int argc, char **argv)
     salt_index_t *ix = salt_index_load(prefix, 0);
     if (!ix) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return 1; }
     ao.l_seed = salt_index_seed_len(ix);
+    g_bam.ix = ix;
     ao.l_overlap = overlap > 0 ? overlap : ao.l_seed;                      // aln.c:223
     std::vector<int> devs((size_t)n_gpus);
     for (int i = 0; i < n_gpus; ++i) devs[(size_t)i] = i;
@@ -1138,6 +1191,13 @@ int main(int argc, char **argv)
         if (!g_bgzf.on) { fwrite(hb.data(), 1, (size_t)w, stdout); fwrite(pg.data(), 1, (size_t)wp, stdout); return true; }
         std::string text(hb.data(), (size_t)w), z;
         text.append(pg.data(), (size_t)wp);
+        if (g_bam.on) {                                      // the same text inside the BAM header, then the reference list of the same contig table
+            std::string bh(text.size() + (size_t)w + 64 + 16 * (size_t)salt_index_n_seqs(ix), '\0');
+            const int64_t wb = salt_bam_header(ix, text.data(), text.size(), reinterpret_cast<uint8_t *>(&bh[0]), bh.size());
+            if (wb < 0) { fprintf(stderr, "[salt] BAM header too large\n"); return false; }
+            bh.resize((size_t)wb);
+            text.swap(bh);
+        }
         if (!bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] zlib failed on the SAM header\n"); return false; }
         fwrite(z.data(), 1, z.size(), stdout);
         g_bgzf.text_bytes += text.size(); g_bgzf.file_bytes += z.size();
@@ -1301,7 +1361,7 @@ int main(int argc, char **argv)
                 }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &so, &po, *b, pool); else format_batch(ix, &so, *b, pool);
-                if (g_bgzf.on && !bgzf_batch(b->sam, pool)) { fprintf(stderr, "[salt] zlib failed on a SAM block\n"); set_failed(); break; }
+                if (g_bgzf.on && !bgzf_batch(b->sam, pool)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
                 t_fmt = t_fmt + (now() - tf0);
                 std::unique_lock<std::mutex> lk(mu);
                 done.push_back(std::move(b));

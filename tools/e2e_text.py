@@ -4,7 +4,8 @@ then runs `salt -d -c` for every settings string given on the command line ("ENV
 A setting IN=bgzf / IN=gz runs on a blocked-gzip / plain-gzip copy of the FASTQ (written once, 32 processes); OUT=null sends the SAM to
 /dev/null; ARGS=--bgzf adds arguments to the `salt` command line (several: separated by '+'), so that one invocation runs plain and
 compressed legs side by side; PROF=<dir> runs under rocprofv3 --kernel-trace --stats.  SALT_E2E_BIN in the environment names the `salt`
-binary of another build (the parent commit's, say) for the same legs on the same files.
+binary of another build (the parent commit's, say) for the same legs on the same files; a setting BIN=<path> does so for one leg, so that
+two builds alternate inside one invocation.  A leg that fails ends the run: nothing more is started on the device behind it.
 usage: tools/e2e_text.py <n_reads> [settings ...]"""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,15 +80,18 @@ for s in settings:
             made[kind] = 1
             print("   (%s written in %.1f s, %.2f GB)" % (src, time.time() - tz, os.path.getsize(src) / 1e9))
     t0 = time.time()
-    cmd = [salt, "-d", "-c", "-t", env.pop("T", "64")] + [a for a in env.pop("ARGS", "").split("+") if a] + [w["prefix"], src]
+    cmd = [env.pop("BIN", salt), "-d", "-c", "-t", env.pop("T", "64")] + [a for a in env.pop("ARGS", "").split("+") if a] + [w["prefix"], src]
     prof = env.pop("PROF", "")                                  # PROF=<dir>: the run under rocprofv3 --kernel-trace --stats, summary CSV into <dir>
     if prof:
         env["TMPDIR"] = "/tmp"
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.abspath(prof), "-o", "kt", "--"] + cmd
     with open("/dev/null" if to_null else sam, "wb") as fo:
-        r = subprocess.run(cmd, stdout=fo, stderr=subprocess.PIPE, env=env, cwd="/tmp" if prof else None)
+        r = subprocess.run(cmd, stdout=fo, stderr=subprocess.PIPE, env=env, cwd="/tmp" if prof else None, timeout=600)
     tail = [l for l in r.stderr.decode().splitlines() if l.startswith("[salt") or l.startswith("[alnse_core]: total")]
     print("== %s  (rc %d, process %.1f s%s)" % (s or "defaults", r.returncode, time.time() - t0, "" if to_null else ", %.3f GB written" % (os.path.getsize(sam) / 1e9)))
     for l in tail:
         print("   ", l)
     sys.stdout.flush()
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr.decode()[-2000:])
+        sys.exit(1)
