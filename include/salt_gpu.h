@@ -262,7 +262,8 @@ int  salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t 
                           const uint32_t *cand, const uint32_t *cand_offs, int mode, uint8_t *out);
 
 /* Work-queue counters of the LAST batch (diagnostics): [0] reads k_light handed to k_heavy, [2] reads whose gapped pass
- * was deferred, [5] k_gap items (32 candidates each), [6] k_cigar items, [7] k_cigar's queue head; [1], [3], [4] read 0. */
+ * was deferred, [5] k_gap items (32 candidates each), [6] k_cigar items, [7] k_cigar's queue head; [1] / [3] the longest R / C list among
+ * the 64 segments of the seed walk queues; [4] reads 0. */
 int  salt_gpu_ws_queue_counts(salt_gpu_ws_t *ws, uint32_t out[8]);
 
 /* counters of the last batch(es) since the previous call; resets them */

@@ -236,17 +236,24 @@ struct SeedCtx {                       // passed BY VALUE everywhere: anything r
     bool inreg;                        // seeds of up to 33 bases sit in 3 + 2 registers (bases wb*16 .. wb*16+47)
 };
 __device__ __forceinline__ bool seed_valid(const SeedCtx c) { return c.L >= c.k && c.s + c.k <= c.L; }
-__device__ __forceinline__ SeedCtx seed_ctx(const SeedParams &sp, const uint32_t *tb, uint32_t item, uint32_t lkt_len)
+// everything of a seed's context that needs no load: where its strand's words lie in the tb record, and the seed's place in the read
+__device__ __forceinline__ SeedCtx seed_ctx_geom(const SeedParams &sp, const uint32_t *tb, uint32_t item, uint32_t lkt_len)
 {
     SeedCtx c;
     const uint32_t slot = item % sp.spr, rs = item / sp.spr, strand = rs & 1u, r = rs >> 1;
     // the read as k_pack left it: 2-bit codes (first base in the high bits) and 'is N' bits of this strand
     const uint32_t *rec = tb + (uint64_t)r * sp.pg.tb_stride;
     c.t2 = rec + strand * sp.pg.nw16; c.tn = rec + 2 * sp.pg.nw16 + strand * sp.pg.nw32;
-    c.L = rec[2 * sp.pg.nw16 + 2 * sp.pg.nw32];
+    c.L = 0;                           // seed_ctx loads it; a queued walk has passed seed_valid and needs it no more
     c.k = (uint32_t)sp.l_seed; c.W = lkt_len; c.s = slot * (uint32_t)sp.l_overlap; c.inreg = c.k <= 33;
     c.wb = c.s >> 4; c.nb = c.s >> 5;
     c.w0 = c.w1 = c.w2 = c.n0 = c.n1 = 0;
+    return c;
+}
+__device__ __forceinline__ SeedCtx seed_ctx(const SeedParams &sp, const uint32_t *tb, uint32_t item, uint32_t lkt_len)
+{
+    SeedCtx c = seed_ctx_geom(sp, tb, item, lkt_len);
+    c.L = (tb + (uint64_t)(item / sp.spr >> 1) * sp.pg.tb_stride)[2 * sp.pg.nw16 + 2 * sp.pg.nw32];
     if (seed_valid(c)) { c.w0 = c.t2[c.wb]; c.w1 = c.t2[c.wb + 1]; c.w2 = c.t2[c.wb + 2]; c.n0 = c.tn[c.nb]; c.n1 = c.tn[c.nb + 1]; }     // stays inside the record (PackGeom)
     return c;
 }
@@ -261,112 +268,177 @@ __device__ __forceinline__ bool seed_is_n(const SeedCtx c, uint32_t i)
     return (c.tn[i >> 5] >> (31 - (i & 31u))) & 1u;
 }
 
-// One-row C interval `row` with head bases s .. s+it still to consume (newest first): the located position, or 0xFFFFFFFF when the
-// read and the text in front of that suffix differ.  Everything by value: what a lambda captures by reference ends up in scratch.
-__device__ __forceinline__ uint32_t seed_resolve_unique(const uint32_t *__restrict__ c_sa, const uint32_t *__restrict__ text, uint32_t c_seq_len,
-                                                        uint32_t s, uint32_t wb, uint32_t nb, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t n0, uint32_t n1,
-                                                        int it, uint32_t row, uint32_t &n_aux, const uint4 *__restrict__ c_ctx = nullptr, uint32_t ctx_len = 0)
+// ---- the rest of a search behind the W-mer table, as a per-lane state and a step ---------------------------------------------------
+// C: bwt_match_exact_alt (bwt.c:281-309) from interval [k, l] with head bases s .. s+i still to consume, newest first, then the
+// interval-shrinking extension (alnse.c:246-258).  R: Rbwt_exact_match_backward (rbwt.c:619-648) and its extension, which has no N guard: an
+// N walks the '#' column there (alnse.c:279-291).  A step is cut in two, seed_walk_issue (the step's loads: at most ONE memory round trip)
+// and seed_walk_finish (what the phase does with them), so that k_seed_walk can put the loads of all its lanes, whatever their phases, in
+// front of one wait.  This is the only statement of the rules: seed_c_rest / seed_r_rest loop over the same two functions.
+//   WK_HEAD  one Occ step on head base s + i.
+//   WK_EXT   one Occ step on base s - ext - 1 while the interval is wider than max_seed.
+//   WK_SA    (C) the interval is ONE row and cannot branch any more: the search succeeds iff the read's remaining head bases equal the text
+//            in front of that suffix.  This step fetches the row's context record, which holds the suffix's position AND the CTX_N_B bases
+//            in front of it (salt_ctx_record.h; side B is complete iff CTX_N_B <= p0 <= ctx_len), or without the table the suffix-array
+//            entry; the seed leaves located (.w = 2: .x = .y = the genome position), dead, or goes on to
+//   WK_TEXT  (C) the comparison against the 2-bit text: at most two pieces of up to 16 bases, the later bases (consumed first) first.
+//   WK_REC / WK_CTX are k_seed_walk's own (a refilled lane's queue record and tb words).
+enum : uint32_t { WK_IDLE = 0, WK_REC, WK_CTX, WK_HEAD, WK_EXT, WK_SA, WK_TEXT };
+struct Walk { uint32_t ph, k, l, ext, p0; int i; };                 // p0: WK_TEXT's suffix position
+// What a step reads, as addresses: up to four 16-byte pieces from each of pa and pb (the Occ blocks of the interval's two ends; the context
+// record; k_seed_walk's queue record) and up to three / two words from ps / pt (the base's tb words when it is not in registers, the
+// suffix-array entry, the text pieces; k_seed_walk's tb words).  walk_fetch does the loads: every register of WalkLoads is written by
+// ONE load and by nothing else, whatever the phase -- a register shared between differently shaped loads would be copied into place
+// behind its load, and the copy waits for the load right where it was issued.  Pieces not asked for stay unset and are not read.
+struct WalkReq { const uint4 *pa, *pb; const uint32_t *ps, *pt; uint32_t na, nb, ns, nt; };
+struct WalkLoads { uint4 a[4], b[4]; uint32_t s[3], t[2]; };
+__device__ __forceinline__ WalkReq walk_req_none() { return WalkReq{ nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u, 0u }; }
+__device__ __forceinline__ WalkLoads walk_fetch(const WalkReq q)
 {
-        const uint32_t m = (uint32_t)it + 1u;
-        const uint32_t reln = s - (nb << 5);
-        const uint64_t vn = ((uint64_t)n0 << 32) | n1;
-        if (c_ctx && m <= CTX_N_B) {
-            // the context table's record of the row holds the suffix's position AND the CTX_N_B bases in front of it: one load instead of
-            // the suffix-array load followed by the text load (salt_ctx_record.h; side B is complete iff CTX_N_B <= p0 <= ctx_len)
-            const uint4 rec = c_ctx[row];
-            const uint32_t p0c = rec.x == 0xFFFFFFFFu ? c_seq_len : rec.x;
-            if (p0c >= CTX_N_B && p0c <= ctx_len) {
-                n_aux += 1u << 10;
-                if (((vn >> (64 - reln - m)) & ((1ull << m) - 1ull)) != 0) return 0xFFFFFFFFu;
-                const uint32_t lo = ctx_front_lo(rec), hi = ctx_front_hi(rec);
-                uint32_t rlo = 0, rhi = 0;
-                for (uint32_t u = 0; u < m; ++u) {                            // read base s + it - u faces genome base p0 - 1 - u
-                    const uint32_t rel = s + (uint32_t)it - u - (wb << 4);
-                    const uint32_t ws = rel < 16 ? w0 : rel < 32 ? w1 : w2;
-                    const uint32_t code = (ws >> (30 - 2 * (rel & 15u))) & 3u;
-                    rlo |= (code & 1u) << u; rhi |= (code >> 1) << u;
-                }
-                const uint32_t mk = (1u << m) - 1u;
-                return (((lo ^ rlo) | (hi ^ rhi)) & mk) == 0 ? p0c - m : 0xFFFFFFFFu;
-            }
+    WalkLoads ld;
+    if (q.na > 0) ld.a[0] = q.pa[0];
+    if (q.na > 1) ld.a[1] = q.pa[1];
+    if (q.na > 2) { ld.a[2] = q.pa[2]; ld.a[3] = q.pa[3]; }
+    if (q.nb > 0) { ld.b[0] = q.pb[0]; ld.b[1] = q.pb[1]; }
+    if (q.nb > 2) { ld.b[2] = q.pb[2]; ld.b[3] = q.pb[3]; }
+    if (q.ns > 0) ld.s[0] = q.ps[0];
+    if (q.ns > 1) ld.s[1] = q.ps[1];
+    if (q.ns > 2) ld.s[2] = q.ps[2];
+    if (q.nt > 0) ld.t[0] = q.pt[0];
+    if (q.nt > 1) ld.t[1] = q.pt[1];
+    return ld;
+}
+
+__device__ __forceinline__ uint32_t walk_pos(const SeedCtx c, const Walk w) { return w.ph == WK_HEAD ? c.s + (uint32_t)w.i : c.s - w.ext - 1u; }
+__device__ __forceinline__ bool walk_pos_inreg(const SeedCtx c, uint32_t pos) { return c.inreg && pos >= c.s; }
+// behind the head bases, and after every extension step: the extension while the interval is still wide and bases are left, else the row
+__device__ __forceinline__ bool walk_enter_ext(const SeedParams &sp, const SeedCtx c, Walk &w, uint4 &row)
+{
+    if (w.l - w.k > sp.max_seed && w.ext < c.s) { w.ph = WK_EXT; return false; }
+    row = make_uint4(w.k, w.l, c.s - w.ext, 1); w.ph = WK_IDLE;
+    return true;
+}
+// every function returns true when the walk has ended, with its row in `row`
+template <bool R>
+__device__ __forceinline__ bool seed_walk_begin(const SeedParams &sp, const SeedCtx c, uint32_t k, uint32_t l, int i_top, Walk &w, uint4 &row)
+{
+    w.k = k; w.l = l; w.i = i_top; w.ext = 0; w.p0 = 0;
+    if (i_top < 0) return walk_enter_ext(sp, c, w, row);
+    w.ph = (!R && c.inreg && sp.resolve_unique && k == l) ? WK_SA : WK_HEAD;
+    return false;
+}
+template <bool R>
+__device__ __forceinline__ WalkReq seed_walk_issue(const IndexView &ix, const SeedParams &sp, const SeedCtx c, const Walk w)
+{
+    WalkReq q = walk_req_none();
+    if (!R && w.ph == WK_SA) {
+        if (ix.c_ctx && (uint32_t)w.i + 1u <= CTX_N_B) { q.pa = ix.c_ctx + w.k; q.na = 1; } else { q.ps = ix.c_sa + w.k; q.ns = 1; }
+    } else if (!R && w.ph == WK_TEXT) {
+        const uint32_t m = (uint32_t)w.i + 1u, t0 = w.p0 - (m > 16u ? 16u : m);
+        q.ps = ix.text + (t0 >> 4); q.ns = 2;
+        if (m > 16u) { q.pt = ix.text + ((w.p0 - m) >> 4); q.nt = 2; }
+    } else {
+        const uint32_t pos = walk_pos(c, w);
+        const bool inr = walk_pos_inreg(c, pos);
+        if (!inr) { q.ps = c.t2 + (pos >> 4); q.ns = 1; q.pt = c.tn + (pos >> 5); q.nt = 1; }
+        // an N already visible in the registers ends the walk without a fetch; one that comes with the tb words is seen behind the wait, and
+        // the blocks requested beside it are dropped uncounted
+        if (!(inr && seed_is_n(c, pos) && !(R && w.ph == WK_EXT))) {
+            if (R) { r_occ2_addr(ix, w.k, w.l + 1u, q.pa, q.pb); q.na = 4; q.nb = q.pb ? 4u : 0u; }
+            else { c_occ2_addr(ix, w.k - 1u, w.l, q.pa, q.pb); q.na = q.pa ? 2u : 0u; q.nb = q.pb ? 2u : 0u; }
         }
-        uint32_t p0 = c_sa[row];
-        if (p0 == 0xFFFFFFFFu) p0 = c_seq_len;            // row 0: the empty suffix
-        bool ok = ((vn >> (64 - reln - m)) & ((1ull << m) - 1ull)) == 0 && p0 >= m;
-        uint32_t steps = m;
-        for (uint32_t done = 0; done < m && ok; ) {          // at most two pieces of up to 16 bases, the later bases (consumed first) first
+    }
+    return q;
+}
+template <bool R>
+__device__ __forceinline__ bool seed_walk_finish(const IndexView &ix, const SeedParams &sp, const SeedCtx c, Walk &w, const WalkLoads ld, uint4 &row,
+                                                 uint32_t &n_occ, uint32_t &n_aux)
+{
+    const uint32_t s = c.s;
+    const uint4 dead = make_uint4(1, 0, 0, 0);
+    if (!R && w.ph == WK_SA) {
+        const uint32_t m = (uint32_t)w.i + 1u, reln = s - (c.nb << 5);
+        const uint64_t vn = ((uint64_t)c.n0 << 32) | c.n1;
+        const bool head_n = ((vn >> (64 - reln - m)) & ((1ull << m) - 1ull)) != 0;
+        const uint32_t ctx_len = ix.c_seq_len < ix.ref_len ? ix.c_seq_len : ix.ref_len;
+        const bool rec = ix.c_ctx && m <= CTX_N_B;           // the row's context record, whose .x is the suffix-array entry again
+        const uint32_t sa0 = rec ? ld.a[0].x : ld.s[0];
+        const uint32_t p0 = sa0 == 0xFFFFFFFFu ? ix.c_seq_len : sa0;      // row 0: the empty suffix
+        n_aux += 1u << 10;                                   // one suffix-array load (bits 10..20; the context record counts as one)
+        if (rec && p0 >= CTX_N_B && p0 <= ctx_len) {
+            const uint32_t lo = ctx_front_lo(ld.a[0]), hi = ctx_front_hi(ld.a[0]);
+            uint32_t rlo = 0, rhi = 0;
+            for (uint32_t u = 0; u < m; ++u) {               // read base s + i - u faces genome base p0 - 1 - u
+                const uint32_t rel = s + (uint32_t)w.i - u - (c.wb << 4);
+                const uint32_t ws = rel < 16 ? c.w0 : rel < 32 ? c.w1 : c.w2;
+                const uint32_t code = (ws >> (30 - 2 * (rel & 15u))) & 3u;
+                rlo |= (code & 1u) << u; rhi |= (code >> 1) << u;
+            }
+            const uint32_t mk = (1u << m) - 1u;
+            const bool same = !head_n && (((lo ^ rlo) | (hi ^ rhi)) & mk) == 0;
+            row = same ? make_uint4(p0 - m, p0 - m, s, 2) : dead; w.ph = WK_IDLE;
+            return true;
+        }
+        if (head_n || p0 < m) { row = dead; w.ph = WK_IDLE; return true; }
+        w.p0 = p0; w.ph = WK_TEXT;
+        return false;
+    }
+    if (!R && w.ph == WK_TEXT) {
+        const uint32_t m = (uint32_t)w.i + 1u;
+        bool ok = true;
+        for (uint32_t done = 0, piece = 0; done < m && ok; ++piece) {
             const uint32_t cnt = (m - done) > 16u ? 16u : (m - done);
-            const uint32_t r0 = s + (m - done - cnt), t0 = p0 - done - cnt;       // read bases r0 .. r0+cnt-1 against text t0 ..
-            const uint32_t rel = r0 - (wb << 4), rr = rel & 15u;
-            const uint64_t vr = rel < 16 ? (((uint64_t)w0 << 32) | w1) : (((uint64_t)w1 << 32) | w2);
+            const uint32_t r0 = s + (m - done - cnt), t0 = w.p0 - done - cnt;     // read bases r0 .. r0+cnt-1 against text t0 ..
+            const uint32_t rel = r0 - (c.wb << 4), rr = rel & 15u;
+            const uint64_t vr = rel < 16 ? (((uint64_t)c.w0 << 32) | c.w1) : (((uint64_t)c.w1 << 32) | c.w2);
             const uint32_t xr = (uint32_t)((vr >> (64 - 2 * rr - 2 * cnt)) & ((1ull << (2 * cnt)) - 1ull));
-            const uint32_t tj = t0 >> 4, tr = t0 & 15u;
-            const uint64_t vt = ((uint64_t)text[tj] << 32) | text[tj + 1];
-            n_aux += 1u << 21;                               // one 8-byte text load
+            const uint32_t tr = t0 & 15u;
+            const uint64_t vt = piece == 0 ? (((uint64_t)ld.s[0] << 32) | ld.s[1]) : (((uint64_t)ld.t[0] << 32) | ld.t[1]);
+            n_aux += 1u << 21;                               // one 8-byte text load (bits 21..31)
             const uint32_t xt = (uint32_t)((vt >> (64 - 2 * tr - 2 * cnt)) & ((1ull << (2 * cnt)) - 1ull));
-            const uint32_t diff = xr ^ xt;
-            if (diff) { ok = false; steps = done + ((uint32_t)__ffs((int)diff) - 1u) / 2u + 1u; }
+            ok = xr == xt;
             done += cnt;
         }
-        (void)steps;
-        n_aux += 1u << 10;                                   // one suffix-array load
-        return ok ? p0 - m : 0xFFFFFFFFu;
+        row = ok ? make_uint4(w.p0 - m, w.p0 - m, s, 2) : dead; w.ph = WK_IDLE;
+        return true;
     }
+    const bool head = w.ph == WK_HEAD;
+    const uint32_t pos = walk_pos(c, w);
+    const bool inr = walk_pos_inreg(c, pos);
+    const bool isn = inr ? seed_is_n(c, pos) : ((ld.t[0] >> (31 - (pos & 31u))) & 1u) != 0;
+    const uint4 stop = head ? dead : make_uint4(w.k, w.l, s - w.ext, 1);      // a head step that fails kills the seed, an extension step only ends the extension
+    if (isn && !(R && !head)) { row = stop; w.ph = WK_IDLE; return true; }
+    const uint32_t b = isn ? 4u : inr ? seed_base2(c, pos) : (ld.s[0] >> (30 - 2 * (pos & 15u))) & 3u;
+    uint32_t ok, ol;
+    if (R) n_occ += r_occ2_eval(ix, ROcc2{ ROccBlk{ ld.a[0], ld.a[1], ld.a[2], ld.a[3] }, ROccBlk{ ld.b[0], ld.b[1], ld.b[2], ld.b[3] } }, w.k, w.l + 1u, b, ok, ol);
+    else n_occ += c_occ2_eval(ix, COcc2{ ld.a[0], ld.a[1], ld.b[0], ld.b[1] }, w.k - 1u, w.l, b, ok, ol);
+    if (ok + 1u > ol) { row = stop; w.ph = WK_IDLE; return true; }             // the interval would be empty
+    { const uint32_t first = R ? pick5(ix.r_cum, b) : pick4(ix.c_L2, b); w.k = first + ok + 1u; w.l = first + ol; }
+    if (head) {
+        if (--w.i >= 0) { if (!R && c.inreg && sp.resolve_unique && w.k == w.l) w.ph = WK_SA; return false; }
+    } else ++w.ext;
+    return walk_enter_ext(sp, c, w, row);
+}
 
-// The rest of a C search (bwt.c:281-309) from interval [kc, lc] with head bases s .. s+i_top still to consume, newest first,
-// then the interval-shrinking extension (alnse.c:246-258).  A C interval of ONE row cannot branch any more: the search
-// succeeds iff the read's remaining bases equal the text in front of that suffix, so one suffix-array load and one text load
-// replace the remaining Occ steps and the seed leaves already located (.w = 2: .x = .y = the genome position).
+// the whole walk on one lane, as a loop over the step
+template <bool R>
+__device__ __forceinline__ uint4 seed_walk_rest(const IndexView &ix, const SeedParams &sp, const SeedCtx c, uint32_t k, uint32_t l, int i_top,
+                                                uint32_t &n_occ, uint32_t &n_aux)
+{
+    Walk w; uint4 row = make_uint4(1, 0, 0, 0);
+    bool done = seed_walk_begin<R>(sp, c, k, l, i_top, w, row);
+    while (!done) { const WalkLoads ld = walk_fetch(seed_walk_issue<R>(ix, sp, c, w)); done = seed_walk_finish<R>(ix, sp, c, w, ld, row, n_occ, n_aux); }
+    return row;
+}
 __device__ __forceinline__ uint4 seed_c_rest(const IndexView &ix, const SeedParams &sp, const SeedCtx c, uint32_t kc, uint32_t lc, int i_top,
                                              uint32_t &n_occ_c, uint32_t &n_aux)
 {
-    const uint32_t s = c.s;
-    const bool uniq = c.inreg && sp.resolve_unique;
-    bool alive = true, located = false;
-    if (uniq && kc == lc && i_top >= 0) { const uint32_t p = seed_resolve_unique(ix.c_sa, ix.text, ix.c_seq_len, s, c.wb, c.nb, c.w0, c.w1, c.w2, c.n0, c.n1, i_top, kc, n_aux, ix.c_ctx, ix.c_seq_len < ix.ref_len ? ix.c_seq_len : ix.ref_len); alive = p != 0xFFFFFFFFu; located = alive; if (alive) kc = lc = p; }
-    for (int i = i_top; i >= 0 && alive && !located; --i) {
-        if (seed_is_n(c, s + (uint32_t)i)) { alive = false; break; }
-        const uint32_t b = seed_base2(c, s + (uint32_t)i);
-        uint32_t ok, ol; n_occ_c += c_occ2(ix, kc - 1, lc, b, ok, ol);
-        { const uint32_t l2 = pick4(ix.c_L2, b); kc = l2 + ok + 1; lc = l2 + ol; } alive = kc <= lc;
-        if (uniq && alive && kc == lc && i > 0) { const uint32_t p = seed_resolve_unique(ix.c_sa, ix.text, ix.c_seq_len, s, c.wb, c.nb, c.w0, c.w1, c.w2, c.n0, c.n1, i - 1, kc, n_aux, ix.c_ctx, ix.c_seq_len < ix.ref_len ? ix.c_seq_len : ix.ref_len); alive = p != 0xFFFFFFFFu; located = alive; if (alive) kc = lc = p; }
-    }
-    if (!alive) return make_uint4(1, 0, 0, 0);
-    if (located) return make_uint4(kc, kc, s, 2);
-    uint32_t ext = 0;                                         // shrink big intervals leftwards (alnse.c:246-258)
-    while (lc - kc > sp.max_seed && ext < s) {
-        if (seed_is_n(c, s - ext - 1)) break;
-        const uint32_t b = seed_base2(c, s - ext - 1);
-        uint32_t ok, ol; n_occ_c += c_occ2(ix, kc - 1, lc, b, ok, ol);
-        if (ok + 1 > ol) break;
-        { const uint32_t l2 = pick4(ix.c_L2, b); kc = l2 + ok + 1; lc = l2 + ol; } ++ext;
-        if (lc - kc <= sp.max_seed) break;
-    }
-    return make_uint4(kc, lc, s - ext, 1);
+    return seed_walk_rest<false>(ix, sp, c, kc, lc, i_top, n_occ_c, n_aux);
 }
-
-// The rest of an R search (rbwt.c:619-648) and its extension, which has no N guard (alnse.c:279-291)
 __device__ __forceinline__ uint4 seed_r_rest(const IndexView &ix, const SeedParams &sp, const SeedCtx c, uint32_t kr, uint32_t lr, int i_top,
                                              uint32_t &n_occ_r)
 {
-    const uint32_t s = c.s;
-    bool alive = true;
-    for (int i = i_top; i >= 0 && alive; --i) {
-        if (seed_is_n(c, s + (uint32_t)i)) { alive = false; break; }
-        const uint32_t b = seed_base2(c, s + (uint32_t)i);
-        uint32_t ok, ol; n_occ_r += r_occ2(ix, kr, lr + 1, b, ok, ol);
-        { const uint32_t cm = pick5(ix.r_cum, b); kr = cm + ok + 1; lr = cm + ol; } alive = kr <= lr;
-    }
-    if (!alive) return make_uint4(1, 0, 0, 0);
-    uint32_t ext = 0;
-    while (lr - kr > sp.max_seed && ext < s) {
-        const uint32_t b = seed_is_n(c, s - ext - 1) ? 4u : seed_base2(c, s - ext - 1);               // an N walks the '#' column
-        uint32_t ok, ol; n_occ_r += r_occ2(ix, kr, lr + 1, b, ok, ol);
-        if (ok + 1 > ol) break;
-        { const uint32_t cm = pick5(ix.r_cum, b); kr = cm + ok + 1; lr = cm + ol; } ++ext;
-        if (lr - kr <= sp.max_seed) break;
-    }
-    return make_uint4(kr, lr, s - ext, 1);
+    uint32_t n_aux = 0;
+    return seed_walk_rest<true>(ix, sp, c, kr, lr, i_top, n_occ_r, n_aux);
 }
 
 static constexpr uint32_t WQ_SEG = 64, WQ_STRIDE = 64;            // segments per walk queue; words between their counters
@@ -440,16 +512,21 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
                         else if (ok0) oc = make_uint4(u.x - m, u.x - m, c.s, 2);
                         else if (ok1) oc = make_uint4(u.z - m, u.z - m, c.s, 2);
                     }
-                    else if ((v.x == v.y && c.inreg && sp.resolve_unique) || i_top < 0) oc = seed_c_rest(ix, sp, c, v.x, v.y, i_top, n_occ_c, n_lkt);   // no walk left (or only the extension)
-                    else { pend_c = true; pk_c = v.x; pl_c = v.y; }
+                    else {
+                        // everything else walks in k_seed_walk, unless the walk ends before its first fetch (k = W and no extension).  The
+                        // whole walk inlined here (seed_c_rest) for the few shapes that need no Occ step cost every seed's gather path
+                        // its registers: 40 bytes of scratch at the 64 VGPRs of eight waves per SIMD
+                        Walk w;
+                        if (!seed_walk_begin<false>(sp, c, v.x, v.y, i_top, w, oc)) { pend_c = true; pk_c = v.x; pl_c = v.y; }
+                    }
                 }
                 if (!sp.seed_only_ref) {
                     if (v.z <= v.w) { pend_r = true; pk_r = v.z; pl_r = v.w; }
                 }
             }
         }
-        if (!pend_c) sai_c[item] = oc;
-        if (!pend_r) sai_r[item] = orr;
+        sai_c[item] = oc;                                     // a queued seed's row is the dead one here: k_seed_walk stores only the rows of walks that end
+        sai_r[item] = orr;                                    //   alive, and the stores of a wave cover whole lines
     }
     // collect: one LDS atomic per wave and list
     {
@@ -477,33 +554,77 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
     }
 }
 
-// k_seed_walk: the walks k_seed queued, one per lane and lanes densely packed: R searches first, then C searches (similar lengths side by
-// side: a wave pays for the longest of its 64 walks).  Inside k_seed a block of 256 seeds kept ~70 lanes busy with walks while it held its
-// wave slots; here every lane of every resident wave has one, which is what raises the number of requests in flight.  Block b serves
-// segment b % WQ_SEG with the other blocks of that segment, in strides.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+// k_seed_walk: the walks k_seed queued, in turns.  In a turn every busy lane does ONE step of its walk (seed_walk_issue / seed_walk_finish:
+// one memory round trip), and the lanes whose walks have ended take the next records of the wave's slice, so a wave no longer pays for the
+// longest of 64 walks (R walks die after 1 to 5 steps, C walks of repeat seeds run their head and up to s extension steps) with the other
+// lanes idle.  A refilled lane's dependent loads are lane states too (WK_REC: the queue record, WK_CTX: the read's tb words, then the walk's
+// phases), and a turn first issues the loads of ALL its lanes and then uses them: one wait per turn, whatever the mix of phases.
+//   Work is handed out statically: block b serves segment b % WQ_SEG, and wave w of the nw waves on that segment owns the records
+// [n w / nw, n (w + 1) / nw) of both of its lists, the first list in front of the second (C first: the long walks start first and the short R
+// walks fill the lanes they leave).  No atomics, nothing a wave could wait for.  The ballot and the cursor sit at the top of the turn
+// with all 64 lanes present and no lane leaves the loop on its own (loops in which lane groups leave one by one have
+// hung); every turn consumes records or advances every live walk, and a walk has at most k - W + s + 4 turns.
+//   k_seed has written the dead row for every queued seed, so only a walk that ends alive stores its row.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_seed_walk(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb, uint4 *__restrict__ sai_c, uint4 *__restrict__ sai_r,
-            const uint4 *__restrict__ wq, const uint32_t *__restrict__ wq_cnt, uint32_t wq_seg_cap, unsigned long long *__restrict__ ctr)
+            const uint4 *__restrict__ wq, const uint32_t *__restrict__ wq_cnt, uint32_t wq_seg_cap, uint32_t r_first, unsigned long long *__restrict__ ctr)
 {
-    const uint32_t seg = blockIdx.x & (WQ_SEG - 1u), bb = blockIdx.x / WQ_SEG, nbb = gridDim.x / WQ_SEG;
-    uint32_t n_aux = 0, n_occ_c = 0, n_occ_r = 0;
-    for (uint32_t which = 0; which < 2; ++which) {
-        const uint32_t n = wq_cnt[(which * WQ_SEG + seg) * WQ_STRIDE];
-        const uint4 *q = wq + ((size_t)which * WQ_SEG + seg) * wq_seg_cap;
-        for (uint32_t t = bb * 256u + threadIdx.x; t < n; t += nbb * 256u) {
-            const uint4 e = q[t];
-            const SeedCtx c = seed_ctx(sp, tb, e.x, ix.r_lkt_len);
-            const int i_top = (int)(c.k - c.W) - 1;
-            if (which == 0) sai_r[e.x] = seed_r_rest(ix, sp, c, e.y, e.z, i_top, n_occ_r);
-            else sai_c[e.x] = seed_c_rest(ix, sp, c, e.y, e.z, i_top, n_occ_c, n_aux);
+    const uint32_t seg = blockIdx.x & (WQ_SEG - 1u);
+    const uint32_t wv = (blockIdx.x / WQ_SEG) * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = (gridDim.x / WQ_SEG) * 4u;
+    const uint64_t lt = (1ull << lane_id()) - 1ull;
+    const uint32_t la = r_first ? 0u : 1u, lb = la ^ 1u;                       // list 0: R searches, list 1: C searches
+    const uint32_t na = wq_cnt[(la * WQ_SEG + seg) * WQ_STRIDE], nb = wq_cnt[(lb * WQ_SEG + seg) * WQ_STRIDE];
+    const uint32_t a0 = (uint32_t)((uint64_t)na * wv / nw), a1 = (uint32_t)((uint64_t)na * (wv + 1u) / nw);
+    const uint32_t b0 = (uint32_t)((uint64_t)nb * wv / nw), b1 = (uint32_t)((uint64_t)nb * (wv + 1u) / nw);
+    const uint4 *qa = wq + ((size_t)la * WQ_SEG + seg) * wq_seg_cap + a0, *qb = wq + ((size_t)lb * WQ_SEG + seg) * wq_seg_cap + b0;
+    const uint32_t tot_a = a1 - a0, tot = tot_a + (b1 - b0);
+    const int i_top = (int)((uint32_t)sp.l_seed - ix.r_lkt_len) - 1;
+    uint32_t n_aux = 0, n_sa = 0, n_text = 0, n_occ_c = 0, n_occ_r = 0;
+    Walk w; w.ph = WK_IDLE; w.k = w.l = w.ext = w.p0 = 0; w.i = 0;
+    SeedCtx c = seed_ctx_geom(sp, tb, 0, ix.r_lkt_len);
+    uint32_t item = 0, cur = 0;
+    bool is_r = false;
+    const uint4 *qp = qa;
+    for (;;) {
+        // ---- all 64 lanes: who is idle, is anything left, who takes which record ----
+        const uint64_t idle = __ballot(w.ph == WK_IDLE);
+        if (cur >= tot && idle == ~0ull) break;                               // the one exit, wave-uniform
+        if (cur < tot) {
+            const uint32_t t = cur + (uint32_t)__popcll(idle & lt);
+            if (w.ph == WK_IDLE && t < tot) {
+                const bool in_a = t < tot_a;
+                qp = in_a ? qa + t : qb + (t - tot_a); is_r = (in_a ? la : lb) == 0u; w.ph = WK_REC;
+            }
+            const uint32_t nx = cur + (uint32_t)__popcll(idle);
+            cur = nx < tot ? nx : tot;
         }
+        // ---- every lane's loads of this turn ----
+        WalkReq q = walk_req_none();
+        if (w.ph == WK_REC) { q.pa = qp; q.na = 1; }
+        else if (w.ph == WK_CTX) { q.ps = c.t2 + c.wb; q.ns = 3; q.pt = c.tn + c.nb; q.nt = 2; }     // stays inside the record (PackGeom)
+        else if (w.ph != WK_IDLE) q = is_r ? seed_walk_issue<true>(ix, sp, c, w) : seed_walk_issue<false>(ix, sp, c, w);
+        const WalkLoads ld = walk_fetch(q);
+        // ---- and what their phases do with them ----
+        bool done = false;
+        uint4 row = make_uint4(1, 0, 0, 0);
+        if (w.ph == WK_REC) {
+            item = ld.a[0].x; w.k = ld.a[0].y; w.l = ld.a[0].z;
+            c = seed_ctx_geom(sp, tb, item, ix.r_lkt_len); w.ph = WK_CTX;
+        } else if (w.ph == WK_CTX) {
+            c.w0 = ld.s[0]; c.w1 = ld.s[1]; c.w2 = ld.s[2]; c.n0 = ld.t[0]; c.n1 = ld.t[1];
+            done = is_r ? seed_walk_begin<true>(sp, c, w.k, w.l, i_top, w, row) : seed_walk_begin<false>(sp, c, w.k, w.l, i_top, w, row);
+        } else if (w.ph != WK_IDLE) {
+            done = is_r ? seed_walk_finish<true>(ix, sp, c, w, ld, row, n_occ_r, n_aux) : seed_walk_finish<false>(ix, sp, c, w, ld, row, n_occ_c, n_aux);
+        }
+        if (done && row.x <= row.y) (is_r ? sai_r : sai_c)[item] = row;
+        n_sa += (n_aux >> 10) & 2047u; n_text += n_aux >> 21; n_aux = 0;       // a lane does many walks here: the packed fields would run over
     }
     if (ctr) {
-        for (int o = 32; o > 0; o >>= 1) { n_aux += __shfl_down(n_aux, o); n_occ_c += __shfl_down(n_occ_c, o); n_occ_r += __shfl_down(n_occ_r, o); }
+        for (int o = 32; o > 0; o >>= 1) { n_sa += __shfl_down(n_sa, o); n_text += __shfl_down(n_text, o); n_occ_c += __shfl_down(n_occ_c, o); n_occ_r += __shfl_down(n_occ_r, o); }
         if (lane_id() == 0) {
             atomicAdd(ctr + SALT_CTR_OCC_C, n_occ_c); atomicAdd(ctr + SALT_CTR_OCC_R, n_occ_r);
             atomicAdd(ctr + SALT_CTR_D_COCC_SEED, n_occ_c); atomicAdd(ctr + SALT_CTR_D_ROCC_SEED, n_occ_r);
-            atomicAdd(ctr + SALT_CTR_D_SA_SEED, (n_aux >> 10) & 2047u); atomicAdd(ctr + SALT_CTR_D_TEXT_SEED, n_aux >> 21);
+            atomicAdd(ctr + SALT_CTR_D_SA_SEED, n_sa); atomicAdd(ctr + SALT_CTR_D_TEXT_SEED, n_text);
         }
     }
 }
@@ -2551,7 +2672,8 @@ void launch_seed(const IndexView &ix, const SeedParams &sp, const uint32_t *tb, 
     hipMemsetAsync(wq_cnt, 0, (size_t)seed_wq_cnt_words() * 4, st);
     hipLaunchKernelGGL(k_seed, dim3(blocks), dim3(256), 0, st, ix, sp, tb, sai_c, sai_r, wq, wq_cnt, cap, ctr);
     walk_blocks = (walk_blocks + WQ_SEG - 1) / WQ_SEG * WQ_SEG;
-    hipLaunchKernelGGL(k_seed_walk, dim3(walk_blocks), dim3(256), 0, st, ix, sp, tb, sai_c, sai_r, wq, wq_cnt, cap, ctr);
+    static const uint32_t r_first = getenv("SALT_GPU_WALK_R_FIRST") && atoi(getenv("SALT_GPU_WALK_R_FIRST")) ? 1u : 0u;      // measurements: the R list in front of the C list
+    hipLaunchKernelGGL(k_seed_walk, dim3(walk_blocks), dim3(256), 0, st, ix, sp, tb, sai_c, sai_r, wq, wq_cnt, cap, r_first, ctr);
 }
 
 void launch_light(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint8_t *, const uint32_t *, const uint4 *sai_c,

@@ -120,6 +120,29 @@ __device__ __forceinline__ uint32_t c_occ2(const IndexView &ix, const uint32_t k
     return (ks ? 0u : 1u) + (second ? 1u : 0u);
 }
 
+// The same step in two halves for callers that wait once per step (the seed walks): where both ends' blocks lie, so that BOTH can be
+// requested before either is used (a wide interval then costs one round trip and not two), and the evaluation.  An end without a block
+// ('$' row, whole text) gives nullptr and its half is not read; so does l when it shares k's block, which then serves both (two loads
+// of one line in flight together reached the fabric as two requests).  The count returned is c_occ2's.
+struct COcc2 { uint4 cntk, plk, cntl, pll; };
+__device__ __forceinline__ void c_occ2_addr(const IndexView &ix, const uint32_t k, const uint32_t l, const uint4 *&pk, const uint4 *&pl)
+{
+    const bool ks = k == ix.c_seq_len || k == 0xFFFFFFFFu, ls = l == ix.c_seq_len || l == 0xFFFFFFFFu;
+    const uint32_t kk = k - (k >= ix.c_primary), ll = l - (l >= ix.c_primary);
+    pk = ks ? nullptr : reinterpret_cast<const uint4 *>(ix.c_occ + (kk >> 6));
+    pl = ls || (!ks && (ll >> 6) == (kk >> 6)) ? nullptr : reinterpret_cast<const uint4 *>(ix.c_occ + (ll >> 6));
+}
+__device__ __forceinline__ uint32_t c_occ2_eval(const IndexView &ix, const COcc2 r, const uint32_t k, const uint32_t l, const uint32_t c, uint32_t &ok, uint32_t &ol)
+{
+    const uint32_t full = pick4(ix.c_L2 + 1, c) - pick4(ix.c_L2, c);
+    const bool ks = k == ix.c_seq_len || k == 0xFFFFFFFFu, ls = l == ix.c_seq_len || l == 0xFFFFFFFFu;
+    const uint32_t kk = k - (k >= ix.c_primary), ll = l - (l >= ix.c_primary);
+    ok = ks ? (k == ix.c_seq_len ? full : 0u) : c_occ_eval(r.cntk, r.plk, kk, c);
+    const bool second = !ls && (ks || (ll >> 6) != (kk >> 6));
+    ol = ls ? (l == ix.c_seq_len ? full : 0u) : c_occ_eval(second ? r.cntl : r.cntk, second ? r.pll : r.plk, ll, c);
+    return (ks ? 0u : 1u) + (second ? 1u : 0u);
+}
+
 // symbol k of the $-removed C BWT (bwt_B0, bwt.h:64) -- used only by the attach-time SA expansion
 __device__ __forceinline__ uint32_t c_sym(const IndexView &ix, uint32_t k)
 {
@@ -176,6 +199,22 @@ __device__ __forceinline__ uint32_t r_occ2(const IndexView &ix, uint32_t a, uint
     const bool second = (b >> 7) != (a >> 7);
     if (second) r = r_occ_load(ix, b >> 7);
     ob = r_occ_eval(r, b, c);
+    return second ? 2u : 1u;
+}
+
+// r_occ2 in two halves (see c_occ2_addr)
+struct ROcc2 { ROccBlk a, b; };
+__device__ __forceinline__ void r_occ2_addr(const IndexView &ix, uint32_t a, uint32_t b, const uint4 *&pa, const uint4 *&pb)
+{
+    a -= (a > ix.r_inv_sa0); b -= (b > ix.r_inv_sa0);
+    pa = reinterpret_cast<const uint4 *>(ix.r_occ + (a >> 7)); pb = (b >> 7) != (a >> 7) ? reinterpret_cast<const uint4 *>(ix.r_occ + (b >> 7)) : nullptr;
+}
+__device__ __forceinline__ uint32_t r_occ2_eval(const IndexView &ix, const ROcc2 r, uint32_t a, uint32_t b, const uint32_t c, uint32_t &oa, uint32_t &ob)
+{
+    a -= (a > ix.r_inv_sa0); b -= (b > ix.r_inv_sa0);
+    const bool second = (b >> 7) != (a >> 7);
+    oa = r_occ_eval(r.a, a, c);
+    ob = r_occ_eval(second ? r.b : r.a, b, c);
     return second ? 2u : 1u;
 }
 

@@ -42,7 +42,7 @@ struct salt_gpu_ws {
     uint32_t max_reads = 0; uint64_t max_bases = 0;
     uint8_t *d_seqs = nullptr; uint32_t *d_offs = nullptr; salt_result_t *d_results = nullptr;
     uint4 *d_sai_c = nullptr, *d_sai_r = nullptr; uint64_t sai_cap = 0;
-    uint4 *d_wq = nullptr; uint32_t *d_wq_cnt = nullptr; uint32_t walk_blocks = 2048;      // k_seed's walk queues (sized with the seed arrays), k_seed_walk's grid
+    uint4 *d_wq = nullptr; uint32_t *d_wq_cnt = nullptr; uint32_t walk_blocks = 512; bool no_unique = false;      // k_seed's walk queues (sized with the seed arrays), k_seed_walk's grid; SALT_GPU_NO_UNIQUE
     uint32_t *d_pm = nullptr, *d_tb = nullptr; uint64_t pm_cap = 0, tb_cap = 0;     // k_pack's records (words)
     uint8_t *d_heads = nullptr, *h_heads = nullptr;          // first 128 bytes of every result row: dense device copy + pinned host staging
     unsigned long long *d_ctr = nullptr;
@@ -326,8 +326,12 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
         uint32_t gap_per_cu = 16;
         if (const char *e2 = getenv("SALT_GPU_GAP_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) gap_per_cu = (uint32_t)v; }
         ws->gap_blocks = (uint32_t)prop.multiProcessorCount * gap_per_cu;
-        ws->walk_blocks = (uint32_t)prop.multiProcessorCount * 8u;            // k_seed_walk: 8 waves per SIMD in blocks of four waves
+        // k_seed_walk: 2 waves per SIMD in blocks of four waves.  Its lanes are all busy, so the grid is set by the four-stream step and not by
+        // the kernel alone: 2 per CU 464 - 467 Mreads/s, 4 per CU 445 - 459, 8 per CU 450 - 458 (profiles/r07/ab_grid_and_order.log)
+        ws->walk_blocks = (uint32_t)prop.multiProcessorCount * 2u;
         if (const char *e2 = getenv("SALT_GPU_WALK_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) ws->walk_blocks = (uint32_t)prop.multiProcessorCount * (uint32_t)v; }
+        if (const char *e2 = getenv("SALT_GPU_NO_UNIQUE")) ws->no_unique = atoi(e2) != 0;                    // A/B and tests: every C search walks
+        if (const char *e2 = getenv("SALT_GPU_WALK_BLOCKS")) { int v = atoi(e2); if (v > 0 && v <= 65536) ws->walk_blocks = (uint32_t)v; }      // tests: an absolute grid (rounded up to 64s), so that a wave's slice is long
         CHKW(hipMalloc((void **)&ws->d_wq_cnt, (size_t)seed_wq_cnt_words() * 4));
         CHKW(hipMalloc(&ws->d_lvtab, (uint64_t)ws->heavy_blocks * lv_table_bytes()));
         const char *e = getenv("SALT_GPU_ALL_HEAVY");
@@ -409,7 +413,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     }
     SeedParams sp; sp.pg = pg; sp.n_reads = n_reads; sp.spr = spr; sp.l_seed = o->l_seed; sp.l_overlap = o->l_overlap;
     sp.max_seed = o->max_seed; sp.seed_only_ref = o->seed_only_ref;
-    { static const bool off = getenv("SALT_GPU_NO_UNIQUE") && atoi(getenv("SALT_GPU_NO_UNIQUE")); sp.resolve_unique = !off; }
+    sp.resolve_unique = !ws->no_unique;
     if (n_reads > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads than the workspace holds");
     AlignParams ap; ap.pg = pg; ap.n_reads = n_reads; ap.spr = spr; ap.l_seed = o->l_seed; ap.max_locate = o->max_locate; ap.max_hits = o->max_hits;
     ap.all_heavy = ws->all_heavy; ap.pe = pe; ap.dbg_stop = 0; ap.heavy_stop = 0; ap.max_amb = pe ? 5u : 200u;
@@ -1340,6 +1344,12 @@ extern "C" int salt_gpu_ws_queue_counts(salt_gpu_ws_t *ws, uint32_t out[8])
     SeCtl c; HIPCHK(hipMemcpy(&c, ws->d_qctl, sizeof c, hipMemcpyDeviceToHost));
     memset(out, 0, 32);
     out[0] = c.light_queued; out[2] = c.gap_slots; out[5] = c.gap_items; out[6] = c.cigar_items; out[7] = c.cigar_head;
+    {   // the longest R list and the longest C list among the segments of k_seed's walk queues
+        std::vector<uint32_t> wc(seed_wq_cnt_words());
+        HIPCHK(hipMemcpy(wc.data(), ws->d_wq_cnt, wc.size() * 4, hipMemcpyDeviceToHost));
+        const uint32_t per_list = seed_wq_cnt_words() / 2u, stride = per_list / 64u;
+        for (uint32_t i = 0; i < 64u; ++i) { out[1] = std::max(out[1], wc[i * stride]); out[3] = std::max(out[3], wc[per_list + i * stride]); }
+    }
     return SALT_OK;
 }
 
