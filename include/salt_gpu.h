@@ -32,6 +32,7 @@ extern "C" {
 #define SALT_E_NOMEM        -3
 #define SALT_E_INDEX        -4   /* malformed index arrays */
 #define SALT_E_CAPACITY     -5   /* batch larger than the workspace was created for */
+#define SALT_E_DATA         -6   /* damaged compressed input */
 
 #define SALT_MAX_READ_LEN   512  /* bases per read handled by the kernels */
 #define SALT_MAX_HITS       5    /* aln.h:133 */
@@ -214,6 +215,25 @@ int  salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on);
  * (0 for an empty text; no end-of-file block).  The same text gives the same bytes on every run.  SALT_E_CAPACITY when out_cap is too
  * small: n_bytes + 31 bytes per block is the exact bound, 65 536 bytes per block always suffice. */
 int  salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes);
+/* BGZF input (blocked-gzip FASTQ): the members of a file inflated on the device (k_bgzf_inflate, one workgroup per member: stored, fixed and
+ * dynamic blocks, any number per member; the CRC-32 and ISIZE of every member checked there).  Only the compressed bytes cross to the device.
+ * A member that does not inflate to exactly its ISIZE bytes with its CRC-32 makes the call return SALT_E_DATA; salt_gpu_last_error() names the
+ * first such member and the reason.  Damaged input cannot make a kernel read or write outside the member's bytes and its own text range.
+ *
+ * salt_gpu_bgzf_inflate: host buffers in and out.  bgzf[0 .. n_bytes) must be whole members (an end-of-file block is one, of no text); they are
+ * found by their BSIZE fields.  *out_bytes = the text's length, also with SALT_E_CAPACITY (out_cap smaller than that; nothing is written then). */
+int  salt_gpu_bgzf_inflate(int device, const void *bgzf, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes);
+/* The members of one chunk -> the workspace's device text buffer, which holds them until the next call.  blocks[0 .. n_cbytes) (page-locked for
+ * an asynchronous copy) holds n_blocks members back to back; c_off / u_off (n_blocks + 1 entries each, ascending, from 0) say where every
+ * member starts in blocks and where its text starts in the text: the caller has them from the BSIZE and ISIZE fields, without inflating. */
+int  salt_gpu_ws_inflate_bgzf(salt_gpu_ws_t *ws, const void *blocks, uint64_t n_cbytes, uint32_t n_blocks, const uint32_t *c_off, const uint32_t *u_off);
+/* Bytes [off, off + n) of that text to the host: the caller looks for record boundaries in a window, not in the whole text. */
+int  salt_gpu_ws_text_peek(salt_gpu_ws_t *ws, uint64_t off, uint64_t n, void *dst);
+/* salt_gpu_align_se_text over bytes [off, off + n_bytes) of that text (a device-to-device copy where the other takes its block from the host);
+ * add_newline: a newline is put behind the range (the file's last record lacks its own).  Results and returns as salt_gpu_align_se_text,
+ * SALT_E_INVAL for a range that is not whole 4-line FASTQ records included. */
+int  salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_text_opt_t *topt, uint64_t off, uint64_t n_bytes, int add_newline,
+                                const char **sam, uint64_t *sam_bytes, uint32_t *n_reads);
 int  salt_gpu_host_alloc(uint64_t bytes, void **ptr);      /* page-locked host memory for the text buffers */
 void salt_gpu_host_free(void *ptr);
 /* Multi-GPU drivers (`salt --gpus N`, which stands where alnse_core's pthread fan-out is, alnse.c:1419-1429): the host NUMA node of a device

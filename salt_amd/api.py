@@ -394,6 +394,22 @@ def bgzf_deflate(data, device=0):
     return out.raw[:n.value]
 
 
+def bgzf_inflate(data, device=0):
+    """Whole BGZF members (blocked gzip; an end-of-file block is one) -> their text, by the device kernel behind blocked-gzip FASTQ input.
+    SaltError when a member is damaged: the message names the first such member and the reason."""
+    g = gpu_lib()
+    g.salt_gpu_bgzf_inflate.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    data = bytes(data)
+    n = ctypes.c_uint64(0)
+    rc = g.salt_gpu_bgzf_inflate(int(device), data, len(data), None, 0, ctypes.byref(n))       # the text's length (ISIZE fields): nothing runs yet
+    if rc != -5:                                                                               # SALT_E_CAPACITY: there is text
+        _gpu_check(rc)
+        return b""
+    out = ctypes.create_string_buffer(n.value)
+    _gpu_check(g.salt_gpu_bgzf_inflate(int(device), data, len(data), out, n.value, ctypes.byref(n)))
+    return out.raw[:n.value]
+
+
 BAM_MAX_NAME = 254      # bytes of a BAM read name (l_read_name is one byte and counts the NUL)
 
 

@@ -13,6 +13,7 @@
 #include <vector>
 #include <algorithm>
 #include "salt_kernels.h"
+#include "salt_inflate_block.h"
 #include <rccl/rccl.h>
 
 using namespace salt;
@@ -66,6 +67,10 @@ struct salt_gpu_ws {
     bool sam_bam = false;
     uint32_t *d_bz_slots = nullptr, *d_bz_sizes = nullptr; unsigned long long *d_bz_offs = nullptr; uint8_t *d_bz_out = nullptr; uint64_t bz_blocks_cap = 0;
     char *h_bz = nullptr; uint64_t h_bz_cap = 0;                             // page-locked, only for a compressed block that outgrows h_sam
+    // salt_gpu_ws_inflate_bgzf: a chunk's BGZF members, their offsets and status words, and the text they inflate to (allocated on first use, grown on demand)
+    uint8_t *d_zin = nullptr; uint64_t zin_cap = 0; unsigned long long *d_zoff = nullptr; uint32_t *d_zstat = nullptr; uint64_t zblocks_cap = 0;
+    uint8_t *d_text = nullptr; uint64_t text_cap = 0, text_bytes = 0;
+    std::vector<unsigned long long> h_zoff; std::vector<uint32_t> h_zstat;
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
     uint32_t heavy_blocks = 2048, gap_blocks = 2048;
     QueueRange *d_ranges = nullptr;                                           // k_heavy's queue ranges: k_light's push counters, the heads
@@ -351,6 +356,7 @@ extern "C" void salt_gpu_ws_destroy(salt_gpu_ws_t *ws)
     hipSetDevice(ws->ix->device);
     hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_wq_cnt); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_ranges); hipFree(ws->d_qctl); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
     hipFree(ws->d_raw); hipFree(ws->d_tile); hipFree(ws->d_lines); hipFree(ws->d_rec); hipFree(ws->d_tctl); hipFree(ws->d_samoff); hipFree(ws->d_samslot); hipFree(ws->d_samseg); hipFree(ws->d_scan); hipFree(ws->d_sam); hipFree(ws->d_rg);
+    hipFree(ws->d_zin); hipFree(ws->d_zoff); hipFree(ws->d_zstat); hipFree(ws->d_text);
     if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam);
     hipFree(ws->d_bz_slots); hipFree(ws->d_bz_sizes); hipFree(ws->d_bz_offs); hipFree(ws->d_bz_out); if (ws->h_bz) hipHostFree(ws->h_bz);
     hipFree(ws->d_pe_scr); hipFree(ws->d_pairs); hipFree(ws->d_req); hipFree(ws->d_swres); hipFree(ws->d_pctl); hipFree(ws->d_sw_scr); hipFree(ws->d_pcq);
@@ -705,6 +711,118 @@ extern "C" int salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_by
     return done(SALT_OK);
 }
 
+// ---- BGZF input: members inflated on the device ----
+static int inflate_status(const uint32_t *status, uint64_t n_blocks)
+{
+    for (uint64_t b = 0; b < n_blocks; ++b)
+        if (status[b]) return fail(SALT_E_DATA, "BGZF member " + std::to_string(b) + ": " + bgzf::inflate_reason(status[b]));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_bgzf_inflate(int device, const void *bgzf_, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!out_bytes || (n_bytes && !bgzf_)) return fail(SALT_E_INVAL, "null argument");
+    *out_bytes = 0;
+    if (n_bytes == 0) return SALT_OK;
+    // the members, by their BSIZE fields; the text offsets, by their ISIZE fields
+    const uint8_t *z = static_cast<const uint8_t *>(bgzf_);
+    std::vector<unsigned long long> c_off, u_off;
+    uint64_t at = 0, u = 0;
+    while (at < n_bytes) {
+        const uint8_t *h = z + at;
+        uint64_t bsize = 0;
+        if (n_bytes - at >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && h[3] == 4) {
+            const uint32_t xlen = h[10] | h[11] << 8;
+            for (uint32_t p = 12; p + 4 <= 12 + xlen && at + p + 6 <= n_bytes; ) {
+                const uint32_t slen = h[p + 2] | h[p + 3] << 8;
+                if (h[p] == 'B' && h[p + 1] == 'C' && slen == 2) { bsize = (h[p + 4] | h[p + 5] << 8) + 1u; break; }
+                p += 4 + slen;
+            }
+        }
+        if (bsize < 26 || bsize > n_bytes - at)
+            return fail(SALT_E_DATA, "BGZF member " + std::to_string(c_off.size()) + ": " + (bsize ? "its BSIZE points past the end of the data" : bgzf::inflate_reason(bgzf::INFL_E_HEADER)));
+        const uint8_t *t = h + bsize - 4;
+        const uint32_t isize = t[0] | t[1] << 8 | t[2] << 16 | (uint32_t)t[3] << 24;
+        if (isize > bgzf::INFL_MAX) return fail(SALT_E_DATA, "BGZF member " + std::to_string(c_off.size()) + ": " + bgzf::inflate_reason(bgzf::INFL_E_SIZE));
+        c_off.push_back(at); u_off.push_back(u);
+        at += bsize; u += isize;
+    }
+    const uint64_t n_blocks = c_off.size();
+    c_off.push_back(at); u_off.push_back(u);
+    *out_bytes = u;
+    if (u > out_cap) return fail(SALT_E_CAPACITY, "output buffer smaller than the text (" + std::to_string(u) + " bytes)");
+    if (u && !out) return fail(SALT_E_INVAL, "null argument");
+    if (n_blocks > 0x7FFFFFFFull) return fail(SALT_E_CAPACITY, "more than 2^31 BGZF members in one call");
+    int n_dev = 0;
+    HIPCHK(hipGetDeviceCount(&n_dev));
+    if (n_dev <= 0) return fail(SALT_E_HIP, "no HIP device visible: the BGZF kernels cannot run (there is no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    uint8_t *d_in = nullptr, *d_out = nullptr; unsigned long long *d_off = nullptr; uint32_t *d_stat = nullptr;
+    auto done = [&](int rc) { hipFree(d_in); hipFree(d_out); hipFree(d_off); hipFree(d_stat); return rc; };
+    DONECHK(hipMalloc((void **)&d_in, n_bytes + 64));
+    DONECHK(hipMalloc((void **)&d_out, u + 64));
+    DONECHK(hipMalloc((void **)&d_off, 2 * (n_blocks + 1) * 8));
+    DONECHK(hipMalloc((void **)&d_stat, n_blocks * 4));
+    DONECHK(hipMemcpy(d_in, z, n_bytes, hipMemcpyHostToDevice));
+    DONECHK(hipMemcpy(d_off, c_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice));
+    DONECHK(hipMemcpy(d_off + n_blocks + 1, u_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice));
+    DONECHK(launch_bgzf_inflate(d_in, d_off, d_off + n_blocks + 1, (uint32_t)n_blocks, d_out, d_stat, nullptr));
+    std::vector<uint32_t> status(n_blocks);
+    DONECHK(hipMemcpy(status.data(), d_stat, n_blocks * 4, hipMemcpyDeviceToHost));
+    if (int rc = inflate_status(status.data(), n_blocks)) { *out_bytes = 0; return done(rc); }
+    if (u) DONECHK(hipMemcpy(out, d_out, u, hipMemcpyDeviceToHost));
+    return done(SALT_OK);
+}
+
+extern "C" int salt_gpu_ws_inflate_bgzf(salt_gpu_ws_t *ws, const void *blocks, uint64_t n_cbytes, uint32_t n_blocks, const uint32_t *c_off, const uint32_t *u_off)
+{
+    if (!ws || (n_blocks && (!blocks || !c_off || !u_off))) return fail(SALT_E_INVAL, "null argument");
+    ws->text_bytes = 0;
+    if (n_blocks == 0) return SALT_OK;
+    if (n_blocks > 0x7FFFFFFFu || c_off[0] != 0 || u_off[0] != 0 || c_off[n_blocks] > n_cbytes) return fail(SALT_E_INVAL, "bad BGZF member offsets");
+    for (uint32_t b = 0; b < n_blocks; ++b)
+        if (c_off[b + 1] < c_off[b] || u_off[b + 1] < u_off[b]) return fail(SALT_E_INVAL, "bad BGZF member offsets");
+    HIPCHK(hipSetDevice(ws->ix->device));
+    hipStream_t st = ws->stream;
+    const uint64_t n_text = u_off[n_blocks];
+    REGROW(ws->d_zin, ws->zin_cap, (uint64_t)c_off[n_blocks] + 64, uint8_t);
+    REGROW(ws->d_text, ws->text_cap, n_text + 64, uint8_t);
+    if (n_blocks > ws->zblocks_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        hipFree(ws->d_zoff); hipFree(ws->d_zstat); ws->d_zoff = nullptr; ws->d_zstat = nullptr; ws->zblocks_cap = 0;
+        const uint64_t want = (uint64_t)n_blocks + n_blocks / 4 + 1;
+        HIPCHK(hipMalloc((void **)&ws->d_zoff, 2 * (want + 1) * 8));
+        HIPCHK(hipMalloc((void **)&ws->d_zstat, want * 4));
+        ws->zblocks_cap = want;
+    }
+    ws->h_zoff.resize(2 * ((size_t)n_blocks + 1)); ws->h_zstat.resize(n_blocks);
+    for (uint32_t b = 0; b <= n_blocks; ++b) { ws->h_zoff[b] = c_off[b]; ws->h_zoff[(size_t)n_blocks + 1 + b] = u_off[b]; }
+    HIPCHK(hipMemcpyAsync(ws->d_zin, blocks, c_off[n_blocks], hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ws->d_zoff, ws->h_zoff.data(), ws->h_zoff.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_bgzf_inflate(ws->d_zin, ws->d_zoff, ws->d_zoff + n_blocks + 1, n_blocks, ws->d_text, ws->d_zstat, st));
+    HIPCHK(hipMemcpyAsync(ws->h_zstat.data(), ws->d_zstat, (uint64_t)n_blocks * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = inflate_status(ws->h_zstat.data(), n_blocks)) return rc;
+    ws->text_bytes = n_text;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_text_peek(salt_gpu_ws_t *ws, uint64_t off, uint64_t n, void *dst)
+{
+    if (!ws || (n && !dst)) return fail(SALT_E_INVAL, "null argument");
+    if (off > ws->text_bytes || n > ws->text_bytes - off) return fail(SALT_E_INVAL, "range outside the inflated text");
+    if (n == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ws->ix->device));
+    HIPCHK(hipMemcpyAsync(dst, ws->d_text + off, n, hipMemcpyDeviceToHost, ws->stream));
+    HIPCHK(hipStreamSynchronize(ws->stream));
+    return SALT_OK;
+}
+
+// The text entry points behind their arguments: the block comes from the host (fastq) or from the workspace's inflated text (d_src, with
+// a newline put behind it when add_newline); everything behind the copy-in is one body.
+static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, const uint8_t *d_src, uint64_t n_bytes, int add_newline,
+                        const char **sam, uint64_t *sam_bytes, uint32_t *n_reads);
+
 extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, uint64_t n_bytes,
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
 {
@@ -713,6 +831,30 @@ extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     if (n_bytes == 0) return SALT_OK;
     if (n_bytes >= 0xFFFFFFF0ull) return fail(SALT_E_CAPACITY, "FASTQ block of 4 GiB or more");
     if (fastq[n_bytes - 1] != '\n') return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
+    return se_text_impl(ws, o, to, fastq, nullptr, n_bytes, 0, sam, sam_bytes, n_reads);
+}
+
+extern "C" int salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, uint64_t off, uint64_t n_bytes, int add_newline,
+                                          const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
+{
+    if (!ws || !o || !to || !sam || !sam_bytes || !n_reads) return fail(SALT_E_INVAL, "null argument");
+    *sam = nullptr; *sam_bytes = 0; *n_reads = 0;
+    if (off > ws->text_bytes || n_bytes > ws->text_bytes - off) return fail(SALT_E_INVAL, "range outside the inflated text");
+    if (n_bytes == 0) return SALT_OK;
+    if (n_bytes >= 0xFFFFFFF0ull) return fail(SALT_E_CAPACITY, "FASTQ block of 4 GiB or more");
+    if (!add_newline) {
+        char last = 0;
+        if (int rc = salt_gpu_ws_text_peek(ws, off + n_bytes - 1, 1, &last)) return rc;
+        if (last != '\n') return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
+    }
+    return se_text_impl(ws, o, to, nullptr, ws->d_text + off, n_bytes, add_newline, sam, sam_bytes, n_reads);
+}
+
+static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, const uint8_t *d_src, uint64_t n_bytes, int add_newline,
+                        const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
+{
+    const uint64_t n_src = n_bytes;
+    if (d_src && add_newline) ++n_bytes;
     salt_gpu_index *ix = ws->ix;
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
@@ -732,7 +874,12 @@ extern "C" int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
         if (need > ws->scan_bytes) { HIPCHK(hipStreamSynchronize(st)); hipFree(ws->d_scan); ws->d_scan = nullptr; ws->scan_bytes = 0; HIPCHK(hipMalloc(&ws->d_scan, need)); ws->scan_bytes = need; }
     }
     mark();
-    HIPCHK(hipMemcpyAsync(ws->d_raw, fastq, n_bytes, hipMemcpyHostToDevice, st));
+    if (d_src) {
+        static const char nl = '\n';
+        HIPCHK(hipMemcpyAsync(ws->d_raw, d_src, n_src, hipMemcpyDeviceToDevice, st));
+        if (add_newline) HIPCHK(hipMemcpyAsync(ws->d_raw + n_src, &nl, 1, hipMemcpyHostToDevice, st));
+    } else
+        HIPCHK(hipMemcpyAsync(ws->d_raw, fastq, n_bytes, hipMemcpyHostToDevice, st));
     // newline count first: the line table is sized by it
     uint32_t n_nl = 0;
     HIPCHK(launch_fq_count(ws->d_raw, n_bytes, ws->d_tile, ws->d_scan, ws->scan_bytes, st));

@@ -212,6 +212,12 @@ inline uint64_t bgzf_blocks(uint64_t n) { return (n + BGZF_CUT_BYTES - 1) / BGZF
 inline uint64_t bgzf_bound(uint64_t n) { return n + 31 * bgzf_blocks(n); }       // a stored block: 18 + 5 + text + 8
 hipError_t launch_bgzf_deflate(const uint8_t *text, uint64_t n, uint32_t *slots, uint32_t *sizes, unsigned long long *offs, uint8_t *out, hipStream_t st);
 
+// ---- BGZF input (salt_inflate.hip) ----
+// members[c_off[b] .. c_off[b + 1]) -> text[u_off[b] .. u_off[b + 1]) for every b < n_blocks, one workgroup per member; status[b] = 0 or the
+// reason member b is bad (salt_inflate_block.h: nothing of a bad member's text is written).  The offsets are device arrays of n_blocks + 1.
+hipError_t launch_bgzf_inflate(const uint8_t *members, const unsigned long long *c_off, const unsigned long long *u_off, uint32_t n_blocks,
+                               uint8_t *text, uint32_t *status, hipStream_t st);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

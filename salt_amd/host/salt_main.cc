@@ -40,6 +40,12 @@
 extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on) __attribute__((weak));
 // Likewise the device's BAM record kernels: without them --bam encodes the records on the host, from the SAM text (salt_bam_from_sam).
 extern "C" int salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on) __attribute__((weak));
+// Blocked gzip input inflated on the device: the same way, and only with SALT_INFLATE_DEVICE=1 -- one decoding lane per CU is slower than the
+// workers' zlib threads ("BGZF input").  Without all three, without the variable or with SALT_INFLATE_HOST=1 the workers inflate with zlib.
+extern "C" int salt_gpu_ws_inflate_bgzf(salt_gpu_ws_t *ws, const void *blocks, uint64_t n_cbytes, uint32_t n_blocks, const uint32_t *c_off, const uint32_t *u_off) __attribute__((weak));
+extern "C" int salt_gpu_ws_text_peek(salt_gpu_ws_t *ws, uint64_t off, uint64_t n, void *dst) __attribute__((weak));
+extern "C" int salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_text_opt_t *topt, uint64_t off, uint64_t n_bytes, int add_newline,
+                                          const char **sam, uint64_t *sam_bytes, uint32_t *n_reads) __attribute__((weak));
 
 namespace {
 
@@ -613,6 +619,27 @@ static uint64_t next_record_start(const char *buf, uint64_t n, uint64_t from, bo
     return n;
 }
 
+// next_record_start over text that lies on the device: text bytes [base, base + n) stand where buf[0 .. n) stands there (add_nl: a newline
+// counts as byte n - 1, the file's last record lacks its own).  The function looks forward only, so it is run on a window peeked from
+// `from` on -- 64 KiB, then TEXT_SLACK, then everything -- and a window that ends before the text does is widened when it answers "none":
+// the offset is the one the whole buffer would give.  Returns false when the peek fails.
+static bool next_record_start_dev(salt_gpu_ws_t *ws, std::vector<char> &win, uint64_t base, uint64_t n, bool add_nl, uint64_t from, bool at_file_start, uint64_t *res)
+{
+    const uint64_t ctx = from ? 1 : 0;                        // the byte in front of `from`: is `from` a line start?
+    const uint64_t widths[3] = { 1u << 16, TEXT_SLACK, n };
+    for (int i = 0; i < 3; ++i) {
+        const uint64_t w_lo = from - ctx, w_hi = std::min(n, from + widths[i]), wn = w_hi - w_lo;
+        const bool nl_in = add_nl && w_hi == n;               // the window reaches the newline that is not in the text
+        win.resize((size_t)wn + 1);
+        if (salt_gpu_ws_text_peek(ws, base + w_lo, wn - (nl_in ? 1 : 0), win.data())) return false;
+        if (nl_in) win[(size_t)wn - 1] = '\n';
+        const uint64_t r = from < n ? next_record_start(win.data(), wn, ctx, ctx ? win[0] == '\n' : at_file_start) : wn;
+        if (r < wn || w_hi == n) { *res = r < wn ? w_lo + r : n; return true; }
+    }
+    *res = n;
+    return true;
+}
+
 // What the text path needs to know before the index is there: chunk size, workers, and -- from the first 64 KB of the file -- how many
 // reads a chunk is expected to hold and how much SAM they turn into.  Workspaces are sized by that expectation (+ 30 %), not by the
 // worst case of 32-byte records; a chunk that holds more reads (SALT_E_CAPACITY) has its worker re-create the workspace for the worst
@@ -726,6 +753,9 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
     const uint64_t n_chunks = (R.file_size + R.chunk - 1) / R.chunk;
     // blocked gzip input: every worker inflates with a few helper threads (a block inflates at ~0.3 GB/s on one core; a worker's chunk must
     // not take longer to inflate than the device takes for the chunks of the other workers)
+    const bool dev_inflate = R.bgzf && salt_gpu_ws_inflate_bgzf && salt_gpu_ws_text_peek && salt_gpu_align_se_text_dev &&
+                             getenv("SALT_INFLATE_DEVICE") && atoi(getenv("SALT_INFLATE_DEVICE")) && !(getenv("SALT_INFLATE_HOST") && atoi(getenv("SALT_INFLATE_HOST")));
+    if (R.bgzf) fprintf(stderr, "[salt] BGZF input: %s inflate, %llu blocks\n", dev_inflate ? "device" : "host", (unsigned long long)(R.bgzf->coff.size() - 1));
     int inflate_helpers = 0;
     if (R.bgzf) { inflate_helpers = 5; if (const char *e = getenv("SALT_INFLATE_HELPERS")) { const int v = atoi(e); if (v >= 0 && v <= 64) inflate_helpers = v; } }
     std::vector<std::thread> workers;
@@ -736,6 +766,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
             salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk];
             pin_to_device_node(wk / n_workers_per_gpu);
             std::vector<unsigned char> cbuf;                              // blocked gzip input: the compressed bytes of a chunk's blocks
+            std::vector<char> win; std::vector<uint32_t> zc, zu;          // ... inflated on the device: the windows peeked from its text, the chunk's block offsets
             const bool trace = getenv("SALT_TEXT_TRACE") != nullptr;      // per-worker timeline on stderr
             const double tw_start = now(); int n_calls = 0; double t_first = 0, t_rest = 0;
             uint32_t ws_reads = max_reads;
@@ -754,6 +785,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                 double tr0 = now();
                 uint64_t got = 0;
                 char *const buf0 = buf;                               // (blocked input inflates whole blocks: the chunk's bytes then start inside the buffer)
+                bool on_dev = false; uint64_t dev_base = 0;           // the chunk's text lies in the workspace, byte rd_lo of the file at dev_base
                 if (R.bgzf) {
                     // the blocks that hold text bytes [rd_lo, rd_hi): read as one piece, inflated side by side by this worker and its helpers
                     const Bgzf &B = *R.bgzf;
@@ -762,13 +794,27 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                     if (b1 >= B.uoff.size()) b1 = B.uoff.size() - 1;
                     const uint64_t c0 = B.coff[b0], c1 = B.coff[b1], u0 = B.uoff[b0];
                     bool ok = B.uoff[b1] - u0 <= P.in_cap - 64;
-                    if (ok) {
+                    // on the device: the compressed blocks go into the page-locked buffer as they are (blocks that deflate did not shrink can
+                    // outgrow it by their headers: such a chunk is inflated here)
+                    on_dev = dev_inflate && ok && c1 - c0 <= P.in_cap - 64 && c1 - c0 < 0xFFFFFFFFull && B.uoff[b1] - u0 < 0xFFFFFFFFull;
+                    if (on_dev) {
+                        uint64_t cg = 0;
+                        while (cg < c1 - c0) { const ssize_t r = pread(R.fd, buf0 + cg, c1 - c0 - cg, (off_t)(c0 + cg)); if (r <= 0) break; cg += (uint64_t)r; }
+                        ok = cg == c1 - c0;
+                        zc.resize(b1 - b0 + 1); zu.resize(b1 - b0 + 1);
+                        for (size_t b = b0; b <= b1; ++b) { zc[b - b0] = (uint32_t)(B.coff[b] - c0); zu[b - b0] = (uint32_t)(B.uoff[b] - u0); }
+                        if (ok) {
+                            const int zrc = salt_gpu_ws_inflate_bgzf(ws, buf0, c1 - c0, (uint32_t)(b1 - b0), zc.data(), zu.data());
+                            if (zrc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); if (zrc != SALT_E_DATA) { set_failed(); break; } ok = false; }
+                        }
+                        dev_base = rd_lo - u0;
+                    } else if (ok) {
                         cbuf.resize((size_t)(c1 - c0));
                         uint64_t cg = 0;
                         while (cg < c1 - c0) { const ssize_t r = pread(R.fd, cbuf.data() + cg, c1 - c0 - cg, (off_t)(c0 + cg)); if (r <= 0) break; cg += (uint64_t)r; }
                         ok = cg == c1 - c0;
                     }
-                    if (ok) {
+                    if (ok && !on_dev) {
                         std::atomic<size_t> nb{ b0 }; std::atomic<bool> bad{ false };
                         auto work = [&]() {
                             for (;;) {
@@ -794,25 +840,45 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                     }
                     if (got != rd_hi - rd_lo) { fprintf(stderr, "[salt] short read on %s\n", fn_reads); set_failed(); break; }
                 }
-                t_read = t_read + (now() - tr0);
                 uint64_t n = got;
-                if (rd_hi == R.file_size && n && buf[n - 1] != '\n') buf[n++] = '\n';          // a last record without its newline
                 const uint64_t b0 = lo - rd_lo;                                                  // offset of file byte `lo` in buf
-                const uint64_t beg = next_record_start(buf, n, b0, lo == 0 || buf[b0 - 1] == '\n');
-                uint64_t end = n;
-                if (hi < R.file_size) end = next_record_start(buf, n, hi - rd_lo, buf[hi - rd_lo - 1] == '\n');
+                uint64_t beg = 0, end = 0; bool add_nl = false;
+                if (on_dev) {
+                    // the same cuts from windows of the device's text
+                    char last = '\n';
+                    bool pk = !(rd_hi == R.file_size && n) || salt_gpu_ws_text_peek(ws, dev_base + n - 1, 1, &last) == 0;
+                    if (last != '\n') { add_nl = true; ++n; }
+                    pk = pk && next_record_start_dev(ws, win, dev_base, n, add_nl, b0, lo == 0, &beg);
+                    end = n;
+                    if (pk && hi < R.file_size) pk = next_record_start_dev(ws, win, dev_base, n, add_nl, hi - rd_lo, false, &end);
+                    if (!pk) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
+                    t_read = t_read + (now() - tr0);
+                } else {
+                    t_read = t_read + (now() - tr0);
+                    if (rd_hi == R.file_size && n && buf[n - 1] != '\n') buf[n++] = '\n';      // a last record without its newline
+                    beg = next_record_start(buf, n, b0, lo == 0 || buf[b0 - 1] == '\n');
+                    end = n;
+                    if (hi < R.file_size) end = next_record_start(buf, n, hi - rd_lo, buf[hi - rd_lo - 1] == '\n');
+                }
                 if (hi < R.file_size && end == n) { fprintf(stderr, "[salt] a FASTQ record longer than %llu bytes near offset %llu\n", (unsigned long long)TEXT_SLACK, (unsigned long long)hi); set_failed(); break; }
                 const uint64_t beg2 = std::min(beg, end);
                 const char *sam = nullptr; uint64_t sam_bytes = 0; uint32_t n_reads = 0;
                 double tg0 = now();
-                int grc = end > beg2 ? salt_gpu_align_se_text(ws, &ao, &to, buf + beg2, end - beg2, &sam, &sam_bytes, &n_reads) : 0;
+                // (on the device the range ends with the text's own newline, or with the one put behind the file's last record)
+                auto align = [&]() {
+                    if (!on_dev) return salt_gpu_align_se_text(ws, &ao, &to, buf + beg2, end - beg2, &sam, &sam_bytes, &n_reads);
+                    const bool nl = add_nl && end == n;
+                    return salt_gpu_align_se_text_dev(ws, &ao, &to, dev_base + beg2, end - beg2 - (nl ? 1 : 0), nl ? 1 : 0, &sam, &sam_bytes, &n_reads);
+                };
+                int grc = end > beg2 ? align() : 0;
                 if (grc == SALT_E_CAPACITY && ws_reads < worst_reads) {                         // shorter records than the file's head promised
                     if (trace) fprintf(stderr, "[salt] worker %d: chunk %llu holds more than %u reads, workspace re-created for %u\n", wk, (unsigned long long)k, ws_reads, worst_reads);
                     salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = worst_reads;
                     grc = salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws);
                     if (!grc && g_bgzf.device) grc = salt_gpu_ws_set_sam_bgzf(ws, 1);
                     if (!grc && g_bam.device) grc = salt_gpu_ws_set_sam_bam(ws, 1);
-                    if (!grc) grc = salt_gpu_align_se_text(ws, &ao, &to, buf + beg2, end - beg2, &sam, &sam_bytes, &n_reads);
+                    if (!grc && on_dev) grc = salt_gpu_ws_inflate_bgzf(ws, buf0, zc.back(), (uint32_t)(zc.size() - 1), zc.data(), zu.data());      // the new workspace's text
+                    if (!grc) grc = align();
                 }
                 if (grc == SALT_E_INVAL && g_bam.device && strncmp(salt_gpu_last_error(), "BAM:", 4) == 0) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 if (grc == SALT_E_INVAL) {
