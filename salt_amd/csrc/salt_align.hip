@@ -281,12 +281,12 @@ __device__ __forceinline__ bool seed_is_n(const SeedCtx c, uint32_t i)
 //            in front of it (salt_ctx_record.h; side B is complete iff CTX_N_B <= p0 <= ctx_len), or without the table the suffix-array
 //            entry; the seed leaves located (.w = 2: .x = .y = the genome position), dead, or goes on to
 //   WK_TEXT  (C) the comparison against the 2-bit text: at most two pieces of up to 16 bases, the later bases (consumed first) first.
-//   WK_REC / WK_CTX are k_seed_walk's own (a refilled lane's queue record and tb words).
-enum : uint32_t { WK_IDLE = 0, WK_REC, WK_CTX, WK_HEAD, WK_EXT, WK_SA, WK_TEXT };
+//   WK_REC is k_seed_walk's own (a refilled lane's queue record, which carries the seed's tb words).
+enum : uint32_t { WK_IDLE = 0, WK_REC, WK_HEAD, WK_EXT, WK_SA, WK_TEXT };
 struct Walk { uint32_t ph, k, l, ext, p0; int i; };                 // p0: WK_TEXT's suffix position
 // What a step reads, as addresses: up to four 16-byte pieces from each of pa and pb (the Occ blocks of the interval's two ends; the context
-// record; k_seed_walk's queue record) and up to three / two words from ps / pt (the base's tb words when it is not in registers, the
-// suffix-array entry, the text pieces; k_seed_walk's tb words).  walk_fetch does the loads: every register of WalkLoads is written by
+// record; the two halves of k_seed_walk's queue record) and up to three / two words from ps / pt (the base's tb words when it is not in
+// registers, the suffix-array entry, the text pieces).  walk_fetch does the loads: every register of WalkLoads is written by
 // ONE load and by nothing else, whatever the phase -- a register shared between differently shaped loads would be copied into place
 // behind its load, and the copy waits for the load right where it was issued.  Pieces not asked for stay unset and are not read.
 struct WalkReq { const uint4 *pa, *pb; const uint32_t *ps, *pt; uint32_t na, nb, ns, nt; };
@@ -442,6 +442,7 @@ __device__ __forceinline__ uint4 seed_r_rest(const IndexView &ix, const SeedPara
 }
 
 static constexpr uint32_t WQ_SEG = 64, WQ_STRIDE = 64;            // segments per walk queue; words between their counters
+static constexpr uint32_t WQ_REC = 2;                             // uint4 per walk record: (item, k, l, n0) (w0, w1, w2, n1)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
        uint4 *__restrict__ sai_c, uint4 *__restrict__ sai_r, uint4 *__restrict__ wq, uint32_t *__restrict__ wq_cnt, uint32_t wq_seg_cap,
@@ -449,7 +450,9 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
 {
     // walks still to do go to the queues k_seed_walk drains: [0] R searches, [1] C searches.  The block counts its walks in LDS, reserves
     // their slots in ONE of WQ_SEG segments per list with one atomic (an atomic on one address is served every ~11 ns: 31 000 blocks on one
-    // counter would be a third of a millisecond) and every lane stores its own record.
+    // counter would be a third of a millisecond) and every lane stores its own record: two uint4, (item, k, l, n0) and (w0, w1, w2, n1), the
+    // five tb words seed_ctx has loaded, so that the walk needs no fetch from the read's tb record before its first step (a seed beyond the
+    // in-register limit carries them unused).  The slots of a block are dense in its segment: the stores still cover whole lines.
     __shared__ uint32_t q_n[2], q_base[2];
     const uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n_items = (uint64_t)sp.n_reads * 2u * sp.spr;
     const uint64_t lt = (1ull << lane_id()) - 1ull;
@@ -458,8 +461,10 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
     __syncthreads();
     bool pend_c = false, pend_r = false;
     uint32_t pk_c = 0, pl_c = 0, pk_r = 0, pl_r = 0, at_r = 0, at_c = 0;
+    uint32_t cw0 = 0, cw1 = 0, cw2 = 0, cn0 = 0, cn1 = 0;     // the seed's tb words, for its walk records
     if (item < n_items) {
         const SeedCtx c = seed_ctx(sp, tb, (uint32_t)item, ix.r_lkt_len);
+        cw0 = c.w0; cw1 = c.w1; cw2 = c.w2; cn0 = c.n0; cn1 = c.n1;
         uint4 oc = make_uint4(1, 0, 0, 0), orr = make_uint4(1, 0, 0, 0);
         if (seed_valid(c)) {
             const uint32_t e = c.s + c.k - 1, W = c.W;
@@ -540,8 +545,14 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
     const uint32_t seg = blockIdx.x & (WQ_SEG - 1u);
     if (threadIdx.x < 2 && q_n[threadIdx.x]) q_base[threadIdx.x] = atomicAdd(&wq_cnt[(threadIdx.x * WQ_SEG + seg) * WQ_STRIDE], q_n[threadIdx.x]);
     __syncthreads();
-    if (pend_r) wq[(size_t)seg * wq_seg_cap + q_base[0] + at_r] = make_uint4((uint32_t)item, pk_r, pl_r, 0u);
-    if (pend_c) wq[((size_t)WQ_SEG + seg) * wq_seg_cap + q_base[1] + at_c] = make_uint4((uint32_t)item, pk_c, pl_c, 0u);
+    if (pend_r) {
+        uint4 *rec = wq + ((size_t)seg * wq_seg_cap + q_base[0] + at_r) * WQ_REC;
+        rec[0] = make_uint4((uint32_t)item, pk_r, pl_r, cn0); rec[1] = make_uint4(cw0, cw1, cw2, cn1);
+    }
+    if (pend_c) {
+        uint4 *rec = wq + (((size_t)WQ_SEG + seg) * wq_seg_cap + q_base[1] + at_c) * WQ_REC;
+        rec[0] = make_uint4((uint32_t)item, pk_c, pl_c, cn0); rec[1] = make_uint4(cw0, cw1, cw2, cn1);
+    }
     if (ctr) {                                                // one atomic per wave and counter
         for (int o = 32; o > 0; o >>= 1) {
             n_lkt += __shfl_down(n_lkt, o); n_occ_c += __shfl_down(n_occ_c, o); n_occ_r += __shfl_down(n_occ_r, o);
@@ -557,13 +568,14 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
 // k_seed_walk: the walks k_seed queued, in turns.  In a turn every busy lane does ONE step of its walk (seed_walk_issue / seed_walk_finish:
 // one memory round trip), and the lanes whose walks have ended take the next records of the wave's slice, so a wave no longer pays for the
 // longest of 64 walks (R walks die after 1 to 5 steps, C walks of repeat seeds run their head and up to s extension steps) with the other
-// lanes idle.  A refilled lane's dependent loads are lane states too (WK_REC: the queue record, WK_CTX: the read's tb words, then the walk's
-// phases), and a turn first issues the loads of ALL its lanes and then uses them: one wait per turn, whatever the mix of phases.
+// lanes idle.  A refilled lane's dependent load is a lane state too (WK_REC: both halves of the queue record, which hold the seed's interval
+// and its tb words; the walk begins behind that wait and issues its first step in the next turn), and a turn first issues the loads of ALL
+// its lanes and then uses them: one wait per turn, whatever the mix of phases.
 //   Work is handed out statically: block b serves segment b % WQ_SEG, and wave w of the nw waves on that segment owns the records
 // [n w / nw, n (w + 1) / nw) of both of its lists, the first list in front of the second (C first: the long walks start first and the short R
 // walks fill the lanes they leave).  No atomics, nothing a wave could wait for.  The ballot and the cursor sit at the top of the turn
 // with all 64 lanes present and no lane leaves the loop on its own (loops in which lane groups leave one by one have
-// hung); every turn consumes records or advances every live walk, and a walk has at most k - W + s + 4 turns.
+// hung); every turn consumes records or advances every live walk, and a walk has at most k - W + s + 3 turns.
 //   k_seed has written the dead row for every queued seed, so only a walk that ends alive stores its row.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_seed_walk(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb, uint4 *__restrict__ sai_c, uint4 *__restrict__ sai_r,
@@ -576,7 +588,7 @@ k_seed_walk(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb, uint4 
     const uint32_t na = wq_cnt[(la * WQ_SEG + seg) * WQ_STRIDE], nb = wq_cnt[(lb * WQ_SEG + seg) * WQ_STRIDE];
     const uint32_t a0 = (uint32_t)((uint64_t)na * wv / nw), a1 = (uint32_t)((uint64_t)na * (wv + 1u) / nw);
     const uint32_t b0 = (uint32_t)((uint64_t)nb * wv / nw), b1 = (uint32_t)((uint64_t)nb * (wv + 1u) / nw);
-    const uint4 *qa = wq + ((size_t)la * WQ_SEG + seg) * wq_seg_cap + a0, *qb = wq + ((size_t)lb * WQ_SEG + seg) * wq_seg_cap + b0;
+    const uint4 *qa = wq + (((size_t)la * WQ_SEG + seg) * wq_seg_cap + a0) * WQ_REC, *qb = wq + (((size_t)lb * WQ_SEG + seg) * wq_seg_cap + b0) * WQ_REC;
     const uint32_t tot_a = a1 - a0, tot = tot_a + (b1 - b0);
     const int i_top = (int)((uint32_t)sp.l_seed - ix.r_lkt_len) - 1;
     uint32_t n_aux = 0, n_sa = 0, n_text = 0, n_occ_c = 0, n_occ_r = 0;
@@ -593,26 +605,24 @@ k_seed_walk(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb, uint4 
             const uint32_t t = cur + (uint32_t)__popcll(idle & lt);
             if (w.ph == WK_IDLE && t < tot) {
                 const bool in_a = t < tot_a;
-                qp = in_a ? qa + t : qb + (t - tot_a); is_r = (in_a ? la : lb) == 0u; w.ph = WK_REC;
+                qp = in_a ? qa + (size_t)t * WQ_REC : qb + (size_t)(t - tot_a) * WQ_REC; is_r = (in_a ? la : lb) == 0u; w.ph = WK_REC;
             }
             const uint32_t nx = cur + (uint32_t)__popcll(idle);
             cur = nx < tot ? nx : tot;
         }
         // ---- every lane's loads of this turn ----
         WalkReq q = walk_req_none();
-        if (w.ph == WK_REC) { q.pa = qp; q.na = 1; }
-        else if (w.ph == WK_CTX) { q.ps = c.t2 + c.wb; q.ns = 3; q.pt = c.tn + c.nb; q.nt = 2; }     // stays inside the record (PackGeom)
+        if (w.ph == WK_REC) { q.pa = qp; q.na = WQ_REC; }
         else if (w.ph != WK_IDLE) q = is_r ? seed_walk_issue<true>(ix, sp, c, w) : seed_walk_issue<false>(ix, sp, c, w);
         const WalkLoads ld = walk_fetch(q);
         // ---- and what their phases do with them ----
         bool done = false;
         uint4 row = make_uint4(1, 0, 0, 0);
         if (w.ph == WK_REC) {
-            item = ld.a[0].x; w.k = ld.a[0].y; w.l = ld.a[0].z;
-            c = seed_ctx_geom(sp, tb, item, ix.r_lkt_len); w.ph = WK_CTX;
-        } else if (w.ph == WK_CTX) {
-            c.w0 = ld.s[0]; c.w1 = ld.s[1]; c.w2 = ld.s[2]; c.n0 = ld.t[0]; c.n1 = ld.t[1];
-            done = is_r ? seed_walk_begin<true>(sp, c, w.k, w.l, i_top, w, row) : seed_walk_begin<false>(sp, c, w.k, w.l, i_top, w, row);
+            item = ld.a[0].x;
+            c = seed_ctx_geom(sp, tb, item, ix.r_lkt_len);
+            c.w0 = ld.a[1].x; c.w1 = ld.a[1].y; c.w2 = ld.a[1].z; c.n0 = ld.a[0].w; c.n1 = ld.a[1].w;
+            done = is_r ? seed_walk_begin<true>(sp, c, ld.a[0].y, ld.a[0].z, i_top, w, row) : seed_walk_begin<false>(sp, c, ld.a[0].y, ld.a[0].z, i_top, w, row);
         } else if (w.ph != WK_IDLE) {
             done = is_r ? seed_walk_finish<true>(ix, sp, c, w, ld, row, n_occ_r, n_aux) : seed_walk_finish<false>(ix, sp, c, w, ld, row, n_occ_c, n_aux);
         }
@@ -2660,7 +2670,9 @@ void launch_pe_final(const IndexView &ix, const PackGeom &pg, uint32_t n_pairs, 
 // launch wrappers (called from salt_gpu.hip)
 // ---------------------------------------------------------------------------------------------
 uint32_t seed_wq_seg_cap(uint64_t items) { return (uint32_t)(((items + 255) / 256 + WQ_SEG - 1) / WQ_SEG) * 256u; }      // every seed of every block of a segment
-size_t seed_wq_words(uint64_t items) { return (size_t)2 * WQ_SEG * seed_wq_seg_cap(items) * 4; }                              // uint4 records of both lists, in words
+// 32-byte records of both lists, in words.  Sized for the worst case, every seed walking in both searches: 64 bytes a seed, 512 MB for a
+// workspace at 8 M seeds (10^6 reads of 100 bases at the default stride; 256 MB while a record was one uint4)
+size_t seed_wq_words(uint64_t items) { return (size_t)2 * WQ_SEG * seed_wq_seg_cap(items) * WQ_REC * 4; }
 uint32_t seed_wq_cnt_words() { return 2u * WQ_SEG * WQ_STRIDE; }
 void launch_seed(const IndexView &ix, const SeedParams &sp, const uint32_t *tb, uint4 *sai_c, uint4 *sai_r, uint4 *wq, uint32_t *wq_cnt,
                  uint32_t walk_blocks, unsigned long long *ctr, hipStream_t st)
@@ -2669,7 +2681,6 @@ void launch_seed(const IndexView &ix, const SeedParams &sp, const uint32_t *tb, 
     if (!items) return;
     uint32_t blocks = (uint32_t)((items + 255) / 256);
     const uint32_t cap = seed_wq_seg_cap(items);
-    hipMemsetAsync(wq_cnt, 0, (size_t)seed_wq_cnt_words() * 4, st);
     hipLaunchKernelGGL(k_seed, dim3(blocks), dim3(256), 0, st, ix, sp, tb, sai_c, sai_r, wq, wq_cnt, cap, ctr);
     walk_blocks = (walk_blocks + WQ_SEG - 1) / WQ_SEG * WQ_SEG;
     static const uint32_t r_first = getenv("SALT_GPU_WALK_R_FIRST") && atoi(getenv("SALT_GPU_WALK_R_FIRST")) ? 1u : 0u;      // measurements: the R list in front of the C list

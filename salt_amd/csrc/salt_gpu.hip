@@ -74,6 +74,8 @@ struct salt_gpu_ws {
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
     uint32_t heavy_blocks = 2048, gap_blocks = 2048;
     QueueRange *d_ranges = nullptr;                                           // k_heavy's queue ranges: k_light's push counters, the heads
+    // d_qctl, d_ranges and d_wq_cnt are blocks of ONE allocation, every block 256-byte aligned: one memset per call zeroes them all
+    uint8_t *d_zero = nullptr; size_t zero_bytes = 0;
     int all_heavy = 0;
     hipStream_t stream = nullptr;
     bool timing = false;
@@ -306,8 +308,14 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
     CHKW(hipMalloc((void **)&ws->d_results, (uint64_t)max_reads * sizeof(salt_result_t)));
     CHKW(hipMemset(ws->d_results, 0, (uint64_t)max_reads * sizeof(salt_result_t)));
     CHKW(hipMalloc((void **)&ws->d_queue, queue_words(max_reads) * 4));         // the reads k_light queues (flat, and the segments they arrive in) + k_heavy's overflow queue
-    CHKW(hipMalloc((void **)&ws->d_ranges, QUEUE_RANGES * sizeof(QueueRange)));
-    CHKW(hipMalloc((void **)&ws->d_qctl, sizeof(SeCtl)));
+    {
+        const size_t a = 256, n_ranges = (QUEUE_RANGES * sizeof(QueueRange) + a - 1) / a * a, n_ctl = (sizeof(SeCtl) + a - 1) / a * a;
+        const size_t n_cnt = ((size_t)seed_wq_cnt_words() * 4 + a - 1) / a * a;
+        CHKW(hipMalloc((void **)&ws->d_zero, n_ranges + n_ctl + n_cnt));
+        ws->zero_bytes = n_ranges + n_ctl + n_cnt;
+        ws->d_ranges = reinterpret_cast<QueueRange *>(ws->d_zero); ws->d_qctl = reinterpret_cast<SeCtl *>(ws->d_zero + n_ranges);
+        ws->d_wq_cnt = reinterpret_cast<uint32_t *>(ws->d_zero + n_ranges + n_ctl);
+    }
     ws->gcap = max_reads < (1u << 20) ? max_reads : (1u << 20);         // slots for reads whose gapped pass is deferred (44 B each + their rows in the pool)
     if (const char *e3 = getenv("SALT_GPU_NO_GAP_DEFER")) if (atoi(e3)) ws->gcap = 0;
     if (const char *e3 = getenv("SALT_GPU_GAP_SLOTS")) { const int v = atoi(e3); if (v > 0 && (uint32_t)v < ws->gcap) ws->gcap = (uint32_t)v; }     // tests: the overflow pass
@@ -332,12 +340,13 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
         if (const char *e2 = getenv("SALT_GPU_GAP_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) gap_per_cu = (uint32_t)v; }
         ws->gap_blocks = (uint32_t)prop.multiProcessorCount * gap_per_cu;
         // k_seed_walk: 2 waves per SIMD in blocks of four waves.  Its lanes are all busy, so the grid is set by the four-stream step and not by
-        // the kernel alone: 2 per CU 464 - 467 Mreads/s, 4 per CU 445 - 459, 8 per CU 450 - 458 (profiles/r07/ab_grid_and_order.log)
+        // the kernel alone: 2 per CU 464 - 467 Mreads/s, 4 per CU 445 - 459, 8 per CU 450 - 458 (profiles/r07/ab_grid_and_order.log).  Measured again
+        // with the walk that starts from its record (one turn less): 2 per CU 470 - 479, 3 per CU 469 - 479, 4 per CU 468 - 471; no range lies
+        // above the range at 2 (profiles/r08/ab_walk_grid.log)
         ws->walk_blocks = (uint32_t)prop.multiProcessorCount * 2u;
         if (const char *e2 = getenv("SALT_GPU_WALK_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) ws->walk_blocks = (uint32_t)prop.multiProcessorCount * (uint32_t)v; }
         if (const char *e2 = getenv("SALT_GPU_NO_UNIQUE")) ws->no_unique = atoi(e2) != 0;                    // A/B and tests: every C search walks
         if (const char *e2 = getenv("SALT_GPU_WALK_BLOCKS")) { int v = atoi(e2); if (v > 0 && v <= 65536) ws->walk_blocks = (uint32_t)v; }      // tests: an absolute grid (rounded up to 64s), so that a wave's slice is long
-        CHKW(hipMalloc((void **)&ws->d_wq_cnt, (size_t)seed_wq_cnt_words() * 4));
         CHKW(hipMalloc(&ws->d_lvtab, (uint64_t)ws->heavy_blocks * lv_table_bytes()));
         const char *e = getenv("SALT_GPU_ALL_HEAVY");
         ws->all_heavy = e && atoi(e) != 0;
@@ -354,7 +363,7 @@ extern "C" void salt_gpu_ws_destroy(salt_gpu_ws_t *ws)
 {
     if (!ws) return;
     hipSetDevice(ws->ix->device);
-    hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_wq_cnt); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_ranges); hipFree(ws->d_qctl); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
+    hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_zero); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
     hipFree(ws->d_raw); hipFree(ws->d_tile); hipFree(ws->d_lines); hipFree(ws->d_rec); hipFree(ws->d_tctl); hipFree(ws->d_samoff); hipFree(ws->d_samslot); hipFree(ws->d_samseg); hipFree(ws->d_scan); hipFree(ws->d_sam); hipFree(ws->d_rg);
     hipFree(ws->d_zin); hipFree(ws->d_zoff); hipFree(ws->d_zstat); hipFree(ws->d_text);
     if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam);
@@ -433,8 +442,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     unsigned long long *ctr = o->collect_counters ? ws->d_ctr : nullptr;
     const bool timed = ws->timing && ws->n_timed < MAX_TIMED;
     hipEvent_t *ev = timed ? &ws->ev[(size_t)ws->n_timed * EV_PER_CALL] : nullptr;
-    HIPCHK(hipMemsetAsync(ws->d_qctl, 0, sizeof(SeCtl), st));
-    HIPCHK(hipMemsetAsync(ws->d_ranges, 0, QUEUE_RANGES * sizeof(QueueRange), st));
+    HIPCHK(hipMemsetAsync(ws->d_zero, 0, ws->zero_bytes, st));            // the batch's control words, k_heavy's queue ranges, the walk queues' counters
     if (timed) HIPCHK(hipEventRecord(ev[0], st));
     launch_pack(pg, n_reads, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_pm, ws->d_tb, st);
     if (timed) HIPCHK(hipEventRecord(ev[1], st));

@@ -57,8 +57,9 @@ struct AlignParams {
 static const uint32_t PE_LOCI_CAP = 0x40000;    // loci per strand a PE mate may enumerate = MAX_LOC_POS (alnse.c:42,533); global scratch
 
 void launch_pack(const PackGeom &pg, uint32_t n_reads, const uint8_t *seqs, const uint32_t *offs, uint32_t *pm, uint32_t *tb, hipStream_t st);
-// k_seed (W-mer gather, in-register resolves, walks queued) + k_seed_walk (the queued walks, one per lane).  wq: seed_wq_words(items) words,
-// wq_cnt: seed_wq_cnt_words() words (zeroed inside); walk_blocks: 256-lane blocks of the walk kernel (CUs x 2: two waves per SIMD)
+// k_seed (W-mer gather, in-register resolves, walks queued) + k_seed_walk (the queued walks, one per lane).  wq: seed_wq_words(items) words
+// (a walk record is 32 bytes: the seed, its interval and its five tb words), wq_cnt: seed_wq_cnt_words() words, which the caller has
+// zeroed on the stream; walk_blocks: 256-lane blocks of the walk kernel (CUs x 2: two waves per SIMD)
 void launch_seed(const IndexView &ix, const SeedParams &sp, const uint32_t *tb, uint4 *sai_c, uint4 *sai_r, uint4 *wq, uint32_t *wq_cnt,
                  uint32_t walk_blocks, unsigned long long *ctr, hipStream_t st);
 size_t seed_wq_words(uint64_t items);
