@@ -160,9 +160,14 @@ int  salt_gpu_align_se(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, uint32_t n_
  * (<P>.C.pac bytes, needed by the singleton rescue), l_pac bases. */
 typedef struct { uint32_t min_tlen, max_tlen; } salt_pe_opt_t;      /* -a 250, -b 550 (aln.c:43-44) */
 int  salt_gpu_index_set_pac(salt_gpu_index_t *ix, const uint8_t *pac, uint64_t l_pac);
+/* The context records of the R rows (16 B per row of the R index, outside the image): built at attach when the C rows have theirs and
+ * the device has the room, else by salt_gpu_index_set_pac once it has.  *dev_ptr is NULL and *bytes 0 when the index goes without. */
+int  salt_gpu_index_r_ctx(const salt_gpu_index_t *ix, void **dev_ptr, uint64_t *bytes);
+/* The epoch the workspace's NEXT alignment call runs at (1 .. 2^24 - 1; the R seed rows of a call carry it, salt_device.h). */
+int  salt_gpu_ws_epoch(const salt_gpu_ws_t *ws, uint32_t *next_epoch);
 int  salt_gpu_align_pe(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_pe_opt_t *pe, uint32_t n_pairs,
                        const uint8_t *seqs, const uint32_t *offs, salt_result_t *results);
-/* Same on device-resident buffers (2 * n_pairs reads); only enqueues on `hip_stream`. */
+/* Same on device-resident buffers (2 * n_pairs reads); only enqueues on `hip_stream`; not to be stream-captured and replayed (see salt_gpu_align_se_resident). */
 int  salt_gpu_align_pe_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_pe_opt_t *pe, uint32_t n_pairs,
                                 uint32_t max_read_len, const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream);
 /* Mate rescues of the LAST paired batch that could not be finished as the reference would (their banded traceback needs
@@ -241,7 +246,9 @@ void salt_gpu_host_free(void *ptr);
 int  salt_gpu_device_numa_node(int device, int *node);
 int  salt_gpu_device_count(int *n);
 
-/* Same work on device-resident buffers; only enqueues on `hip_stream` (a hipStream_t, NULL = default). */
+/* Same work on device-resident buffers; only enqueues on `hip_stream` (a hipStream_t, NULL = default).  Every call is its own enqueue:
+ * the kernels take the call's epoch by value from the workspace (the R seed rows of another call are dead by it), so a call must not
+ * be captured into a hipGraph and replayed -- a replay would run at the captured epoch and take the previous replay's rows for live. */
 int  salt_gpu_align_se_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, uint32_t n_reads,
                                 uint32_t max_read_len, const void *d_seqs, const void *d_offs,
                                 void *d_results, void *hip_stream);

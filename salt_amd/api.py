@@ -558,6 +558,22 @@ class GpuAligner:
             done += m
         return res
 
+    def r_ctx(self):
+        """(device pointer or None, bytes) of the R rows' context table of this aligner's index."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_r_ctx.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _gpu_check(lib.salt_gpu_index_r_ctx(self._ix, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def epoch(self):
+        """The epoch the workspace's next alignment call runs at."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_epoch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        e = ctypes.c_uint32()
+        _gpu_check(lib.salt_gpu_ws_epoch(self._ws, ctypes.byref(e)))
+        return e.value
+
     def set_pac(self, index):
         """Uploads the 2-bit genome the singleton rescue aligns against (once per device index; forks made afterwards share it)."""
         if not getattr(self, "_pac_set", False):

@@ -465,7 +465,7 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
     if (item < n_items) {
         const SeedCtx c = seed_ctx(sp, tb, (uint32_t)item, ix.r_lkt_len);
         cw0 = c.w0; cw1 = c.w1; cw2 = c.w2; cn0 = c.n0; cn1 = c.n1;
-        uint4 oc = make_uint4(1, 0, 0, 0), orr = make_uint4(1, 0, 0, 0);
+        uint4 oc = make_uint4(1, 0, 0, 0);
         if (seed_valid(c)) {
             const uint32_t e = c.s + c.k - 1, W = c.W;
             // W-mer at the seed tail: both searches start from their tabulated interval
@@ -531,7 +531,7 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
             }
         }
         sai_c[item] = oc;                                     // a queued seed's row is the dead one here: k_seed_walk stores only the rows of walks that end
-        sai_r[item] = orr;                                    //   alive, and the stores of a wave cover whole lines
+                                                              //   alive.  No R row is written: one without this call's epoch is dead (sai_r_row)
     }
     // collect: one LDS atomic per wave and list
     {
@@ -576,7 +576,8 @@ k_seed(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb,
 // walks fill the lanes they leave).  No atomics, nothing a wave could wait for.  The ballot and the cursor sit at the top of the turn
 // with all 64 lanes present and no lane leaves the loop on its own (loops in which lane groups leave one by one have
 // hung); every turn consumes records or advances every live walk, and a walk has at most k - W + s + 3 turns.
-//   k_seed has written the dead row for every queued seed, so only a walk that ends alive stores its row.
+//   k_seed has written the dead C row for every queued seed and an R row counts only with this call's epoch in it (sai_r_row, salt_device.h),
+// so only a walk that ends alive stores its row.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_seed_walk(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb, uint4 *__restrict__ sai_c, uint4 *__restrict__ sai_r,
             const uint4 *__restrict__ wq, const uint32_t *__restrict__ wq_cnt, uint32_t wq_seg_cap, uint32_t r_first, unsigned long long *__restrict__ ctr)
@@ -626,7 +627,7 @@ k_seed_walk(IndexView ix, SeedParams sp, const uint32_t *__restrict__ tb, uint4 
         } else if (w.ph != WK_IDLE) {
             done = is_r ? seed_walk_finish<true>(ix, sp, c, w, ld, row, n_occ_r, n_aux) : seed_walk_finish<false>(ix, sp, c, w, ld, row, n_occ_c, n_aux);
         }
-        if (done && row.x <= row.y) (is_r ? sai_r : sai_c)[item] = row;
+        if (done && row.x <= row.y) { if (is_r) { row.w = sai_r_pack(sp.epoch, row.w); sai_r[item] = row; } else sai_c[item] = row; }
         n_sa += (n_aux >> 10) & 2047u; n_text += n_aux >> 21; n_aux = 0;       // a lane does many walks here: the packed fields would run over
     }
     if (ctr) {
@@ -792,6 +793,7 @@ struct CandArgs {                      // everything by value: a by-reference In
     uint32_t ref_len, spr, max_locate, r, L; int strand; bool gap_mode; unsigned long long *phase;
     uint32_t *loci; uint32_t loci_cap; int pe;
     bool finish;                   // false: stop after locate (unsorted, duplicates and out-of-range loci still in)
+    uint32_t epoch;                // the call's epoch: which R rows are live (sai_r_row, salt_device.h)
     const uint4 *r_ctx;                    // non-null (with c_ctx): the R rows' records, used the same way
     const uint4 *c_ctx; uint32_t ctx_k;    // non-null: rows come from the context table and a row whose window has more than 3 mismatches for
                                            // certain (ctx_reject, salt_device.h) is counted against the caps but not stored.  Gap-free pass only.
@@ -837,7 +839,7 @@ __device__ __attribute__((noinline)) CandStats build_candidates(W &w)      // A 
         uint4 v2[2] = { make_uint4(1, 0, 0, 0), make_uint4(1, 0, 0, 0) };
         if (slot < ap.spr) {                                  // both lists' loads are in flight together
             const u32x4_t tc = sai_c[base_item + slot], tr = sai_r[base_item + slot];
-            v2[0] = make_uint4(tc.x, tc.y, tc.z, tc.w); v2[1] = make_uint4(tr.x, tr.y, tr.z, tr.w);
+            v2[0] = make_uint4(tc.x, tc.y, tc.z, tc.w); v2[1] = sai_r_row(make_uint4(tr.x, tr.y, tr.z, tr.w), a.epoch);
         }
 #pragma unroll
         for (int which = 0; which < 2; ++which) {
@@ -1602,7 +1604,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
         // Located rows first, unsorted: only loci that can pass (<= 3 mismatches, inside the reference) matter to the
         // sequential rule, so the sort (alnse.c:726-729), the duplicate filter (alnse.c:758-762) and the rule run on
         // those few; the result is the one the full sorted list gives.
-        const CandStats cs = build_candidates_call<PE, GL>(CandArgs{ ix.c_sa, ix.r_pos, sai_c, sai_r, ix.ref_len, ap.spr, ap.max_locate, r, L, strand, false, phase, pe_loci, loci_cap, ap.pe, false, ix.r_ctx, ix.c_ctx, ix.ctx_k }, w);
+        const CandStats cs = build_candidates_call<PE, GL>(CandArgs{ ix.c_sa, ix.r_pos, sai_c, sai_r, ix.ref_len, ap.spr, ap.max_locate, r, L, strand, false, phase, pe_loci, loci_cap, ap.pe, false, ap.epoch, ix.r_ctx, ix.c_ctx, ix.ctx_k }, w);
         if (glob) { loci = cs.in_lds ? w.loci : pe_loci; cand_e = cs.in_lds ? w.cand_e : pe_cand; }
         pc.t = phase ? __builtin_amdgcn_s_memtime() : 0;
         const uint32_t n_loc = cs.n_cand; c_sa_c += cs.n_sa_c; c_sa_r += cs.n_sa_r; c_loci += cs.n_loci; c_ctx_rej += cs.n_ctx_rej; c_ctx_rows += cs.n_ctx_rows;
@@ -1654,7 +1656,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
                     uint32_t n = n_loc_s[1];
                     if (strand == 0 || ix.c_ctx != nullptr) {
                         WSYNC();
-                        const CandStats cs = build_candidates_call<PE, GL>(CandArgs{ ix.c_sa, ix.r_pos, sai_c, sai_r, ix.ref_len, ap.spr, ap.max_locate, r, L, strand, true, phase, pe_loci, loci_cap, ap.pe, false, nullptr, nullptr, 0 }, w);
+                        const CandStats cs = build_candidates_call<PE, GL>(CandArgs{ ix.c_sa, ix.r_pos, sai_c, sai_r, ix.ref_len, ap.spr, ap.max_locate, r, L, strand, true, phase, pe_loci, loci_cap, ap.pe, false, ap.epoch, nullptr, nullptr, 0 }, w);
                         if (glob) { loci = cs.in_lds ? w.loci : pe_loci; cand_e = cs.in_lds ? w.cand_e : pe_cand; }
                         c_sa_c += cs.n_sa_c; c_sa_r += cs.n_sa_r; c_loci += cs.n_loci;
                         n = cs.n_cand;
@@ -1707,7 +1709,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
         }
         for (int strand = 0; strand < 2; ++strand) {
             pc.stamp(SALT_CTR_T_GAP);
-            const CandStats cs = build_candidates_call<PE, GL>(CandArgs{ ix.c_sa, ix.r_pos, sai_c, sai_r, ix.ref_len, ap.spr, ap.max_locate, r, L, strand, true, phase, pe_loci, loci_cap, ap.pe, true, nullptr, nullptr, 0 }, w);
+            const CandStats cs = build_candidates_call<PE, GL>(CandArgs{ ix.c_sa, ix.r_pos, sai_c, sai_r, ix.ref_len, ap.spr, ap.max_locate, r, L, strand, true, phase, pe_loci, loci_cap, ap.pe, true, ap.epoch, nullptr, nullptr, 0 }, w);
             if (glob) { loci = cs.in_lds ? w.loci : pe_loci; cand_e = cs.in_lds ? w.cand_e : pe_cand; }
             pc.t = phase ? __builtin_amdgcn_s_memtime() : 0;
             const uint32_t n_cand = cs.n_cand; c_sa_c += cs.n_sa_c; c_sa_r += cs.n_sa_r; c_loci += cs.n_loci;
@@ -2183,7 +2185,7 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
             // cap bites; here it cannot (<= 64 rows per list), and the loci are sorted afterwards anyway.
             const uint32_t l = lane >> 4, slot = lane & 15u;
             uint4 v = make_uint4(1, 0, 0, 0);
-            if (slot < ap.spr) v = ((l & 1) ? sai_r : sai_c)[((uint64_t)r * 2u + (l >> 1)) * ap.spr + slot];
+            if (slot < ap.spr) { v = ((l & 1) ? sai_r : sai_c)[((uint64_t)r * 2u + (l >> 1)) * ap.spr + slot]; if (l & 1) v = sai_r_row(v, ap.epoch); }
             uint32_t sz = v.w ? v.y - v.x + 1u : 0u;
             if (sz > 65u) sz = 65u;                                         // keeps the sums below from wrapping
             uint32_t inc = sz;                                              // inclusive prefix sum within the 16-lane row
@@ -2476,7 +2478,7 @@ k_light2(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
             // half-lane = (list, slot); list: 0 C/fwd 1 R/fwd 2 C/rev 3 R/rev (see k_light)
             const uint32_t l = hl >> 3, slot = hl & 7u;
             uint4 v = make_uint4(1, 0, 0, 0);
-            if (slot < ap.spr) v = ((l & 1) ? sai_r : sai_c)[((uint64_t)r * 2u + (l >> 1)) * ap.spr + slot];
+            if (slot < ap.spr) { v = ((l & 1) ? sai_r : sai_c)[((uint64_t)r * 2u + (l >> 1)) * ap.spr + slot]; if (l & 1) v = sai_r_row(v, ap.epoch); }
             uint32_t sz = v.w ? v.y - v.x + 1u : 0u;
             if (sz > 65u) sz = 65u;
             uint32_t inc = sz;                                              // inclusive prefix sum within the 8-lane row

@@ -61,13 +61,26 @@ struct IndexView {
     const COcc *c_occ; const uint32_t *c_sa; const uint32_t *lkt;
     const ROcc *r_occ; const uint32_t *r_pos; const uint4 *wlkt; const uint32_t *ref; const uint32_t *text;
     const uint4 *c_ctx; uint32_t ctx_k;                            // nullptr: absent
-    const uint4 *r_ctx;                                            // the same records for the R rows (.x = r_pos of the row); outside the image, built with the paired-end genome (set_pac); nullptr: absent
+    const uint4 *r_ctx;                                            // the same records for the R rows (.x = r_pos of the row); outside the image, built at attach (or by set_pac once there is room); nullptr: absent
     uint32_t c_primary, c_L2[5], c_seq_len;
     uint32_t r_text_len, r_inv_sa0, r_cum[6];
     uint32_t ref_len, lkt_len, r_lkt_len;
 };
 
 // ---- c_ctx records: salt_ctx_record.h (geometry, pack, build, the read's side, ctx_reject; shared with the host model) ----
+
+// ---- seed rows (sai_c / sai_r): (first row, last row, read offset, flag); flag 0 dead, 1 an interval, 2 .x is a genome position ----
+// C rows are all written by every call (k_seed).  R rows are written only by the walks that end alive (k_seed_walk), with the call's
+// epoch above the flag: .w = (epoch << 8) | flag.  Whatever another call left in a row, or the zeroes of a fresh array, is dead: the
+// workspace's epoch is never 0, grows by one a call, and the array is zeroed again before it restarts at 1.
+static const uint32_t SAI_EPOCH_MAX = (1u << 24) - 1u;
+__device__ __forceinline__ uint32_t sai_r_pack(uint32_t epoch, uint32_t flag) { return (epoch << 8) | flag; }
+// the row as its consumers know it: .w is the flag (0 / 1 / 2), 0 when the row is not of this call
+__device__ __forceinline__ uint4 sai_r_row(uint4 v, uint32_t epoch)
+{
+    v.w = (v.w >> 8) == epoch ? v.w & 0xffu : 0u;
+    return v;
+}
 
 __device__ __forceinline__ uint32_t sel4(uint4 v, uint32_t c)
 {

@@ -34,7 +34,7 @@ struct salt_gpu_index {
     ImageHeader hdr;               // host copy
     IndexView view;
     uint8_t *d_pac = nullptr; uint64_t l_pac = 0;      // 2-bit genome for the PE singleton rescue (not part of the image)
-    uint4 *d_rctx = nullptr;                            // context records of the R rows (paired end; not part of the image)
+    uint4 *d_rctx = nullptr;                            // context records of the R rows (attach_r_ctx; not part of the image)
     int64_t *d_c_off = nullptr; uint32_t *d_c_name_off = nullptr; char *d_c_names = nullptr; int32_t n_contigs = 0;     // contig table for the SAM kernels
 };
 
@@ -43,6 +43,7 @@ struct salt_gpu_ws {
     uint32_t max_reads = 0; uint64_t max_bases = 0;
     uint8_t *d_seqs = nullptr; uint32_t *d_offs = nullptr; salt_result_t *d_results = nullptr;
     uint4 *d_sai_c = nullptr, *d_sai_r = nullptr; uint64_t sai_cap = 0;
+    uint32_t epoch = 1;                                 // the next call's epoch (1 .. SAI_EPOCH_MAX, salt_device.h): d_sai_r is zeroed when allocated and when the epoch restarts
     uint4 *d_wq = nullptr; uint32_t *d_wq_cnt = nullptr; uint32_t walk_blocks = 512; bool no_unique = false;      // k_seed's walk queues (sized with the seed arrays), k_seed_walk's grid; SALT_GPU_NO_UNIQUE
     uint32_t *d_pm = nullptr, *d_tb = nullptr; uint64_t pm_cap = 0, tb_cap = 0;     // k_pack's records (words)
     uint8_t *d_heads = nullptr, *h_heads = nullptr;          // first 128 bytes of every result row: dense device copy + pinned host staging
@@ -109,6 +110,25 @@ static void make_view(salt_gpu_index *ix)
 
 extern "C" const char *salt_gpu_last_error(void) { return g_err.c_str(); }
 extern "C" uint32_t salt_gpu_result_size(void) { return (uint32_t)sizeof(salt_result_t); }
+
+// Context records for the R rows as well (r_ctx: 16 B per row of the R index, 20 GiB at GRCh38 scale; outside the image), when the C rows
+// have theirs and the device keeps the caller's reserve free beside them for what comes after; SALT_GPU_NO_RCTX=1 leaves
+// them out.  Results do not depend on them (ctx_reject is a lower bound).  The image is in place and W is chosen: the table never
+// costs the W-mer table a base.  Does nothing when the table is there; without the room the index simply goes without (device of ix current).
+static const uint64_t R_CTX_RESERVE_ATTACH = 40ull << 30;      // no workspace exists yet: the benchmark's four workspaces, result buffers and paired-end scratch (38.5 GiB)
+static const uint64_t R_CTX_RESERVE_PAC = 32ull << 30;         // set_pac, as ever: the caller's workspaces usually exist by then
+static int attach_r_ctx(salt_gpu_index *ix, const uint64_t R_CTX_RESERVE)
+{
+    if (!ix->view.c_ctx || ix->d_rctx || (getenv("SALT_GPU_NO_RCTX") && atoi(getenv("SALT_GPU_NO_RCTX")))) return SALT_OK;
+    const uint64_t rbytes = ((uint64_t)ix->hdr.r_text_len + 1) * 16;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (uint64_t)free_b >= rbytes + R_CTX_RESERVE && hipMalloc((void **)&ix->d_rctx, rbytes) == hipSuccess) {
+        launch_build_r_ctx(ix->view, ix->hdr.ctx_k, ix->d_rctx, nullptr);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { hipFree(ix->d_rctx); ix->d_rctx = nullptr; return fail(SALT_E_HIP, "building the R context records failed"); }
+        ix->view.r_ctx = ix->d_rctx;
+    } else { (void)hipGetLastError(); ix->d_rctx = nullptr; }
+    return SALT_OK;
+}
 
 extern "C" int salt_gpu_index_attach(const salt_host_index_t *h, int device, salt_gpu_index_t **out)
 {
@@ -222,6 +242,7 @@ extern "C" int salt_gpu_index_attach(const salt_host_index_t *h, int device, sal
     CHK2(hipDeviceSynchronize());
     hipFree(d_sa_s); hipFree(d_r_sa);
 #undef CHK2
+    if (attach_r_ctx(ix, R_CTX_RESERVE_ATTACH)) g_err.clear();      // single end uses the R rows' records too; a build that fails has freed them and the index goes without: no error to report
     *out = ix;
     return SALT_OK;
 }
@@ -264,13 +285,14 @@ extern "C" int salt_gpu_index_image_compact(const salt_gpu_index_t *ix, void **d
     return SALT_OK;
 }
 
-// the W-mer table and the context table of an image whose compact part is in place (device of ix current)
+// the W-mer table and the context tables of an image whose compact part is in place (device of ix current)
 static int rebuild_wlkt(salt_gpu_index *ix)
 {
     launch_build_wlkt(ix->view, ix->hdr.r_lkt_len, reinterpret_cast<uint4 *>(ix->image + ix->hdr.off_wlkt), nullptr);
     if (ix->hdr.off_ctx) launch_build_c_ctx(ix->view, ix->hdr.ctx_k, reinterpret_cast<uint4 *>(ix->image + ix->hdr.off_ctx), nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
+    if (attach_r_ctx(ix, R_CTX_RESERVE_ATTACH)) g_err.clear();      // as salt_gpu_index_attach
     return SALT_OK;
 }
 
@@ -345,6 +367,7 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
         // above the range at 2 (profiles/r08/ab_walk_grid.log)
         ws->walk_blocks = (uint32_t)prop.multiProcessorCount * 2u;
         if (const char *e2 = getenv("SALT_GPU_WALK_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) ws->walk_blocks = (uint32_t)prop.multiProcessorCount * (uint32_t)v; }
+        if (const char *e2 = getenv("SALT_GPU_SAI_EPOCH")) { const long long v = atoll(e2); if (v >= 1 && v <= (long long)SAI_EPOCH_MAX) ws->epoch = (uint32_t)v; }     // tests: the first call's epoch, so that a few calls cross the restart
         if (const char *e2 = getenv("SALT_GPU_NO_UNIQUE")) ws->no_unique = atoi(e2) != 0;                    // A/B and tests: every C search walks
         if (const char *e2 = getenv("SALT_GPU_WALK_BLOCKS")) { int v = atoi(e2); if (v > 0 && v <= 65536) ws->walk_blocks = (uint32_t)v; }      // tests: an absolute grid (rounded up to 64s), so that a wave's slice is long
         CHKW(hipMalloc(&ws->d_lvtab, (uint64_t)ws->heavy_blocks * lv_table_bytes()));
@@ -413,6 +436,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
         hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); ws->d_sai_c = ws->d_sai_r = ws->d_wq = nullptr; ws->sai_cap = 0;
         HIPCHK(hipMalloc((void **)&ws->d_sai_c, items * sizeof(uint4)));
         HIPCHK(hipMalloc((void **)&ws->d_sai_r, items * sizeof(uint4)));
+        HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, items * sizeof(uint4), st));      // no row of any epoch
         HIPCHK(hipMalloc((void **)&ws->d_wq, seed_wq_words(items) * 4));
         ws->sai_cap = items;
     }
@@ -430,8 +454,12 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     sp.max_seed = o->max_seed; sp.seed_only_ref = o->seed_only_ref;
     sp.resolve_unique = !ws->no_unique;
     if (n_reads > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads than the workspace holds");
+    // R rows carry the call's epoch (sai_r_row, salt_device.h): nobody writes the dead ones.  Before the epoch restarts the array is zeroed
+    // on the call's stream, in front of k_seed: a row stored 2^24 - 1 calls ago must not come back to life
+    if (ws->epoch > SAI_EPOCH_MAX) { HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, ws->sai_cap * sizeof(uint4), st)); ws->epoch = 1; }
+    sp.epoch = ws->epoch++;
     AlignParams ap; ap.pg = pg; ap.n_reads = n_reads; ap.spr = spr; ap.l_seed = o->l_seed; ap.max_locate = o->max_locate; ap.max_hits = o->max_hits;
-    ap.all_heavy = ws->all_heavy; ap.pe = pe; ap.dbg_stop = 0; ap.heavy_stop = 0; ap.max_amb = pe ? 5u : 200u;
+    ap.all_heavy = ws->all_heavy; ap.pe = pe; ap.dbg_stop = 0; ap.heavy_stop = 0; ap.max_amb = pe ? 5u : 200u; ap.epoch = sp.epoch;
 #ifdef SALT_DIAG
     { const char *e = getenv("SALT_GPU_LIGHT_STOP"); ap.dbg_stop = e ? atoi(e) : 0; } { static const int hs = getenv("SALT_GPU_HEAVY_STOP") ? atoi(getenv("SALT_GPU_HEAVY_STOP")) : 0; ap.heavy_stop = hs; }
 #endif
@@ -610,6 +638,7 @@ extern "C" int salt_gpu_ws_reserve_text(salt_gpu_ws_t *ws, const salt_aln_opt_t 
         hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); ws->d_sai_c = ws->d_sai_r = ws->d_wq = nullptr; ws->sai_cap = 0;
         HIPCHK(hipMalloc((void **)&ws->d_sai_c, items * sizeof(uint4)));
         HIPCHK(hipMalloc((void **)&ws->d_sai_r, items * sizeof(uint4)));
+        HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, items * sizeof(uint4), st)); HIPCHK(hipStreamSynchronize(st));      // no row of any epoch, whichever stream the calls use
         HIPCHK(hipMalloc((void **)&ws->d_wq, seed_wq_words(items) * 4));
         ws->sai_cap = items;
     }
@@ -1528,17 +1557,20 @@ extern "C" int salt_gpu_index_set_pac(salt_gpu_index_t *ix, const uint8_t *pac, 
     HIPCHK(hipMemset(ix->d_pac, 0, bytes + 16));
     HIPCHK(hipMemcpy(ix->d_pac, pac, bytes, hipMemcpyHostToDevice));
     ix->l_pac = l_pac;
-    // Paired end: context records for the R rows as well (16 B per row of the R index, 20 GiB at GRCh38 scale), when the C rows have theirs
-    // and the device has the room; SALT_GPU_NO_RCTX=1 leaves them out.  Results do not depend on it (ctx_reject is a lower bound).
-    if (ix->view.c_ctx && !ix->d_rctx && !(getenv("SALT_GPU_NO_RCTX") && atoi(getenv("SALT_GPU_NO_RCTX")))) {
-        const uint64_t rbytes = ((uint64_t)ix->hdr.r_text_len + 1) * 16;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (uint64_t)free_b >= rbytes + (32ull << 30) && hipMalloc((void **)&ix->d_rctx, rbytes) == hipSuccess) {
-            launch_build_r_ctx(ix->view, ix->hdr.ctx_k, ix->d_rctx, nullptr);
-            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { hipFree(ix->d_rctx); ix->d_rctx = nullptr; return fail(SALT_E_HIP, "building the R context records failed"); }
-            ix->view.r_ctx = ix->d_rctx;
-        } else ix->d_rctx = nullptr;
-    }
+    return attach_r_ctx(ix, R_CTX_RESERVE_PAC);      // an index attached without the room for its R context records gets them now, if the room is there
+}
+
+extern "C" int salt_gpu_index_r_ctx(const salt_gpu_index_t *ix, void **dev_ptr, uint64_t *bytes)
+{
+    if (!ix || !dev_ptr || !bytes) return fail(SALT_E_INVAL, "null argument");
+    *dev_ptr = ix->d_rctx; *bytes = ix->d_rctx ? ((uint64_t)ix->hdr.r_text_len + 1) * 16 : 0;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_epoch(const salt_gpu_ws_t *ws, uint32_t *next_epoch)
+{
+    if (!ws || !next_epoch) return fail(SALT_E_INVAL, "null argument");
+    *next_epoch = ws->epoch > SAI_EPOCH_MAX ? 1u : ws->epoch;      // past the last one: the next call zeroes the R rows and restarts
     return SALT_OK;
 }
 

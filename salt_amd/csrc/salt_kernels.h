@@ -38,6 +38,7 @@ struct SeedParams {
     uint32_t max_seed;
     int32_t  seed_only_ref;
     int32_t  resolve_unique;        // finish one-row C intervals against the genome text (k_seed)
+    uint32_t epoch;                 // the call's epoch (1 .. 2^24 - 1): k_seed_walk stores it in the live R rows (sai_r_pack, salt_device.h)
     PackGeom pg;
 };
 
@@ -53,6 +54,7 @@ struct AlignParams {
     int32_t  pe;                    // 1: mates of a paired-end batch -- alnse_overlap semantics (alnse.c:985-1044, 501-629):
                                     //    per-interval locate cap, gapped bound stays 3, > 5 N skips the mate
     uint32_t max_amb;               // reads with more N than this are left untouched (200 SE / 5 PE)
+    uint32_t epoch;                 // the call's epoch: an R row of another call is dead (sai_r_row, salt_device.h)
 };
 static const uint32_t PE_LOCI_CAP = 0x40000;    // loci per strand a PE mate may enumerate = MAX_LOC_POS (alnse.c:42,533); global scratch
 
