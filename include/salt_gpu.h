@@ -334,6 +334,29 @@ int  salt_gpu_polish_lv(salt_gpu_polish_t *p, const uint8_t *codes, const uint32
 int  salt_gpu_polish_sw(salt_gpu_polish_t *p, const uint8_t *codes, const uint32_t *offs, uint32_t n_reads, const salt_polish_item_t *items,
                         uint32_t n_items, int want_cigar, int32_t *score, int32_t *read_span, uint16_t *cigars, uint16_t *n_cigar);
 
+/* polish over text: SAM record lines in, polished record lines out -- what the reference's `polish` does between reading a record and
+ * printing it (samParser.c:84-190; polish.c:448-816), for one block on the device: the strtok field rules, the XA items, contig names ->
+ * genome offsets, the offset sort and rm_repeat_hits, the shrinking window, every score (k_polish, or Smith-Waterman under use_sw), the
+ * winners, under `paired` the pairing walk and pair choice, the winners' CIGARs and the records of polish_sam_se / polish_sam_pe.
+ * Needs the contig table (bntann1_t offset + name per sequence).
+ * In:  sam[0 .. n_bytes), n_bytes < 2^31: whole record lines only (the header is the caller's); a last line without its newline is
+ *      allowed; under `paired` an even number of records (a last record without its mate is dropped, polish.c:455-456).
+ * Out: *out points into a page-locked buffer the handle owns, valid until the next call on it: the polished records in input order.
+ *      An empty line ends the input as in the reference (samParser.c:87-90): the records before it are polished, *stopped = 1, nothing
+ *      behind it is looked at.
+ * Errors (SALT_E_INVAL, no records returned; salt_gpu_last_error() has the text): a record with fewer than 11 fields (its index in the
+ * block is named), a contig that is not in the table (named), a read of more than SALT_MAX_READ_LEN bases, a hit beyond the genome
+ * ("Out of reference length"), under use_sw an alignment beyond the build's band, a winner without an alignment within 13 edits.
+ * Of several bad records the one reported is the smallest index the stage that found it refuses: a malformed record or an over-long
+ * read (found while counting) is reported before an unknown contig or a hit beyond the genome in an earlier record (found while filling).
+ * The handle keeps its device and page-locked buffers and grows them when a block needs more. */
+int  salt_gpu_polish_set_contigs(salt_gpu_polish_t *p, int32_t n, const int64_t *offsets, const char *const *names);
+typedef struct { int32_t paired, use_sw; } salt_polish_opt_t;              /* -p, -s */
+int  salt_gpu_polish_text(salt_gpu_polish_t *p, const salt_polish_opt_t *opt, const char *sam, uint64_t n_bytes,
+                          const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped);
+/* of the last call: records, hits parsed, unique hits scored, clipped windows, CIGAR items, proper pairs, output bytes, 0 */
+int  salt_gpu_polish_text_stats(salt_gpu_polish_t *p, uint64_t out[8]);
+
 /* ---- index construction on the device (salt-idx's heavy steps; row N1) ----------------------------------------------
  * Replaces, for texts of any length the 32-bit formats admit (n < 2^32 - 16): bwt_bwtgen / Rbwt_bwt_bwtgen (Index_src/bwt_gen.c,
  * 4bit_bwt_gen.c:1044-1130), bwt_bwtupdate_core (bwtmisc.c:121-143), bwt_cal_sa (bwt.c:48-68), LKT_build_lookuptable

@@ -665,6 +665,71 @@ class GpuAligner:
         self._ix = None
 
 
+class _PolishOpt(ctypes.Structure):
+    _fields_ = [("paired", ctypes.c_int32), ("use_sw", ctypes.c_int32)]
+
+
+POLISH_STATS = ("records", "hits_parsed", "unique_hits", "clipped_windows", "cigar_items", "proper_pairs", "output_bytes", "reserved")
+
+
+class Polisher:
+    """`polish` for a caller that holds SAM text: record lines in, polished record lines out, one device call per block
+    (salt_gpu_polish_text).  Takes the 2-bit genome and the contig table from the Index."""
+
+    def __init__(self, index, device=0):
+        lib = gpu_lib()
+        lib.salt_gpu_polish_open.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
+        lib.salt_gpu_polish_close.argtypes = [ctypes.c_void_p]
+        lib.salt_gpu_polish_set_contigs.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.salt_gpu_polish_text.argtypes = [ctypes.c_void_p, ctypes.POINTER(_PolishOpt), ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]
+        lib.salt_gpu_polish_text_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        self._h = ctypes.c_void_p()
+        self.device = device
+        self.stopped, self.n_records = False, 0
+        pac, l_pac = index.pac()
+        _gpu_check(lib.salt_gpu_polish_open(device, pac, l_pac, ctypes.byref(self._h)))
+        cs = index.contigs()
+        offs = (ctypes.c_int64 * len(cs))(*[c[0] for c in cs])
+        names = (ctypes.c_char_p * len(cs))(*[c[2] for c in cs])
+        try:
+            _gpu_check(lib.salt_gpu_polish_set_contigs(self._h, len(cs), offs, names))
+        except SaltError:
+            self.close()
+            raise
+
+    def polish_text(self, sam, paired=False, sw=False):
+        """One block of whole SAM record lines (no header) -> the polished records, in input order.  `stopped` says whether an empty
+        line ended the block early; `n_records` how many records were polished."""
+        sam = bytes(sam)
+        self.stopped, self.n_records = False, 0                   # of this call, also when it raises
+        opt = _PolishOpt(1 if paired else 0, 1 if sw else 0)
+        out, n, recs, stopped = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_int()
+        _gpu_check(gpu_lib().salt_gpu_polish_text(self._h, ctypes.byref(opt), sam, len(sam), ctypes.byref(out), ctypes.byref(n), ctypes.byref(recs), ctypes.byref(stopped)))
+        self.stopped, self.n_records = bool(stopped.value), recs.value
+        return ctypes.string_at(out.value, n.value) if n.value else b""
+
+    def stats(self):
+        """The eight counts of the last polish_text call, in the order of POLISH_STATS."""
+        out = (ctypes.c_uint64 * 8)()
+        _gpu_check(gpu_lib().salt_gpu_polish_text_stats(self._h, out))
+        return [int(x) for x in out]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            gpu_lib().salt_gpu_polish_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
 _NT4 = np.full(256, 4, dtype=np.uint8)
 for _i, _c in enumerate("ACGT"):
     _NT4[ord(_c)] = _i

@@ -1126,7 +1126,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
 // ---------------------------------------------------------------------------------------------
 // polish (row N4)
 // ---------------------------------------------------------------------------------------------
-struct salt_gpu_polish { int device = 0; uint8_t *d_pac = nullptr; uint64_t l_pac = 0; void *d_tabs = nullptr; uint32_t n_blocks = 0; };
+struct salt_gpu_polish { int device = 0; uint8_t *d_pac = nullptr; uint64_t l_pac = 0; void *d_tabs = nullptr; uint32_t n_blocks = 0; PolishText *text = nullptr; };
 
 extern "C" int salt_gpu_polish_open(int device, const uint8_t *pac, uint64_t l_pac, salt_gpu_polish_t **out)
 {
@@ -1147,7 +1147,36 @@ extern "C" int salt_gpu_polish_open(int device, const uint8_t *pac, uint64_t l_p
     *out = p;
     return SALT_OK;
 }
-extern "C" void salt_gpu_polish_close(salt_gpu_polish_t *p) { if (!p) return; hipSetDevice(p->device); hipFree(p->d_pac); hipFree(p->d_tabs); delete p; }
+extern "C" void salt_gpu_polish_close(salt_gpu_polish_t *p) { if (!p) return; hipSetDevice(p->device); polish_text_free(p->text); hipFree(p->d_pac); hipFree(p->d_tabs); delete p; }
+
+// SAM record lines in, polished record lines out: the whole of `polish` for one block on the device (salt_polish.hip)
+extern "C" int salt_gpu_polish_set_contigs(salt_gpu_polish_t *p, int32_t n, const int64_t *offsets, const char *const *names)
+{
+    if (!p || n < 0 || (n && (!offsets || !names))) return fail(SALT_E_INVAL, "null argument");
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->text) p->text = polish_text_new();
+    std::string err;
+    const int rc = polish_text_set_contigs(p->text, n, offsets, names, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+extern "C" int salt_gpu_polish_text(salt_gpu_polish_t *p, const salt_polish_opt_t *opt, const char *sam, uint64_t n_bytes,
+                                    const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped)
+{
+    if (!p || !opt || (!sam && n_bytes) || !out || !out_bytes || !n_records || !stopped) return fail(SALT_E_INVAL, "null argument");
+    if (n_bytes >> 31) return fail(SALT_E_INVAL, "polish text: a block holds less than 2^31 bytes");
+    if (!p->text) return fail(SALT_E_INVAL, "polish text: no contig table (salt_gpu_polish_set_contigs)");
+    HIPCHK(hipSetDevice(p->device));
+    std::string err;
+    const int rc = polish_text_run(p->text, p->d_pac, p->l_pac, p->d_tabs, p->n_blocks, opt->paired != 0, opt->use_sw != 0, sam, n_bytes, out, out_bytes, n_records, stopped, err);
+    if (rc) { *out_bytes = 0; *n_records = 0; return fail(rc, err); }
+    return SALT_OK;
+}
+extern "C" int salt_gpu_polish_text_stats(salt_gpu_polish_t *p, uint64_t out[8])
+{
+    if (!p || !out) return fail(SALT_E_INVAL, "null argument");
+    for (int i = 0; i < 8; ++i) out[i] = p->text ? polish_text_stats(p->text)[i] : 0;
+    return SALT_OK;
+}
 
 extern "C" int salt_gpu_polish_lv(salt_gpu_polish_t *p, const uint8_t *codes, const uint32_t *offs, uint32_t n_reads, const salt_polish_item_t *items,
                                   uint32_t n_items, const uint8_t *pool, uint32_t pool_stride, uint32_t n_pool, int want_cigar,

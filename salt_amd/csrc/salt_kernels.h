@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <string>
 #include "../../include/salt_gpu.h"
 #include "salt_device.h"
 
@@ -206,6 +207,17 @@ hipError_t launch_sam_write(const SamDev &d, uint32_t n, const uint32_t *off, ch
 hipError_t launch_bam_len(const SamDev &d, uint32_t n, uint32_t *off, unsigned long long *total64, uint32_t *err, void *tmp, size_t tmp_bytes, hipStream_t st);
 hipError_t launch_bam_write(const SamDev &d, uint32_t n, const uint32_t *off, char *out, hipStream_t st);
 static const uint32_t FQ_TILE = 1024;                                          // bytes per newline-count tile (k_fq_count)
+
+// ---- polish over SAM text (salt_polish.hip) ----
+// The text state of a polish handle: its device and page-locked buffers (grown when a block needs more) and the sorted contig table.
+// polish_text_run: record lines in, polished record lines out (salt_gpu_polish_text); err: the message of a non-zero return.
+struct PolishText;
+PolishText *polish_text_new();
+void polish_text_free(PolishText *t);
+const uint64_t *polish_text_stats(const PolishText *t);        // the eight words of salt_gpu_polish_text_stats
+int polish_text_set_contigs(PolishText *t, int32_t n, const int64_t *offsets, const char *const *names, std::string &err);
+int polish_text_run(PolishText *t, const uint8_t *d_pac, uint64_t l_pac, void *d_tabs, uint32_t n_blocks, int paired, int use_sw, const char *sam, uint64_t n_bytes,
+                    const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped, std::string &err);
 
 // ---- BGZF output (salt_bgzf.hip) ----
 // text[0 .. n) (readable up to the next multiple of 4) -> out: ceil(n / BGZF_CUT_BYTES) BGZF blocks, contiguous and in order, bgzf_bound(n) bytes at

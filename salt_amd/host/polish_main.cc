@@ -11,8 +11,15 @@
 // the first mate's name, an empty line ending the input.  `-s` re-scores by Smith-Waterman instead (+2 / -2, N 0, gaps 3 / 1): the same
 // two device calls go to salt_gpu_polish_sw, which runs the mate-rescue kernel k_sw with polish's matrix; soft clips come from the
 // alignment's read span (polish.c:209-222).
+//
+// Two paths give the same bytes.  The device path (run_device; the default, 8 x the host path's rate: profiles/r10/polish_text.log) reads the file in blocks of 32 MiB (SALT_POLISH_CHUNK=<bytes>)
+// into page-locked memory, cut behind whole records (whole pairs under -p), and hands each to salt_gpu_polish_text, where parsing, hit lists,
+// scoring, pairing and printing are kernels (salt_amd/csrc/salt_polish.hip).  The host path (run_batch; SALT_POLISH_HOST=1, and what a library
+// without the text entry point gets) is the rest of this file: the second statement of the same rules.  One line on stderr says which ran.
 #include "../../include/salt_host.h"
+#include <fcntl.h>
 #include <getopt.h>
+#include <unistd.h>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +27,12 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
+
+// Taken weakly: `polish` also links and runs against a libsalt_gpu without the text entry points (an older build); it then takes the host path.
+extern "C" int salt_gpu_polish_set_contigs(salt_gpu_polish_t *p, int32_t n, const int64_t *offsets, const char *const *names) __attribute__((weak));
+extern "C" int salt_gpu_polish_text(salt_gpu_polish_t *p, const salt_polish_opt_t *opt, const char *sam, uint64_t n_bytes,
+                                    const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped) __attribute__((weak));
+extern "C" int salt_gpu_polish_text_stats(salt_gpu_polish_t *p, uint64_t out[8]) __attribute__((weak));
 
 namespace {
 
@@ -279,6 +292,87 @@ bool run_batch(Ctx &C, std::vector<Rec> &recs, bool paired, bool use_sw)
     return true;
 }
 
+bool write_all(const char *p, uint64_t n)
+{
+    while (n) {
+        const ssize_t w = write(1, p, n);
+        if (w < 0) return false;
+        p += w; n -= (uint64_t)w;
+    }
+    return true;
+}
+
+// The device path: the header is skipped here, the file goes through salt_gpu_polish_text in blocks cut behind whole records (whole pairs
+// under -p) and the polished text is written as it comes back.  The host only moves bytes.
+bool run_device(Ctx &C, const char *path, bool paired, bool use_sw)
+{
+    std::vector<int64_t> offs; std::vector<const char *> names;
+    for (int i = 0; i < salt_index_n_seqs(C.ix); ++i) { int64_t off = 0; const char *nm = nullptr; salt_index_seq(C.ix, i, &off, nullptr, &nm); offs.push_back(off); names.push_back(nm); }
+    if (salt_gpu_polish_set_contigs(C.gp, (int32_t)offs.size(), offs.data(), names.data())) { fprintf(stderr, "[polish] %s\n", salt_gpu_last_error()); return false; }
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { fprintf(stderr, "[Error]: Can't open file %s\n", path); return false; }
+    uint64_t chunk = 32ull << 20;
+    if (const char *e = getenv("SALT_POLISH_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk = (uint64_t)v; }
+    if (chunk > (1ull << 30)) chunk = 1ull << 30;               // a block holds less than 2^31 bytes
+    uint64_t cap = chunk + (1u << 16), len = 0;
+    char *buf = nullptr;
+    if (salt_gpu_host_alloc(cap, (void **)&buf)) { fprintf(stderr, "[polish] %s\n", salt_gpu_last_error()); close(fd); return false; }
+    bool eof = false, ok = true, in_header = true, stop = false;
+    uint64_t sum[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n_blocks = 0;
+    const salt_polish_opt_t opt = { paired ? 1 : 0, use_sw ? 1 : 0 };
+    auto more = [&]() -> bool {                                 // room for and bytes of at least one more read
+        if (len == cap) {
+            char *nb = nullptr;
+            if (cap >= (1ull << 31) - (1u << 20) || salt_gpu_host_alloc(cap * 2, (void **)&nb)) { fprintf(stderr, "[polish] a record does not fit a block\n"); return false; }
+            memcpy(nb, buf, len); salt_gpu_host_free(buf); buf = nb; cap *= 2;
+        }
+        const ssize_t got = read(fd, buf + len, cap - len);
+        if (got < 0) { fprintf(stderr, "[Error]: reading %s failed\n", path); return false; }
+        if (got == 0) eof = true; else len += (uint64_t)got;
+        return true;
+    };
+    while (ok && !stop) {
+        while (!eof && len < chunk) if (!more()) { ok = false; break; }
+        if (!ok) break;
+        uint64_t p = 0;
+        bool starved = false;
+        while (in_header) {                                     // sam_skipHeader (samParser.c:43-55)
+            if (p >= len) { if (eof) in_header = false; else starved = true; break; }
+            if (buf[p] != '@') { in_header = false; break; }
+            const char *nl = (const char *)memchr(buf + p, '\n', len - p);
+            if (!nl) { if (eof) { p = len; in_header = false; } else starved = true; break; }
+            p = (uint64_t)(nl - buf) + 1;
+        }
+        if (p) { memmove(buf, buf + p, len - p); len -= p; }
+        if (starved) { if (!more()) ok = false; continue; }
+        if (len == 0) { if (eof) break; continue; }
+        // the block: whole records, whole pairs under -p, at least one; no more than needed to pass `chunk` bytes
+        uint64_t cut = 0, q = 0, n_rec = 0;
+        if (eof) cut = len;
+        else
+            while (q < len) {
+                const char *nl = (const char *)memchr(buf + q, '\n', len - q);
+                if (!nl) break;
+                q = (uint64_t)(nl - buf) + 1; ++n_rec;
+                if (!paired || !(n_rec & 1)) { cut = q; if (cut >= chunk) break; }
+            }
+        if (cut == 0) { if (!more()) ok = false; continue; }      // not one whole record (pair) yet
+        const char *out = nullptr; uint64_t out_bytes = 0, st[8]; uint32_t n = 0; int stopped = 0;
+        if (salt_gpu_polish_text(C.gp, &opt, buf, cut, &out, &out_bytes, &n, &stopped)) { fprintf(stderr, "[polish] %s\n", salt_gpu_last_error()); ok = false; break; }
+        if (!write_all(out, out_bytes)) { fprintf(stderr, "[Error]: writing the output failed\n"); ok = false; break; }
+        if (salt_gpu_polish_text_stats(C.gp, st) == 0) for (int k = 0; k < 8; ++k) sum[k] += st[k];
+        ++n_blocks;
+        if (stopped) stop = true;
+        memmove(buf, buf + cut, len - cut); len -= cut;
+        if (eof && len == 0) break;
+    }
+    fprintf(stderr, "[polish] device path: %llu block(s), %llu records, %llu hits parsed, %llu unique hits scored, %llu clipped windows, %llu CIGAR items, %llu proper pairs, %llu bytes\n",
+            (unsigned long long)n_blocks, (unsigned long long)sum[0], (unsigned long long)sum[1], (unsigned long long)sum[2], (unsigned long long)sum[3], (unsigned long long)sum[4],
+            (unsigned long long)sum[5], (unsigned long long)sum[6]);
+    salt_gpu_host_free(buf); close(fd);
+    return ok;
+}
+
 int usage()
 {
     fprintf(stderr, "\npolish  [OPT]  <index.prefix>  <SAM>\n\nOPT:    -h, --help  print help\n        -p, --pe    paired end mode\n"
@@ -305,6 +399,18 @@ int main(int argc, char **argv)
     C.pac = salt_index_pac(C.ix, &C.l_pac);
     for (int i = 0; i < salt_index_n_seqs(C.ix); ++i) { int64_t off = 0; const char *nm = nullptr; salt_index_seq(C.ix, i, &off, nullptr, &nm); C.contig_off[nm] = off; }
     if (salt_gpu_polish_open(0, C.pac, C.l_pac, &C.gp)) { fprintf(stderr, "[polish] %s\n", salt_gpu_last_error()); return 1; }
+    // SALT_POLISH_HOST=1 keeps the host path below (the second statement of the rules); a library without the text entry point takes it too
+    // and SALT_POLISH_DEVICE=1 asks for the device path, whatever the default is
+    const bool DEVICE_IS_DEFAULT = true;       // by measurement: profiles/r10/polish_text.log
+    const bool want_host = getenv("SALT_POLISH_HOST") && atoi(getenv("SALT_POLISH_HOST"));
+    const bool want_device = getenv("SALT_POLISH_DEVICE") && atoi(getenv("SALT_POLISH_DEVICE"));
+    if (!want_host && (DEVICE_IS_DEFAULT || want_device) && salt_gpu_polish_text != nullptr && salt_gpu_polish_set_contigs != nullptr && salt_gpu_polish_text_stats != nullptr) {
+        const bool ok = run_device(C, argv[optind + 1], paired != 0, use_sw != 0);
+        salt_gpu_polish_close(C.gp);
+        salt_index_free(C.ix);
+        return ok ? 0 : 1;
+    }
+    fprintf(stderr, "[polish] host path\n");
     FILE *fp = fopen(argv[optind + 1], "r");
     if (!fp) { fprintf(stderr, "[Error]: Can't open file %s\n", argv[optind + 1]); return 1; }
     const size_t BATCH = 200000;                                // records per pair of device calls (even: pairs stay together)
