@@ -216,6 +216,20 @@ int  salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on);
  * every 32 640 bytes of the record stream (records straddle blocks, as the format allows), without it the raw records.  A read name longer
  * than 254 bytes cannot be a BAM name: the call fails with SALT_E_INVAL and a message that starts with "BAM:". */
 int  salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on);
+/* Polished output (`salt --polish`): after salt_gpu_ws_set_polish(ws, mode) -- 0 off, 1 Landau-Vishkin re-scoring (polish's default), 2
+ * Smith-Waterman (polish -s) -- salt_gpu_align_se_text, salt_gpu_align_se_text_dev and salt_gpu_align_pe_text return in *sam the records the
+ * reference's `polish` prints for the block's SAM lines, and no SAM line is ever formatted: the hits go from the result rows straight into
+ * the polish kernels (salt_polish.hip, k_pl_rows), on the call's stream, where the SAM kernels ran.  No header.  A skipped read (more than
+ * 200 N) gives no record; a pair with a skipped mate gives none for either mate.  *n_reads / *n_pairs count the input as before.  The
+ * records pass through the device compressor when salt_gpu_ws_set_sam_bgzf is on.  -c / -d / the read group change nothing here.
+ * Needs salt_gpu_index_set_pac (single end too: the index's own device copy of the 2-bit genome is what the windows are read from) and the
+ * contig table; SALT_E_INVAL names what is missing.  Cannot be combined with salt_gpu_ws_set_sam_bam (SALT_E_INVAL, whichever is set second).
+ * A failed record gives the errors of salt_gpu_polish_text: "Out of reference length", the band message under mode 2, "push cigar error".
+ * The polish buffers and Landau-Vishkin tables are the workspace's own, allocated by the first call and freed with it.
+ * Outside the contract: a read with an empty name (in SAM text the leading tab vanishes under strtok and `polish` shifts the fields; here the
+ * record is printed with its empty name); an index with two contigs of one name (`polish` resolves the name to the last of them; here a hit
+ * keeps the contig it lies in). */
+int  salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode);
 /* The same kernels on their own, host buffers in and out: text[0 .. n_bytes) -> ceil(n_bytes / 32640) BGZF blocks in out, *out_bytes of them
  * (0 for an empty text; no end-of-file block).  The same text gives the same bytes on every run.  SALT_E_CAPACITY when out_cap is too
  * small: n_bytes + 31 bytes per block is the exact bound, 65 536 bytes per block always suffice. */

@@ -600,6 +600,14 @@ class GpuAligner:
         gpu_lib().salt_gpu_ws_set_sam_bam.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _gpu_check(gpu_lib().salt_gpu_ws_set_sam_bam(self._ws, 1 if on else 0))
 
+    def set_polish(self, mode):
+        """The text entry points return the records `polish` makes of the block's SAM lines instead of the lines themselves, straight from
+        the result rows: mode 0 off, 1 (or "lv") Landau-Vishkin re-scoring, 2 (or "sw") Smith-Waterman.  Needs set_pac and set_contigs
+        first; excludes set_sam_bam."""
+        mode = {"off": 0, "lv": 1, "sw": 2}.get(mode, mode)
+        gpu_lib().salt_gpu_ws_set_polish.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _gpu_check(gpu_lib().salt_gpu_ws_set_polish(self._ws, int(mode)))
+
     def align_se_text(self, opt, fastq):
         """One block of whole 4-line FASTQ records -> (the block's SAM lines, or what set_sam_bam / set_sam_bgzf make of them; reads)."""
         lib = gpu_lib()

@@ -66,6 +66,9 @@ struct salt_gpu_ws {
     bool sam_bgzf = false;
     // salt_gpu_ws_set_sam_bam: the text entry points write BAM records (k_bam_len / k_bam_write) where they wrote SAM lines
     bool sam_bam = false;
+    // salt_gpu_ws_set_polish: the text entry points return the polished records of the block (salt_polish.hip) where they returned its SAM
+    // lines; the polish buffers and Landau-Vishkin tables are this workspace's (allocated on first use)
+    int polish = 0; PolishText *pl = nullptr; void *d_pl_tabs = nullptr; uint32_t pl_blocks = 0;
     uint32_t *d_bz_slots = nullptr, *d_bz_sizes = nullptr; unsigned long long *d_bz_offs = nullptr; uint8_t *d_bz_out = nullptr; uint64_t bz_blocks_cap = 0;
     char *h_bz = nullptr; uint64_t h_bz_cap = 0;                             // page-locked, only for a compressed block that outgrows h_sam
     // salt_gpu_ws_inflate_bgzf: a chunk's BGZF members, their offsets and status words, and the text they inflate to (allocated on first use, grown on demand)
@@ -391,6 +394,7 @@ extern "C" void salt_gpu_ws_destroy(salt_gpu_ws_t *ws)
     hipFree(ws->d_zin); hipFree(ws->d_zoff); hipFree(ws->d_zstat); hipFree(ws->d_text);
     if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam);
     hipFree(ws->d_bz_slots); hipFree(ws->d_bz_sizes); hipFree(ws->d_bz_offs); hipFree(ws->d_bz_out); if (ws->h_bz) hipHostFree(ws->h_bz);
+    polish_text_free(ws->pl); hipFree(ws->d_pl_tabs);
     hipFree(ws->d_pe_scr); hipFree(ws->d_pairs); hipFree(ws->d_req); hipFree(ws->d_swres); hipFree(ws->d_pctl); hipFree(ws->d_sw_scr); hipFree(ws->d_pcq);
     if (ws->stream) hipStreamDestroy(ws->stream);
     for (auto &e : ws->ev) if (e) hipEventDestroy(e);
@@ -716,11 +720,55 @@ extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on)
 
 static const char *const BAM_NAME_ERROR = "BAM: a read name in this block is longer than 254 bytes, the most a BAM record holds (its length byte counts the NUL)";
 
+static const char *const POLISH_BAM_ERROR = "polished records cannot be written as BAM: salt_gpu_ws_set_polish and salt_gpu_ws_set_sam_bam exclude each other";
+
 extern "C" int salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on)
 {
     if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (on && ws->polish) return fail(SALT_E_INVAL, POLISH_BAM_ERROR);
     ws->sam_bam = on != 0;
     return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (mode < 0 || mode > 2) return fail(SALT_E_INVAL, "polish mode: 0 off, 1 Landau-Vishkin, 2 Smith-Waterman");
+    if (mode) {
+        if (ws->sam_bam) return fail(SALT_E_INVAL, POLISH_BAM_ERROR);
+        if (!ws->ix->d_pac) return fail(SALT_E_INVAL, "polish needs the 2-bit genome: call salt_gpu_index_set_pac first");
+        if (!ws->ix->d_c_off || ws->ix->n_contigs < 1) return fail(SALT_E_INVAL, "polish needs the contig table: call salt_gpu_index_set_contigs first");
+    }
+    ws->polish = mode;
+    return SALT_OK;
+}
+
+// The polish stage of a text call, where the SAM kernels run without it: the block's records from its result rows (polish_rows_len: all but
+// the bytes; *total = how many they are), then -- the caller has made room in ws->d_sam -- polish_rows_write.
+static int ws_polish_len(salt_gpu_ws_t *ws, uint32_t n_rec, uint32_t max_len, int paired, hipStream_t st, uint64_t *total)
+{
+    salt_gpu_index *ix = ws->ix;
+    if (!ix->d_pac || !ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "polish needs the 2-bit genome and the contig table (salt_gpu_index_set_pac, salt_gpu_index_set_contigs)");
+    if (!ws->pl) ws->pl = polish_text_new();
+    if (!ws->d_pl_tabs) {
+        int cus = 0;
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device));
+        ws->pl_blocks = (uint32_t)cus * 8u;
+        HIPCHK(hipMalloc(&ws->d_pl_tabs, (uint64_t)ws->pl_blocks * lv_table_bytes()));
+    }
+    PolishRows in;
+    in.raw = ws->d_raw; in.fq = ws->d_rec; in.codes = ws->d_seqs; in.offs = ws->d_offs; in.res = ws->d_results; in.n_rec = n_rec; in.max_len = max_len;
+    in.c_off = ix->d_c_off; in.c_name_off = ix->d_c_name_off; in.c_names = ix->d_c_names; in.n_contigs = ix->n_contigs;
+    in.pac = ix->d_pac; in.l_pac = ix->l_pac; in.tabs = ws->d_pl_tabs; in.n_blocks = ws->pl_blocks; in.paired = paired; in.use_sw = ws->polish == 2; in.st = st;
+    std::string err;
+    const int rc = polish_rows_len(ws->pl, in, total, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+static int ws_polish_write(salt_gpu_ws_t *ws, hipStream_t st)
+{
+    std::string err;
+    const int rc = polish_rows_write(ws->pl, ws->d_sam, st, err);
+    return rc ? fail(rc, err) : SALT_OK;
 }
 
 extern "C" int salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_bytes, void *out, uint64_t out_cap, uint64_t *out_bytes)
@@ -970,13 +1018,20 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
     d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
     d.pe = 0; d.min_tlen = d.max_tlen = 0; d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(ctl[1]);
     if (to->rg_id && rg.empty()) return fail(SALT_E_INVAL, "empty read group id");
-    if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
-    else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
     uint32_t total = 0, bam_err = 0; unsigned long long total64 = 0;
-    HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
-    if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (ws->polish) {
+        uint64_t pl_total = 0;
+        rc = ws_polish_len(ws, n_rec, ctl[1], 0, st, &pl_total);
+        if (rc) return rc;
+        total = (uint32_t)pl_total;
+    } else {
+        if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
+        else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
+        HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
+        if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
     if (bam_err) return fail(SALT_E_INVAL, BAM_NAME_ERROR);
     if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
     mark();
@@ -988,7 +1043,9 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
         ws->sam_cap = want;
     }
     mark();
-    if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    if (ws->polish && total == 0) { *sam = ws->h_sam; *sam_bytes = 0; *n_reads = n_rec; return SALT_OK; }      // nothing but skipped reads: no record, no block
+    if (ws->polish) { rc = ws_polish_write(ws, st); if (rc) return rc; }
+    else if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
     else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
     const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
     if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
@@ -1091,14 +1148,22 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     d.text = ix->view.text; d.ref = ix->view.ref; d.xa_cigar = to->print_xa_cigar; d.nm_md = to->print_nm_md;
     d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
     d.pe = 1; d.min_tlen = pe->min_tlen; d.max_tlen = pe->max_tlen; d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(ctl[1]);
-    if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
-    else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
     uint32_t total = 0, n_over = 0, bam_err = 0; unsigned long long total64 = 0;
-    HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
-    if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
-    if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (!ws->polish) {
+        if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
+        else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
+        HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
+        if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
+    }
+    if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));      // (polish: read with the first count words of its own)
+    if (!ws->polish) HIPCHK(hipStreamSynchronize(st));
+    else {
+        uint64_t pl_total = 0;
+        rc = ws_polish_len(ws, n_rec, ctl[1], 1, st, &pl_total);
+        if (rc && !n_over) return rc;
+        total = (uint32_t)pl_total;
+    }
     if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W) "
                                              "or a CIGAR of more than SALT_MAX_CIGAR_OPS operations: the rows of this batch would differ from the reference's");
     if (bam_err) return fail(SALT_E_INVAL, BAM_NAME_ERROR);
@@ -1110,7 +1175,9 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
         HIPCHK(hipHostMalloc((void **)&ws->h_sam, want, hipHostMallocDefault));
         ws->sam_cap = want;
     }
-    if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    if (ws->polish && total == 0) { *sam = ws->h_sam; *sam_bytes = 0; *n_pairs = n; return SALT_OK; }
+    if (ws->polish) { rc = ws_polish_write(ws, st); if (rc) return rc; }
+    else if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
     else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
     const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
     if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }

@@ -218,6 +218,17 @@ const uint64_t *polish_text_stats(const PolishText *t);        // the eight word
 int polish_text_set_contigs(PolishText *t, int32_t n, const int64_t *offsets, const char *const *names, std::string &err);
 int polish_text_run(PolishText *t, const uint8_t *d_pac, uint64_t l_pac, void *d_tabs, uint32_t n_blocks, int paired, int use_sw, const char *sam, uint64_t n_bytes,
                     const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped, std::string &err);
+// The fused route (salt_gpu_ws_set_polish): the polished records of the block a text call of the aligner has just aligned, from its result
+// rows and its FASTQ text, all device pointers of the caller's; every kernel goes on `st`.  The contig table is the index's own, in its own
+// order.  polish_rows_len: everything up to the records' lengths, *total = the bytes they take; polish_rows_write: the records into d_out
+// (the caller's, at least *total bytes), enqueued only.  Statuses become the errors of polish_text_run.
+struct PolishRows {
+    const uint8_t *raw; const FqRec *fq; const uint8_t *codes; const uint32_t *offs; const salt_result_t *res; uint32_t n_rec, max_len;
+    const int64_t *c_off; const uint32_t *c_name_off; const char *c_names; int32_t n_contigs;
+    const uint8_t *pac; uint64_t l_pac; void *tabs; uint32_t n_blocks; int paired, use_sw; hipStream_t st;
+};
+int polish_rows_len(PolishText *t, const PolishRows &in, uint64_t *total, std::string &err);
+int polish_rows_write(PolishText *t, char *d_out, hipStream_t st, std::string &err);
 
 // ---- BGZF output (salt_bgzf.hip) ----
 // text[0 .. n) (readable up to the next multiple of 4) -> out: ceil(n / BGZF_CUT_BYTES) BGZF blocks, contiguous and in order, bgzf_bound(n) bytes at

@@ -182,6 +182,56 @@ PL_HD bool pl_hits(const uint8_t *s, const PlFields &f, const PlContigs &ct, boo
     return true;
 }
 
+// ---- hits straight from a result row (salt --polish: no SAM line in between) ---------------------------------------------------
+// bns_coor_pac2real's search (bntseq.c:269-289), the one the SAM writer names a position's contig by (seq_id_dev, salt_text.hip)
+PL_HD int32_t pl_seq_id(const int64_t *c_off, int32_t n, int64_t coor)
+{
+    int32_t left = 0, mid = 0, right = n;
+    while (left < right) {
+        mid = (left + right) >> 1;
+        if (coor >= c_off[mid]) {
+            if (mid == n - 1) break;
+            if (coor < c_off[mid + 1]) break;
+            left = mid + 1;
+        } else right = mid;
+    }
+    return mid;
+}
+static const uint32_t PL_ROW_HITS = 5 + 1;                                  // hits of one strand of a row at most: SALT_MAX_HITS and the primary
+// The record-to-hits rule of the fused route: the hits pl_parse + pl_hits find in the line sam_head / sam_head_pe / sam_tags
+// (salt_text.hip) write for row q, in the same order, without the line.  Row: salt_result_t (pos, strand, n_hits, hits).
+//   primary   iff q.pos != 0xFFFFFFFF (single end: the line has flag 4 and RNAME "*" otherwise; paired end: flag 4, whatever RNAME
+//             shows -- an unmapped mate is printed at its mate's place), on strand q.strand (paired end: 0x10 iff strand == 1)
+//   XA items  hits[s][k], k < n_hits[s], strand 0 first, but those at the primary's position on either strand (sam_tags skips them);
+//             a single-end unmapped read has no tags at all (sam.c:105-125), an unmapped mate of a pair has them
+//   offset    the hit's position in the genome: the line says contig + (pos - c_off[contig] + 1) and pl_hits adds c_off[contig] - 1 back
+//   contig    the index's own number of the contig the hit lies in (c_off / the names of the fused route's PlContigs are the index's table
+//             as it stands: the tail only reads a hit's contig name and never searches the table, so no name-sorted copy is made)
+// h0 / h1: PL_ROW_HITS entries each.
+// pl_row_rev: bit 0x10 of the line's FLAG.  The printer needs it although QUAL is as sequenced on this route: polish_sam_se / _pe put a tab
+// behind QUAL exactly when they print it the way the line had it (polish.c:289,292), and the line had it reversed under 0x10.
+template <class Row> PL_HD bool pl_row_rev(const Row &q, bool paired) { return paired ? q.strand == 1 : (q.pos != 0xFFFFFFFFu && q.strand != 0); }
+template <class Row>
+PL_HD void pl_row_hits(const Row &q, bool paired, const int64_t *c_off, int32_t n_contigs, PlHit *h0, PlHit *h1, uint32_t nh[2])
+{
+    nh[0] = nh[1] = 0;
+    PlHit *h[2] = { h0, h1 };
+    const uint32_t primary = q.pos;
+    const bool mapped = primary != 0xFFFFFFFFu;
+    if (!mapped && !paired) return;
+    for (int s = -1; s < 2; ++s) {
+        const uint32_t n = s < 0 ? (mapped ? 1u : 0u) : (q.n_hits[s] < PL_ROW_HITS - 1 ? q.n_hits[s] : PL_ROW_HITS - 1);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t at = s < 0 ? primary : q.hits[s][k].pos;
+            if (s >= 0 && at == primary) continue;
+            const uint32_t st = s >= 0 ? (uint32_t)s : (pl_row_rev(q, paired) ? 1u : 0u);
+            const int32_t c = pl_seq_id(c_off, n_contigs, (int64_t)at);
+            PlHit x; x.offset = at; x.pos = (uint32_t)((int64_t)at - c_off[c] + 1); x.contig = (uint32_t)c; x.score = 0;
+            h[st][nh[st]++] = x;
+        }
+    }
+}
+
 // sort by offset (equal offsets are equal hits under one table: the order among them does not matter), then rm_repeat_hits
 PL_HD void pl_sift(PlHit *h, uint32_t i, uint32_t n)
 {
@@ -318,6 +368,7 @@ template <class E> PL_HD void pl_put_str(E &o, const char *s) { while (*s) o.put
 // what the printer needs of one record and its winner
 struct PlOut {
     const uint8_t *name; uint32_t name_len; const uint8_t *qual; uint32_t qual_len; const uint8_t *codes; uint32_t l_seq; int32_t flag;
+    int32_t qual_seq;                                                    // QUAL is as sequenced whatever flag says (the fused route); 0: as the SAM line had it
     PlWin w; uint32_t pos; const uint8_t *chrom; uint32_t chrom_len;     // of the winning hit
     int32_t star; const uint16_t *cigar; uint32_t n_cigar; int32_t clip_front, clip_back;       // star: the LV "*" rule at distance 13
 };
@@ -336,8 +387,10 @@ template <class E> PL_HD void pl_put_seq_qual(E &o, const PlOut &r)
     else for (uint32_t j = L; j-- > 0;) { const uint8_t c = d[j]; o.put("ACGTN"[c < 4 ? 3 - c : 4]); }
     o.put('\t');
     const bool rev_in = (r.flag & 0x10) != 0;
-    if ((rev_in && r.w.strand == 0) || (!rev_in && r.w.strand != 0)) for (uint32_t j = r.qual_len; j-- > 0;) o.put((char)r.qual[j]);
-    else { o.span(r.qual, r.qual_len); o.put('\t'); }             // the tab of printf("%s\t", s) (polish.c:289,292)
+    const bool flip = (rev_in && r.w.strand == 0) || (!rev_in && r.w.strand != 0);      // against the line's QUAL
+    if (r.qual_seq ? r.w.strand != 0 : flip) for (uint32_t j = r.qual_len; j-- > 0;) o.put((char)r.qual[j]);
+    else o.span(r.qual, r.qual_len);
+    if (!flip) o.put('\t');                                      // the tab of printf("%s\t", s) (polish.c:289,292)
     o.put('\n');
 }
 template <class E> PL_HD void pl_print_se(E &o, const PlOut &r)           // polish_sam_se

@@ -9,6 +9,12 @@
 // Extra long options (not in the reference): --gpus N (default 1); --bgzf: everything written to stdout is one BGZF stream (blocked gzip,
 // htslib's .sam.gz container), the SAM blocks deflated on the device before they cross to the host; --bam: the stream is a BAM file -- the same
 // container around binary records (SAM spec 4.2), which the device writes in place of the SAM text.
+// --polish[=lv|sw]: stdout carries the records the reference's second program, `polish` (Polish_src/polish.c), prints for this run's SAM
+// lines -- every reported hit re-scored against the plain genome by Landau-Vishkin (lv, polish's default) or Smith-Waterman (sw, polish -s)
+// -- and no SAM text exists in between: on the text path the hits go from the result rows into the polish kernels
+// (salt_gpu_ws_set_polish); the host pipeline formats a batch's lines, drops the empty ones and passes the rest through
+// salt_gpu_polish_text.  No header (`polish` prints none).  A skipped read (more than 200 N) gives no record, a pair with a skipped mate
+// none for either mate.  -c -d -g change nothing in this output.  Not with --bam.
 // Flags the reference parses but ignores stay ignored (-n -e -M -O -E -l -X).  -p <mate1> <mate2>: paired end
 // (alnpe_core, Align_src/alnpe.c:530-661) through salt_gpu_align_pe.
 #include "../../include/salt_host.h"
@@ -47,9 +53,18 @@ extern "C" int salt_gpu_ws_text_peek(salt_gpu_ws_t *ws, uint64_t off, uint64_t n
 extern "C" int salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_text_opt_t *topt, uint64_t off, uint64_t n_bytes, int add_newline,
                                           const char **sam, uint64_t *sam_bytes, uint32_t *n_reads) __attribute__((weak));
 
+// Likewise the polish stage behind the aligner (--polish) and the polish handle the host pipeline passes its lines through.
+extern "C" int salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode) __attribute__((weak));
+extern "C" int salt_gpu_polish_open(int device, const uint8_t *pac, uint64_t l_pac, salt_gpu_polish_t **out) __attribute__((weak));
+extern "C" void salt_gpu_polish_close(salt_gpu_polish_t *p) __attribute__((weak));
+extern "C" int salt_gpu_polish_set_contigs(salt_gpu_polish_t *p, int32_t n, const int64_t *offsets, const char *const *names) __attribute__((weak));
+extern "C" int salt_gpu_polish_text(salt_gpu_polish_t *p, const salt_polish_opt_t *opt, const char *sam, uint64_t n_bytes,
+                                    const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped) __attribute__((weak));
+
 namespace {
 
 const int N_SEQS = 100000;
+int g_polish = 0;                             // --polish: 0 off, 1 Landau-Vishkin, 2 Smith-Waterman
 
 struct Batch {
     long seq_no = 0;
@@ -338,6 +353,31 @@ void pin_to_device_node(int device)
 }
 
 // ---------------------------------------------------------------------------------------------
+// --polish on the host pipeline: the lines of a formatted batch that `polish` is to see -- no empty line (a skipped read's, the paired-end
+// driver's), and neither record of a pair with a skipped mate -- through salt_gpu_polish_text; the batch's text becomes the polished records.
+bool polish_batch(salt_gpu_polish_t *gp, bool pe, Batch &b)
+{
+    std::string lines;
+    size_t total = 0;
+    for (const std::string &p : b.sam) total += p.size();
+    lines.reserve(total);
+    size_t j = 0;                                            // line of the batch: single end record j; paired end record j / 2, then its blank line
+    for (const std::string &p : b.sam)
+        for (size_t at = 0; at < p.size(); ++j) {
+            const char *e = (const char *)memchr(p.data() + at, '\n', p.size() - at);
+            const size_t end = e ? (size_t)(e - p.data()) + 1 : p.size();
+            bool keep = end - at > 1;
+            if (keep && pe) { const size_t r = j / 2; keep = r < b.res.size() && !b.res[r].skipped && !b.res[r ^ 1].skipped; }
+            if (keep) lines.append(p, at, end - at);
+            at = end;
+        }
+    const salt_polish_opt_t po = { pe ? 1 : 0, g_polish == 2 ? 1 : 0 };
+    const char *out = nullptr; uint64_t out_bytes = 0; uint32_t n = 0; int stopped = 0;
+    if (salt_gpu_polish_text(gp, &po, lines.data(), lines.size(), &out, &out_bytes, &n, &stopped)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    b.sam.assign(1, std::string(out, (size_t)out_bytes));
+    return true;
+}
+
 // --bgzf: the header, every SAM block in input order and htslib's empty end-of-file block, as independent gzip members of at most
 // BGZF_CUT text bytes each.  On the text path the device deflates the SAM block behind the kernel that wrote it
 // (salt_gpu_ws_set_sam_bgzf); everything else -- the header, the host pipeline, a libsalt_gpu without that entry point, and the text
@@ -501,6 +541,8 @@ int usage()
             "               --bgzf                   write the SAM stream as BGZF blocks (.sam.gz), deflated on the GPU [False]\n"
             "               --bam                    write BAM: binary records from the GPU inside BGZF blocks (implies --bgzf;\n"
             "                                        read names of up to 254 bytes) [False]\n"
+            "               --polish[=lv|sw]         print the records `polish` (lv) or `polish -s` (sw) makes of the SAM lines, re-scored\n"
+            "                                        on the GPU, no header; not with --bam [False]\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -771,7 +813,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
             const double tw_start = now(); int n_calls = 0; double t_first = 0, t_rest = 0;
             uint32_t ws_reads = max_reads;
             std::string zbuf;                                             // --bgzf with the host compressor: this worker's blocks
-            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) ||
+            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) || (g_polish && salt_gpu_ws_set_polish(ws, g_polish)) ||
                 (head_read_len && salt_gpu_ws_reserve_text(ws, &ao, R.chunk + TEXT_SLACK, (uint32_t)(ws_reads / 1.3), head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
                 fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
             }
@@ -877,6 +919,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
                     grc = salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws);
                     if (!grc && g_bgzf.device) grc = salt_gpu_ws_set_sam_bgzf(ws, 1);
                     if (!grc && g_bam.device) grc = salt_gpu_ws_set_sam_bam(ws, 1);
+                    if (!grc && g_polish) grc = salt_gpu_ws_set_polish(ws, g_polish);
                     if (!grc && on_dev) grc = salt_gpu_ws_inflate_bgzf(ws, buf0, zc.back(), (uint32_t)(zc.size() - 1), zc.data(), zu.data());      // the new workspace's text
                     if (!grc) grc = align();
                 }
@@ -1085,7 +1128,7 @@ static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const
             salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk];
             pin_to_device_node(wk / P.wpg);
             std::string zbuf;
-            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) ||
+            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) || (g_polish && salt_gpu_ws_set_polish(ws, g_polish)) ||
                 (P.head_read_len && salt_gpu_ws_reserve_text(ws, &ao, P.in_cap, P.max_reads, P.head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
                 fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
             }
@@ -1178,7 +1221,7 @@ int main(int argc, char **argv)
         { "threads", 1, 0, 't' }, { "num", 1, 0, 'n' }, { "help", 0, 0, 'h' }, { "pe", 0, 0, 'p' }, { "min_tlen", 1, 0, 'a' },
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
-        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { 0, 0, 0, 0 } };
+        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 }, { 0, 0, 0, 0 } };
     int c;
     while ((c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0) {
         switch (c) {
@@ -1196,11 +1239,17 @@ int main(int argc, char **argv)
         case 1000: n_gpus = atoi(optarg); break;
         case 1001: g_bgzf.on = true; break;
         case 1002: g_bam.on = true; g_bgzf.on = true; break;
+        case 1003:
+            if (!optarg || strcmp(optarg, "lv") == 0) g_polish = 1;
+            else if (strcmp(optarg, "sw") == 0) g_polish = 2;
+            else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
+            break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
         }
     }
+    if (g_polish && g_bam.on) { fprintf(stderr, "[opt_parse]: --polish and --bam cannot be combined: polished records are written as text only (--polish --bgzf compresses them)\n"); return 1; }
     if (optind + 2 + pe > argc) { fprintf(stderr, "[opt_parse]: index prefix and read file can't be omited!\n"); return 1; }
     if (n_threads < 1) n_threads = 1;
     if (n_gpus < 1) n_gpus = 1;
@@ -1242,12 +1291,16 @@ int main(int argc, char **argv)
     std::vector<salt_gpu_index_t *> gix((size_t)n_gpus, nullptr);
     if (salt_gpu_index_attach(salt_index_host_view(ix), 0, &gix[0])) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
     if (salt_gpu_index_replicate(gix[0], devs.data(), n_gpus, gix.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    if (pe) {                                             // the singleton rescue aligns against the 2-bit genome (alnpe.c:327-393)
+    if (g_polish && (!salt_gpu_ws_set_polish || !salt_gpu_polish_open || !salt_gpu_polish_close || !salt_gpu_polish_set_contigs || !salt_gpu_polish_text)) {
+        fprintf(stderr, "[salt] --polish: this libsalt_gpu has no polish stage\n"); return 1;
+    }
+    if (pe || g_polish) {                                 // the singleton rescue aligns against the 2-bit genome (alnpe.c:327-393); --polish re-scores against it
         uint64_t l_pac = 0; const uint8_t *pac = salt_index_pac(ix, &l_pac);
         for (int i = 0; i < n_gpus; ++i)
             if (salt_gpu_index_set_pac(gix[(size_t)i], pac, l_pac)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
     }
     auto print_header = [&]() -> bool {                  // aln_samhead (sam.c:56-84)
+        if (g_polish) return true;                          // `polish` prints no header
         std::vector<char> hb(16 << 20);
         int w = salt_sam_header(ix, &so, hb.data(), hb.size());
         if (w < 0) { fprintf(stderr, "[salt] SAM header too large\n"); return false; }
@@ -1390,6 +1443,18 @@ int main(int argc, char **argv)
         workers.emplace_back([&, g]() {
             pin_to_device_node(g / WPG);                      // before the pool: its threads inherit the node
             Pool pool(fmt_threads);
+            // --polish: this worker's polish handle (its own copy of the 2-bit genome and the sorted contig table)
+            std::unique_ptr<salt_gpu_polish_t, void (*)(salt_gpu_polish_t *)> gp(nullptr, salt_gpu_polish_close ? salt_gpu_polish_close : +[](salt_gpu_polish_t *) {});
+            if (g_polish) {
+                uint64_t l_pac = 0; const uint8_t *pac = salt_index_pac(ix, &l_pac);
+                const int n = salt_index_n_seqs(ix);
+                std::vector<int64_t> off((size_t)n); std::vector<const char *> nm((size_t)n);
+                for (int i = 0; i < n; ++i) salt_index_seq(ix, i, &off[(size_t)i], nullptr, &nm[(size_t)i]);
+                salt_gpu_polish_t *h = nullptr;
+                if (salt_gpu_polish_open(g / WPG, pac, l_pac, &h) || (gp.reset(h), salt_gpu_polish_set_contigs(h, n, off.data(), nm.data()))) {
+                    fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
+                }
+            }
             for (;;) {
                 std::unique_ptr<Batch> b;
                 {
@@ -1427,6 +1492,7 @@ int main(int argc, char **argv)
                 }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &so, &po, *b, pool); else format_batch(ix, &so, *b, pool);
+                if (g_polish && !polish_batch(gp.get(), pe != 0, *b)) { set_failed(); break; }
                 if (g_bgzf.on && !bgzf_batch(b->sam, pool)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
                 t_fmt = t_fmt + (now() - tf0);
                 std::unique_lock<std::mutex> lk(mu);
