@@ -38,48 +38,79 @@ struct salt_gpu_index {
     int64_t *d_c_off = nullptr; uint32_t *d_c_name_off = nullptr; char *d_c_names = nullptr; int32_t n_contigs = 0;     // contig table for the SAM kernels
 };
 
+// A device buffer with its owner: p[0 .. cap) elements, freed with the owner.  alloc() gives it exactly n elements (what it held is freed
+// first, so a failed call leaves it empty); reserve() is the grow-on-demand rule of every buffer a call may find too small: nothing when it is
+// large enough, else the stream is drained (kernels queued on it may still read the old one) and it gets a quarter more than asked for.
+template <class T> struct DevBuf {
+    T *p = nullptr; uint64_t cap = 0;
+    DevBuf() = default; DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { hipFree(p); }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+    void release() { hipFree(p); p = nullptr; cap = 0; }
+    hipError_t alloc(uint64_t n) { release(); const hipError_t e = hipMalloc((void **)&p, n * sizeof(T)); if (e == hipSuccess) cap = n; else p = nullptr; return e; }
+    int reserve(uint64_t need, hipStream_t st)
+    {
+        if (need <= cap) return SALT_OK;
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(alloc(need + need / 4));
+        return SALT_OK;
+    }
+};
+// Its sibling in page-locked host memory; adopt() takes a buffer the caller keeps owning.
+template <class T> struct PinBuf {
+    T *p = nullptr; uint64_t cap = 0; bool owned = true;
+    PinBuf() = default; PinBuf(const PinBuf &) = delete; PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p && owned) hipHostFree(p); p = nullptr; cap = 0; owned = true; }
+    void adopt(T *q, uint64_t n) { release(); p = q; cap = n; owned = false; }
+    hipError_t alloc(uint64_t n) { release(); const hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault); if (e == hipSuccess) cap = n; else p = nullptr; return e; }
+};
+
+// Every allocation below is a DevBuf / PinBuf: a new buffer is one field here and one reserve() or alloc() where it is sized.  Buffers that
+// are filled together are sized together, by the reserve_* helpers further down.
 struct salt_gpu_ws {
     salt_gpu_index *ix = nullptr;
-    uint32_t max_reads = 0; uint64_t max_bases = 0;
-    uint8_t *d_seqs = nullptr; uint32_t *d_offs = nullptr; salt_result_t *d_results = nullptr;
-    uint4 *d_sai_c = nullptr, *d_sai_r = nullptr; uint64_t sai_cap = 0;
+    uint32_t max_reads = 0; uint64_t max_bases = 0;              // max_bases: what d_seqs holds (+ 64 bytes of slack)
+    DevBuf<uint8_t> d_seqs; DevBuf<uint32_t> d_offs; DevBuf<salt_result_t> d_results;
+    DevBuf<uint4> d_sai_c, d_sai_r;                              // reserve_seed: both hold d_sai_c.cap items
     uint32_t epoch = 1;                                 // the next call's epoch (1 .. SAI_EPOCH_MAX, salt_device.h): d_sai_r is zeroed when allocated and when the epoch restarts
-    uint4 *d_wq = nullptr; uint32_t *d_wq_cnt = nullptr; uint32_t walk_blocks = 512; bool no_unique = false;      // k_seed's walk queues (sized with the seed arrays), k_seed_walk's grid; SALT_GPU_NO_UNIQUE
-    uint32_t *d_pm = nullptr, *d_tb = nullptr; uint64_t pm_cap = 0, tb_cap = 0;     // k_pack's records (words)
-    uint8_t *d_heads = nullptr, *h_heads = nullptr;          // first 128 bytes of every result row: dense device copy + pinned host staging
-    unsigned long long *d_ctr = nullptr;
-    uint32_t *d_queue = nullptr; SeCtl *d_qctl = nullptr;   // reads k_light hands to k_heavy; the batch's control words
-    void *d_lvtab = nullptr;                          // one LV traceback table per persistent k_heavy block
-    uint8_t *d_gap = nullptr; uint32_t gcap = 0; GapBufs gap{};             // deferred gapped passes
+    DevBuf<uint32_t> d_wq; uint32_t *d_wq_cnt = nullptr; uint32_t walk_blocks = 512; bool no_unique = false;      // k_seed's walk queues (sized with the seed arrays), k_seed_walk's grid; SALT_GPU_NO_UNIQUE
+    DevBuf<uint32_t> d_pm, d_tb;                                 // k_pack's records (words; reserve_pack)
+    DevBuf<uint8_t> d_heads; PinBuf<uint8_t> h_heads;        // first 128 bytes of every result row: dense device copy + pinned host staging
+    DevBuf<unsigned long long> d_ctr;
+    DevBuf<uint32_t> d_queue; SeCtl *d_qctl = nullptr;      // reads k_light hands to k_heavy; the batch's control words
+    DevBuf<uint8_t> d_lvtab;                          // one LV traceback table per persistent k_heavy block
+    DevBuf<uint8_t> d_gap; uint32_t gcap = 0; GapBufs gap{};                // deferred gapped passes
     // paired end (allocated on first use)
-    uint8_t *d_pe_scr = nullptr;                       // per persistent block: PE_LOCI_CAP loci + distances
-    PePair *d_pairs = nullptr; PeSwReq *d_req = nullptr; PeSwRes *d_swres = nullptr; PeCtl *d_pctl = nullptr;
-    uint8_t *d_sw_scr = nullptr; uint64_t sw_scr_bytes = 0; uint32_t sw_blocks = 0; uint32_t pe_pairs_cap = 0;
-    uint32_t *d_pcq = nullptr;                         // k_cigar items of the gapped, not rescued mates
+    DevBuf<uint8_t> d_pe_scr;                          // per persistent block: PE_LOCI_CAP loci + distances
+    DevBuf<PePair> d_pairs; DevBuf<PeSwReq> d_req; DevBuf<PeSwRes> d_swres; DevBuf<PeCtl> d_pctl;      // pe_prepare: all four hold d_pairs.cap pairs
+    DevBuf<uint8_t> d_sw_scr; uint32_t sw_blocks = 0;
+    DevBuf<uint32_t> d_pcq;                            // k_cigar items of the gapped, not rescued mates
     // FASTQ text in / SAM text out (allocated on first use, grown on demand)
-    uint8_t *d_raw = nullptr; uint64_t raw_cap = 0; uint32_t *d_tile = nullptr; uint64_t tile_cap = 0; uint32_t *d_lines = nullptr; uint64_t lines_cap = 0;
-    FqRec *d_rec = nullptr; uint32_t *d_tctl = nullptr, *d_samoff = nullptr; void *d_scan = nullptr; size_t scan_bytes = 0;
-    char *d_sam = nullptr, *h_sam = nullptr; uint64_t sam_cap = 0; char *d_rg = nullptr; std::string rg;
-    char *d_samslot = nullptr; SamSeg *d_samseg = nullptr;      // [max_reads]: the records' formatted heads and tails between k_sam_len and k_sam_write
-    bool h_sam_owned = true;                                                 // false: the caller's page-locked buffer (salt_gpu_ws_reserve_text)
+    DevBuf<uint8_t> d_raw; DevBuf<uint32_t> d_tile, d_lines;
+    DevBuf<FqRec> d_rec; DevBuf<uint32_t> d_tctl, d_samoff; DevBuf<uint8_t> d_scan;      // d_tctl: parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
+    DevBuf<char> d_sam; PinBuf<char> h_sam; DevBuf<char> d_rg; std::string rg;      // h_sam may be the caller's page-locked buffer (salt_gpu_ws_reserve_text)
+    DevBuf<char> d_samslot; DevBuf<SamSeg> d_samseg;            // [max_reads]: the records' formatted heads and tails between k_sam_len and k_sam_write
     // salt_gpu_ws_set_sam_bgzf: the SAM block leaves as BGZF blocks (allocated on first use, grown on demand)
     bool sam_bgzf = false;
     // salt_gpu_ws_set_sam_bam: the text entry points write BAM records (k_bam_len / k_bam_write) where they wrote SAM lines
     bool sam_bam = false;
     // salt_gpu_ws_set_polish: the text entry points return the polished records of the block (salt_polish.hip) where they returned its SAM
     // lines; the polish buffers and Landau-Vishkin tables are this workspace's (allocated on first use)
-    int polish = 0; PolishText *pl = nullptr; void *d_pl_tabs = nullptr; uint32_t pl_blocks = 0;
-    uint32_t *d_bz_slots = nullptr, *d_bz_sizes = nullptr; unsigned long long *d_bz_offs = nullptr; uint8_t *d_bz_out = nullptr; uint64_t bz_blocks_cap = 0;
-    char *h_bz = nullptr; uint64_t h_bz_cap = 0;                             // page-locked, only for a compressed block that outgrows h_sam
+    int polish = 0; PolishText *pl = nullptr; DevBuf<uint8_t> d_pl_tabs; uint32_t pl_blocks = 0;
+    DevBuf<uint32_t> d_bz_slots, d_bz_sizes; DevBuf<unsigned long long> d_bz_offs; DevBuf<uint8_t> d_bz_out;      // bgzf_bufs_alloc: d_bz_sizes.cap blocks
+    PinBuf<char> h_bz;                                                       // only for a compressed block that outgrows h_sam
     // salt_gpu_ws_inflate_bgzf: a chunk's BGZF members, their offsets and status words, and the text they inflate to (allocated on first use, grown on demand)
-    uint8_t *d_zin = nullptr; uint64_t zin_cap = 0; unsigned long long *d_zoff = nullptr; uint32_t *d_zstat = nullptr; uint64_t zblocks_cap = 0;
-    uint8_t *d_text = nullptr; uint64_t text_cap = 0, text_bytes = 0;
+    DevBuf<uint8_t> d_zin; DevBuf<unsigned long long> d_zoff; DevBuf<uint32_t> d_zstat;      // d_zoff: 2 x (d_zstat.cap + 1) offsets
+    DevBuf<uint8_t> d_text; uint64_t text_bytes = 0;
     std::vector<unsigned long long> h_zoff; std::vector<uint32_t> h_zstat;
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
     uint32_t heavy_blocks = 2048, gap_blocks = 2048;
     QueueRange *d_ranges = nullptr;                                           // k_heavy's queue ranges: k_light's push counters, the heads
     // d_qctl, d_ranges and d_wq_cnt are blocks of ONE allocation, every block 256-byte aligned: one memset per call zeroes them all
-    uint8_t *d_zero = nullptr; size_t zero_bytes = 0;
+    DevBuf<uint8_t> d_zero;
     int all_heavy = 0;
     hipStream_t stream = nullptr;
     bool timing = false;
@@ -328,17 +359,16 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
     ws->ix = ix; ws->max_reads = max_reads; ws->max_bases = max_bases;
 #define CHKW(x) do { hipError_t e2 = (x); if (e2 != hipSuccess) { salt_gpu_ws_destroy(ws); \
     return fail(SALT_E_NOMEM, std::string(#x) + ": " + hipGetErrorString(e2)); } } while (0)
-    CHKW(hipMalloc((void **)&ws->d_seqs, max_bases + 64));
-    CHKW(hipMalloc((void **)&ws->d_offs, ((uint64_t)max_reads + 1) * 4));
-    CHKW(hipMalloc((void **)&ws->d_results, (uint64_t)max_reads * sizeof(salt_result_t)));
+    CHKW(ws->d_seqs.alloc(max_bases + 64));
+    CHKW(ws->d_offs.alloc((uint64_t)max_reads + 1));
+    CHKW(ws->d_results.alloc(max_reads));
     CHKW(hipMemset(ws->d_results, 0, (uint64_t)max_reads * sizeof(salt_result_t)));
-    CHKW(hipMalloc((void **)&ws->d_queue, queue_words(max_reads) * 4));         // the reads k_light queues (flat, and the segments they arrive in) + k_heavy's overflow queue
+    CHKW(ws->d_queue.alloc(queue_words(max_reads)));         // the reads k_light queues (flat, and the segments they arrive in) + k_heavy's overflow queue
     {
         const size_t a = 256, n_ranges = (QUEUE_RANGES * sizeof(QueueRange) + a - 1) / a * a, n_ctl = (sizeof(SeCtl) + a - 1) / a * a;
         const size_t n_cnt = ((size_t)seed_wq_cnt_words() * 4 + a - 1) / a * a;
-        CHKW(hipMalloc((void **)&ws->d_zero, n_ranges + n_ctl + n_cnt));
-        ws->zero_bytes = n_ranges + n_ctl + n_cnt;
-        ws->d_ranges = reinterpret_cast<QueueRange *>(ws->d_zero); ws->d_qctl = reinterpret_cast<SeCtl *>(ws->d_zero + n_ranges);
+        CHKW(ws->d_zero.alloc(n_ranges + n_ctl + n_cnt));
+        ws->d_ranges = reinterpret_cast<QueueRange *>(ws->d_zero.p); ws->d_qctl = reinterpret_cast<SeCtl *>(ws->d_zero + n_ranges);
         ws->d_wq_cnt = reinterpret_cast<uint32_t *>(ws->d_zero + n_ranges + n_ctl);
     }
     ws->gcap = max_reads < (1u << 20) ? max_reads : (1u << 20);         // slots for reads whose gapped pass is deferred (44 B each + their rows in the pool)
@@ -347,7 +377,7 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
     if (ws->gcap) {
         size_t gbytes = 0;
         gap_bufs_layout(nullptr, ws->gcap, nullptr, &gbytes);
-        CHKW(hipMalloc((void **)&ws->d_gap, gbytes));
+        CHKW(ws->d_gap.alloc(gbytes));
     }
     {
         hipDeviceProp_t prop;
@@ -373,11 +403,11 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
         if (const char *e2 = getenv("SALT_GPU_SAI_EPOCH")) { const long long v = atoll(e2); if (v >= 1 && v <= (long long)SAI_EPOCH_MAX) ws->epoch = (uint32_t)v; }     // tests: the first call's epoch, so that a few calls cross the restart
         if (const char *e2 = getenv("SALT_GPU_NO_UNIQUE")) ws->no_unique = atoi(e2) != 0;                    // A/B and tests: every C search walks
         if (const char *e2 = getenv("SALT_GPU_WALK_BLOCKS")) { int v = atoi(e2); if (v > 0 && v <= 65536) ws->walk_blocks = (uint32_t)v; }      // tests: an absolute grid (rounded up to 64s), so that a wave's slice is long
-        CHKW(hipMalloc(&ws->d_lvtab, (uint64_t)ws->heavy_blocks * lv_table_bytes()));
+        CHKW(ws->d_lvtab.alloc((uint64_t)ws->heavy_blocks * lv_table_bytes()));
         const char *e = getenv("SALT_GPU_ALL_HEAVY");
         ws->all_heavy = e && atoi(e) != 0;
     }
-    CHKW(hipMalloc((void **)&ws->d_ctr, SALT_CTR_N * sizeof(unsigned long long)));
+    CHKW(ws->d_ctr.alloc(SALT_CTR_N));
     CHKW(hipMemset(ws->d_ctr, 0, SALT_CTR_N * sizeof(unsigned long long)));
     CHKW(hipStreamCreate(&ws->stream));
 #undef CHKW
@@ -389,16 +419,10 @@ extern "C" void salt_gpu_ws_destroy(salt_gpu_ws_t *ws)
 {
     if (!ws) return;
     hipSetDevice(ws->ix->device);
-    hipFree(ws->d_seqs); hipFree(ws->d_offs); hipFree(ws->d_results); hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); hipFree(ws->d_pm); hipFree(ws->d_tb); hipFree(ws->d_heads); if (ws->h_heads) hipHostFree(ws->h_heads); hipFree(ws->d_ctr); hipFree(ws->d_queue); hipFree(ws->d_zero); hipFree(ws->d_lvtab); hipFree(ws->d_gap);
-    hipFree(ws->d_raw); hipFree(ws->d_tile); hipFree(ws->d_lines); hipFree(ws->d_rec); hipFree(ws->d_tctl); hipFree(ws->d_samoff); hipFree(ws->d_samslot); hipFree(ws->d_samseg); hipFree(ws->d_scan); hipFree(ws->d_sam); hipFree(ws->d_rg);
-    hipFree(ws->d_zin); hipFree(ws->d_zoff); hipFree(ws->d_zstat); hipFree(ws->d_text);
-    if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam);
-    hipFree(ws->d_bz_slots); hipFree(ws->d_bz_sizes); hipFree(ws->d_bz_offs); hipFree(ws->d_bz_out); if (ws->h_bz) hipHostFree(ws->h_bz);
-    polish_text_free(ws->pl); hipFree(ws->d_pl_tabs);
-    hipFree(ws->d_pe_scr); hipFree(ws->d_pairs); hipFree(ws->d_req); hipFree(ws->d_swres); hipFree(ws->d_pctl); hipFree(ws->d_sw_scr); hipFree(ws->d_pcq);
     if (ws->stream) hipStreamDestroy(ws->stream);
     for (auto &e : ws->ev) if (e) hipEventDestroy(e);
-    delete ws;
+    polish_text_free(ws->pl);
+    delete ws;                                                // its buffers free themselves
 }
 
 static int check_opt(const salt_gpu_index *ix, const salt_aln_opt_t *o, uint32_t max_len, uint32_t *spr_out)
@@ -418,6 +442,36 @@ static int check_opt(const salt_gpu_index *ix, const salt_aln_opt_t *o, uint32_t
 static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint32_t n_reads, uint32_t max_read_len,
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe);
 
+// ---- the workspace's buffer families: each is sized here and nowhere else ----
+// The seed-interval arrays and k_seed's walk queues, for `items` seeds.  d_sai_r is zeroed when allocated: no row of any epoch (sai_r_row,
+// salt_device.h).  settle: the zeroing is waited for, for a caller that does not know which stream the calls will use.  d_sai_c comes last:
+// its capacity is the one compared, so a failed allocation is made up for by the next call.
+static int reserve_seed(salt_gpu_ws_t *ws, uint64_t items, hipStream_t st, bool settle)
+{
+    if (items <= ws->d_sai_c.cap) return SALT_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    ws->d_sai_c.release(); ws->d_sai_r.release(); ws->d_wq.release();
+    HIPCHK(ws->d_sai_r.alloc(items));
+    HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, items * sizeof(uint4), st));
+    if (settle) HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ws->d_wq.alloc(seed_wq_words(items)));
+    HIPCHK(ws->d_sai_c.alloc(items));
+    return SALT_OK;
+}
+
+// k_pack's records of n_reads reads of geometry pg; sized for all the reads the workspace takes, so that only a longer read regrows them.
+// d_heads / h_heads are sized by max_reads alone and stay (freeing them here left fetch_results with dangling pointers)
+static int reserve_pack(salt_gpu_ws_t *ws, uint32_t n_reads, const PackGeom &pg, hipStream_t st)
+{
+    if ((uint64_t)n_reads * pg.pm_stride <= ws->d_pm.cap && (uint64_t)n_reads * pg.tb_stride <= ws->d_tb.cap) return SALT_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t nr = n_reads > ws->max_reads ? n_reads : ws->max_reads;
+    ws->d_tb.release();
+    HIPCHK(ws->d_pm.alloc(nr * pg.pm_stride));
+    HIPCHK(ws->d_tb.alloc(nr * pg.tb_stride));
+    return SALT_OK;
+}
+
 extern "C" int salt_gpu_align_se_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint32_t n_reads, uint32_t max_read_len,
                                           const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream)
 {
@@ -434,33 +488,16 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     if (rc) return rc;
     HIPCHK(hipSetDevice(ws->ix->device));
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    uint64_t items = (uint64_t)n_reads * 2u * spr;
-    if (items > ws->sai_cap) {                     // grows rarely; not on the steady-state path
-        HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); ws->d_sai_c = ws->d_sai_r = ws->d_wq = nullptr; ws->sai_cap = 0;
-        HIPCHK(hipMalloc((void **)&ws->d_sai_c, items * sizeof(uint4)));
-        HIPCHK(hipMalloc((void **)&ws->d_sai_r, items * sizeof(uint4)));
-        HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, items * sizeof(uint4), st));      // no row of any epoch
-        HIPCHK(hipMalloc((void **)&ws->d_wq, seed_wq_words(items) * 4));
-        ws->sai_cap = items;
-    }
+    if (int rc2 = reserve_seed(ws, (uint64_t)n_reads * 2u * spr, st, false)) return rc2;      // grow rarely; not on the steady-state path
     const PackGeom pg = PackGeom::make(max_read_len);
-    if ((uint64_t)n_reads * pg.pm_stride > ws->pm_cap || (uint64_t)n_reads * pg.tb_stride > ws->tb_cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        // d_heads / h_heads are sized by max_reads alone and stay (freeing them here left fetch_results with dangling pointers)
-        hipFree(ws->d_pm); hipFree(ws->d_tb); ws->d_pm = ws->d_tb = nullptr; ws->pm_cap = ws->tb_cap = 0;
-        const uint64_t nr = n_reads > ws->max_reads ? n_reads : ws->max_reads;
-        HIPCHK(hipMalloc((void **)&ws->d_pm, nr * pg.pm_stride * 4));
-        HIPCHK(hipMalloc((void **)&ws->d_tb, nr * pg.tb_stride * 4));
-        ws->pm_cap = nr * pg.pm_stride; ws->tb_cap = nr * pg.tb_stride;
-    }
+    if (int rc2 = reserve_pack(ws, n_reads, pg, st)) return rc2;
     SeedParams sp; sp.pg = pg; sp.n_reads = n_reads; sp.spr = spr; sp.l_seed = o->l_seed; sp.l_overlap = o->l_overlap;
     sp.max_seed = o->max_seed; sp.seed_only_ref = o->seed_only_ref;
     sp.resolve_unique = !ws->no_unique;
     if (n_reads > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads than the workspace holds");
     // R rows carry the call's epoch (sai_r_row, salt_device.h): nobody writes the dead ones.  Before the epoch restarts the array is zeroed
     // on the call's stream, in front of k_seed: a row stored 2^24 - 1 calls ago must not come back to life
-    if (ws->epoch > SAI_EPOCH_MAX) { HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, ws->sai_cap * sizeof(uint4), st)); ws->epoch = 1; }
+    if (ws->epoch > SAI_EPOCH_MAX) { HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, ws->d_sai_r.cap * sizeof(uint4), st)); ws->epoch = 1; }
     sp.epoch = ws->epoch++;
     AlignParams ap; ap.pg = pg; ap.n_reads = n_reads; ap.spr = spr; ap.l_seed = o->l_seed; ap.max_locate = o->max_locate; ap.max_hits = o->max_hits;
     ap.all_heavy = ws->all_heavy; ap.pe = pe; ap.dbg_stop = 0; ap.heavy_stop = 0; ap.max_amb = pe ? 5u : 200u; ap.epoch = sp.epoch;
@@ -470,15 +507,15 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     // located rows beyond the LDS list (SALT_MAX_LOCATE) live in a global list per persistent block: paired end always may need it (0x40000
     // loci per strand, alnse.c:42,533), single end when -m is above the LDS list (the reference grows its vector, alnse.c:678, kvec.h)
     const bool glob_loci = pe || o->max_locate > SALT_MAX_LOCATE;
-    if (glob_loci && !ws->d_pe_scr) HIPCHK(hipMalloc((void **)&ws->d_pe_scr, (uint64_t)ws->heavy_blocks * PE_LOCI_CAP * 5));
-    unsigned long long *ctr = o->collect_counters ? ws->d_ctr : nullptr;
+    if (glob_loci && !ws->d_pe_scr) HIPCHK(ws->d_pe_scr.alloc((uint64_t)ws->heavy_blocks * PE_LOCI_CAP * 5));
+    unsigned long long *ctr = o->collect_counters ? ws->d_ctr.p : nullptr;
     const bool timed = ws->timing && ws->n_timed < MAX_TIMED;
     hipEvent_t *ev = timed ? &ws->ev[(size_t)ws->n_timed * EV_PER_CALL] : nullptr;
-    HIPCHK(hipMemsetAsync(ws->d_zero, 0, ws->zero_bytes, st));            // the batch's control words, k_heavy's queue ranges, the walk queues' counters
+    HIPCHK(hipMemsetAsync(ws->d_zero, 0, ws->d_zero.cap, st));            // the batch's control words, k_heavy's queue ranges, the walk queues' counters
     if (timed) HIPCHK(hipEventRecord(ev[0], st));
     launch_pack(pg, n_reads, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_pm, ws->d_tb, st);
     if (timed) HIPCHK(hipEventRecord(ev[1], st));
-    launch_seed(ws->ix->view, sp, ws->d_tb, ws->d_sai_c, ws->d_sai_r, ws->d_wq, ws->d_wq_cnt, ws->walk_blocks, ctr, st);
+    launch_seed(ws->ix->view, sp, ws->d_tb, ws->d_sai_c, ws->d_sai_r, reinterpret_cast<uint4 *>(ws->d_wq.p), ws->d_wq_cnt, ws->walk_blocks, ctr, st);
     if (timed) HIPCHK(hipEventRecord(ev[2], st));
     if (!ap.all_heavy)
         launch_light(ws->ix->view, ap, ws->d_pm, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_sai_c, ws->d_sai_r,
@@ -486,7 +523,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
     if (timed) HIPCHK(hipEventRecord(ev[3], st));
     launch_heavy(ws->ix->view, ap, ws->d_pm, ws->d_sai_c, ws->d_sai_r,
                  static_cast<salt_result_t *>(d_results), ws->d_queue, ctr, ws->heavy_blocks, ws->gap_blocks, ws->d_lvtab,
-                 gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr : nullptr, timed ? ev + 4 : nullptr, st);
+                 gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr.p : nullptr, timed ? ev + 4 : nullptr, st);
     if (timed) { HIPCHK(hipEventRecord(ev[7], st)); ws->ev_pe[ws->n_timed] = 0; ++ws->n_timed; }
     HIPCHK(hipGetLastError());
     return SALT_OK;
@@ -500,8 +537,8 @@ static_assert(offsetof(salt_result_t, cigar) + 8 * sizeof(uint16_t) == HEAD_BYTE
 static int fetch_results(salt_gpu_ws_t *ws, uint32_t n_reads, salt_result_t *results, hipStream_t st)
 {
     if (!ws->d_heads) {
-        HIPCHK(hipMalloc((void **)&ws->d_heads, (uint64_t)ws->max_reads * HEAD_BYTES));
-        HIPCHK(hipHostMalloc((void **)&ws->h_heads, (uint64_t)ws->max_reads * HEAD_BYTES, hipHostMallocDefault));
+        HIPCHK(ws->h_heads.alloc((uint64_t)ws->max_reads * HEAD_BYTES));
+        HIPCHK(ws->d_heads.alloc((uint64_t)ws->max_reads * HEAD_BYTES));
     }
     launch_heads(ws->d_results, n_reads, ws->d_heads, st);
     HIPCHK(hipMemcpyAsync(ws->h_heads, ws->d_heads, (uint64_t)n_reads * HEAD_BYTES, hipMemcpyDeviceToHost, st));
@@ -611,8 +648,53 @@ extern "C" int salt_gpu_device_count(int *n)
     return SALT_OK;
 }
 
-#define REGROW(ptr, cap, need, type) do { if ((need) > (cap)) { HIPCHK(hipStreamSynchronize(st)); hipFree(ptr); (ptr) = nullptr; (cap) = 0; \
-    const uint64_t want_ = (need) + (need) / 4; HIPCHK(hipMalloc((void **)&(ptr), want_ * sizeof(type))); (cap) = want_; } } while (0)
+// The raw block and what follows its capacity: the newline counters of its tiles (two blocks' counters lie 4 words apart, and the paired-end
+// entry rounds both up: TILE_SLACK covers either entry, so a workspace reserved once serves both) and the scan scratch.  d_tctl is the
+// parse control words | the SAM block's byte count in 64 bits | k_bam_len's error word.
+static const uint64_t TILE_SLACK = 16;
+static int reserve_parse(salt_gpu_ws_t *ws, uint64_t raw_bytes, hipStream_t st)
+{
+    if (int rc = ws->d_raw.reserve(raw_bytes + 64, st)) return rc;
+    if (!ws->d_tctl) HIPCHK(ws->d_tctl.alloc(8));
+    if (int rc = ws->d_tile.reserve(ws->d_raw.cap / FQ_TILE + TILE_SLACK, st)) return rc;
+    const size_t need = text_scan_bytes(std::max<uint64_t>(ws->d_tile.cap, (uint64_t)ws->max_reads + 2));
+    if (need > ws->d_scan.cap) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(ws->d_scan.alloc(need)); }
+    return SALT_OK;
+}
+
+// The codes of the block's reads; max_bases is what the resident entry points compare with
+static int reserve_seqs(salt_gpu_ws_t *ws, uint64_t bases, hipStream_t st)
+{
+    if (bases <= ws->max_bases) return SALT_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    ws->max_bases = 0;
+    HIPCHK(ws->d_seqs.alloc(bases + bases / 4 + 64));
+    ws->max_bases = bases + bases / 4;
+    return SALT_OK;
+}
+
+// What the record kernels keep per read between their length pass and their write pass: sized once, by max_reads
+static int reserve_records(salt_gpu_ws_t *ws)
+{
+    if (!ws->d_rec) HIPCHK(ws->d_rec.alloc(ws->max_reads));
+    if (!ws->d_samoff) HIPCHK(ws->d_samoff.alloc((uint64_t)ws->max_reads + 2));
+    if (!ws->d_samslot) HIPCHK(ws->d_samslot.alloc((uint64_t)ws->max_reads * SAM_SLOT));
+    if (!ws->d_samseg) HIPCHK(ws->d_samseg.alloc(ws->max_reads));
+    return SALT_OK;
+}
+
+// The output block on the device and its page-locked twin: `want` bytes of each when they hold fewer than `need`.  The callers have read the
+// block's length back (or have queued nothing yet), so nothing on the stream uses the old ones.  host, when it holds `want` bytes, is the
+// caller's page-locked buffer and serves as the twin.  d_sam comes last: its capacity is the one compared.
+static int reserve_sam(salt_gpu_ws_t *ws, uint64_t need, uint64_t want, void *host, uint64_t host_bytes)
+{
+    if (need <= ws->d_sam.cap) return SALT_OK;
+    ws->d_sam.release();
+    if (host && host_bytes >= want) ws->h_sam.adopt(static_cast<char *>(host), want);
+    else HIPCHK(ws->h_sam.alloc(want));
+    HIPCHK(ws->d_sam.alloc(want));
+    return SALT_OK;
+}
 
 // Sizes every buffer a text call of up to max_block_bytes / est_reads reads of max_read_len bases will ask for, so that the first call
 // on the workspace finds them (a later, larger block still regrows them).  One-time work a driver does next to attaching the index.
@@ -626,83 +708,43 @@ extern "C" int salt_gpu_ws_reserve_text(salt_gpu_ws_t *ws, const salt_aln_opt_t 
     if (rc) return rc;
     HIPCHK(hipSetDevice(ws->ix->device));
     hipStream_t st = ws->stream;
-    REGROW(ws->d_raw, ws->raw_cap, max_block_bytes + 64, uint8_t);
-    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
-    REGROW(ws->d_tile, ws->tile_cap, ws->raw_cap / FQ_TILE + 4, uint32_t);
-    {
-        const size_t need = text_scan_bytes(std::max<uint64_t>(ws->tile_cap, (uint64_t)ws->max_reads + 2));
-        if (need > ws->scan_bytes) { hipFree(ws->d_scan); ws->d_scan = nullptr; ws->scan_bytes = 0; HIPCHK(hipMalloc(&ws->d_scan, need)); ws->scan_bytes = need; }
-    }
-    REGROW(ws->d_lines, ws->lines_cap, 4ull * est_reads + 8, uint32_t);
-    if (!ws->d_rec) HIPCHK(hipMalloc((void **)&ws->d_rec, (uint64_t)ws->max_reads * sizeof(FqRec)));
-    if (!ws->d_samoff) HIPCHK(hipMalloc((void **)&ws->d_samoff, ((uint64_t)ws->max_reads + 2) * 4));
-    if (!ws->d_samslot) { HIPCHK(hipMalloc((void **)&ws->d_samslot, (uint64_t)ws->max_reads * SAM_SLOT)); HIPCHK(hipMalloc((void **)&ws->d_samseg, (uint64_t)ws->max_reads * sizeof(SamSeg))); }
-    const uint64_t items = (uint64_t)est_reads * 2u * spr;
-    if (items > ws->sai_cap) {
-        hipFree(ws->d_sai_c); hipFree(ws->d_sai_r); hipFree(ws->d_wq); ws->d_sai_c = ws->d_sai_r = ws->d_wq = nullptr; ws->sai_cap = 0;
-        HIPCHK(hipMalloc((void **)&ws->d_sai_c, items * sizeof(uint4)));
-        HIPCHK(hipMalloc((void **)&ws->d_sai_r, items * sizeof(uint4)));
-        HIPCHK(hipMemsetAsync(ws->d_sai_r, 0, items * sizeof(uint4), st)); HIPCHK(hipStreamSynchronize(st));      // no row of any epoch, whichever stream the calls use
-        HIPCHK(hipMalloc((void **)&ws->d_wq, seed_wq_words(items) * 4));
-        ws->sai_cap = items;
-    }
-    const PackGeom pg = PackGeom::make(max_read_len);
-    if ((uint64_t)ws->max_reads * pg.pm_stride > ws->pm_cap || (uint64_t)ws->max_reads * pg.tb_stride > ws->tb_cap) {
-        hipFree(ws->d_pm); hipFree(ws->d_tb); ws->d_pm = ws->d_tb = nullptr; ws->pm_cap = ws->tb_cap = 0;
-        HIPCHK(hipMalloc((void **)&ws->d_pm, (uint64_t)ws->max_reads * pg.pm_stride * 4));
-        HIPCHK(hipMalloc((void **)&ws->d_tb, (uint64_t)ws->max_reads * pg.tb_stride * 4));
-        ws->pm_cap = (uint64_t)ws->max_reads * pg.pm_stride; ws->tb_cap = (uint64_t)ws->max_reads * pg.tb_stride;
-    }
+    if ((rc = reserve_parse(ws, max_block_bytes, st))) return rc;
+    if ((rc = ws->d_lines.reserve(4ull * est_reads + 8, st))) return rc;
+    if ((rc = reserve_records(ws))) return rc;
+    if ((rc = reserve_seed(ws, (uint64_t)est_reads * 2u * spr, st, true))) return rc;      // settled: whichever stream the calls use
+    if ((rc = reserve_pack(ws, ws->max_reads, PackGeom::make(max_read_len), st))) return rc;
     if (host_sam && host_sam_bytes > est_sam_bytes + 64) est_sam_bytes = host_sam_bytes - 64;
-    if (est_sam_bytes + 64 > ws->sam_cap) {
-        hipFree(ws->d_sam); ws->d_sam = nullptr; if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam); ws->h_sam = nullptr; ws->sam_cap = 0;
-        HIPCHK(hipMalloc((void **)&ws->d_sam, est_sam_bytes + 64));
-        if (host_sam && host_sam_bytes >= est_sam_bytes + 64) { ws->h_sam = static_cast<char *>(host_sam); ws->h_sam_owned = false; }
-        else { HIPCHK(hipHostMalloc((void **)&ws->h_sam, est_sam_bytes + 64, hipHostMallocDefault)); ws->h_sam_owned = true; }
-        ws->sam_cap = est_sam_bytes + 64;
-    }
-    return SALT_OK;
+    return reserve_sam(ws, est_sam_bytes + 64, est_sam_bytes + 64, host_sam, host_sam_bytes);
 }
 
 // ---- BGZF: the SAM block deflated on the device, behind k_sam_write on the same stream ----
-struct BgzfBufs { uint32_t *slots = nullptr, *sizes = nullptr; unsigned long long *offs = nullptr; uint8_t *out = nullptr; };
-static int bgzf_alloc(uint64_t n_blocks, BgzfBufs &b)
+// The deflate kernels' buffers for n_blocks blocks; sizes comes last: its capacity is the block count a caller compares
+static hipError_t bgzf_bufs_alloc(DevBuf<uint32_t> &slots, DevBuf<uint32_t> &sizes, DevBuf<unsigned long long> &offs, DevBuf<uint8_t> &out, uint64_t n_blocks)
 {
-    HIPCHK(hipMalloc((void **)&b.slots, n_blocks * BGZF_SLOT_BYTES));
-    HIPCHK(hipMalloc((void **)&b.sizes, n_blocks * 4));
-    HIPCHK(hipMalloc((void **)&b.offs, (n_blocks + 1) * 8));
-    HIPCHK(hipMalloc((void **)&b.out, n_blocks * (BGZF_CUT_BYTES + 31)));      // bgzf_bound of n_blocks full blocks
-    return SALT_OK;
+    hipError_t e;
+    slots.release(); sizes.release(); offs.release(); out.release();
+    if ((e = slots.alloc(n_blocks * (BGZF_SLOT_BYTES / 4))) != hipSuccess) return e;
+    if ((e = offs.alloc(n_blocks + 1)) != hipSuccess) return e;
+    if ((e = out.alloc(n_blocks * (BGZF_CUT_BYTES + 31))) != hipSuccess) return e;      // bgzf_bound of n_blocks full blocks
+    return sizes.alloc(n_blocks);
 }
-static void bgzf_free(BgzfBufs &b) { hipFree(b.slots); hipFree(b.sizes); hipFree(b.offs); hipFree(b.out); b = BgzfBufs(); }
 
 // ws->d_sam[0 .. total) -> whole BGZF blocks in page-locked host memory (*sam, *sam_bytes); no end-of-file block
 static int ws_sam_bgzf(salt_gpu_ws_t *ws, uint64_t total, hipStream_t st, const char **sam, uint64_t *sam_bytes)
 {
     const uint64_t n_blocks = bgzf_blocks(total);
-    if (n_blocks > ws->bz_blocks_cap) {
+    if (n_blocks > ws->d_bz_sizes.cap) {
         HIPCHK(hipStreamSynchronize(st));
-        BgzfBufs b; b.slots = ws->d_bz_slots; b.sizes = ws->d_bz_sizes; b.offs = ws->d_bz_offs; b.out = ws->d_bz_out;
-        bgzf_free(b); ws->d_bz_slots = ws->d_bz_sizes = nullptr; ws->d_bz_offs = nullptr; ws->d_bz_out = nullptr; ws->bz_blocks_cap = 0;
-        const uint64_t want = n_blocks + n_blocks / 4 + 1;
-        const int rc = bgzf_alloc(want, b);
-        ws->d_bz_slots = b.slots; ws->d_bz_sizes = b.sizes; ws->d_bz_offs = b.offs; ws->d_bz_out = b.out;
-        if (rc) return rc;
-        ws->bz_blocks_cap = want;
+        HIPCHK(bgzf_bufs_alloc(ws->d_bz_slots, ws->d_bz_sizes, ws->d_bz_offs, ws->d_bz_out, n_blocks + n_blocks / 4 + 1));
     }
-    HIPCHK(launch_bgzf_deflate(reinterpret_cast<const uint8_t *>(ws->d_sam), total, ws->d_bz_slots, ws->d_bz_sizes, ws->d_bz_offs, ws->d_bz_out, st));
+    HIPCHK(launch_bgzf_deflate(reinterpret_cast<const uint8_t *>(ws->d_sam.p), total, ws->d_bz_slots, ws->d_bz_sizes, ws->d_bz_offs, ws->d_bz_out, st));
     unsigned long long bytes = 0;
     HIPCHK(hipMemcpyAsync(&bytes, ws->d_bz_offs + n_blocks, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (bytes > bgzf_bound(total)) return fail(SALT_E_HIP, "BGZF blocks larger than their bound");
     char *dst = ws->h_sam;
-    if (bytes > ws->sam_cap) {                               // incompressible text: up to 31 bytes per block more than the text the SAM buffers were sized for
-        if (bytes > ws->h_bz_cap) {
-            if (ws->h_bz) hipHostFree(ws->h_bz);
-            ws->h_bz = nullptr; ws->h_bz_cap = 0;
-            HIPCHK(hipHostMalloc((void **)&ws->h_bz, bytes + bytes / 4, hipHostMallocDefault));
-            ws->h_bz_cap = bytes + bytes / 4;
-        }
+    if (bytes > ws->h_sam.cap) {                             // incompressible text: up to 31 bytes per block more than the text the SAM buffers were sized for
+        if (bytes > ws->h_bz.cap) HIPCHK(ws->h_bz.alloc(bytes + bytes / 4));
         dst = ws->h_bz;
     }
     HIPCHK(hipMemcpyAsync(dst, ws->d_bz_out, bytes, hipMemcpyDeviceToHost, st));
@@ -717,8 +759,6 @@ extern "C" int salt_gpu_ws_set_sam_bgzf(salt_gpu_ws_t *ws, int on)
     ws->sam_bgzf = on != 0;
     return SALT_OK;
 }
-
-static const char *const BAM_NAME_ERROR = "BAM: a read name in this block is longer than 254 bytes, the most a BAM record holds (its length byte counts the NUL)";
 
 static const char *const POLISH_BAM_ERROR = "polished records cannot be written as BAM: salt_gpu_ws_set_polish and salt_gpu_ws_set_sam_bam exclude each other";
 
@@ -754,7 +794,7 @@ static int ws_polish_len(salt_gpu_ws_t *ws, uint32_t n_rec, uint32_t max_len, in
         int cus = 0;
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device));
         ws->pl_blocks = (uint32_t)cus * 8u;
-        HIPCHK(hipMalloc(&ws->d_pl_tabs, (uint64_t)ws->pl_blocks * lv_table_bytes()));
+        HIPCHK(ws->d_pl_tabs.alloc((uint64_t)ws->pl_blocks * lv_table_bytes()));
     }
     PolishRows in;
     in.raw = ws->d_raw; in.fq = ws->d_rec; in.codes = ws->d_seqs; in.offs = ws->d_offs; in.res = ws->d_results; in.n_rec = n_rec; in.max_len = max_len;
@@ -781,19 +821,18 @@ extern "C" int salt_gpu_bgzf_deflate(int device, const void *text, uint64_t n_by
     if (n_dev <= 0) return fail(SALT_E_HIP, "no HIP device visible: the BGZF kernels cannot run (there is no CPU fallback)");
     HIPCHK(hipSetDevice(device));
     const uint64_t n_blocks = bgzf_blocks(n_bytes);
-    BgzfBufs b; uint8_t *d_text = nullptr;
-    auto done = [&](int rc) { bgzf_free(b); hipFree(d_text); return rc; };
-    if (int rc = bgzf_alloc(n_blocks, b)) return done(rc);
-    DONECHK(hipMalloc((void **)&d_text, n_bytes + 64));
-    DONECHK(hipMemcpy(d_text, text, n_bytes, hipMemcpyHostToDevice));
-    DONECHK(launch_bgzf_deflate(d_text, n_bytes, b.slots, b.sizes, b.offs, b.out, nullptr));
+    DevBuf<uint32_t> slots, sizes; DevBuf<unsigned long long> offs; DevBuf<uint8_t> blocks, d_text;      // freed on every return
+    HIPCHK(bgzf_bufs_alloc(slots, sizes, offs, blocks, n_blocks));
+    HIPCHK(d_text.alloc(n_bytes + 64));
+    HIPCHK(hipMemcpy(d_text, text, n_bytes, hipMemcpyHostToDevice));
+    HIPCHK(launch_bgzf_deflate(d_text, n_bytes, slots, sizes, offs, blocks, nullptr));
     unsigned long long bytes = 0;
-    DONECHK(hipMemcpy(&bytes, b.offs + n_blocks, 8, hipMemcpyDeviceToHost));
-    if (bytes > bgzf_bound(n_bytes)) return done(fail(SALT_E_HIP, "BGZF blocks larger than their bound"));
-    if (bytes > out_cap) return done(fail(SALT_E_CAPACITY, "output buffer smaller than the BGZF blocks (" + std::to_string(bytes) + " bytes; 65536 per block always suffice)"));
-    DONECHK(hipMemcpy(out, b.out, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&bytes, offs + n_blocks, 8, hipMemcpyDeviceToHost));
+    if (bytes > bgzf_bound(n_bytes)) return fail(SALT_E_HIP, "BGZF blocks larger than their bound");
+    if (bytes > out_cap) return fail(SALT_E_CAPACITY, "output buffer smaller than the BGZF blocks (" + std::to_string(bytes) + " bytes; 65536 per block always suffice)");
+    HIPCHK(hipMemcpy(out, blocks, bytes, hipMemcpyDeviceToHost));
     *out_bytes = bytes;
-    return done(SALT_OK);
+    return SALT_OK;
 }
 
 // ---- BGZF input: members inflated on the device ----
@@ -842,21 +881,20 @@ extern "C" int salt_gpu_bgzf_inflate(int device, const void *bgzf_, uint64_t n_b
     HIPCHK(hipGetDeviceCount(&n_dev));
     if (n_dev <= 0) return fail(SALT_E_HIP, "no HIP device visible: the BGZF kernels cannot run (there is no CPU fallback)");
     HIPCHK(hipSetDevice(device));
-    uint8_t *d_in = nullptr, *d_out = nullptr; unsigned long long *d_off = nullptr; uint32_t *d_stat = nullptr;
-    auto done = [&](int rc) { hipFree(d_in); hipFree(d_out); hipFree(d_off); hipFree(d_stat); return rc; };
-    DONECHK(hipMalloc((void **)&d_in, n_bytes + 64));
-    DONECHK(hipMalloc((void **)&d_out, u + 64));
-    DONECHK(hipMalloc((void **)&d_off, 2 * (n_blocks + 1) * 8));
-    DONECHK(hipMalloc((void **)&d_stat, n_blocks * 4));
-    DONECHK(hipMemcpy(d_in, z, n_bytes, hipMemcpyHostToDevice));
-    DONECHK(hipMemcpy(d_off, c_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice));
-    DONECHK(hipMemcpy(d_off + n_blocks + 1, u_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice));
-    DONECHK(launch_bgzf_inflate(d_in, d_off, d_off + n_blocks + 1, (uint32_t)n_blocks, d_out, d_stat, nullptr));
+    DevBuf<uint8_t> d_in, d_out; DevBuf<unsigned long long> d_off; DevBuf<uint32_t> d_stat;      // freed on every return
+    HIPCHK(d_in.alloc(n_bytes + 64));
+    HIPCHK(d_out.alloc(u + 64));
+    HIPCHK(d_off.alloc(2 * (n_blocks + 1)));
+    HIPCHK(d_stat.alloc(n_blocks));
+    HIPCHK(hipMemcpy(d_in, z, n_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_off, c_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_off + n_blocks + 1, u_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(launch_bgzf_inflate(d_in, d_off, d_off + n_blocks + 1, (uint32_t)n_blocks, d_out, d_stat, nullptr));
     std::vector<uint32_t> status(n_blocks);
-    DONECHK(hipMemcpy(status.data(), d_stat, n_blocks * 4, hipMemcpyDeviceToHost));
-    if (int rc = inflate_status(status.data(), n_blocks)) { *out_bytes = 0; return done(rc); }
-    if (u) DONECHK(hipMemcpy(out, d_out, u, hipMemcpyDeviceToHost));
-    return done(SALT_OK);
+    HIPCHK(hipMemcpy(status.data(), d_stat, n_blocks * 4, hipMemcpyDeviceToHost));
+    if (int rc = inflate_status(status.data(), n_blocks)) { *out_bytes = 0; return rc; }
+    if (u) HIPCHK(hipMemcpy(out, d_out, u, hipMemcpyDeviceToHost));
+    return SALT_OK;
 }
 
 extern "C" int salt_gpu_ws_inflate_bgzf(salt_gpu_ws_t *ws, const void *blocks, uint64_t n_cbytes, uint32_t n_blocks, const uint32_t *c_off, const uint32_t *u_off)
@@ -870,15 +908,14 @@ extern "C" int salt_gpu_ws_inflate_bgzf(salt_gpu_ws_t *ws, const void *blocks, u
     HIPCHK(hipSetDevice(ws->ix->device));
     hipStream_t st = ws->stream;
     const uint64_t n_text = u_off[n_blocks];
-    REGROW(ws->d_zin, ws->zin_cap, (uint64_t)c_off[n_blocks] + 64, uint8_t);
-    REGROW(ws->d_text, ws->text_cap, n_text + 64, uint8_t);
-    if (n_blocks > ws->zblocks_cap) {
+    if (int rc = ws->d_zin.reserve((uint64_t)c_off[n_blocks] + 64, st)) return rc;
+    if (int rc = ws->d_text.reserve(n_text + 64, st)) return rc;
+    if (n_blocks > ws->d_zstat.cap) {                        // d_zstat last: its capacity is the one compared
         HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_zoff); hipFree(ws->d_zstat); ws->d_zoff = nullptr; ws->d_zstat = nullptr; ws->zblocks_cap = 0;
         const uint64_t want = (uint64_t)n_blocks + n_blocks / 4 + 1;
-        HIPCHK(hipMalloc((void **)&ws->d_zoff, 2 * (want + 1) * 8));
-        HIPCHK(hipMalloc((void **)&ws->d_zstat, want * 4));
-        ws->zblocks_cap = want;
+        ws->d_zstat.release();
+        HIPCHK(ws->d_zoff.alloc(2 * (want + 1)));
+        HIPCHK(ws->d_zstat.alloc(want));
     }
     ws->h_zoff.resize(2 * ((size_t)n_blocks + 1)); ws->h_zstat.resize(n_blocks);
     for (uint32_t b = 0; b <= n_blocks; ++b) { ws->h_zoff[b] = c_off[b]; ws->h_zoff[(size_t)n_blocks + 1 + b] = u_off[b]; }
@@ -935,6 +972,97 @@ extern "C" int salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_
     return se_text_impl(ws, o, to, nullptr, ws->d_text + off, n_bytes, add_newline, sam, sam_bytes, n_reads);
 }
 
+static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, uint32_t n_pairs, uint32_t max_len,
+                            const void *d_seqs, const void *d_offs, void *d_results, hipStream_t st);
+
+// SALT_TEXT_TRACE: the stage clocks of a workspace's first single-end text call
+struct TextTrace {
+    bool on = false; double tm[8]; int n = 0;
+    void mark() { if (on && n < 8) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); tm[n++] = (double)ts.tv_sec + ts.tv_nsec * 1e-9; } }
+};
+
+// Behind the parse kernels: their control words back (ctl[0] what is wrong, ctl[2] where; ctl[1] = *max_len, the longest read), then the reads'
+// codes.  blocks: "block" or "blocks", as the entry point takes one or two.
+static int text_codes(salt_gpu_ws_t *ws, uint32_t n_rec, const char *blocks, hipStream_t st, uint32_t *max_len)
+{
+    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0;
+    HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bases, ws->d_offs + n_rec, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ctl[0]) {
+        const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
+                         : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
+        return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the " + blocks + ": " + what);
+    }
+    if (int rc = reserve_seqs(ws, bases, st)) return rc;
+    HIPCHK(launch_fq_codes(ws->d_raw, ws->d_rec, ws->d_offs, n_rec, ws->d_seqs, st));
+    *max_len = ctl[1];
+    return SALT_OK;
+}
+
+// The output stage of both text entry points, behind the align kernels queued on st: the block's n_rec records as SAM lines, BAM records or
+// polished records (a length pass, room for the block, a write pass), then the block to page-locked host memory, deflated into BGZF blocks
+// first when the workspace says so.  pe: the paired-end options, null for single end.  A new output mode is a branch of the two passes here.
+static int text_emit(salt_gpu_ws_t *ws, const salt_text_opt_t *to, const salt_pe_opt_t *pe, uint32_t n_rec, uint32_t max_len, hipStream_t st, TextTrace &tr,
+                     const char **sam, uint64_t *sam_bytes)
+{
+    salt_gpu_index *ix = ws->ix;
+    const std::string rg = to->rg_id ? to->rg_id : "";
+    if (to->rg_id && rg.empty()) return fail(SALT_E_INVAL, "empty read group id");
+    if (rg != ws->rg || (!rg.empty() && !ws->d_rg)) {
+        HIPCHK(hipStreamSynchronize(st));
+        ws->d_rg.release();
+        if (!rg.empty()) { HIPCHK(ws->d_rg.alloc(rg.size() + 1)); HIPCHK(hipMemcpy(ws->d_rg, rg.data(), rg.size(), hipMemcpyHostToDevice)); }
+        ws->rg = rg;
+    }
+    SamDev d;
+    d.raw = ws->d_raw; d.rec = ws->d_rec; d.seqs = ws->d_seqs; d.offs = ws->d_offs; d.res = ws->d_results;
+    d.c_off = ix->d_c_off; d.c_name_off = ix->d_c_name_off; d.c_names = ix->d_c_names; d.n_contigs = ix->n_contigs;
+    d.text = ix->view.text; d.ref = ix->view.ref; d.xa_cigar = to->print_xa_cigar; d.nm_md = to->print_nm_md;
+    d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
+    d.pe = pe ? 1 : 0; d.min_tlen = pe ? pe->min_tlen : 0; d.max_tlen = pe ? pe->max_tlen : 0;
+    d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(max_len);
+    // ---- lengths: the block's byte count, and with it every status word of the call, in one batch of copies ----
+    uint32_t total = 0, n_over = 0, bam_err = 0; unsigned long long total64 = 0; int rc = SALT_OK;
+    if (!ws->polish) {
+        unsigned long long *d_total64 = reinterpret_cast<unsigned long long *>(ws->d_tctl + 4);
+        if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, d_total64, ws->d_tctl + 6, ws->d_scan, ws->d_scan.cap, st));
+        else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, d_total64, ws->d_scan, ws->d_scan.cap, st));
+        HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&total64, d_total64, 8, hipMemcpyDeviceToHost, st));
+        if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
+    }
+    if (pe && ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));      // (polish: read with the first count words of its own)
+    if (!ws->polish) HIPCHK(hipStreamSynchronize(st));
+    else {
+        uint64_t pl_total = 0;
+        rc = ws_polish_len(ws, n_rec, max_len, pe ? 1 : 0, st, &pl_total);
+        if (rc && !n_over) return rc;
+        total = (uint32_t)pl_total;
+    }
+    // a mate rescue that did not fit says more about the batch than what followed from it
+    if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W) "
+                                             "or a CIGAR of more than SALT_MAX_CIGAR_OPS operations: the rows of this batch would differ from the reference's");
+    if (bam_err) return fail(SALT_E_INVAL, "BAM: a read name in this block is longer than 254 bytes, the most a BAM record holds (its length byte counts the NUL)");
+    if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
+    tr.mark();
+    if ((rc = reserve_sam(ws, (uint64_t)total + 64, (uint64_t)total + total / 4 + 64, nullptr, 0))) return rc;
+    tr.mark();
+    if (ws->polish && total == 0) { *sam = ws->h_sam; *sam_bytes = 0; return SALT_OK; }      // nothing but skipped reads: no record, no block
+    // ---- write, and out ----
+    if (ws->polish) { if ((rc = ws_polish_write(ws, st))) return rc; }
+    else if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
+    if (ws->sam_bgzf) { if ((rc = ws_sam_bgzf(ws, total, st, sam, sam_bytes))) return rc; }      // (sets them last)
+    else {
+        HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *sam = ws->h_sam; *sam_bytes = total;
+    }
+    tr.mark();
+    return SALT_OK;
+}
+
 static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, const uint8_t *d_src, uint64_t n_bytes, int add_newline,
                         const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
 {
@@ -944,21 +1072,13 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
     hipStream_t st = ws->stream;
-    const bool trace = ws->text_calls++ == 0 && getenv("SALT_TEXT_TRACE");
-    double tm[8]; int n_tm = 0;
-    auto mark = [&]() { if (trace && n_tm < 8) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); tm[n_tm++] = (double)ts.tv_sec + ts.tv_nsec * 1e-9; } };
-    mark();
+    TextTrace tr; tr.on = ws->text_calls++ == 0 && getenv("SALT_TEXT_TRACE");
+    tr.mark();
     // ---- the raw block and its lines ----
-    REGROW(ws->d_raw, ws->raw_cap, n_bytes + 64, uint8_t);
+    int rc = reserve_parse(ws, n_bytes, st);
+    if (rc) return rc;
     const uint64_t n_tiles = (n_bytes + FQ_TILE - 1) / FQ_TILE;
-    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
-    {   // tile counters + scan scratch follow the raw capacity
-        const uint64_t tiles_cap = ws->raw_cap / FQ_TILE + 4;
-        REGROW(ws->d_tile, ws->tile_cap, tiles_cap, uint32_t);
-        const size_t need = text_scan_bytes(std::max<uint64_t>(ws->tile_cap, (uint64_t)ws->max_reads + 2));
-        if (need > ws->scan_bytes) { HIPCHK(hipStreamSynchronize(st)); hipFree(ws->d_scan); ws->d_scan = nullptr; ws->scan_bytes = 0; HIPCHK(hipMalloc(&ws->d_scan, need)); ws->scan_bytes = need; }
-    }
-    mark();
+    tr.mark();
     if (d_src) {
         static const char nl = '\n';
         HIPCHK(hipMemcpyAsync(ws->d_raw, d_src, n_src, hipMemcpyDeviceToDevice, st));
@@ -967,103 +1087,36 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
         HIPCHK(hipMemcpyAsync(ws->d_raw, fastq, n_bytes, hipMemcpyHostToDevice, st));
     // newline count first: the line table is sized by it
     uint32_t n_nl = 0;
-    HIPCHK(launch_fq_count(ws->d_raw, n_bytes, ws->d_tile, ws->d_scan, ws->scan_bytes, st));
+    HIPCHK(launch_fq_count(ws->d_raw, n_bytes, ws->d_tile, ws->d_scan, ws->d_scan.cap, st));
     HIPCHK(hipMemcpyAsync(&n_nl, ws->d_tile + n_tiles, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (n_nl % 4 != 0) return fail(SALT_E_INVAL, "FASTQ block does not hold whole 4-line records (" + std::to_string(n_nl) + " lines)");
     const uint32_t n_rec = n_nl / 4;
     if (n_rec > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads in the block (" + std::to_string(n_rec) + ") than the workspace holds");
     if (n_rec == 0) return SALT_OK;
-    mark();
-    REGROW(ws->d_lines, ws->lines_cap, (uint64_t)n_nl + 8, uint32_t);
+    tr.mark();
+    if ((rc = ws->d_lines.reserve((uint64_t)n_nl + 8, st))) return rc;
     HIPCHK(launch_fq_lines(ws->d_raw, n_bytes, ws->d_tile, ws->d_lines, st));
     // ---- records, offsets, codes ----
-    if (!ws->d_rec) HIPCHK(hipMalloc((void **)&ws->d_rec, (uint64_t)ws->max_reads * sizeof(FqRec)));
-    HIPCHK(launch_fq_parse(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, ws->d_scan, ws->scan_bytes, st));
-    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0;
-    HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&bases, ws->d_offs + n_rec, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ctl[0]) {
-        const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
-                         : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
-        return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the block: " + what);
-    }
-    if ((uint64_t)bases > ws->max_bases) {
-        HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_seqs); ws->d_seqs = nullptr;
-        HIPCHK(hipMalloc((void **)&ws->d_seqs, (uint64_t)bases + bases / 4 + 64));
-        ws->max_bases = (uint64_t)bases + bases / 4;
-    }
-    HIPCHK(launch_fq_codes(ws->d_raw, ws->d_rec, ws->d_offs, n_rec, ws->d_seqs, st));
+    if ((rc = reserve_records(ws))) return rc;
+    HIPCHK(launch_fq_parse(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, ws->d_scan, ws->d_scan.cap, st));
+    uint32_t max_len = 0;
+    if ((rc = text_codes(ws, n_rec, "block", st, &max_len))) return rc;
     // ---- align ----
-    mark();
-    int rc = align_resident_impl(ws, o, n_rec, ctl[1], ws->d_seqs, ws->d_offs, ws->d_results, st, 0);
-    if (rc) return rc;
-    mark();
+    tr.mark();
+    if ((rc = align_resident_impl(ws, o, n_rec, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st, 0))) return rc;
+    tr.mark();
     // ---- SAM text ----
-    const std::string rg = to->rg_id ? to->rg_id : "";
-    if (rg != ws->rg || (!rg.empty() && !ws->d_rg)) {
-        HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_rg); ws->d_rg = nullptr;
-        if (!rg.empty()) { HIPCHK(hipMalloc((void **)&ws->d_rg, rg.size() + 1)); HIPCHK(hipMemcpy(ws->d_rg, rg.data(), rg.size(), hipMemcpyHostToDevice)); }
-        ws->rg = rg;
-    }
-    if (!ws->d_samoff) HIPCHK(hipMalloc((void **)&ws->d_samoff, ((uint64_t)ws->max_reads + 2) * 4));
-    if (!ws->d_samslot) { HIPCHK(hipMalloc((void **)&ws->d_samslot, (uint64_t)ws->max_reads * SAM_SLOT)); HIPCHK(hipMalloc((void **)&ws->d_samseg, (uint64_t)ws->max_reads * sizeof(SamSeg))); }
-    SamDev d;
-    d.raw = ws->d_raw; d.rec = ws->d_rec; d.seqs = ws->d_seqs; d.offs = ws->d_offs; d.res = ws->d_results;
-    d.c_off = ix->d_c_off; d.c_name_off = ix->d_c_name_off; d.c_names = ix->d_c_names; d.n_contigs = ix->n_contigs;
-    d.text = ix->view.text; d.ref = ix->view.ref; d.xa_cigar = to->print_xa_cigar; d.nm_md = to->print_nm_md;
-    d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
-    d.pe = 0; d.min_tlen = d.max_tlen = 0; d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(ctl[1]);
-    if (to->rg_id && rg.empty()) return fail(SALT_E_INVAL, "empty read group id");
-    uint32_t total = 0, bam_err = 0; unsigned long long total64 = 0;
-    if (ws->polish) {
-        uint64_t pl_total = 0;
-        rc = ws_polish_len(ws, n_rec, ctl[1], 0, st, &pl_total);
-        if (rc) return rc;
-        total = (uint32_t)pl_total;
-    } else {
-        if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
-        else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
-        HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
-        if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (bam_err) return fail(SALT_E_INVAL, BAM_NAME_ERROR);
-    if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
-    mark();
-    if ((uint64_t)total + 64 > ws->sam_cap) {
-        hipFree(ws->d_sam); ws->d_sam = nullptr; if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam); ws->h_sam = nullptr; ws->sam_cap = 0; ws->h_sam_owned = true;
-        const uint64_t want = (uint64_t)total + total / 4 + 64;
-        HIPCHK(hipMalloc((void **)&ws->d_sam, want));
-        HIPCHK(hipHostMalloc((void **)&ws->h_sam, want, hipHostMallocDefault));
-        ws->sam_cap = want;
-    }
-    mark();
-    if (ws->polish && total == 0) { *sam = ws->h_sam; *sam_bytes = 0; *n_reads = n_rec; return SALT_OK; }      // nothing but skipped reads: no record, no block
-    if (ws->polish) { rc = ws_polish_write(ws, st); if (rc) return rc; }
-    else if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
-    else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
-    const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
-    if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
-    else {
-        HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    mark();
-    if (trace && n_tm == 8)
+    if ((rc = text_emit(ws, to, nullptr, n_rec, max_len, st, tr, sam, sam_bytes))) return rc;
+    if (tr.on && tr.n == 8) {
+        const double *tm = tr.tm;
         fprintf(stderr, "[salt_gpu] first text call (ms): raw buffers %.1f, copy in + count %.1f, lines/parse/codes %.1f, align launch (+ its buffers) %.1f, "
                         "kernels + SAM lengths %.1f, SAM buffers %.1f, write + copy out %.1f\n", (tm[1] - tm[0]) * 1e3, (tm[2] - tm[1]) * 1e3, (tm[3] - tm[2]) * 1e3,
                 (tm[4] - tm[3]) * 1e3, (tm[5] - tm[4]) * 1e3, (tm[6] - tm[5]) * 1e3, (tm[7] - tm[6]) * 1e3);
-    *sam = host_sam; *sam_bytes = host_bytes; *n_reads = n_rec;
+    }
+    *n_reads = n_rec;
     return SALT_OK;
 }
-
-static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, uint32_t n_pairs, uint32_t max_len,
-                            const void *d_seqs, const void *d_offs, void *d_results, hipStream_t st);
 
 // Paired end: two blocks holding the same number of whole 4-line records (mates in file order); the SAM block holds both records of
 // every pair, each followed by the reference's empty line (alnpe.c:640-648).
@@ -1083,20 +1136,15 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     HIPCHK(hipSetDevice(ix->device));
     hipStream_t st = ws->stream;
     const uint64_t b2 = (n1 + 3) & ~3ull;                      // block 2 behind block 1, on a word boundary
-    REGROW(ws->d_raw, ws->raw_cap, b2 + n2 + 64, uint8_t);
+    int rc = reserve_parse(ws, b2 + n2, st);
+    if (rc) return rc;
     const uint64_t t1 = (n1 + FQ_TILE - 1) / FQ_TILE, t2 = (n2 + FQ_TILE - 1) / FQ_TILE;
-    if (!ws->d_tctl) HIPCHK(hipMalloc((void **)&ws->d_tctl, 32));      // parse ctl[4] | the SAM block's byte count in 64 bits | k_bam_len's error word
-    {
-        REGROW(ws->d_tile, ws->tile_cap, ws->raw_cap / FQ_TILE + 16, uint32_t);
-        const size_t need = text_scan_bytes(std::max<uint64_t>(ws->tile_cap, (uint64_t)ws->max_reads + 2));
-        if (need > ws->scan_bytes) { HIPCHK(hipStreamSynchronize(st)); hipFree(ws->d_scan); ws->d_scan = nullptr; ws->scan_bytes = 0; HIPCHK(hipMalloc(&ws->d_scan, need)); ws->scan_bytes = need; }
-    }
     uint32_t *tile1 = ws->d_tile, *tile2 = ws->d_tile + t1 + 4;
     HIPCHK(hipMemcpyAsync(ws->d_raw, fastq1, n1, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ws->d_raw + b2, fastq2, n2, hipMemcpyHostToDevice, st));
     uint32_t nl[2] = { 0, 0 };
-    HIPCHK(launch_fq_count(ws->d_raw, n1, tile1, ws->d_scan, ws->scan_bytes, st));
-    HIPCHK(launch_fq_count(ws->d_raw + b2, n2, tile2, ws->d_scan, ws->scan_bytes, st));
+    HIPCHK(launch_fq_count(ws->d_raw, n1, tile1, ws->d_scan, ws->d_scan.cap, st));
+    HIPCHK(launch_fq_count(ws->d_raw + b2, n2, tile2, ws->d_scan, ws->d_scan.cap, st));
     HIPCHK(hipMemcpyAsync(&nl[0], tile1 + t1, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&nl[1], tile2 + t2, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -1105,90 +1153,24 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     const uint32_t n = nl[0] / 4, n_rec = 2 * n;
     if (n_rec > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads in the blocks (" + std::to_string(n_rec) + ") than the workspace holds");
     if (n == 0) return SALT_OK;
-    REGROW(ws->d_lines, ws->lines_cap, (uint64_t)nl[0] + nl[1] + 24, uint32_t);
+    if ((rc = ws->d_lines.reserve((uint64_t)nl[0] + nl[1] + 24, st))) return rc;
     uint32_t *lines1 = ws->d_lines, *lines2 = ws->d_lines + nl[0] + 8;
     HIPCHK(launch_fq_lines(ws->d_raw, n1, tile1, lines1, st));
     HIPCHK(launch_fq_lines(ws->d_raw + b2, n2, tile2, lines2, st));
-    if (!ws->d_rec) HIPCHK(hipMalloc((void **)&ws->d_rec, (uint64_t)ws->max_reads * sizeof(FqRec)));
+    if ((rc = reserve_records(ws))) return rc;
     HIPCHK(launch_fq_ctl_init(ws->d_tctl, st));
     HIPCHK(hipMemsetAsync(ws->d_offs + n_rec, 0, 4, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, 0u, lines1, n, 0u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, (uint32_t)b2, lines2, n, 1u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
-    HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->scan_bytes, st));
-    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0;
-    HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&bases, ws->d_offs + n_rec, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ctl[0]) {
-        const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
-                         : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
-        return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the blocks: " + what);
-    }
-    if ((uint64_t)bases > ws->max_bases) {
-        hipFree(ws->d_seqs); ws->d_seqs = nullptr;
-        HIPCHK(hipMalloc((void **)&ws->d_seqs, (uint64_t)bases + bases / 4 + 64));
-        ws->max_bases = (uint64_t)bases + bases / 4;
-    }
-    HIPCHK(launch_fq_codes(ws->d_raw, ws->d_rec, ws->d_offs, n_rec, ws->d_seqs, st));
-    int rc = pe_resident_impl(ws, o, pe, n, ctl[1], ws->d_seqs, ws->d_offs, ws->d_results, st);
-    if (rc) return rc;
-    const std::string rg = to->rg_id ? to->rg_id : "";
-    if (to->rg_id && rg.empty()) return fail(SALT_E_INVAL, "empty read group id");
-    if (rg != ws->rg || (!rg.empty() && !ws->d_rg)) {
-        HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_rg); ws->d_rg = nullptr;
-        if (!rg.empty()) { HIPCHK(hipMalloc((void **)&ws->d_rg, rg.size() + 1)); HIPCHK(hipMemcpy(ws->d_rg, rg.data(), rg.size(), hipMemcpyHostToDevice)); }
-        ws->rg = rg;
-    }
-    if (!ws->d_samoff) HIPCHK(hipMalloc((void **)&ws->d_samoff, ((uint64_t)ws->max_reads + 2) * 4));
-    if (!ws->d_samslot) { HIPCHK(hipMalloc((void **)&ws->d_samslot, (uint64_t)ws->max_reads * SAM_SLOT)); HIPCHK(hipMalloc((void **)&ws->d_samseg, (uint64_t)ws->max_reads * sizeof(SamSeg))); }
-    SamDev d;
-    d.raw = ws->d_raw; d.rec = ws->d_rec; d.seqs = ws->d_seqs; d.offs = ws->d_offs; d.res = ws->d_results;
-    d.c_off = ix->d_c_off; d.c_name_off = ix->d_c_name_off; d.c_names = ix->d_c_names; d.n_contigs = ix->n_contigs;
-    d.text = ix->view.text; d.ref = ix->view.ref; d.xa_cigar = to->print_xa_cigar; d.nm_md = to->print_nm_md;
-    d.rg = ws->d_rg; d.rg_len = to->rg_id ? (int32_t)rg.size() : 0;
-    d.pe = 1; d.min_tlen = pe->min_tlen; d.max_tlen = pe->max_tlen; d.slot = ws->d_samslot; d.seg = ws->d_samseg; d.tb = ws->d_tb; d.pg = PackGeom::make(ctl[1]);
-    uint32_t total = 0, n_over = 0, bam_err = 0; unsigned long long total64 = 0;
-    if (!ws->polish) {
-        if (ws->sam_bam) HIPCHK(launch_bam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_tctl + 6, ws->d_scan, ws->scan_bytes, st));
-        else HIPCHK(launch_sam_len(d, n_rec, ws->d_samoff, reinterpret_cast<unsigned long long *>(ws->d_tctl + 4), ws->d_scan, ws->scan_bytes, st));
-        HIPCHK(hipMemcpyAsync(&total, ws->d_samoff + n_rec, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&total64, ws->d_tctl + 4, 8, hipMemcpyDeviceToHost, st));
-        if (ws->sam_bam) HIPCHK(hipMemcpyAsync(&bam_err, ws->d_tctl + 6, 4, hipMemcpyDeviceToHost, st));
-    }
-    if (ws->d_pctl) HIPCHK(hipMemcpyAsync(&n_over, &ws->d_pctl->overflow, 4, hipMemcpyDeviceToHost, st));      // (polish: read with the first count words of its own)
-    if (!ws->polish) HIPCHK(hipStreamSynchronize(st));
-    else {
-        uint64_t pl_total = 0;
-        rc = ws_polish_len(ws, n_rec, ctl[1], 1, st, &pl_total);
-        if (rc && !n_over) return rc;
-        total = (uint32_t)pl_total;
-    }
-    if (n_over) return fail(SALT_E_CAPACITY, std::to_string(n_over) + " mate rescue(s) need a Smith-Waterman band wider than this build holds (SW_BAND_W) "
-                                             "or a CIGAR of more than SALT_MAX_CIGAR_OPS operations: the rows of this batch would differ from the reference's");
-    if (bam_err) return fail(SALT_E_INVAL, BAM_NAME_ERROR);
-    if (total64 >> 32) return fail(SALT_E_CAPACITY, "the SAM text of this block passes 4 GiB (its offsets are 32-bit): hand over smaller blocks (SALT_CHUNK_MB)");
-    if ((uint64_t)total + 64 > ws->sam_cap) {
-        hipFree(ws->d_sam); ws->d_sam = nullptr; if (ws->h_sam && ws->h_sam_owned) hipHostFree(ws->h_sam); ws->h_sam = nullptr; ws->sam_cap = 0; ws->h_sam_owned = true;
-        const uint64_t want = (uint64_t)total + total / 4 + 64;
-        HIPCHK(hipMalloc((void **)&ws->d_sam, want));
-        HIPCHK(hipHostMalloc((void **)&ws->h_sam, want, hipHostMallocDefault));
-        ws->sam_cap = want;
-    }
-    if (ws->polish && total == 0) { *sam = ws->h_sam; *sam_bytes = 0; *n_pairs = n; return SALT_OK; }
-    if (ws->polish) { rc = ws_polish_write(ws, st); if (rc) return rc; }
-    else if (ws->sam_bam) HIPCHK(launch_bam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
-    else HIPCHK(launch_sam_write(d, n_rec, ws->d_samoff, ws->d_sam, st));
-    const char *host_sam = ws->h_sam; uint64_t host_bytes = total;
-    if (ws->sam_bgzf) { rc = ws_sam_bgzf(ws, total, st, &host_sam, &host_bytes); if (rc) return rc; }
-    else {
-        HIPCHK(hipMemcpyAsync(ws->h_sam, ws->d_sam, total, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    *sam = host_sam; *sam_bytes = host_bytes; *n_pairs = n;
+    HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->d_scan.cap, st));
+    uint32_t max_len = 0;
+    if ((rc = text_codes(ws, n_rec, "blocks", st, &max_len))) return rc;
+    if ((rc = pe_resident_impl(ws, o, pe, n, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st))) return rc;
+    TextTrace tr;                                               // off: the stage clocks are single end's
+    if ((rc = text_emit(ws, to, pe, n_rec, max_len, st, tr, sam, sam_bytes))) return rc;
+    *n_pairs = n;
     return SALT_OK;
 }
-#undef REGROW
 
 // ---------------------------------------------------------------------------------------------
 // polish (row N4)
@@ -1695,18 +1677,16 @@ extern "C" int salt_gpu_ws_pe_counts(salt_gpu_ws_t *ws, uint32_t out[8])
 
 static int pe_prepare(salt_gpu_ws_t *ws, uint32_t n_pairs, hipStream_t st)
 {
-    if (n_pairs > ws->pe_pairs_cap) {
+    if (n_pairs > ws->d_pairs.cap) {
         HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_pairs); hipFree(ws->d_req); hipFree(ws->d_swres); hipFree(ws->d_pcq);
-        ws->d_pairs = nullptr; ws->d_req = nullptr; ws->d_swres = nullptr; ws->d_pcq = nullptr; ws->pe_pairs_cap = 0;   // a failed malloc below leaves a consistent (empty) state
-        HIPCHK(hipMalloc((void **)&ws->d_pcq, (uint64_t)n_pairs * 2 * 4));
-        HIPCHK(hipMalloc((void **)&ws->d_pairs, (uint64_t)n_pairs * sizeof(PePair)));
-        HIPCHK(hipMalloc((void **)&ws->d_req, (uint64_t)n_pairs * 2 * sizeof(PeSwReq)));
-        HIPCHK(hipMalloc((void **)&ws->d_swres, (uint64_t)n_pairs * 2 * sizeof(PeSwRes)));
-        ws->pe_pairs_cap = n_pairs;
+        ws->d_pairs.release(); ws->d_req.release(); ws->d_swres.release(); ws->d_pcq.release();
+        HIPCHK(ws->d_pcq.alloc((uint64_t)n_pairs * 2));
+        HIPCHK(ws->d_req.alloc((uint64_t)n_pairs * 2));
+        HIPCHK(ws->d_swres.alloc((uint64_t)n_pairs * 2));
+        HIPCHK(ws->d_pairs.alloc(n_pairs));                   // last: its capacity is the one compared, a failed allocation above leaves it empty
     }
     if (!ws->d_pctl) {
-        HIPCHK(hipMalloc((void **)&ws->d_pctl, sizeof(PeCtl)));
+        HIPCHK(ws->d_pctl.alloc(1));
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, ws->ix->device));
         ws->sw_blocks = (uint32_t)prop.multiProcessorCount;             // CUs: k_sw runs up to SW_MAX_BLOCKS_PER_CU blocks on each
@@ -1736,12 +1716,10 @@ static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sa
     // one group (8 lanes) per rescue in flight; rescues are a few per cent of the mates, so a small batch does not need the full grid
     sw_geom_limit(geom, n_pairs / 96u < 256u ? 256u : n_pairs / 96u);
     const uint64_t need = sw_scratch_bytes(geom);
-    if (need > ws->sw_scr_bytes) {
+    if (need > ws->d_sw_scr.cap) {
         HIPCHK(hipStreamSynchronize(st));
-        hipFree(ws->d_sw_scr); ws->d_sw_scr = nullptr; ws->sw_scr_bytes = 0;
-        hipError_t e = hipMalloc((void **)&ws->d_sw_scr, need);
+        const hipError_t e = ws->d_sw_scr.alloc(need);
         if (e != hipSuccess) return fail(SALT_E_NOMEM, std::string("hipMalloc(rescue scratch): ") + hipGetErrorString(e));
-        ws->sw_scr_bytes = need;
     }
     launch_sw(ws->ix->view, ws->ix->d_pac, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs), ws->d_req, ws->d_pctl, ws->d_swres,
               ws->d_sw_scr, geom, max_len, st);

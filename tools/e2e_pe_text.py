@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end paired-end runs of the `salt` binary on the GRCh38-scale workload (GPU box): builds the index once, writes the two FASTQ
 files of <n_pairs> pairs of 2 x 150 bases, then runs `salt -d -c -p -a 250 -b 550` for every settings string ("ENV=VAL,ENV=VAL";
-"" = defaults; OUT=null writes to /dev/null).   usage: tools/e2e_pe_text.py <n_pairs> [settings ...]"""
+"" = defaults; OUT=null writes to /dev/null; BIN=<path> runs the `salt` binary of another build for that leg, as in tools/e2e_text.py).
+A leg that fails ends the run: nothing more is started on the device behind it.   usage: tools/e2e_pe_text.py <n_pairs> [settings ...]"""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -32,13 +33,13 @@ salt = os.path.join(ROOT, "salt_amd", "bin", "salt")
 for s in settings:
     env = dict(os.environ)
     for kv in filter(None, s.split(",")):
-        a, b = kv.split("=")
+        a, b = kv.split("=", 1)
         env[a] = b
     sam = os.path.join(w["dir"], "e2e_pe.sam")
     to_null = env.pop("OUT", "") == "null"
     t0 = time.time()
     with open("/dev/null" if to_null else sam, "wb") as fo:
-        cmd = [salt, "-d", "-c", "-p", "-a", "250", "-b", "550", "-t", env.pop("T", "64"), w["prefix"]] + fq
+        cmd = [env.pop("BIN", salt), "-d", "-c", "-p", "-a", "250", "-b", "550", "-t", env.pop("T", "64"), w["prefix"]] + fq
         if env.pop("ROCPROF", ""):                            # kernel-trace statistics of this run under gpurun_out/pe_prof
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(ROOT, "gpurun_out", "pe_prof"), "-o", "pe", "--"] + cmd
         r = subprocess.run(cmd, stdout=fo, stderr=subprocess.PIPE, env=env)
@@ -47,3 +48,6 @@ for s in settings:
     for l in tail[-6:]:
         print("   ", l)
     sys.stdout.flush()
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr.decode()[-2000:])
+        sys.exit(1)
