@@ -2741,26 +2741,36 @@ uint32_t diag_rule_words() { return 6 + 2 * NHIT; }
 // ---------------------------------------------------------------------------------------------
 // k_diag_lv: unit access to the verify / LV device functions for the golden vectors (tests only)
 // ---------------------------------------------------------------------------------------------
+// One case per block for mismatch_capped, lv_wave and lv_cigar.  lv_lanes takes one candidate per lane, staged by lane_text as k_gap
+// and k_heavy stage theirs: the block of case c runs it for the lane_n[c] cases lane_case[lane_first[c] ..) -- 64 different cases
+// of one (L, k), each lane with its own read and window, or case c alone in every lane -- and writes their out[.][2]; a case
+// some other block serves has lane_n = 0.  Cases beyond the lane kernel's limits get -2 there.
+__host__ __device__ static inline bool lv_fit_dev(uint32_t L, uint32_t k) { return k <= (uint32_t)LLV_K && L + 4 <= 8u * (LLV_TW - 1); }
+bool lv_lanes_fit(uint32_t L, uint32_t k) { return lv_fit_dev(L, k); }
+
 __global__ void __launch_bounds__(64)
 k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ kdiff,
-          const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs, int32_t *__restrict__ out /* [n][4] */,
+          const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs, const uint32_t *__restrict__ lane_first,
+          const uint32_t *__restrict__ lane_n, const uint32_t *__restrict__ lane_case, int32_t *__restrict__ out /* [n][4] */,
           uint16_t *__restrict__ cig_out /* [n][64] */, LvTables *__restrict__ lvtab)
 {
     __shared__ WaveLds w;
+    __shared__ uint32_t lane_pm[LLV_N][LLV_TW];
     const uint32_t c = blockIdx.x, lane = lane_id();
     if (c >= n_cases) return;
     const uint32_t off = offs[c], L = offs[c + 1] - off, p = pos[c];
     const uint32_t nw = (L + 7) >> 3;
-    for (uint32_t j = lane; j < nw; j += 64) {
+    auto pm_word = [&](uint32_t o, uint32_t j) -> uint32_t {
         uint32_t word = 0;
         for (uint32_t q = 0; q < 8; ++q) {
-            uint32_t i = j * 8 + q, cc = i < L ? seqs[off + i] : 5u;
+            uint32_t i = j * 8 + q, cc = i < L ? seqs[o + i] : 5u;
             word |= (cc < 4 ? (1u << cc) : (cc == 4 ? 15u : 0u)) << (4 * q);
         }
-        w.pm[0][j] = word;
-    }
+        return word;
+    };
+    for (uint32_t j = lane; j < nw; j += 64) w.pm[0][j] = pm_word(off, j);
     WSYNC();
-    int32_t v = -2, e_wave = -2, e_lane = -2, n_cig = -2;
+    int32_t v = -2, e_wave = -1, n_cig = -2;
     if (p + L <= ix.ref_len) v = (int32_t)mismatch_capped(ix, w.pm[0], L, p);
     const bool in_range = !(p > ix.ref_len || p + L + 4 > ix.ref_len);
     const int k = (int)kdiff[c];
@@ -2769,40 +2779,38 @@ k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, cons
         int dd;
         e_wave = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, k, nullptr, dd);
         WSYNC();
-        if (k <= LLV_K && L + 4 <= 8u * (LLV_TW - 1)) {
-            const uint32_t tl = L + 4, w0 = p >> 3, sh = (p & 7u) * 4u, nwt = (tl + 7) >> 3;
-            uint32_t lo = ix.ref[w0];
-            for (uint32_t j = 0; j < LLV_TW && lane < LLV_N; ++j) {    // every lane stages the same window
-                uint32_t word = 0;
-                if (j < nwt) {
-                    const uint32_t hi = ix.ref[w0 + j + 1];
-                    word = sh ? ((lo >> sh) | (hi << (32 - sh))) : lo;
-                    const uint32_t rem = tl - j * 8;
-                    if (rem < 8) word &= (1u << (4 * rem)) - 1u;
-                    lo = hi;
-                }
-                w.u.llv.T[lane * LLV_TW + j] = word;
-            }
-            uint32_t el = lv_lanes(w.u.llv, w.pm[0], (int)L, (int)L + 4, k, lane < LLV_N);
-            el = (uint32_t)__shfl((int)el, 0);
-            e_lane = el == 255 ? -1 : (int32_t)el;
-            WSYNC();
-        }
-        if (e_wave >= 0 && e_wave < LVK) {
-            lv_cigar(ix.ref, w, lvtab + blockIdx.x, 0, L, p, e_wave);
-            n_cig = w.n_cig;
-            if (lane < (uint32_t)w.n_cig) cig_out[(size_t)c * SALT_MAX_CIGAR_OPS + lane] = w.cig[lane];
-        }
-    } else { e_wave = -1; e_lane = -1; }
-    if (lane == 0) { out[c * 4 + 0] = v; out[c * 4 + 1] = e_wave; out[c * 4 + 2] = e_lane; out[c * 4 + 3] = n_cig; }
+    }
+    const bool fit = lv_fit_dev(L, (uint32_t)k);
+    const uint32_t gn = fit ? lane_n[c] : 0u;
+    if (gn) {                                                             // gn is 1 or LLV_N
+        const uint32_t m = lane_case[lane_first[c] + lane % gn], mo = offs[m], mp = pos[m];      // same L and k as case c
+        for (uint32_t j = 0; j < nw; ++j) lane_pm[lane][j] = pm_word(mo, j);
+        const bool act = !(mp > ix.ref_len || mp + L + 4 > ix.ref_len);   // ed_diff guard, as k_gap has it
+        if (act) lane_text(ix.ref, w.u.llv.T + lane * LLV_TW, mp, L + 4);
+        WSYNC();
+        const uint32_t el = lv_lanes(w.u.llv, lane_pm[lane], (int)L, (int)L + 4, k, act);
+        if (lane < gn) out[(size_t)m * 4 + 2] = el == 255 ? -1 : (int32_t)el;
+        WSYNC();
+    }
+    if (in_range && e_wave >= 0 && e_wave < LVK) {
+        lv_cigar(ix.ref, w, lvtab + blockIdx.x, 0, L, p, e_wave);
+        n_cig = w.n_cig;
+        if (lane < (uint32_t)w.n_cig) cig_out[(size_t)c * SALT_MAX_CIGAR_OPS + lane] = w.cig[lane];
+    }
+    if (lane == 0) {
+        out[(size_t)c * 4 + 0] = v; out[(size_t)c * 4 + 1] = e_wave; out[(size_t)c * 4 + 3] = n_cig;
+        if (!fit) out[(size_t)c * 4 + 2] = -2;
+    }
 }
 
 size_t lv_table_bytes() { return sizeof(LvTables); }
 
 void launch_diag_lv(const IndexView &ix, uint32_t n, const uint32_t *pos, const uint32_t *kdiff, const uint8_t *seqs,
-                    const uint32_t *offs, int32_t *out, uint16_t *cig, void *lvtab, hipStream_t st)
+                    const uint32_t *offs, const uint32_t *lane_first, const uint32_t *lane_n, const uint32_t *lane_case,
+                    int32_t *out, uint16_t *cig, void *lvtab, hipStream_t st)
 {
-    if (n) hipLaunchKernelGGL(k_diag_lv, dim3(n), dim3(64), 0, st, ix, n, pos, kdiff, seqs, offs, out, cig, static_cast<LvTables *>(lvtab));
+    if (n) hipLaunchKernelGGL(k_diag_lv, dim3(n), dim3(64), 0, st, ix, n, pos, kdiff, seqs, offs, lane_first, lane_n, lane_case, out, cig,
+                              static_cast<LvTables *>(lvtab));
 }
 
 // k_diag_verify: unit access to the candidate verifiers (tests only).  One wave per case: the read seqs[offs[c]..offs[c+1]) against

@@ -8,6 +8,8 @@
 #include <time.h>
 #include <cstddef>
 #include <cctype>
+#include <map>
+#include <utility>
 #include <string>
 #include <thread>
 #include <vector>
@@ -1438,18 +1440,42 @@ extern "C" int salt_gpu_diag_lv(const uint32_t *ref_words, uint32_t ref_len, uin
     HIPCHK(hipMalloc((void **)&d_k, (uint64_t)n_cases * 4)); HIPCHK(hipMemcpy(d_k, kdiff, (uint64_t)n_cases * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMalloc((void **)&d_offs, ((uint64_t)n_cases + 1) * 4)); HIPCHK(hipMemcpy(d_offs, offs, ((uint64_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMalloc((void **)&d_seqs, bases + 64)); HIPCHK(hipMemcpy(d_seqs, seqs, bases, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&d_out, (uint64_t)n_cases * 16));
+    HIPCHK(hipMalloc((void **)&d_out, (uint64_t)n_cases * 16)); HIPCHK(hipMemset(d_out, 0xFD, (uint64_t)n_cases * 16));
     HIPCHK(hipMalloc((void **)&d_cig, (uint64_t)n_cases * SALT_MAX_CIGAR_OPS * 2)); HIPCHK(hipMemset(d_cig, 0, (uint64_t)n_cases * SALT_MAX_CIGAR_OPS * 2));
     IndexView v; memset(&v, 0, sizeof v);
     v.ref = d_ref; v.ref_len = ref_len;
     void *d_tab = nullptr;
     HIPCHK(hipMalloc(&d_tab, (uint64_t)n_cases * lv_table_bytes()));
-    launch_diag_lv(v, n_cases, d_pos, d_k, d_seqs, d_offs, d_out, d_cig, d_tab, nullptr);
+    // the lane kernel's share: where 64 cases have one (L, k) the first one's block runs all of them, a lane each; the others go alone
+    std::vector<uint32_t> lane_first(n_cases + 1, 0u), lane_n(n_cases + 1, 0u), lane_case;
+    {
+        std::map<std::pair<uint32_t, uint32_t>, std::vector<uint32_t>> by_shape;
+        for (uint32_t c = 0; c < n_cases; ++c) {
+            if (offs[c + 1] < offs[c]) return fail(SALT_E_INVAL, "offsets must not decrease");
+            if (lv_lanes_fit(offs[c + 1] - offs[c], kdiff[c])) by_shape[std::make_pair(offs[c + 1] - offs[c], kdiff[c])].push_back(c);
+        }
+        for (const auto &kv : by_shape) {
+            const std::vector<uint32_t> &cs = kv.second;
+            for (size_t i = 0; i < cs.size();) {
+                const uint32_t take = cs.size() - i >= 64 ? 64u : 1u;
+                lane_first[cs[i]] = (uint32_t)lane_case.size(); lane_n[cs[i]] = take;
+                lane_case.insert(lane_case.end(), cs.begin() + i, cs.begin() + i + take);
+                i += take;
+            }
+        }
+        lane_case.push_back(0u);
+    }
+    uint32_t *d_lf = nullptr, *d_ln = nullptr, *d_lc = nullptr;
+    HIPCHK(hipMalloc((void **)&d_lf, lane_first.size() * 4)); HIPCHK(hipMemcpy(d_lf, lane_first.data(), lane_first.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc((void **)&d_ln, lane_n.size() * 4)); HIPCHK(hipMemcpy(d_ln, lane_n.data(), lane_n.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc((void **)&d_lc, lane_case.size() * 4)); HIPCHK(hipMemcpy(d_lc, lane_case.data(), lane_case.size() * 4, hipMemcpyHostToDevice));
+    launch_diag_lv(v, n_cases, d_pos, d_k, d_seqs, d_offs, d_lf, d_ln, d_lc, d_out, d_cig, d_tab, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out4, d_out, (uint64_t)n_cases * 16, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cigars, d_cig, (uint64_t)n_cases * SALT_MAX_CIGAR_OPS * 2, hipMemcpyDeviceToHost));
     hipFree(d_ref); hipFree(d_pos); hipFree(d_k); hipFree(d_offs); hipFree(d_seqs); hipFree(d_out); hipFree(d_cig); hipFree(d_tab);
+    hipFree(d_lf); hipFree(d_ln); hipFree(d_lc);
     return SALT_OK;
 }
 

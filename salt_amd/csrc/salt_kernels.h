@@ -171,8 +171,11 @@ void launch_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *val,
 uint32_t diag_rule_words();
 void launch_diag_verify(const uint32_t *ref, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs, const uint32_t *cand,
                         const uint32_t *coffs, int mode, uint8_t *out, hipStream_t st);
+// lane_first / lane_n / lane_case: which cases the block of case c hands to the one-candidate-per-lane kernel (k_diag_lv)
 void launch_diag_lv(const IndexView &ix, uint32_t n, const uint32_t *pos, const uint32_t *kdiff, const uint8_t *seqs,
-                    const uint32_t *offs, int32_t *out, uint16_t *cig, void *lvtab, hipStream_t st);
+                    const uint32_t *offs, const uint32_t *lane_first, const uint32_t *lane_n, const uint32_t *lane_case,
+                    int32_t *out, uint16_t *cig, void *lvtab, hipStream_t st);
+bool lv_lanes_fit(uint32_t L, uint32_t k);          // within the lane kernel's limits (LLV_K, LLV_TW)
 
 // ---- FASTQ text in, SAM text out (salt_text.hip) ----
 struct FqRec { uint32_t name_off, name_len, seq_off, len, qual_off; };        // one 4-line record: offsets into the raw block

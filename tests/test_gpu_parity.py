@@ -79,47 +79,12 @@ def test_gpu_fields_match_oracle_on_synthetic_repeats(tiny, optargs):
 
 def test_gpu_verify_and_lv_units_match_reference_vectors():
     """ed_mismatch / ed_diff / ed_diff_withcigar known answers printed by the reference's own units
-    (tests/golden/lv_vectors.txt) against both LV kernels and the CIGAR traceback on the GPU."""
-    import ctypes
-    import salt_amd
+    (tests/golden/lv_vectors.txt) against both LV kernels and the CIGAR traceback on the GPU.  The one-candidate-per-lane
+    kernel must answer every vector within its limits (gap_cases.run_lv_units) and none beyond them."""
+    import gap_cases
     from conftest import GOLDEN
-    lib = salt_amd.gpu_lib()
-    lib.salt_gpu_diag_lv.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 6
-    ref = None
-    pos, kd, kmis, want, seqs, offs = [], [], [], [], [], [0]
-    with open(os.path.join(GOLDEN, "lv_vectors.txt")) as f:
-        for line in f:
-            t = line.split()
-            if t[0] == "R":
-                l_ref = int(t[1])
-                ref = np.array([int(x, 16) for x in t[2:]], dtype=np.uint32)
-                continue
-            pos.append(int(t[1])); kmis.append(int(t[3])); kd.append(int(t[4]))
-            s = np.frombuffer(t[5].encode(), dtype=np.uint8) - 48
-            seqs.append(s); offs.append(offs[-1] + len(s))
-            want.append((int(t[6]), int(t[7]), int(t[8]), t[9]))
-    n = len(pos)
-    pos_a, kd_a = np.array(pos, dtype=np.uint32), np.array(kd, dtype=np.uint32)
-    seq_a, off_a = np.concatenate(seqs).astype(np.uint8), np.array(offs, dtype=np.uint32)
-    out = np.zeros((n, 4), dtype=np.int32)
-    cig = np.zeros((n, 64), dtype=np.uint16)
-    rc = lib.salt_gpu_diag_lv(ref.ctypes.data, l_ref, n, pos_a.ctypes.data, kd_a.ctypes.data, seq_a.ctypes.data,
-                              off_a.ctypes.data, out.ctypes.data, cig.ctypes.data)
-    assert rc == 0, lib.salt_gpu_last_error()
-    n_lane = 0
-    for i in range(n):
-        mis, diff, cret, ctext = want[i]
-        L = offs[i + 1] - offs[i]
-        v = int(out[i, 0])
-        assert (v if v <= kmis[i] else -1) == mis, ("mismatch", i)
-        assert int(out[i, 1]) == diff, ("lv_wave", i, out[i], want[i])
-        if int(out[i, 2]) != -2 or (kd[i] <= 12 and L <= 129 and diff != -1 and False):
-            assert int(out[i, 2]) == diff, ("lv_lanes", i, out[i], want[i])
-            n_lane += 1
-        if 0 <= diff < 31:
-            got = "".join("%d%s" % (int(x) >> 4, "MID"[int(x) & 3]) for x in cig[i, :int(out[i, 3])])
-            assert got == ctext, ("cigar", i, got, ctext)
-    assert n_lane > 1000
+    n, n_lane = gap_cases.run_lv_units(os.path.join(GOLDEN, "lv_vectors.txt"))
+    assert n == 4000 and n_lane > 1000
 
 
 def test_cli_salt_matches_reference_golden(tmp_path):

@@ -3,7 +3,8 @@
 * tests/golden/lambda/expect_se_*.sam were printed by the real reference (`oracle/_ref/salt`,
   compiled in place from /root/reference by oracle/Makefile) -- see tests/golden/make_fixtures.py.
 * tests/golden/lv_vectors.txt was printed by oracle/ref_harness.c linked against the reference's
-  LandauVishkin.c / editdistance.c.
+  LandauVishkin.c / editdistance.c; tests/golden/lv_vectors_shapes.txt.gz by its --shapes mode.
+* tests/golden/lambda/expect_gap_*.sam.gz: the reference on reads that all take the gapped pass (make_gap_fixture.py).
 Bar: byte-identical SAM, exact integers / CIGAR strings.
 """
 import ctypes
@@ -13,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import gap_cases
 from conftest import EXTRA_CASES, LAMBDA, GOLDEN, read_cases
 
 SE_CASES = [c for c in read_cases() if c.startswith("se_")]
@@ -68,6 +70,43 @@ def test_oracle_units_match_reference_vectors(oracle_lib):
                 assert (buf.value.decode() or "-") == cig
             n += 1
     assert n == 4000
+
+
+@pytest.mark.parametrize("case", sorted(gap_cases.GAP_CASES))
+def test_oracle_sam_matches_reference_on_the_gap_fixture(case, oracle_cli, tmp_path):
+    """The reference's own SAM for reads built to have no gap-free hit (make_gap_fixture.py): 40..512 bases, indels of 1..L/10+1 bases at
+    both sides of the 8-base words of the Landau-Vishkin windows, windows that end at the genome's end, indel mates of 100..250 bases.
+    The golden files keep the gapped records they are for: gap_cases.MINIMA per file, 40 per read length."""
+    args, _ = gap_cases.GAP_CASES[case]
+    want = gap_cases.golden(case)
+    n, n_gap, n_xa, by_len = gap_cases.census(want)
+    assert all(have >= need for have, need in zip((n, n_gap, n_xa), gap_cases.MINIMA[case])), (n, n_gap, n_xa)
+    assert min(by_len.values()) >= gap_cases.MIN_GAPPED_PER_LENGTH, by_len
+    out = subprocess.run([oracle_cli] + args + [os.path.join(LAMBDA, "idx")] + gap_cases.plain_paths(case, tmp_path), check=True,
+                         capture_output=True).stdout
+    assert out == want, gap_cases.diff_message(out, want)
+
+
+def test_oracle_units_match_reference_shape_vectors(oracle_lib):
+    """ed_mismatch / ed_diff / ed_diff_withcigar on the shape vectors (ref_harness.c --shapes): lengths 19..512, bounds {L/10, 3, 12, 13,
+    30}, indel runs up to 30 bases, windows at the reference's end.  The file keeps what the GPU unit test needs of it."""
+    lib = oracle_lib
+    l_ref, ref, vecs = gap_cases.load_lv_vectors(os.path.join(GOLDEN, "lv_vectors_shapes.txt.gz"))
+    assert len(vecs) == 3000
+    refp = np.concatenate([ref, np.zeros(8, dtype=np.uint32)])
+    rp = refp.ctypes.data_as(ctypes.c_void_p)
+    for i, v in enumerate(vecs):
+        seq = np.ascontiguousarray(v.seq)
+        sp = seq.ctypes.data_as(ctypes.c_void_p)
+        L = len(seq)
+        if v.mis != -9:
+            assert lib.so_ed_mismatch(rp, v.pos, sp, L, v.kmis) == v.mis, i
+        assert lib.so_ed_diff(rp, l_ref, v.pos, L + 4, sp, L, v.kdiff) == v.diff, i
+        if 0 <= v.diff < 31:
+            buf = ctypes.create_string_buffer(512)
+            assert lib.so_ed_diff_cigar(rp, v.pos, L + 4, sp, L, v.diff, buf, 400) == v.cret, i
+            assert (buf.value.decode() or "-") == v.cigar, i
+    gap_cases.check_lv_vector_census(l_ref, vecs)
 
 
 PE_CASES = [c for c in read_cases() if c.startswith("pe_")]
