@@ -204,7 +204,6 @@ struct RawReader {
     }
 };
 
-
 // Helper threads of one align worker, created once (a batch needs three parallel loops; spawning threads for each costs more
 // than the loops' bodies at 100 000 reads per batch).
 class Pool {
@@ -623,19 +622,55 @@ static bool bgzf_inflate(const unsigned char *cbuf, size_t csize, char *dst, siz
     return ok;
 }
 
+// file bytes [off, off + n) into dst, in as many reads as it takes; returns the bytes read (fewer than n: an error, or the file ends before)
+static uint64_t pread_full(int fd, void *dst, uint64_t n, uint64_t off)
+{
+    uint64_t got = 0;
+    while (got < n) { const ssize_t r = pread(fd, (char *)dst + got, (size_t)(n - got), (off_t)(off + got)); if (r <= 0) break; got += (uint64_t)r; }
+    return got;
+}
+// The ordered block writer and run state of a text path, single end and paired end: workers claim chunks (next_chunk), block k is written
+// once block k - 1 has been, and a failure stops everyone.  A chunk the device parser refused (SALT_E_INVAL: a multi-line record, a blank
+// line, an empty read -- things kseq.h reads, query.c:103-239): the blocks before it are written, then the host parser takes over at
+// `resume` -- single end a byte offset (a record start: everything before it was strict 4-line FASTQ), paired end a chunk index.
+// One locking rule: a flag that a waiter's predicate reads is stored with that waiter's mutex held, before the notify -- a waiter that has
+// evaluated its predicate but not yet blocked cannot miss the notify.  The paired-end workers wait for the scanners' offsets (PeScan) on
+// this mutex and condition variable too, so a failure or a fallback wakes them like everyone else.
 struct TextRun {
-    const Bgzf *bgzf = nullptr;                              // non-null: `file_size` and every offset below are in the uncompressed text
-    int fd = -1; uint64_t file_size = 0, chunk = 0;
-    std::atomic<uint64_t> next_chunk{ 0 };
-    // output sequencing: block k is written once block k - 1 has been
     std::mutex mu; std::condition_variable cv;
     uint64_t written = 0; long reads_done = 0;
-    int ready = 0; bool go = false;                         // workers that finished their set-up; the clock starts when all have
-    std::atomic<bool> failed{ false };
-    // a chunk the device parser refused (SALT_E_INVAL: a multi-line record, a blank line, an empty read -- things kseq.h reads, query.c:103-239):
-    // the blocks before it are written, then the host parser takes over at fb_off (a record start: everything before it was strict 4-line FASTQ)
-    std::atomic<bool> fallback{ false }; uint64_t fb_off = 0;
+    std::atomic<bool> failed{ false }, fallback{ false }; uint64_t resume = 0; std::atomic<uint64_t> next_chunk{ 0 };
+    std::atomic<double> t_read{ 0 }, t_gpu{ 0 }, t_write{ 0 }, t_last;     // t_last: when the last SAM byte so far was written
+    explicit TextRun(double t0) : t_last(t0) {}
+    void fail() { { std::lock_guard<std::mutex> lk(mu); failed = true; } cv.notify_all(); }
+    void fail_gpu() { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); fail(); }
+    // waits until block k may be written; false when the run failed or fell back instead (claim: a true answer is the fallback's election)
+    bool wait_turn(uint64_t k, bool claim = false)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return failed || fallback || written == k; });
+        const bool mine = !failed && !fallback;
+        if (mine && claim) fallback = true;
+        return mine;
+    }
+    // block k, whose turn it is: its bytes to stdout, then the next block's turn; false (and the run failed) when they cannot be written
+    bool write_block(uint64_t k, const char *sam, uint64_t sam_bytes, long n_reads)
+    {
+        const double tw0 = now(); bool ok = true;
+        for (uint64_t w = 0; w < sam_bytes && ok; ) { const ssize_t r = write(1, sam + w, sam_bytes - w); if (r <= 0) ok = false; else w += (uint64_t)r; }
+        t_write = t_write + (now() - tw0);
+        { const double tn = now(); double cur = t_last.load(); while (tn > cur && !t_last.compare_exchange_weak(cur, tn)) {} }
+        if (!ok) { fprintf(stderr, "[salt] write error on the SAM stream\n"); fail(); return false; }
+        { std::lock_guard<std::mutex> lk(mu); written = k + 1; reads_done += n_reads; fprintf(stderr, "%ld reads have been aligned!\n", reads_done); }
+        cv.notify_all();
+        return true;
+    }
+    // chunk k cannot go through the device parser: once the blocks before it are out, everyone stops and the host pipeline continues there.
+    // True for the first claimant of a run that has not failed: it alone sets `resume` (read after the workers have been joined)
+    bool claim_fallback(uint64_t k) { const bool won = wait_turn(k, true); cv.notify_all(); return won; }
 };
+// a refused chunk is the host parser's, unless what the device refused is the output (a read name no BAM record holds)
+static bool parser_refused(int grc) { return grc == SALT_E_INVAL && !(g_bam.device && strncmp(salt_gpu_last_error(), "BAM:", 4) == 0); }
 
 static const uint64_t TEXT_SLACK = 1u << 20;             // how far past a chunk's end a worker looks for the next record start (longest record it can cut)
 
@@ -766,215 +801,225 @@ TextPlan::~TextPlan()
     for (char *b : sam_buf) if (b) salt_gpu_host_free(b);
 }
 
+// A workspace of the text path on `gix` for chunks of up to max_reads reads, with the run's output modes set.  text_reads non-zero (and a
+// read length known from the file's head): the device buffers for chunks of text_bytes holding that many reads are reserved now, the SAM
+// text landing in worker wk's page-locked buffer.  Returns the first error code; *ws is the caller's to destroy either way.
+static int open_text_ws(salt_gpu_index_t *gix, uint32_t max_reads, salt_gpu_ws_t **ws, const salt_aln_opt_t *ao = nullptr, const TextPlan *P = nullptr, int wk = 0, uint64_t text_bytes = 0, uint32_t text_reads = 0)
+{
+    int rc = salt_gpu_ws_create(gix, max_reads, (uint64_t)max_reads * 160, ws);
+    if (!rc && g_bgzf.device) rc = salt_gpu_ws_set_sam_bgzf(*ws, 1);
+    if (!rc && g_bam.device) rc = salt_gpu_ws_set_sam_bam(*ws, 1);
+    if (!rc && g_polish) rc = salt_gpu_ws_set_polish(*ws, g_polish);
+    if (!rc && text_reads && P->head_read_len) rc = salt_gpu_ws_reserve_text(*ws, ao, text_bytes, text_reads, P->head_read_len, P->sam_cap - 64, P->sam_buf[(size_t)wk], P->sam_cap);
+    return rc;
+}
+// the contig table of the host index, for RNAME / POS on the device and for the polish handles
+struct Contigs {
+    std::vector<int64_t> off; std::vector<const char *> nm;
+    explicit Contigs(const salt_index_t *ix) : off((size_t)salt_index_n_seqs(ix)), nm(off.size()) { for (size_t i = 0; i < off.size(); ++i) salt_index_seq(ix, (int)i, &off[i], nullptr, &nm[i]); }
+    int32_t n() const { return (int32_t)off.size(); }
+};
+// what both text paths begin with: the contig table on every GPU, and the page-locked buffers there
+static bool text_begin(const std::vector<salt_gpu_index_t *> &gix, const Contigs &C, TextPlan &P)
+{
+    fflush(stdout);
+    bool ok = true;
+    for (salt_gpu_index_t *g : gix) ok = ok && salt_gpu_index_set_contigs(g, C.n(), C.off.data(), C.nm.data()) == 0;
+    if (ok && P.alloc.joinable()) P.alloc.join();
+    if (!ok || !P.alloc_ok) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
+    return ok && P.alloc_ok;
+}
+
+// what the workers of a single-end run share besides its TextRun
+struct SeText {
+    const char *fn; int fd = -1; uint64_t file_size = 0, chunk = 0, n_chunks = 0;
+    const Bgzf *bgzf = nullptr;                              // non-null: `file_size` and every offset are in the uncompressed text
+    bool dev_inflate = false; int inflate_helpers = 0;
+    const TextPlan &P; const std::vector<salt_gpu_index_t *> &gix; const salt_aln_opt_t &ao; const salt_text_opt_t to; const double t0;
+};
+
+// One worker of the single-end text path.  A turn of run(): load() chunk k's bytes, cut() them at record starts, align(), write in turn.
+struct SeWorker {
+    TextRun &R; const SeText &S; const int wk;
+    SeWorker(TextRun &r, const SeText &s, int w) : R(r), S(s), wk(w) {}
+    salt_gpu_ws_t *ws = nullptr; uint32_t ws_reads = 0;
+    std::vector<unsigned char> cbuf;                              // blocked gzip input: the compressed bytes of a chunk's blocks
+    std::vector<char> win; std::vector<uint32_t> zc, zu;          // ... inflated on the device: the windows peeked from its text, the chunk's block offsets
+    std::string zbuf;                                             // --bgzf with the host compressor: this worker's blocks
+    // where load() left the chunk's text: n bytes at `text` in the worker's buffer (blocked input inflates whole blocks: the chunk's bytes then
+    // start inside the buffer), or in the workspace with byte 0 at dev_base (on_dev); add_nl: byte n - 1 is a newline the device's text lacks
+    char *text = nullptr; uint64_t dev_base = 0, n = 0; bool on_dev = false, add_nl = false;
+    salt_gpu_index_t *gix() const { return S.gix[(size_t)(wk / S.P.wpg)]; }
+    bool load(uint64_t rd_lo, uint64_t rd_hi);
+    bool cut(uint64_t lo, uint64_t hi, uint64_t rd_lo, uint64_t *beg, uint64_t *end);
+    int align(uint64_t k, uint64_t beg, uint64_t end, const char **sam, uint64_t *sam_bytes, uint32_t *n_reads);
+    void run();
+};
+
+// Text bytes [rd_lo, rd_hi) of the input, three ways: pread from a plain file; blocked gzip inflated by this worker and its helpers; blocked
+// gzip inflated on the device.  The file's last record gets the newline it may lack.  False: reported, and the run failed.
+bool SeWorker::load(uint64_t rd_lo, uint64_t rd_hi)
+{
+    char *const buf = S.P.in_buf[(size_t)wk];
+    text = buf; dev_base = 0; n = rd_hi - rd_lo; on_dev = add_nl = false;
+    if (!S.bgzf) {
+        if (pread_full(S.fd, buf, n, rd_lo) != n) { fprintf(stderr, "[salt] short read on %s\n", S.fn); R.fail(); return false; }
+    } else {
+        // the blocks that hold text bytes [rd_lo, rd_hi): read as one piece, inflated side by side by this worker and its helpers
+        const Bgzf &B = *S.bgzf;
+        const size_t b0 = (size_t)(std::upper_bound(B.uoff.begin(), B.uoff.end(), rd_lo) - B.uoff.begin()) - 1;
+        size_t b1 = (size_t)(std::lower_bound(B.uoff.begin(), B.uoff.end(), rd_hi) - B.uoff.begin());
+        if (b1 >= B.uoff.size()) b1 = B.uoff.size() - 1;
+        const uint64_t c0 = B.coff[b0], c1 = B.coff[b1], u0 = B.uoff[b0];
+        bool ok = B.uoff[b1] - u0 <= S.P.in_cap - 64;
+        // on the device: the compressed blocks go into the page-locked buffer as they are (blocks that deflate did not shrink can
+        // outgrow it by their headers: such a chunk is inflated here)
+        on_dev = S.dev_inflate && ok && c1 - c0 <= S.P.in_cap - 64 && c1 - c0 < 0xFFFFFFFFull && B.uoff[b1] - u0 < 0xFFFFFFFFull;
+        if (on_dev) {
+            ok = pread_full(S.fd, buf, c1 - c0, c0) == c1 - c0;
+            zc.resize(b1 - b0 + 1); zu.resize(b1 - b0 + 1);
+            for (size_t b = b0; b <= b1; ++b) { zc[b - b0] = (uint32_t)(B.coff[b] - c0); zu[b - b0] = (uint32_t)(B.uoff[b] - u0); }
+            if (ok) {
+                const int zrc = salt_gpu_ws_inflate_bgzf(ws, buf, c1 - c0, (uint32_t)(b1 - b0), zc.data(), zu.data());
+                if (zrc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); if (zrc != SALT_E_DATA) { R.fail(); return false; } ok = false; }
+            }
+            dev_base = rd_lo - u0;
+        } else if (ok) {
+            cbuf.resize((size_t)(c1 - c0));
+            std::atomic<size_t> nb{ b0 }; std::atomic<bool> bad{ pread_full(S.fd, cbuf.data(), c1 - c0, c0) != c1 - c0 };
+            auto work = [&]() {
+                for (;;) {
+                    const size_t b = nb.fetch_add(1);
+                    if (b >= b1 || bad) break;
+                    if (!bgzf_inflate(cbuf.data() + (B.coff[b] - c0), (size_t)(B.coff[b + 1] - B.coff[b]), buf + (B.uoff[b] - u0), (size_t)(B.uoff[b + 1] - B.uoff[b]))) bad = true;
+                }
+            };
+            std::vector<std::thread> helpers;
+            for (int h = 0; h < S.inflate_helpers; ++h) helpers.emplace_back(work);
+            work();
+            for (auto &h : helpers) h.join();
+            ok = !bad;
+        }
+        if (!ok) { fprintf(stderr, "[salt] %s: damaged or oversized gzip block near text offset %llu\n", S.fn, (unsigned long long)rd_lo); R.fail(); return false; }
+        text = buf + (rd_lo - u0);
+    }
+    if (rd_hi == S.file_size && n) {                              // a last record without its newline
+        char last = on_dev ? '\n' : text[n - 1];
+        if (on_dev && salt_gpu_ws_text_peek(ws, dev_base + n - 1, 1, &last)) { R.fail_gpu(); return false; }
+        if (last != '\n') { if (on_dev) add_nl = true; else text[n] = '\n'; ++n; }
+    }
+    return true;
+}
+// The chunk's records are those that start in file bytes [lo, hi): *beg and *end are the record starts at or after the two (offsets in the
+// loaded text, which has one byte of context in front and TEXT_SLACK behind), cut on the host's text or from windows of the device's.
+bool SeWorker::cut(uint64_t lo, uint64_t hi, uint64_t rd_lo, uint64_t *beg, uint64_t *end)
+{
+    const uint64_t b0 = lo - rd_lo;                               // offset of file byte `lo` in the text
+    *end = n;
+    if (on_dev) {
+        bool pk = next_record_start_dev(ws, win, dev_base, n, add_nl, b0, lo == 0, beg);
+        if (pk && hi < S.file_size) pk = next_record_start_dev(ws, win, dev_base, n, add_nl, hi - rd_lo, false, end);
+        if (!pk) { R.fail_gpu(); return false; }
+    } else {
+        *beg = next_record_start(text, n, b0, lo == 0 || text[b0 - 1] == '\n');
+        if (hi < S.file_size) *end = next_record_start(text, n, hi - rd_lo, text[hi - rd_lo - 1] == '\n');
+    }
+    if (hi < S.file_size && *end == n) { fprintf(stderr, "[salt] a FASTQ record longer than %llu bytes near offset %llu\n", (unsigned long long)TEXT_SLACK, (unsigned long long)hi); R.fail(); return false; }
+    *beg = std::min(*beg, *end);
+    return true;
+}
+// Text [beg, end) through the device, into a SAM block that lies in the workspace's (or the worker's page-locked) buffer.  A chunk with more
+// reads than the workspace was made for has it re-created once, for the worst case.  Returns the device call's code.
+int SeWorker::align(uint64_t k, uint64_t beg, uint64_t end, const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
+{
+    if (end <= beg) return 0;
+    // (on the device the range ends with the text's own newline, or with the one put behind the file's last record)
+    auto call = [&]() {
+        if (!on_dev) return salt_gpu_align_se_text(ws, &S.ao, &S.to, text + beg, end - beg, sam, sam_bytes, n_reads);
+        const bool nl = add_nl && end == n;
+        return salt_gpu_align_se_text_dev(ws, &S.ao, &S.to, dev_base + beg, end - beg - (nl ? 1 : 0), nl ? 1 : 0, sam, sam_bytes, n_reads);
+    };
+    int grc = call();
+    if (grc == SALT_E_CAPACITY && ws_reads < S.P.worst_reads) {                         // shorter records than the file's head promised
+        if (getenv("SALT_TEXT_TRACE")) fprintf(stderr, "[salt] worker %d: chunk %llu holds more than %u reads, workspace re-created for %u\n", wk, (unsigned long long)k, ws_reads, S.P.worst_reads);
+        salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = S.P.worst_reads;
+        grc = open_text_ws(gix(), ws_reads, &ws);
+        if (!grc && on_dev) grc = salt_gpu_ws_inflate_bgzf(ws, S.P.in_buf[(size_t)wk], zc.back(), (uint32_t)(zc.size() - 1), zc.data(), zu.data());      // the new workspace's text
+        if (!grc) grc = call();
+    }
+    return grc;
+}
+
+void SeWorker::run()
+{
+    pin_to_device_node(wk / S.P.wpg);
+    const bool trace = getenv("SALT_TEXT_TRACE") != nullptr;      // per-worker timeline on stderr
+    const double tw_start = now(); int n_calls = 0; double t_first = 0, t_rest = 0;
+    ws_reads = S.P.max_reads;
+    if (open_text_ws(gix(), ws_reads, &ws, &S.ao, &S.P, wk, S.chunk + TEXT_SLACK, (uint32_t)(ws_reads / 1.3))) { R.fail_gpu(); salt_gpu_ws_destroy(ws); return; }
+    const double t_setup = now() - tw_start;
+    for (;;) {
+        const uint64_t k = R.next_chunk.fetch_add(1);
+        if (k >= S.n_chunks || R.failed || R.fallback) break;
+        // bytes [lo - 1, hi + slack) of the file: one byte of context in front (is `lo` a line start?), slack behind (where does the last record end?)
+        const uint64_t lo = k * S.chunk, hi = std::min(S.file_size, lo + S.chunk);
+        const uint64_t rd_lo = lo ? lo - 1 : 0, rd_hi = std::min(S.file_size, hi + TEXT_SLACK);
+        const double tr0 = now(); uint64_t beg = 0, end = 0;
+        if (!load(rd_lo, rd_hi)) break;
+        if (!on_dev) R.t_read = R.t_read + (now() - tr0);
+        if (!cut(lo, hi, rd_lo, &beg, &end)) break;
+        if (on_dev) R.t_read = R.t_read + (now() - tr0);          // (the windows peeked from the device's text count as reading)
+        const char *sam = nullptr; uint64_t sam_bytes = 0; uint32_t n_reads = 0;
+        const double tg0 = now();
+        const int grc = align(k, beg, end, &sam, &sam_bytes, &n_reads);
+        if (grc && !parser_refused(grc)) { R.fail_gpu(); break; }
+        if (grc) {
+            // not strict 4-line FASTQ in this chunk: when the blocks before it are out, the host parser continues from its first record
+            const std::string why = salt_gpu_last_error();
+            if (R.claim_fallback(k)) {
+                R.resume = rd_lo + beg;
+                fprintf(stderr, "[salt] %s: the host parser takes over at byte %llu of %s\n", why.c_str(), (unsigned long long)R.resume, S.fn);
+            }
+            break;
+        }
+        R.t_gpu = R.t_gpu + (now() - tg0);
+        if (n_calls++ == 0) t_first = now() - tg0; else t_rest += now() - tg0;
+        if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); R.fail(); break; }
+        if (!R.wait_turn(k) || !R.write_block(k, sam, sam_bytes, n_reads)) break;
+    }
+    if (trace) fprintf(stderr, "[salt] worker %d: started %.3f s after the clock, setup %.3f s, first device call %.3f s, %d later calls %.4f s each, done at %.3f s\n", wk,
+                       tw_start - S.t0, t_setup, t_first, n_calls - 1, n_calls > 1 ? t_rest / (n_calls - 1) : 0.0, now() - S.t0);
+    salt_gpu_ws_destroy(ws);
+}
+
 // returns 0 = done, 1 = failed, 2 = *resume_off is where the host pipeline has to take over (everything before it is written)
-static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, int n_gpus, TextPlan &P,
+static int run_se_text(const char *fn_reads, const std::vector<salt_gpu_index_t *> &gix, const Contigs &contigs, TextPlan &P,
                        const salt_aln_opt_t &ao, const salt_sam_opt_t &so, double t0, uint64_t *resume_off)
 {
-    TextRun R;
-    R.fd = open(fn_reads, O_RDONLY);
-    if (R.fd < 0) { fprintf(stderr, "[query_open]: file %s open fail!\n", fn_reads); return 1; }
-    struct stat sb;
-    if (fstat(R.fd, &sb) != 0) { fprintf(stderr, "[salt] cannot stat %s\n", fn_reads); return 1; }
-    R.file_size = (uint64_t)sb.st_size;
-    if (P.bgzf.ok) { R.bgzf = &P.bgzf; R.file_size = P.bgzf.uoff.back(); }
-    R.chunk = P.chunk;
-    fflush(stdout);
-    // contig table for RNAME / POS on the device
-    {
-        const int n = salt_index_n_seqs(ix);
-        std::vector<int64_t> off((size_t)n); std::vector<const char *> nm((size_t)n);
-        for (int i = 0; i < n; ++i) salt_index_seq(ix, i, &off[(size_t)i], nullptr, &nm[(size_t)i]);
-        for (int g = 0; g < n_gpus; ++g)
-            if (salt_gpu_index_set_contigs(gix[(size_t)g], n, off.data(), nm.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    }
-    if (P.alloc.joinable()) P.alloc.join();
-    if (!P.alloc_ok) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    const int n_workers = P.n_workers, n_workers_per_gpu = P.wpg;
-    const uint32_t worst_reads = P.worst_reads, max_reads = P.max_reads, head_read_len = P.head_read_len;
-    const salt_text_opt_t to = { so.print_xa_cigar, so.print_nm_md, so.rg_id };
-    const uint64_t n_chunks = (R.file_size + R.chunk - 1) / R.chunk;
+    SeText S{ fn_reads, open(fn_reads, O_RDONLY), 0, P.chunk, 0, nullptr, false, 0, P, gix, ao, { so.print_xa_cigar, so.print_nm_md, so.rg_id }, t0 };
+    if (S.fd < 0) { fprintf(stderr, "[query_open]: file %s open fail!\n", fn_reads); return 1; }
+    struct stat sb; if (fstat(S.fd, &sb) != 0) { fprintf(stderr, "[salt] cannot stat %s\n", fn_reads); return 1; }
+    S.file_size = (uint64_t)sb.st_size;
+    if (P.bgzf.ok) { S.bgzf = &P.bgzf; S.file_size = P.bgzf.uoff.back(); }
+    S.n_chunks = (S.file_size + S.chunk - 1) / S.chunk;
+    if (!text_begin(gix, contigs, P)) return 1;
     // blocked gzip input: every worker inflates with a few helper threads (a block inflates at ~0.3 GB/s on one core; a worker's chunk must
     // not take longer to inflate than the device takes for the chunks of the other workers)
-    const bool dev_inflate = R.bgzf && salt_gpu_ws_inflate_bgzf && salt_gpu_ws_text_peek && salt_gpu_align_se_text_dev &&
-                             getenv("SALT_INFLATE_DEVICE") && atoi(getenv("SALT_INFLATE_DEVICE")) && !(getenv("SALT_INFLATE_HOST") && atoi(getenv("SALT_INFLATE_HOST")));
-    if (R.bgzf) fprintf(stderr, "[salt] BGZF input: %s inflate, %llu blocks\n", dev_inflate ? "device" : "host", (unsigned long long)(R.bgzf->coff.size() - 1));
-    int inflate_helpers = 0;
-    if (R.bgzf) { inflate_helpers = 5; if (const char *e = getenv("SALT_INFLATE_HELPERS")) { const int v = atoi(e); if (v >= 0 && v <= 64) inflate_helpers = v; } }
+    S.dev_inflate = S.bgzf && salt_gpu_ws_inflate_bgzf && salt_gpu_ws_text_peek && salt_gpu_align_se_text_dev &&
+                    getenv("SALT_INFLATE_DEVICE") && atoi(getenv("SALT_INFLATE_DEVICE")) && !(getenv("SALT_INFLATE_HOST") && atoi(getenv("SALT_INFLATE_HOST")));
+    if (S.bgzf) fprintf(stderr, "[salt] BGZF input: %s inflate, %llu blocks\n", S.dev_inflate ? "device" : "host", (unsigned long long)(S.bgzf->coff.size() - 1));
+    if (S.bgzf) { S.inflate_helpers = 5; if (const char *e = getenv("SALT_INFLATE_HELPERS")) { const int v = atoi(e); if (v >= 0 && v <= 64) S.inflate_helpers = v; } }
+    TextRun R(t0);
     std::vector<std::thread> workers;
-    std::atomic<double> t_read{ 0 }, t_gpu{ 0 }, t_write{ 0 }, t_last{ t0 };     // t_last: when the last SAM byte so far was written
-    auto set_failed = [&]() { { std::lock_guard<std::mutex> lk(R.mu); R.failed = true; } R.cv.notify_all(); };
-    for (int wk = 0; wk < n_workers; ++wk)
-        workers.emplace_back([&, wk]() {
-            salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk];
-            pin_to_device_node(wk / n_workers_per_gpu);
-            std::vector<unsigned char> cbuf;                              // blocked gzip input: the compressed bytes of a chunk's blocks
-            std::vector<char> win; std::vector<uint32_t> zc, zu;          // ... inflated on the device: the windows peeked from its text, the chunk's block offsets
-            const bool trace = getenv("SALT_TEXT_TRACE") != nullptr;      // per-worker timeline on stderr
-            const double tw_start = now(); int n_calls = 0; double t_first = 0, t_rest = 0;
-            uint32_t ws_reads = max_reads;
-            std::string zbuf;                                             // --bgzf with the host compressor: this worker's blocks
-            if (salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) || (g_polish && salt_gpu_ws_set_polish(ws, g_polish)) ||
-                (head_read_len && salt_gpu_ws_reserve_text(ws, &ao, R.chunk + TEXT_SLACK, (uint32_t)(ws_reads / 1.3), head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
-                fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
-            }
-            const double t_setup = now() - tw_start;
-            for (;;) {
-                const uint64_t k = R.next_chunk.fetch_add(1);
-                if (k >= n_chunks || R.failed || R.fallback) break;
-                // bytes [lo - 1, hi + slack) of the file: one byte of context in front (is `lo` a line start?), slack behind (where does the last record end?)
-                const uint64_t lo = k * R.chunk, hi = std::min(R.file_size, lo + R.chunk);
-                const uint64_t rd_lo = lo ? lo - 1 : 0, rd_hi = std::min(R.file_size, hi + TEXT_SLACK);
-                double tr0 = now();
-                uint64_t got = 0;
-                char *const buf0 = buf;                               // (blocked input inflates whole blocks: the chunk's bytes then start inside the buffer)
-                bool on_dev = false; uint64_t dev_base = 0;           // the chunk's text lies in the workspace, byte rd_lo of the file at dev_base
-                if (R.bgzf) {
-                    // the blocks that hold text bytes [rd_lo, rd_hi): read as one piece, inflated side by side by this worker and its helpers
-                    const Bgzf &B = *R.bgzf;
-                    const size_t b0 = (size_t)(std::upper_bound(B.uoff.begin(), B.uoff.end(), rd_lo) - B.uoff.begin()) - 1;
-                    size_t b1 = (size_t)(std::lower_bound(B.uoff.begin(), B.uoff.end(), rd_hi) - B.uoff.begin());
-                    if (b1 >= B.uoff.size()) b1 = B.uoff.size() - 1;
-                    const uint64_t c0 = B.coff[b0], c1 = B.coff[b1], u0 = B.uoff[b0];
-                    bool ok = B.uoff[b1] - u0 <= P.in_cap - 64;
-                    // on the device: the compressed blocks go into the page-locked buffer as they are (blocks that deflate did not shrink can
-                    // outgrow it by their headers: such a chunk is inflated here)
-                    on_dev = dev_inflate && ok && c1 - c0 <= P.in_cap - 64 && c1 - c0 < 0xFFFFFFFFull && B.uoff[b1] - u0 < 0xFFFFFFFFull;
-                    if (on_dev) {
-                        uint64_t cg = 0;
-                        while (cg < c1 - c0) { const ssize_t r = pread(R.fd, buf0 + cg, c1 - c0 - cg, (off_t)(c0 + cg)); if (r <= 0) break; cg += (uint64_t)r; }
-                        ok = cg == c1 - c0;
-                        zc.resize(b1 - b0 + 1); zu.resize(b1 - b0 + 1);
-                        for (size_t b = b0; b <= b1; ++b) { zc[b - b0] = (uint32_t)(B.coff[b] - c0); zu[b - b0] = (uint32_t)(B.uoff[b] - u0); }
-                        if (ok) {
-                            const int zrc = salt_gpu_ws_inflate_bgzf(ws, buf0, c1 - c0, (uint32_t)(b1 - b0), zc.data(), zu.data());
-                            if (zrc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); if (zrc != SALT_E_DATA) { set_failed(); break; } ok = false; }
-                        }
-                        dev_base = rd_lo - u0;
-                    } else if (ok) {
-                        cbuf.resize((size_t)(c1 - c0));
-                        uint64_t cg = 0;
-                        while (cg < c1 - c0) { const ssize_t r = pread(R.fd, cbuf.data() + cg, c1 - c0 - cg, (off_t)(c0 + cg)); if (r <= 0) break; cg += (uint64_t)r; }
-                        ok = cg == c1 - c0;
-                    }
-                    if (ok && !on_dev) {
-                        std::atomic<size_t> nb{ b0 }; std::atomic<bool> bad{ false };
-                        auto work = [&]() {
-                            for (;;) {
-                                const size_t b = nb.fetch_add(1);
-                                if (b >= b1 || bad) break;
-                                if (!bgzf_inflate(cbuf.data() + (B.coff[b] - c0), (size_t)(B.coff[b + 1] - B.coff[b]), buf0 + (B.uoff[b] - u0), (size_t)(B.uoff[b + 1] - B.uoff[b]))) bad = true;
-                            }
-                        };
-                        std::vector<std::thread> helpers;
-                        for (int h = 0; h < inflate_helpers; ++h) helpers.emplace_back(work);
-                        work();
-                        for (auto &h : helpers) h.join();
-                        ok = !bad;
-                    }
-                    if (!ok) { fprintf(stderr, "[salt] %s: damaged or oversized gzip block near text offset %llu\n", fn_reads, (unsigned long long)rd_lo); set_failed(); break; }
-                    buf = buf0 + (rd_lo - u0);
-                    got = rd_hi - rd_lo;
-                } else {
-                    while (got < rd_hi - rd_lo) {
-                        ssize_t r = pread(R.fd, buf + got, rd_hi - rd_lo - got, (off_t)(rd_lo + got));
-                        if (r <= 0) break;
-                        got += (uint64_t)r;
-                    }
-                    if (got != rd_hi - rd_lo) { fprintf(stderr, "[salt] short read on %s\n", fn_reads); set_failed(); break; }
-                }
-                uint64_t n = got;
-                const uint64_t b0 = lo - rd_lo;                                                  // offset of file byte `lo` in buf
-                uint64_t beg = 0, end = 0; bool add_nl = false;
-                if (on_dev) {
-                    // the same cuts from windows of the device's text
-                    char last = '\n';
-                    bool pk = !(rd_hi == R.file_size && n) || salt_gpu_ws_text_peek(ws, dev_base + n - 1, 1, &last) == 0;
-                    if (last != '\n') { add_nl = true; ++n; }
-                    pk = pk && next_record_start_dev(ws, win, dev_base, n, add_nl, b0, lo == 0, &beg);
-                    end = n;
-                    if (pk && hi < R.file_size) pk = next_record_start_dev(ws, win, dev_base, n, add_nl, hi - rd_lo, false, &end);
-                    if (!pk) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
-                    t_read = t_read + (now() - tr0);
-                } else {
-                    t_read = t_read + (now() - tr0);
-                    if (rd_hi == R.file_size && n && buf[n - 1] != '\n') buf[n++] = '\n';      // a last record without its newline
-                    beg = next_record_start(buf, n, b0, lo == 0 || buf[b0 - 1] == '\n');
-                    end = n;
-                    if (hi < R.file_size) end = next_record_start(buf, n, hi - rd_lo, buf[hi - rd_lo - 1] == '\n');
-                }
-                if (hi < R.file_size && end == n) { fprintf(stderr, "[salt] a FASTQ record longer than %llu bytes near offset %llu\n", (unsigned long long)TEXT_SLACK, (unsigned long long)hi); set_failed(); break; }
-                const uint64_t beg2 = std::min(beg, end);
-                const char *sam = nullptr; uint64_t sam_bytes = 0; uint32_t n_reads = 0;
-                double tg0 = now();
-                // (on the device the range ends with the text's own newline, or with the one put behind the file's last record)
-                auto align = [&]() {
-                    if (!on_dev) return salt_gpu_align_se_text(ws, &ao, &to, buf + beg2, end - beg2, &sam, &sam_bytes, &n_reads);
-                    const bool nl = add_nl && end == n;
-                    return salt_gpu_align_se_text_dev(ws, &ao, &to, dev_base + beg2, end - beg2 - (nl ? 1 : 0), nl ? 1 : 0, &sam, &sam_bytes, &n_reads);
-                };
-                int grc = end > beg2 ? align() : 0;
-                if (grc == SALT_E_CAPACITY && ws_reads < worst_reads) {                         // shorter records than the file's head promised
-                    if (trace) fprintf(stderr, "[salt] worker %d: chunk %llu holds more than %u reads, workspace re-created for %u\n", wk, (unsigned long long)k, ws_reads, worst_reads);
-                    salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = worst_reads;
-                    grc = salt_gpu_ws_create(gix[(size_t)(wk / n_workers_per_gpu)], ws_reads, (uint64_t)ws_reads * 160, &ws);
-                    if (!grc && g_bgzf.device) grc = salt_gpu_ws_set_sam_bgzf(ws, 1);
-                    if (!grc && g_bam.device) grc = salt_gpu_ws_set_sam_bam(ws, 1);
-                    if (!grc && g_polish) grc = salt_gpu_ws_set_polish(ws, g_polish);
-                    if (!grc && on_dev) grc = salt_gpu_ws_inflate_bgzf(ws, buf0, zc.back(), (uint32_t)(zc.size() - 1), zc.data(), zu.data());      // the new workspace's text
-                    if (!grc) grc = align();
-                }
-                if (grc == SALT_E_INVAL && g_bam.device && strncmp(salt_gpu_last_error(), "BAM:", 4) == 0) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
-                if (grc == SALT_E_INVAL) {
-                    // not strict 4-line FASTQ in this chunk: when the blocks before it are out, the host parser continues from its first record
-                    const std::string why = salt_gpu_last_error();
-                    std::unique_lock<std::mutex> lk(R.mu);
-                    R.cv.wait(lk, [&] { return R.failed || R.fallback || R.written == k; });
-                    if (!R.failed && !R.fallback) {
-                        R.fb_off = rd_lo + beg2; R.fallback = true;
-                        fprintf(stderr, "[salt] %s: the host parser takes over at byte %llu of %s\n", why.c_str(), (unsigned long long)R.fb_off, fn_reads);
-                    }
-                    lk.unlock(); R.cv.notify_all();
-                    break;
-                }
-                if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
-                t_gpu = t_gpu + (now() - tg0);
-                if (n_calls++ == 0) t_first = now() - tg0; else t_rest += now() - tg0;
-                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
-                // block k is written when block k - 1 has been
-                {
-                    std::unique_lock<std::mutex> lk(R.mu);
-                    R.cv.wait(lk, [&] { return R.failed || R.fallback || R.written == k; });
-                    if (R.failed || R.written != k) break;
-                }
-                double tw0 = now();
-                bool ok = true;
-                for (uint64_t w = 0; w < sam_bytes && ok; ) {
-                    ssize_t r = write(1, sam + w, sam_bytes - w);
-                    if (r <= 0) ok = false; else w += (uint64_t)r;
-                }
-                t_write = t_write + (now() - tw0);
-                { const double tn = now(); double cur = t_last.load(); while (tn > cur && !t_last.compare_exchange_weak(cur, tn)) {} }
-                if (!ok) { fprintf(stderr, "[salt] write error on the SAM stream\n"); set_failed(); break; }
-                {
-                    std::lock_guard<std::mutex> lk(R.mu);
-                    R.written = k + 1; R.reads_done += n_reads;
-                    fprintf(stderr, "%ld reads have been aligned!\n", R.reads_done);
-                }
-                R.cv.notify_all();
-                buf = buf0;
-            }
-            if (trace) fprintf(stderr, "[salt] worker %d: started %.3f s after the clock, setup %.3f s, first device call %.3f s, %d later calls %.4f s each, done at %.3f s\n", wk,
-                               tw_start - t0, t_setup, t_first, n_calls - 1, n_calls > 1 ? t_rest / (n_calls - 1) : 0.0, now() - t0);
-            salt_gpu_ws_destroy(ws);
-        });
+    for (int wk = 0; wk < P.n_workers; ++wk) workers.emplace_back([&R, &S, wk]() { SeWorker(R, S, wk).run(); });
     for (auto &w : workers) w.join();
-    close(R.fd);
-    if (!R.failed && R.fallback) { *resume_off = R.fb_off; return 2; }
-    const double dt = t_last.load() - t0;                   // first chunk claimed .. last SAM byte written (releasing the workspaces is not alignment time)
+    close(S.fd);
+    if (!R.failed && R.fallback) { *resume_off = R.resume; return 2; }
+    const double dt = R.t_last.load() - t0;                 // first chunk claimed .. last SAM byte written (releasing the workspaces is not alignment time)
     fprintf(stderr, "[alnse_core]: total %lf sec escaped\n", dt);
     fprintf(stderr, "[salt] text path: %d worker(s), chunk %llu MiB, blocks written in turn; seconds summed over workers: read %.3f device call %.3f write %.3f "
-                    "(page-locked buffers: %.3f s, while the index was loading)\n", n_workers, (unsigned long long)(R.chunk >> 20), t_read.load(), t_gpu.load(), t_write.load(), P.alloc_s);
-    fprintf(stderr, "[salt] %ld reads, %.3f Mreads/s end to end (FASTQ -> SAM, %d GPU(s))\n", R.reads_done, dt > 0 ? R.reads_done / dt / 1e6 : 0.0, n_gpus);
+                    "(page-locked buffers: %.3f s, while the index was loading)\n", P.n_workers, (unsigned long long)(S.chunk >> 20), R.t_read.load(), R.t_gpu.load(), R.t_write.load(), P.alloc_s);
+    fprintf(stderr, "[salt] %ld reads, %.3f Mreads/s end to end (FASTQ -> SAM, %d GPU(s))\n", R.reads_done, dt > 0 ? R.reads_done / dt / 1e6 : 0.0, (int)gix.size());
     return R.failed ? 1 : 0;
 }
 
@@ -983,8 +1028,7 @@ static int run_se_text(const char *fn_reads, salt_index_t *ix, const std::vector
 // (8 bytes per step) and publishes the byte offset of every pairs_per_chunk-th record; a worker takes chunk k of both files as soon
 // as both offsets are there, calls salt_gpu_align_pe_text and writes its block in turn.
 // ---------------------------------------------------------------------------------------------
-struct PeScan {
-    std::mutex mu; std::condition_variable cv;
+struct PeScan {                                             // guarded by the run's mutex, announced on its condition variable
     std::vector<uint64_t> off[2];                           // off[f][k] = start of chunk k in file f; the last entry of a finished file = its size
     bool done[2] = { false, false }; uint64_t records[2] = { 0, 0 };
     bool bad = false;
@@ -1003,15 +1047,15 @@ static inline uint64_t count_nl8(uint64_t w)               // newlines among the
 // it are counted (a running sum kept under the scan's mutex), finds the chunk starts that fall inside its segment in the bytes it still
 // holds, and publishes them after the segment before it has published its own.
 static const int PE_SCAN_THREADS = 4;
-static void pe_scan_file(const char *fn, int f, uint64_t pairs_per_chunk, PeScan &S, std::atomic<bool> &failed)
+static void pe_scan_file(const char *fn, int f, uint64_t pairs_per_chunk, PeScan &S, TextRun &R)
 {
     const int fd = open(fn, O_RDONLY);
     const uint64_t lines_per_chunk = 4 * pairs_per_chunk;
-    if (fd < 0) { { std::lock_guard<std::mutex> lk(S.mu); S.bad = true; S.done[f] = true; } S.cv.notify_all(); return; }
+    if (fd < 0) { { std::lock_guard<std::mutex> lk(R.mu); S.bad = true; S.done[f] = true; } R.cv.notify_all(); return; }
     struct stat st;
     const uint64_t size = fstat(fd, &st) == 0 ? (uint64_t)st.st_size : 0;
-    { std::lock_guard<std::mutex> lk(S.mu); S.off[f].push_back(0); }
-    S.cv.notify_all();
+    { std::lock_guard<std::mutex> lk(R.mu); S.off[f].push_back(0); }
+    R.cv.notify_all();
     uint64_t SEG = 32ull << 20;
     if (const char *e = getenv("SALT_PE_SCAN_SEG_BYTES")) { const long long v = atoll(e); if (v >= 64) SEG = (uint64_t)v; }      // tests: many segments in a small file
     const uint64_t n_seg = (size + SEG - 1) / SEG;
@@ -1026,10 +1070,9 @@ static void pe_scan_file(const char *fn, int f, uint64_t pairs_per_chunk, PeScan
         std::vector<char> buf((size_t)SEG);
         for (;;) {
             const uint64_t sg = next_seg.fetch_add(1);
-            if (sg >= n_seg || failed) break;
+            if (sg >= n_seg || R.failed) break;
             const uint64_t lo = sg * SEG, want = std::min<uint64_t>(SEG, size - lo);
-            uint64_t got = 0;
-            while (got < want) { const ssize_t r = pread(fd, buf.data() + got, (size_t)(want - got), (off_t)(lo + got)); if (r <= 0) break; got += (uint64_t)r; }
+            const uint64_t got = pread_full(fd, buf.data(), want, lo);
             if (got != want) short_read = true;               // (the file shrank under us: the workers' own reads will fail on it)
             uint64_t c = 0; size_t j = 0;
             for (; j + 8 <= (size_t)got; j += 8) { uint64_t w; memcpy(&w, buf.data() + j, 8); c += count_nl8(w); }
@@ -1040,7 +1083,7 @@ static void pe_scan_file(const char *fn, int f, uint64_t pairs_per_chunk, PeScan
                 cnt[(size_t)sg] = (int64_t)c;
                 while (known < n_seg && cnt[(size_t)known] >= 0) { before[(size_t)known + 1] = before[(size_t)known] + (uint64_t)cnt[(size_t)known]; ++known; }
                 cv.notify_all();
-                while (known <= sg && !failed) cv.wait_for(lk, std::chrono::milliseconds(50));      // (a failed run notifies nobody here)
+                while (known <= sg && !R.failed) cv.wait_for(lk, std::chrono::milliseconds(50));      // (a failed run notifies nobody here)
                 if (known <= sg) break;
                 l0 = before[(size_t)sg];
                 if (sg + 1 == n_seg && got) last_byte = buf[(size_t)got - 1];
@@ -1060,11 +1103,11 @@ static void pe_scan_file(const char *fn, int f, uint64_t pairs_per_chunk, PeScan
             }
             {
                 std::unique_lock<std::mutex> lk(mu);
-                while (published != sg && !failed) cv.wait_for(lk, std::chrono::milliseconds(50));
+                while (published != sg && !R.failed) cv.wait_for(lk, std::chrono::milliseconds(50));
                 if (published != sg) break;
                 if (!mine.empty()) {
-                    { std::lock_guard<std::mutex> lk2(S.mu); for (uint64_t o : mine) if (o < size) S.off[f].push_back(o); }      // (a start at the very end is the file's end, added below)
-                    S.cv.notify_all();
+                    { std::lock_guard<std::mutex> lk2(R.mu); for (uint64_t o : mine) if (o < size) S.off[f].push_back(o); }      // (a start at the very end is the file's end, added below)
+                    R.cv.notify_all();
                 }
                 published = sg + 1;
                 cv.notify_all();
@@ -1079,66 +1122,42 @@ static void pe_scan_file(const char *fn, int f, uint64_t pairs_per_chunk, PeScan
     uint64_t lines = known == n_seg ? before[(size_t)n_seg] : 0;
     if (size && last_byte != '\n') ++lines;                   // a last line without its newline
     {
-        std::lock_guard<std::mutex> lk(S.mu);
+        std::lock_guard<std::mutex> lk(R.mu);
         if (S.off[f].back() != size) S.off[f].push_back(size);
         S.records[f] = lines / 4; S.done[f] = true;
-        if (lines % 4 || short_read || (failed && known != n_seg)) S.bad = true;
+        if (lines % 4 || short_read || (R.failed && known != n_seg)) S.bad = true;
     }
-    S.cv.notify_all();
+    R.cv.notify_all();
 }
 
 // returns 0 = done, 1 = failed, 2 = the host pipeline has to take over at resume_off[0 / 1] of the two files (everything before is written):
 // a chunk the device parser refused, a file whose line count is not a multiple of four (a trailing blank line is fine for kseq.h), or files
 // with different numbers of chunks -- the host parser reads what the reference reads and reports what it cannot
-static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, int n_gpus, TextPlan &P,
+static int run_pe_text(const char *fn1, const char *fn2, const std::vector<salt_gpu_index_t *> &gix, const Contigs &contigs, TextPlan &P,
                        const salt_aln_opt_t &ao, const salt_sam_opt_t &so, const salt_pe_opt_t &po, double t0, uint64_t resume_off[2])
 {
     const int fd[2] = { open(fn1, O_RDONLY), open(fn2, O_RDONLY) };
     if (fd[0] < 0 || fd[1] < 0) { fprintf(stderr, "[query_open]: file %s open fail!\n", fd[0] < 0 ? fn1 : fn2); return 1; }
-    fflush(stdout);
-    {
-        const int n = salt_index_n_seqs(ix);
-        std::vector<int64_t> off((size_t)n); std::vector<const char *> nm((size_t)n);
-        for (int i = 0; i < n; ++i) salt_index_seq(ix, i, &off[(size_t)i], nullptr, &nm[(size_t)i]);
-        for (int g = 0; g < n_gpus; ++g)
-            if (salt_gpu_index_set_contigs(gix[(size_t)g], n, off.data(), nm.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    }
-    if (P.alloc.joinable()) P.alloc.join();
-    if (!P.alloc_ok) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
+    if (!text_begin(gix, contigs, P)) return 1;
     const salt_text_opt_t to = { so.print_xa_cigar, so.print_nm_md, so.rg_id };
-    PeScan S;
-    std::atomic<bool> failed{ false }, fallback{ false };
-    std::mutex wmu; std::condition_variable wcv; uint64_t written = 0, fb_chunk = 0; long pairs_done = 0;
-    std::atomic<uint64_t> next_chunk{ 0 };
-    std::atomic<double> t_read{ 0 }, t_gpu{ 0 }, t_write{ 0 }, t_last{ t0 };
-    auto set_failed = [&]() { failed = true; { std::lock_guard<std::mutex> lk(wmu); } wcv.notify_all(); { std::lock_guard<std::mutex> lk(S.mu); } S.cv.notify_all(); };
-    // chunk k cannot go through the device parser: once the blocks before it are out, everyone stops and the host pipeline continues there
+    PeScan S; TextRun R(t0);
     auto fall_back = [&](uint64_t k, const std::string &why) {
-        {
-            std::unique_lock<std::mutex> lk(wmu);
-            wcv.wait(lk, [&] { return failed.load() || fallback.load() || written == k; });
-            if (!failed && !fallback) { fb_chunk = k; fallback = true; fprintf(stderr, "[salt] %s: the host parser takes over at pair chunk %llu\n", why.c_str(), (unsigned long long)k); }
-        }
-        wcv.notify_all(); { std::lock_guard<std::mutex> lk(S.mu); } S.cv.notify_all();
+        if (R.claim_fallback(k)) { R.resume = k; fprintf(stderr, "[salt] %s: the host parser takes over at pair chunk %llu\n", why.c_str(), (unsigned long long)k); }
     };
-    std::thread scan1(pe_scan_file, fn1, 0, P.pairs_per_chunk, std::ref(S), std::ref(failed)), scan2(pe_scan_file, fn2, 1, P.pairs_per_chunk, std::ref(S), std::ref(failed));
+    std::thread scan1(pe_scan_file, fn1, 0, P.pairs_per_chunk, std::ref(S), std::ref(R)), scan2(pe_scan_file, fn2, 1, P.pairs_per_chunk, std::ref(S), std::ref(R));
     std::vector<std::thread> workers;
     for (int wk = 0; wk < P.n_workers; ++wk)
         workers.emplace_back([&, wk]() {
-            salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk];
+            salt_gpu_ws_t *ws = nullptr; char *buf = P.in_buf[(size_t)wk]; std::string zbuf;
             pin_to_device_node(wk / P.wpg);
-            std::string zbuf;
-            if (salt_gpu_ws_create(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, (uint64_t)(P.max_reads + 64) * 160, &ws) || (g_bgzf.device && salt_gpu_ws_set_sam_bgzf(ws, 1)) || (g_bam.device && salt_gpu_ws_set_sam_bam(ws, 1)) || (g_polish && salt_gpu_ws_set_polish(ws, g_polish)) ||
-                (P.head_read_len && salt_gpu_ws_reserve_text(ws, &ao, P.in_cap, P.max_reads, P.head_read_len, P.sam_cap - 64, P.sam_buf[(size_t)wk], P.sam_cap))) {
-                fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
-            }
+            if (open_text_ws(gix[(size_t)(wk / P.wpg)], P.max_reads + 64, &ws, &ao, &P, wk, P.in_cap, P.max_reads)) { R.fail_gpu(); salt_gpu_ws_destroy(ws); return; }
             for (;;) {
-                const uint64_t k = next_chunk.fetch_add(1);
+                const uint64_t k = R.next_chunk.fetch_add(1);
                 uint64_t lo[2], hi[2]; bool end = false, odd = false;
                 {   // chunk k of both files: its start and end offsets (or the news that there is no chunk k)
-                    std::unique_lock<std::mutex> lk(S.mu);
-                    S.cv.wait(lk, [&] { return failed.load() || fallback.load() || ((S.off[0].size() > k + 1 || S.done[0]) && (S.off[1].size() > k + 1 || S.done[1])); });
-                    if (failed || fallback) break;
+                    std::unique_lock<std::mutex> lk(R.mu);
+                    R.cv.wait(lk, [&] { return R.failed || R.fallback || ((S.off[0].size() > k + 1 || S.done[0]) && (S.off[1].size() > k + 1 || S.done[1])); });
+                    if (R.failed || R.fallback) break;
                     if (S.bad) odd = true;
                     else if (S.off[0].size() <= k + 1 || S.off[1].size() <= k + 1) {
                         // one file has no chunk k: fine if neither has (both finished with the same number of chunks), else the files differ
@@ -1149,94 +1168,87 @@ static int run_pe_text(const char *fn1, const char *fn2, salt_index_t *ix, const
                 if (end) break;
                 if (odd) { fall_back(k, "the read files are not two equally long runs of 4-line records"); break; }
                 const uint64_t n1 = hi[0] - lo[0], n2 = hi[1] - lo[1], b2 = (n1 + 64) & ~63ull;
-                if (b2 + n2 + 2 > P.in_cap) { fprintf(stderr, "[salt] a chunk of %llu pairs is larger than its buffer (records much longer than the file's first ones)\n", (unsigned long long)P.pairs_per_chunk); set_failed(); break; }
-                double tr0 = now();
-                bool ok = true;
-                for (int f = 0; f < 2 && ok; ++f) {
-                    char *dst = buf + (f ? b2 : 0); const uint64_t want = f ? n2 : n1; uint64_t got = 0;
-                    while (got < want) { const ssize_t r = pread(fd[f], dst + got, want - got, (off_t)(lo[f] + got)); if (r <= 0) break; got += (uint64_t)r; }
-                    ok = got == want;
-                }
-                if (!ok) { fprintf(stderr, "[salt] short read on the FASTQ files\n"); set_failed(); break; }
+                if (b2 + n2 + 2 > P.in_cap) { fprintf(stderr, "[salt] a chunk of %llu pairs is larger than its buffer (records much longer than the file's first ones)\n", (unsigned long long)P.pairs_per_chunk); R.fail(); break; }
+                const double tr0 = now();
+                if (pread_full(fd[0], buf, n1, lo[0]) != n1 || pread_full(fd[1], buf + b2, n2, lo[1]) != n2) { fprintf(stderr, "[salt] short read on the FASTQ files\n"); R.fail(); break; }
                 uint64_t m1 = n1, m2 = n2;
                 if (m1 && buf[m1 - 1] != '\n') buf[m1++] = '\n';                              // a last record without its newline
                 if (m2 && buf[b2 + m2 - 1] != '\n') buf[b2 + m2++] = '\n';
-                t_read = t_read + (now() - tr0);
+                R.t_read = R.t_read + (now() - tr0);
                 const char *sam = nullptr; uint64_t sam_bytes = 0; uint32_t n_pairs = 0;
-                double tg0 = now();
+                const double tg0 = now();
                 const int grc = salt_gpu_align_pe_text(ws, &ao, &po, &to, buf, m1, buf + b2, m2, &sam, &sam_bytes, &n_pairs);
-                if (grc == SALT_E_INVAL && g_bam.device && strncmp(salt_gpu_last_error(), "BAM:", 4) == 0) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
-                if (grc == SALT_E_INVAL) { fall_back(k, salt_gpu_last_error()); break; }
-                if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
-                t_gpu = t_gpu + (now() - tg0);
-                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
-                {
-                    std::unique_lock<std::mutex> lk(wmu);
-                    wcv.wait(lk, [&] { return failed.load() || fallback.load() || written == k; });
-                    if (failed || written != k) break;
-                }
-                double tw0 = now();
-                for (uint64_t w = 0; w < sam_bytes && ok; ) { const ssize_t r = write(1, sam + w, sam_bytes - w); if (r <= 0) ok = false; else w += (uint64_t)r; }
-                t_write = t_write + (now() - tw0);
-                { const double tn = now(); double cur = t_last.load(); while (tn > cur && !t_last.compare_exchange_weak(cur, tn)) {} }
-                if (!ok) { fprintf(stderr, "[salt] write error on the SAM stream\n"); set_failed(); break; }
-                { std::lock_guard<std::mutex> lk(wmu); written = k + 1; pairs_done += n_pairs; fprintf(stderr, "%ld reads have been aligned!\n", 2 * pairs_done); }
-                wcv.notify_all();
+                if (grc && !parser_refused(grc)) { R.fail_gpu(); break; }
+                if (grc) { fall_back(k, salt_gpu_last_error()); break; }
+                R.t_gpu = R.t_gpu + (now() - tg0);
+                if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); R.fail(); break; }
+                if (!R.wait_turn(k) || !R.write_block(k, sam, sam_bytes, 2 * (long)n_pairs)) break;
             }
             salt_gpu_ws_destroy(ws);
         });
     for (auto &w : workers) w.join();
-    failed = failed.load();
-    { std::lock_guard<std::mutex> lk(S.mu); } S.cv.notify_all();
     scan1.join(); scan2.join();
     close(fd[0]); close(fd[1]);
-    if (!failed && fallback) {
-        for (int f = 0; f < 2; ++f) resume_off[f] = S.off[f].size() > fb_chunk ? S.off[f][fb_chunk] : (S.off[f].empty() ? 0 : S.off[f].back());
+    if (!R.failed && R.fallback) {
+        for (int f = 0; f < 2; ++f) resume_off[f] = S.off[f].size() > R.resume ? S.off[f][R.resume] : (S.off[f].empty() ? 0 : S.off[f].back());
         return 2;
     }
-    if (!failed && (S.bad || S.records[0] != S.records[1])) {
+    if (!R.failed && (S.bad || S.records[0] != S.records[1])) {
         fprintf(stderr, "[salt] the two read files hold different numbers of reads (%llu / %llu) or broken records\n", (unsigned long long)S.records[0], (unsigned long long)S.records[1]);
         return 1;
     }
-    const double dt = t_last.load() - t0;
+    const long pairs_done = R.reads_done / 2;
+    const double dt = R.t_last.load() - t0;
     fprintf(stderr, "[alnpe_core]: total %lf sec escaped\n", dt);
     fprintf(stderr, "[salt] text path (paired end): %d worker(s), %llu pairs per chunk, blocks written in turn; seconds summed over workers: read %.3f device call %.3f write %.3f "
-                    "(page-locked buffers: %.3f s, while the index was loading)\n", P.n_workers, (unsigned long long)P.pairs_per_chunk, t_read.load(), t_gpu.load(), t_write.load(), P.alloc_s);
-    fprintf(stderr, "[salt] %ld pairs, %.3f M mates/s end to end (FASTQ -> SAM, %d GPU(s))\n", pairs_done, dt > 0 ? 2.0 * pairs_done / dt / 1e6 : 0.0, n_gpus);
-    return failed ? 1 : 0;
+                    "(page-locked buffers: %.3f s, while the index was loading)\n", P.n_workers, (unsigned long long)P.pairs_per_chunk, R.t_read.load(), R.t_gpu.load(), R.t_write.load(), P.alloc_s);
+    fprintf(stderr, "[salt] %ld pairs, %.3f M mates/s end to end (FASTQ -> SAM, %d GPU(s))\n", pairs_done, dt > 0 ? 2.0 * pairs_done / dt / 1e6 : 0.0, (int)gix.size());
+    return R.failed ? 1 : 0;
 }
 
-} // namespace
-
-int main(int argc, char **argv)
+// pair i of a batch and its mate batch = reads 2i, 2i + 1 of iseq / ioff
+static void interleave_mates(const Batch &b, const Batch &m, std::vector<uint8_t> &iseq, std::vector<uint32_t> &ioff)
 {
+    const size_t n = (size_t)b.n();
+    ioff.assign(2 * n + 1, 0);
+    iseq.resize(b.seqs.size() + m.seqs.size());
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t l0 = b.offs[i + 1] - b.offs[i], l1 = m.offs[i + 1] - m.offs[i];
+        memcpy(iseq.data() + ioff[2 * i], b.seqs.data() + b.offs[i], l0); ioff[2 * i + 1] = ioff[2 * i] + l0;
+        memcpy(iseq.data() + ioff[2 * i + 1], m.seqs.data() + m.offs[i], l1); ioff[2 * i + 2] = ioff[2 * i + 1] + l1;
+    }
+}
+struct Opts {
     int n_threads = 1, n_gpus = 1, overlap = -1, pe = 0;
-    salt_aln_opt_t ao; memset(&ao, 0, sizeof ao);
-    ao.max_seed = 50; ao.max_locate = 1000; ao.max_hits = 5;             // aln.c:46-47, aln.h:133
-    salt_sam_opt_t so; memset(&so, 0, sizeof so);
+    salt_aln_opt_t ao{}; salt_sam_opt_t so{};
     salt_pe_opt_t po = { 250, 550 };                                       // aln.c:43-44
-    std::string cmd;
-    for (int i = 0; i < argc; ++i) { if (i) cmd += " "; cmd += argv[i]; }
+    std::string cmd; const char *prefix = nullptr, *fn_reads = nullptr, *fn_mates = nullptr;
+};
+
+// the command line into o (and g_bgzf, g_bam, g_polish); returns -1 to go on, else the exit code
+static int parse_options(int argc, char **argv, Opts &o)
+{
+    o.ao.max_seed = 50; o.ao.max_locate = 1000; o.ao.max_hits = 5;       // aln.c:46-47, aln.h:133
+    for (int i = 0; i < argc; ++i) { if (i) o.cmd += " "; o.cmd += argv[i]; }
     static const struct option lo[] = {
         { "threads", 1, 0, 't' }, { "num", 1, 0, 'n' }, { "help", 0, 0, 'h' }, { "pe", 0, 0, 'p' }, { "min_tlen", 1, 0, 'a' },
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
         { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 }, { 0, 0, 0, 0 } };
-    int c;
-    while ((c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0) {
+    for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
-        case 't': n_threads = atoi(optarg); break;
-        case 'g': so.rg_id = optarg; break;
-        case 's': ao.max_seed = (uint32_t)atoi(optarg); break;
-        case 'm': ao.max_locate = (uint32_t)atoi(optarg); break;
-        case 'c': so.print_xa_cigar = 1; break;
-        case 'd': so.print_nm_md = 1; break;
-        case 'v': ao.seed_only_ref = 1; break;
-        case 'r': overlap = atoi(optarg); break;
-        case 'p': pe = 1; break;
-        case 'a': po.min_tlen = (uint32_t)atoi(optarg); break;
-        case 'b': po.max_tlen = (uint32_t)atoi(optarg); break;
-        case 1000: n_gpus = atoi(optarg); break;
+        case 't': o.n_threads = atoi(optarg); break;
+        case 'g': o.so.rg_id = optarg; break;
+        case 's': o.ao.max_seed = (uint32_t)atoi(optarg); break;
+        case 'm': o.ao.max_locate = (uint32_t)atoi(optarg); break;
+        case 'c': o.so.print_xa_cigar = 1; break;
+        case 'd': o.so.print_nm_md = 1; break;
+        case 'v': o.ao.seed_only_ref = 1; break;
+        case 'r': o.overlap = atoi(optarg); break;
+        case 'p': o.pe = 1; break;
+        case 'a': o.po.min_tlen = (uint32_t)atoi(optarg); break;
+        case 'b': o.po.max_tlen = (uint32_t)atoi(optarg); break;
+        case 1000: o.n_gpus = atoi(optarg); break;
         case 1001: g_bgzf.on = true; break;
         case 1002: g_bam.on = true; g_bgzf.on = true; break;
         case 1003:
@@ -1250,132 +1262,78 @@ int main(int argc, char **argv)
         }
     }
     if (g_polish && g_bam.on) { fprintf(stderr, "[opt_parse]: --polish and --bam cannot be combined: polished records are written as text only (--polish --bgzf compresses them)\n"); return 1; }
-    if (optind + 2 + pe > argc) { fprintf(stderr, "[opt_parse]: index prefix and read file can't be omited!\n"); return 1; }
-    if (n_threads < 1) n_threads = 1;
-    if (n_gpus < 1) n_gpus = 1;
-    const char *prefix = argv[optind], *fn_reads = argv[optind + 1], *fn_mates = pe ? argv[optind + 2] : nullptr;
+    if (optind + 2 + o.pe > argc) { fprintf(stderr, "[opt_parse]: index prefix and read file can't be omited!\n"); return 1; }
+    if (o.n_threads < 1) o.n_threads = 1;
+    if (o.n_gpus < 1) o.n_gpus = 1;
+    o.prefix = argv[optind]; o.fn_reads = argv[optind + 1]; o.fn_mates = o.pe ? argv[optind + 2] : nullptr;
     // the device compressor, unless this libsalt_gpu has none or SALT_BGZF_HOST=1 asks for zlib (A/B runs, tests)
     g_bgzf.device = g_bgzf.on && salt_gpu_ws_set_sam_bgzf != nullptr && !(getenv("SALT_BGZF_HOST") && atoi(getenv("SALT_BGZF_HOST")));
     // the device's record kernels, unless this libsalt_gpu has none or SALT_BAM_HOST=1 asks for the host encoder; records made on the host
     // out of the device's SAM text are deflated there too
     g_bam.device = g_bam.on && salt_gpu_ws_set_sam_bam != nullptr && !(getenv("SALT_BAM_HOST") && atoi(getenv("SALT_BAM_HOST")));
     if (g_bam.on && !g_bam.device) g_bgzf.device = false;
+    return -1;
+}
 
-    // Single end + a plain (not gzipped) strict 4-line FASTQ in a regular file: the text path -- parse, align and format on the device
-    // (run_se_text).  Everything else (paired end, gzip, pipes, multi-line records) goes through the host pipeline below.
-    // SALT_HOST_PIPELINE=1 forces the latter.  Decided before the index is loaded: the text path's page-locked buffers are allocated
-    // by a thread of their own meanwhile.
-    TextPlan plan; bool text_path = false;
-    if (!(getenv("SALT_HOST_PIPELINE") && atoi(getenv("SALT_HOST_PIPELINE")))) {
-        auto plain4 = [](const char *fn) {
-            struct stat sb; unsigned char magic[2] = { 0, 0 };
-            bool plain = stat(fn, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0;
-            if (plain) { FILE *f = fopen(fn, "rb"); plain = f && fread(magic, 1, 2, f) == 2 && !(magic[0] == 0x1f && magic[1] == 0x8b); if (f) fclose(f); }
-            return plain && sniff_four_line(fn);
-        };
-        text_path = plain4(fn_reads) && (!pe || plain4(fn_mates));
-        // single end, blocked gzip (BGZF) whose text starts as strict 4-line FASTQ: the text path over the uncompressed byte range
-        if (!text_path && !pe && bgzf_index(fn_reads, plan.bgzf) && sniff_four_line(fn_reads)) text_path = true;
-        else if (!text_path) plan.bgzf = Bgzf();
-        if (text_path) text_plan(plan, fn_reads, n_gpus, n_threads, pe != 0);
+// aln_samhead (sam.c:56-84)
+static bool print_header(const salt_index_t *ix, const Opts &o)
+{
+    if (g_polish) return true;                              // `polish` prints no header
+    std::vector<char> hb(16 << 20);
+    int w = salt_sam_header(ix, &o.so, hb.data(), hb.size());
+    if (w < 0) { fprintf(stderr, "[salt] SAM header too large\n"); return false; }
+    time_t tt = time(nullptr); struct tm *tmv = localtime(&tt);
+    std::vector<char> pg(o.cmd.size() + 128);
+    const int wp = snprintf(pg.data(), pg.size(), "@PG\tID:snpaln\tPN:snpaln\tCL:\"%s\"\tDS:%d-%d-%d\tVN:0.1beta\n", o.cmd.c_str(), tmv->tm_year + 1900, tmv->tm_mon + 1, tmv->tm_mday);
+    if (!g_bgzf.on) { fwrite(hb.data(), 1, (size_t)w, stdout); fwrite(pg.data(), 1, (size_t)wp, stdout); return true; }
+    std::string text(hb.data(), (size_t)w), z;
+    text.append(pg.data(), (size_t)wp);
+    if (g_bam.on) {                                          // the same text inside the BAM header, then the reference list of the same contig table
+        std::string bh(text.size() + (size_t)w + 64 + 16 * (size_t)salt_index_n_seqs(ix), '\0');
+        const int64_t wb = salt_bam_header(ix, text.data(), text.size(), reinterpret_cast<uint8_t *>(&bh[0]), bh.size());
+        if (wb < 0) { fprintf(stderr, "[salt] BAM header too large\n"); return false; }
+        bh.resize((size_t)wb);
+        text.swap(bh);
     }
-    double t0 = now();
-    fprintf(stderr, "[alnse_core]:  Reload index...\n");
-    salt_index_t *ix = salt_index_load(prefix, 0);
-    if (!ix) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return 1; }
-    ao.l_seed = salt_index_seed_len(ix);
-    g_bam.ix = ix;
-    ao.l_overlap = overlap > 0 ? overlap : ao.l_seed;                      // aln.c:223
-    std::vector<int> devs((size_t)n_gpus);
-    for (int i = 0; i < n_gpus; ++i) devs[(size_t)i] = i;
-    std::vector<salt_gpu_index_t *> gix((size_t)n_gpus, nullptr);
-    if (salt_gpu_index_attach(salt_index_host_view(ix), 0, &gix[0])) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    if (salt_gpu_index_replicate(gix[0], devs.data(), n_gpus, gix.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    if (g_polish && (!salt_gpu_ws_set_polish || !salt_gpu_polish_open || !salt_gpu_polish_close || !salt_gpu_polish_set_contigs || !salt_gpu_polish_text)) {
-        fprintf(stderr, "[salt] --polish: this libsalt_gpu has no polish stage\n"); return 1;
+    if (!bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] zlib failed on the SAM header\n"); return false; }
+    fwrite(z.data(), 1, z.size(), stdout);
+    g_bgzf.text_bytes += text.size(); g_bgzf.file_bytes += z.size();
+    return true;
+}
+
+// N3: -b 0 = infer the insert-size window from the first batch (N_SEQS / 2 pairs), the mates aligned as single-end reads
+// (salt_isize_infer; the reference prints "infer isize func haven't been implemented" here, alnpe.c:586-589)
+static bool infer_isize(Opts &o, const salt_index_t *ix, salt_gpu_index_t *gix)
+{
+    gzFile g1 = gzopen(o.fn_reads, "r"), g2 = gzopen(o.fn_mates, "r");
+    if (!g1 || !g2) { fprintf(stderr, "[query_open]: file %s open fail!\n", g1 ? o.fn_mates : o.fn_reads); return false; }
+    RawReader r1(g1, !sniff_four_line(o.fn_reads)), r2(g2, !sniff_four_line(o.fn_mates));
+    Batch b1, b2; Pool pool(o.n_threads < 16 ? o.n_threads : 16);
+    const int got = r1.take(b1.raw, N_SEQS / 2, b1.rec);
+    if (got == 0 || r2.take(b2.raw, got, b2.rec) != got) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); return false; }
+    parse_batch(b1.raw, b1, pool); parse_batch(b2.raw, b2, pool);
+    std::vector<uint8_t> iseq; std::vector<uint32_t> ioff;
+    interleave_mates(b1, b2, iseq, ioff);
+    gzclose(g1); gzclose(g2);
+    salt_gpu_ws_t *w0 = nullptr;
+    std::vector<salt_result_t> r((size_t)2 * got);
+    if (salt_gpu_ws_create(gix, (uint32_t)(2 * got), (uint64_t)iseq.size() + 64, &w0) ||
+        salt_gpu_align_se(w0, &o.ao, (uint32_t)(2 * got), iseq.data(), ioff.data(), r.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    salt_gpu_ws_destroy(w0);
+    uint32_t used = 0;
+    if (salt_isize_infer(ix, (uint32_t)got, ioff.data(), r.data(), &o.po.min_tlen, &o.po.max_tlen, &used)) {
+        fprintf(stderr, "[alnpe_core]: cannot infer the insert size: %u usable pairs in the first batch (25 needed); give -a / -b\n", used);
+        return false;
     }
-    if (pe || g_polish) {                                 // the singleton rescue aligns against the 2-bit genome (alnpe.c:327-393); --polish re-scores against it
-        uint64_t l_pac = 0; const uint8_t *pac = salt_index_pac(ix, &l_pac);
-        for (int i = 0; i < n_gpus; ++i)
-            if (salt_gpu_index_set_pac(gix[(size_t)i], pac, l_pac)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-    }
-    auto print_header = [&]() -> bool {                  // aln_samhead (sam.c:56-84)
-        if (g_polish) return true;                          // `polish` prints no header
-        std::vector<char> hb(16 << 20);
-        int w = salt_sam_header(ix, &so, hb.data(), hb.size());
-        if (w < 0) { fprintf(stderr, "[salt] SAM header too large\n"); return false; }
-        time_t tt = time(nullptr); struct tm *tmv = localtime(&tt);
-        std::vector<char> pg(cmd.size() + 128);
-        const int wp = snprintf(pg.data(), pg.size(), "@PG\tID:snpaln\tPN:snpaln\tCL:\"%s\"\tDS:%d-%d-%d\tVN:0.1beta\n", cmd.c_str(), tmv->tm_year + 1900, tmv->tm_mon + 1, tmv->tm_mday);
-        if (!g_bgzf.on) { fwrite(hb.data(), 1, (size_t)w, stdout); fwrite(pg.data(), 1, (size_t)wp, stdout); return true; }
-        std::string text(hb.data(), (size_t)w), z;
-        text.append(pg.data(), (size_t)wp);
-        if (g_bam.on) {                                      // the same text inside the BAM header, then the reference list of the same contig table
-            std::string bh(text.size() + (size_t)w + 64 + 16 * (size_t)salt_index_n_seqs(ix), '\0');
-            const int64_t wb = salt_bam_header(ix, text.data(), text.size(), reinterpret_cast<uint8_t *>(&bh[0]), bh.size());
-            if (wb < 0) { fprintf(stderr, "[salt] BAM header too large\n"); return false; }
-            bh.resize((size_t)wb);
-            text.swap(bh);
-        }
-        if (!bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] zlib failed on the SAM header\n"); return false; }
-        fwrite(z.data(), 1, z.size(), stdout);
-        g_bgzf.text_bytes += text.size(); g_bgzf.file_bytes += z.size();
-        return true;
-    };
-    bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
-    if (text_path && !pe) {
-        fprintf(stderr, "%lf sec escaped.\n", now() - t0);
-        if (!print_header()) return 1;
-        const int rc = run_se_text(fn_reads, ix, gix, n_gpus, plan, ao, so, now(), &resume[0]);
-        if (rc != 2) {
-            if (rc == 0) bgzf_finish();
-            for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]);
-            salt_index_free(ix);
-            return rc;
-        }
-        header_out = true;
-    }
-    if (pe && po.max_tlen == 0) {
-        // N3: -b 0 = infer the insert-size window from the first batch (N_SEQS / 2 pairs), the mates aligned as single-end reads
-        // (salt_isize_infer; the reference prints "infer isize func haven't been implemented" here, alnpe.c:586-589)
-        gzFile g1 = gzopen(fn_reads, "r"), g2 = gzopen(fn_mates, "r");
-        if (!g1 || !g2) { fprintf(stderr, "[query_open]: file %s open fail!\n", g1 ? fn_mates : fn_reads); return 1; }
-        RawReader r1(g1, !sniff_four_line(fn_reads)), r2(g2, !sniff_four_line(fn_mates));
-        Batch b1, b2; Pool pool(n_threads < 16 ? n_threads : 16);
-        const int got = r1.take(b1.raw, N_SEQS / 2, b1.rec);
-        if (got == 0 || r2.take(b2.raw, got, b2.rec) != got) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); return 1; }
-        parse_batch(b1.raw, b1, pool); parse_batch(b2.raw, b2, pool);
-        std::vector<uint8_t> iseq(b1.seqs.size() + b2.seqs.size()); std::vector<uint32_t> ioff(2 * (size_t)got + 1, 0);
-        for (int i = 0; i < got; ++i) {
-            const uint32_t l0 = b1.offs[(size_t)i + 1] - b1.offs[(size_t)i], l1 = b2.offs[(size_t)i + 1] - b2.offs[(size_t)i];
-            memcpy(iseq.data() + ioff[2 * (size_t)i], b1.seqs.data() + b1.offs[(size_t)i], l0); ioff[2 * (size_t)i + 1] = ioff[2 * (size_t)i] + l0;
-            memcpy(iseq.data() + ioff[2 * (size_t)i + 1], b2.seqs.data() + b2.offs[(size_t)i], l1); ioff[2 * (size_t)i + 2] = ioff[2 * (size_t)i + 1] + l1;
-        }
-        gzclose(g1); gzclose(g2);
-        salt_gpu_ws_t *w0 = nullptr;
-        std::vector<salt_result_t> r((size_t)2 * got);
-        if (salt_gpu_ws_create(gix[0], (uint32_t)(2 * got), (uint64_t)iseq.size() + 64, &w0) ||
-            salt_gpu_align_se(w0, &ao, (uint32_t)(2 * got), iseq.data(), ioff.data(), r.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
-        salt_gpu_ws_destroy(w0);
-        uint32_t used = 0;
-        if (salt_isize_infer(ix, (uint32_t)got, ioff.data(), r.data(), &po.min_tlen, &po.max_tlen, &used)) {
-            fprintf(stderr, "[alnpe_core]: cannot infer the insert size: %u usable pairs in the first batch (25 needed); give -a / -b\n", used);
-            return 1;
-        }
-        fprintf(stderr, "[alnpe_core]: insert size window [%u, %u] inferred from %u pairs\n", po.min_tlen, po.max_tlen, used);
-    }
-    if (text_path && pe) {
-        fprintf(stderr, "%lf sec escaped.\n", now() - t0);
-        if (!print_header()) return 1;
-        const int rc = run_pe_text(fn_reads, fn_mates, ix, gix, n_gpus, plan, ao, so, po, now(), resume);
-        if (rc != 2) {
-            if (rc == 0) bgzf_finish();
-            for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]);
-            salt_index_free(ix);
-            return rc;
-        }
-        header_out = true;
-    }
+    fprintf(stderr, "[alnpe_core]: insert size window [%u, %u] inferred from %u pairs\n", o.po.min_tlen, o.po.max_tlen, used);
+    return true;
+}
+
+// The host pipeline: reader -> per-GPU workers -> ordered writer (the calling thread), over the whole input or -- header_out -- over what the
+// text path left from resume[0 / 1] on, its header and blocks being out already.  t0: the start of the program's clock.  Returns the exit code.
+static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &contigs, bool header_out, const uint64_t resume[2], double t0)
+{
+    const int n_gpus = o.n_gpus, n_threads = o.n_threads; const bool pe = o.pe != 0;
     // workers per GPU: each takes a batch through parse -> device -> format, so several batches overlap on the host
     const int WPG = n_threads / n_gpus >= 32 ? 4 : n_threads / n_gpus >= 12 ? 3 : 2;
     std::vector<salt_gpu_ws_t *> ws((size_t)n_gpus * WPG, nullptr);
@@ -1383,37 +1341,32 @@ int main(int argc, char **argv)
         if (salt_gpu_ws_create(gix[(size_t)(i / WPG)], N_SEQS, (uint64_t)N_SEQS * SALT_MAX_READ_LEN, &ws[(size_t)i])) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
     fprintf(stderr, "%lf sec escaped.\n", now() - t0);
     t0 = now();
-
-    gzFile fp = gzopen(fn_reads, "r");
-    if (!fp) { fprintf(stderr, "[query_open]: file %s open fail!\n", fn_reads); return 1; }
+    gzFile fp = gzopen(o.fn_reads, "r");
+    if (!fp) { fprintf(stderr, "[query_open]: file %s open fail!\n", o.fn_reads); return 1; }
     gzbuffer(fp, 1 << 20);
     gzFile fp2 = nullptr;
     if (pe) {
-        fp2 = gzopen(fn_mates, "r");
-        if (!fp2) { fprintf(stderr, "[query_open]: file %s open fail!\n", fn_mates); return 1; }
+        fp2 = gzopen(o.fn_mates, "r");
+        if (!fp2) { fprintf(stderr, "[query_open]: file %s open fail!\n", o.fn_mates); return 1; }
         gzbuffer(fp2, 1 << 20);
     }
     if (header_out) {                                     // the text path wrote everything up to these offsets (plain files: a seek)
         fflush(stdout);
         if (gzseek(fp, (z_off_t)resume[0], SEEK_SET) < 0 || (pe && gzseek(fp2, (z_off_t)resume[1], SEEK_SET) < 0)) { fprintf(stderr, "[salt] cannot seek in the read files\n"); return 1; }
-    } else if (!print_header()) return 1;
-
-    // ---- pipeline: reader -> per-GPU workers -> ordered writer ----
+    } else if (!print_header(ix, o)) return 1;
     std::mutex mu; std::condition_variable cv;
     std::deque<std::unique_ptr<Batch>> todo;          // read, not yet aligned
     std::deque<std::unique_ptr<Batch>> done;          // aligned + formatted, any order
     bool eof = false; long n_tot = 0; std::atomic<bool> failed{ false };
-    const size_t max_inflight = (size_t)n_gpus * WPG * 2 + 1;
-    size_t inflight = 0;
+    const size_t max_inflight = (size_t)n_gpus * WPG * 2 + 1; size_t inflight = 0;
     // the flag is stored with `mu` held: a waiter that has evaluated its predicate but not yet blocked cannot miss the notify
     auto set_failed = [&]() { { std::lock_guard<std::mutex> lk(mu); failed = true; } cv.notify_all(); };
-
     std::atomic<double> t_parse{ 0 }, t_gpu{ 0 }, t_fmt{ 0 };
     double t_write = 0, t_read = 0;
     std::thread reader([&]() {
         // (after a hand-over from the text path the head of the file says nothing about what follows: kseq's general reader)
-        RawReader rr(fp, header_out || !sniff_four_line(fn_reads));
-        std::unique_ptr<RawReader> rr2(pe ? new RawReader(fp2, header_out || !sniff_four_line(fn_mates)) : nullptr);
+        RawReader rr(fp, header_out || !sniff_four_line(o.fn_reads));
+        std::unique_ptr<RawReader> rr2(pe ? new RawReader(fp2, header_out || !sniff_four_line(o.fn_mates)) : nullptr);
         const int per_batch = pe ? N_SEQS / 2 : N_SEQS;    // pairs per batch: N_SEQS mates (query_read_multiPairedSeqs, query.c:252-268)
         long seq_no = 0;
         for (;;) {
@@ -1447,11 +1400,8 @@ int main(int argc, char **argv)
             std::unique_ptr<salt_gpu_polish_t, void (*)(salt_gpu_polish_t *)> gp(nullptr, salt_gpu_polish_close ? salt_gpu_polish_close : +[](salt_gpu_polish_t *) {});
             if (g_polish) {
                 uint64_t l_pac = 0; const uint8_t *pac = salt_index_pac(ix, &l_pac);
-                const int n = salt_index_n_seqs(ix);
-                std::vector<int64_t> off((size_t)n); std::vector<const char *> nm((size_t)n);
-                for (int i = 0; i < n; ++i) salt_index_seq(ix, i, &off[(size_t)i], nullptr, &nm[(size_t)i]);
                 salt_gpu_polish_t *h = nullptr;
-                if (salt_gpu_polish_open(g / WPG, pac, l_pac, &h) || (gp.reset(h), salt_gpu_polish_set_contigs(h, n, off.data(), nm.data()))) {
+                if (salt_gpu_polish_open(g / WPG, pac, l_pac, &h) || (gp.reset(h), salt_gpu_polish_set_contigs(h, contigs.n(), contigs.off.data(), contigs.nm.data()))) {
                     fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); return;
                 }
             }
@@ -1470,29 +1420,19 @@ int main(int argc, char **argv)
                     Batch &m = *b->mate;
                     parse_batch(m.raw, m, pool);
                     if (m.n() != b->n()) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); set_failed(); break; }
-                    const size_t n = (size_t)b->n();
-                    ioff.resize(2 * n + 1); ioff[0] = 0;
-                    iseq.resize(b->seqs.size() + m.seqs.size());
-                    for (size_t i = 0; i < n; ++i) {
-                        const uint32_t l0 = b->offs[i + 1] - b->offs[i], l1 = m.offs[i + 1] - m.offs[i];
-                        memcpy(iseq.data() + ioff[2 * i], b->seqs.data() + b->offs[i], l0); ioff[2 * i + 1] = ioff[2 * i] + l0;
-                        memcpy(iseq.data() + ioff[2 * i + 1], m.seqs.data() + m.offs[i], l1); ioff[2 * i + 2] = ioff[2 * i + 1] + l1;
-                    }
+                    interleave_mates(*b, m, iseq, ioff);
                 }
                 t_parse = t_parse + (now() - tp0);
                 if (b->n() == 0) { std::unique_lock<std::mutex> lk(mu); done.push_back(std::move(b)); cv.notify_all(); continue; }
                 b->res.resize((size_t)b->n() * (pe ? 2 : 1));
                 double tg0 = now();
-                int grc = pe ? salt_gpu_align_pe(ws[(size_t)g], &ao, &po, (uint32_t)b->n(), iseq.data(), ioff.data(), b->res.data())
-                             : salt_gpu_align_se(ws[(size_t)g], &ao, (uint32_t)b->n(), b->seqs.data(), b->offs.data(), b->res.data());
+                int grc = pe ? salt_gpu_align_pe(ws[(size_t)g], &o.ao, &o.po, (uint32_t)b->n(), iseq.data(), ioff.data(), b->res.data())
+                             : salt_gpu_align_se(ws[(size_t)g], &o.ao, (uint32_t)b->n(), b->seqs.data(), b->offs.data(), b->res.data());
                 t_gpu = t_gpu + (now() - tg0);
-                if (grc) {
-                    fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
-                    set_failed(); break;
-                }
+                if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
-                if (pe) format_batch_pe(ix, &so, &po, *b, pool); else format_batch(ix, &so, *b, pool);
-                if (g_polish && !polish_batch(gp.get(), pe != 0, *b)) { set_failed(); break; }
+                if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
+                if (g_polish && !polish_batch(gp.get(), pe, *b)) { set_failed(); break; }
                 if (g_bgzf.on && !bgzf_batch(b->sam, pool)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
                 t_fmt = t_fmt + (now() - tf0);
                 std::unique_lock<std::mutex> lk(mu);
@@ -1532,7 +1472,65 @@ int main(int argc, char **argv)
     gzclose(fp);
     if (fp2) gzclose(fp2);
     for (int i = 0; i < n_gpus * WPG; ++i) salt_gpu_ws_destroy(ws[(size_t)i]);
-    for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]);
-    salt_index_free(ix);
     return failed ? 1 : 0;
+}
+
+} // namespace
+
+// options; choice of path (TextPlan); index load and attach; header; text path; host pipeline
+int main(int argc, char **argv)
+{
+    Opts o;
+    if (const int stop = parse_options(argc, argv, o); stop >= 0) return stop;
+    const int n_gpus = o.n_gpus; const bool pe = o.pe != 0;
+    // Single end + a plain (not gzipped) strict 4-line FASTQ in a regular file: the text path -- parse, align and format on the device
+    // (run_se_text).  Everything else (paired end, gzip, pipes, multi-line records) goes through the host pipeline below.
+    // SALT_HOST_PIPELINE=1 forces the latter.  Decided before the index is loaded: the text path's page-locked buffers are allocated
+    // by a thread of their own meanwhile.
+    TextPlan plan; bool text_path = false;
+    if (!(getenv("SALT_HOST_PIPELINE") && atoi(getenv("SALT_HOST_PIPELINE")))) {
+        auto plain4 = [](const char *fn) {
+            struct stat sb; unsigned char magic[2] = { 0, 0 };
+            bool plain = stat(fn, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0;
+            if (plain) { FILE *f = fopen(fn, "rb"); plain = f && fread(magic, 1, 2, f) == 2 && !(magic[0] == 0x1f && magic[1] == 0x8b); if (f) fclose(f); }
+            return plain && sniff_four_line(fn);
+        };
+        text_path = plain4(o.fn_reads) && (!pe || plain4(o.fn_mates));
+        // single end, blocked gzip (BGZF) whose text starts as strict 4-line FASTQ: the text path over the uncompressed byte range
+        if (!text_path && !pe && bgzf_index(o.fn_reads, plan.bgzf) && sniff_four_line(o.fn_reads)) text_path = true;
+        else if (!text_path) plan.bgzf = Bgzf();
+        if (text_path) text_plan(plan, o.fn_reads, n_gpus, o.n_threads, pe);
+    }
+    const double t0 = now();
+    fprintf(stderr, "[alnse_core]:  Reload index...\n");
+    salt_index_t *ix = salt_index_load(o.prefix, 0);
+    if (!ix) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return 1; }
+    o.ao.l_seed = salt_index_seed_len(ix);
+    g_bam.ix = ix;
+    o.ao.l_overlap = o.overlap > 0 ? o.overlap : o.ao.l_seed;              // aln.c:223
+    std::vector<int> devs; for (int i = 0; i < n_gpus; ++i) devs.push_back(i);
+    std::vector<salt_gpu_index_t *> gix((size_t)n_gpus, nullptr);
+    if (salt_gpu_index_attach(salt_index_host_view(ix), 0, &gix[0])) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
+    if (salt_gpu_index_replicate(gix[0], devs.data(), n_gpus, gix.data())) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
+    if (g_polish && (!salt_gpu_ws_set_polish || !salt_gpu_polish_open || !salt_gpu_polish_close || !salt_gpu_polish_set_contigs || !salt_gpu_polish_text)) {
+        fprintf(stderr, "[salt] --polish: this libsalt_gpu has no polish stage\n"); return 1;
+    }
+    if (pe || g_polish) {                                 // the singleton rescue aligns against the 2-bit genome (alnpe.c:327-393); --polish re-scores against it
+        uint64_t l_pac = 0; const uint8_t *pac = salt_index_pac(ix, &l_pac);
+        for (int i = 0; i < n_gpus; ++i)
+            if (salt_gpu_index_set_pac(gix[(size_t)i], pac, l_pac)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
+    }
+    const Contigs contigs(ix);
+    auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
+    if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
+    bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
+    if (text_path) {
+        fprintf(stderr, "%lf sec escaped.\n", now() - t0);
+        if (!print_header(ix, o)) return 1;
+        const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
+                          : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc); }
+        header_out = true;
+    }
+    return leave(run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0));
 }

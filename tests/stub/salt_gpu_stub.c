@@ -10,7 +10,7 @@
 #include <string.h>
 
 struct salt_gpu_index { int device; so_index_t *ora; int owner; };
-struct salt_gpu_ws { struct salt_gpu_index *ix; char *sam; size_t cap; };
+struct salt_gpu_ws { struct salt_gpu_index *ix; char *sam; size_t cap; uint32_t max_reads; };
 static __thread char g_err[256];
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
 
@@ -39,8 +39,8 @@ int salt_gpu_index_set_pac(salt_gpu_index_t *ix, const uint8_t *pac, uint64_t l_
 int salt_gpu_index_set_contigs(salt_gpu_index_t *ix, int32_t n, const int64_t *offsets, const char *const *names) { (void)ix; (void)n; (void)offsets; (void)names; return SALT_OK; }
 int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint64_t max_bases, salt_gpu_ws_t **out)
 {
-    (void)max_reads; (void)max_bases;
-    struct salt_gpu_ws *ws = calloc(1, sizeof *ws); ws->ix = ix; *out = ws; return SALT_OK;
+    (void)max_bases;
+    struct salt_gpu_ws *ws = calloc(1, sizeof *ws); ws->ix = ix; ws->max_reads = max_reads; *out = ws; return SALT_OK;
 }
 int salt_gpu_ws_reserve_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint64_t b, uint32_t r, uint32_t l, uint64_t sb, void *hs, uint64_t hb)
 { (void)ws; (void)o; (void)b; (void)r; (void)l; (void)sb; (void)hs; (void)hb; return SALT_OK; }
@@ -122,6 +122,9 @@ int salt_gpu_align_se_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sal
     *sam = NULL; *sam_bytes = 0; *n_reads = 0;
     if (n_bytes == 0) return SALT_OK;
     if (fq[n_bytes - 1] != '\n') return fail("block must end with a newline");
+    uint64_t n_lines = 0;                                    /* like the device: a block of more records than the workspace was created for is refused whole */
+    for (const char *c = fq; (c = memchr(c, '\n', (size_t)(fq + n_bytes - c))) != NULL; ++c) ++n_lines;
+    if (n_lines / 4 > ws->max_reads) { snprintf(g_err, sizeof g_err, "stub: %llu reads in a workspace for %u", (unsigned long long)(n_lines / 4), ws->max_reads); return SALT_E_CAPACITY; }
     so_opt_t so; so_opt_default(ws->ix->ora, &so);
     so.l_overlap = o->l_overlap; so.max_seed = o->max_seed; so.max_locate = o->max_locate; so.seed_only_ref = o->seed_only_ref;
     so.print_xa_cigar = to->print_xa_cigar; so.print_nm_md = to->print_nm_md; so.rg_id = to->rg_id;

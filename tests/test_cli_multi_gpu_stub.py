@@ -159,6 +159,31 @@ def test_salt_pe_text_path_neither_hangs_nor_shifts_pairs_on_odd_files(stub_tree
         assert want.startswith(got[:len(got) - len(got) % 1])   # whatever came out is a prefix of the right answer: no shifted pairs
 
 
+def test_salt_text_path_regrows_its_workspace_when_records_get_shorter(stub_tree, tmp_path):
+    """Workspaces of the text path are sized from the file's first records (the input of test_gpu_parity's
+    test_cli_text_path_regrows_its_workspace_when_records_get_shorter: a head of 500-byte records, a body of 230-byte ones).  The stub refuses
+    a block of more reads than its workspace was created for, as the device does: the worker re-creates the workspace once, with the
+    output modes of the first, and the SAM is the host pipeline's."""
+    d, prefix = stub_tree
+    src = open(os.path.join(LAMBDA, "reads_se.fq"), "rb").read().splitlines()
+    recs = [src[i:i + 4] for i in range(0, len(src) - 3, 4)]
+    out = []
+    for rep in range(16):
+        for j, r in enumerate(recs):
+            name = b"@r%d_%d" % (rep, j) + (b"_" + b"x" * 280 if rep == 0 and j < 200 else b"")
+            out += [name, r[1], b"+", r[3]]
+    fq = tmp_path / "mixed.fq"
+    fq.write_bytes(b"\n".join(out) + b"\n")
+    assert fq.stat().st_size > 6 << 20
+    env = dict(os.environ, SALT_STUB_PREFIX=prefix, LD_LIBRARY_PATH=str(d / "lib"))
+    cmd = [str(d / "bin" / "salt"), "-d", "-c", "-t", "4", prefix, str(fq)]
+    a = subprocess.run(cmd, capture_output=True, env=dict(env, SALT_CHUNK_MB="4", SALT_TEXT_TRACE="1"), timeout=300)
+    b = subprocess.run(cmd, capture_output=True, env=dict(env, SALT_HOST_PIPELINE="1"), timeout=300)
+    assert a.returncode == 0 and b.returncode == 0, (a.stderr[-300:], b.stderr[-300:])
+    assert b"workspace re-created" in a.stderr, a.stderr[-600:]
+    assert _strip(a.stdout) == _strip(b.stdout)
+
+
 def _bgzf(data, block=65280):
     """Blocked gzip as bgzip writes it: every block a gzip member with the 'BC' extra field (its compressed size - 1), an empty block last."""
     import struct
