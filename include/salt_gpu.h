@@ -179,6 +179,30 @@ int  salt_gpu_ws_pe_overflow(salt_gpu_ws_t *ws, uint32_t *n);
  * k_pe_final, out[4] = the overflow count above; the rest is internal. */
 int  salt_gpu_ws_pe_counts(salt_gpu_ws_t *ws, uint32_t out[8]);
 
+/* ---- allele counts at the index's SNP sites (`salt --snp-counts`) --------------------------------------------------------
+ * A site is a genome position g (0-based in the concatenated coordinate of salt_result_t.pos, 0 <= g < ref_len) whose mixRef mask
+ * (ref[g >> 3] >> 4 * (g & 7)) & 15 lists two or more bases; sites are numbered in ascending g.  While counting is on, every entry point that
+ * leaves result rows (salt_gpu_align_se / _pe, the resident and the text entry points, under salt_gpu_ws_set_polish too) adds, behind the
+ * kernels that finish the rows and on the same stream, what the batch's records show at the sites: a record contributes iff it is mapped
+ * (pos != 0xFFFFFFFF), not skipped, and mapq >= min_mapq; its CIGAR is walked as the SAM / BAM writers lay it out (a paired-end row's
+ * leading soft clip seq_start, the row's M / I / D ops) from g = pos, s = 0 in SEQ as printed (reverse-complemented iff strand != 0 single
+ * end, strand == 1 paired end); every M column where g is a site and SEQ[s] is A, C, G or T adds 1 to counts[site(g)][base].  I and S
+ * advance s, D advances g, a read's N counts nowhere, alternative (XA) hits never count.  counts is uint32[n_sites][4] in the order A C G T;
+ * the sums do not depend on batch order, stream or workspace.  The table and the counts belong to the device index and are shared by all
+ * its workspaces; they lie outside the image (16 bytes per 64 genome positions + 16 per site).  With counting off no kernel is launched,
+ * and before the first enable nothing is allocated.
+ *   salt_gpu_index_snp_enable  the first enable builds the site table and zeroes the counts (SALT_E_NOMEM names the size when there is no
+ *                              room); on = 0 stops counting and keeps both; min_mapq 0 .. 255.  Call with no align call in flight.
+ *   salt_gpu_index_snp_sites   *n_sites, and when pos is given (cap >= *n_sites entries) the sites' genome positions, ascending
+ *   salt_gpu_index_snp_counts  synchronises the device; counts may be NULL (reset only); cap_words >= 4 * n_sites.  No align call in flight.
+ *   salt_gpu_ws_snp_uncount    takes back what the workspace's LAST successful align call added (the call's buffers must be untouched
+ *                              since): for a driver that discards a block it has aligned.  Nothing to take back: SALT_OK.
+ * SALT_E_INVAL, with a message that says which: counting never enabled on the index, cap / cap_words too small, min_mapq above 255. */
+int  salt_gpu_index_snp_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq);
+int  salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites, uint32_t *pos, uint64_t cap);
+int  salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts, uint64_t cap_words, int reset);
+int  salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws);
+
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,
  * strict 4-line FASTQ records: the block is parsed, aligned and formatted on the device; the host only hands over the text and

@@ -74,6 +74,19 @@ int salt_sam_pe(const salt_index_t *ix, const salt_sam_opt_t *opt, const salt_pe
 int64_t salt_bam_header(const salt_index_t *ix, const char *header_text, size_t n_text, uint8_t *out, size_t cap);
 int64_t salt_bam_from_sam(const salt_index_t *ix, const char *sam, size_t n, uint8_t *out, size_t cap, uint64_t *n_records);
 
+/* Allele counts at the index's SNP sites (`salt --snp-counts`): the host twin of salt_gpu_index_snp_sites / _snp_counts, written from the
+ * definition in salt_gpu.h without any code of the device's kernel.  It is the model the device counts are compared with, and what `salt`
+ * counts with when its libsalt_gpu has no salt_gpu_index_snp_enable.
+ *   salt_snp_sites      the genome positions (0-based, concatenated coordinate) whose mixRef mask lists two or more bases, ascending: the
+ *                       first min(cap, n_sites) of them into pos (may be NULL); returns n_sites
+ *   salt_snp_count_sam  counts[site][A C G T] += what the record lines of this program's own SAM text show at the sites: a record counts
+ *                       iff FLAG bit 4 is clear and MAPQ >= min_mapq; global position = contig offset + POS - 1; M columns count where SEQ
+ *                       holds A, C, G or T, I and S advance in SEQ, D on the genome.  Header lines ('@') and empty lines are skipped; any
+ *                       other line that is no SAM record is an error.  n_sites must be the index's.  Returns the records that counted.
+ * Both return -1 with salt_host_last_error() set on failure. */
+int64_t salt_snp_sites(const salt_index_t *ix, uint32_t *pos, uint64_t cap);
+int64_t salt_snp_count_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t *counts, uint64_t n_sites);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

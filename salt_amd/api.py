@@ -438,6 +438,39 @@ def bam_from_sam(index, sam):
     return out.raw[:n]
 
 
+def snp_sites(index):
+    """The genome positions (0-based, concatenated coordinate) whose mixRef mask lists two or more bases, ascending: uint32 array
+    (salt_snp_sites, the host twin of GpuAligner.snp_sites)."""
+    h = host_lib()
+    h.salt_snp_sites.restype = ctypes.c_int64
+    h.salt_snp_sites.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    n = h.salt_snp_sites(index._h, None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    pos = np.zeros(n, dtype=np.uint32)
+    h.salt_snp_sites(index._h, pos.ctypes.data, n)
+    return pos
+
+
+def snp_count_sam(index, sam, min_mapq=0, counts=None):
+    """What this program's own SAM text shows at the SNP sites: (n_sites, 4) uint32 counts, A C G T (salt_snp_count_sam, the host twin of
+    the device's counts).  counts: an array of an earlier call to add into."""
+    h = host_lib()
+    h.salt_snp_sites.restype = ctypes.c_int64
+    h.salt_snp_sites.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_snp_count_sam.restype = ctypes.c_int64
+    h.salt_snp_count_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    sam = bytes(sam)
+    n_sites = h.salt_snp_sites(index._h, None, 0)
+    if counts is None:
+        counts = np.zeros((n_sites, 4), dtype=np.uint32)
+    if counts.dtype != np.uint32 or counts.shape != (n_sites, 4) or not counts.flags.c_contiguous:
+        raise SaltError("snp_count_sam: counts must be a contiguous (%d, 4) uint32 array" % n_sites)
+    if h.salt_snp_count_sam(index._h, sam, len(sam), int(min_mapq), counts.ctypes.data, n_sites) < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    return counts
+
+
 class _TextOpt(ctypes.Structure):
     _fields_ = [("print_xa_cigar", ctypes.c_int32), ("print_nm_md", ctypes.c_int32), ("rg_id", ctypes.c_char_p)]
 
@@ -644,6 +677,34 @@ class GpuAligner:
         co = opt._c()
         _gpu_check(gpu_lib().salt_gpu_align_se_resident(self._ws, ctypes.byref(co), n_reads, max_read_len, d_seqs, d_offs,
                                                         d_results, stream))
+
+    def snp_enable(self, on=True, min_mapq=0):
+        """Count, from now on, what every align call on this aligner's device index (its forks included) shows at the index's SNP sites;
+        records below min_mapq do not count.  The first enable builds the site table and zeroes the counts; on=False stops and keeps both."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_snp_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_snp_enable(self._ix, 1 if on else 0, int(min_mapq)))
+
+    def snp_sites(self):
+        """The sites' genome positions from the device's table, ascending: uint32 array."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_snp_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_uint64]
+        n = ctypes.c_uint32()
+        _gpu_check(lib.salt_gpu_index_snp_sites(self._ix, ctypes.byref(n), None, 0))
+        pos = np.zeros(n.value, dtype=np.uint32)
+        _gpu_check(lib.salt_gpu_index_snp_sites(self._ix, ctypes.byref(n), pos.ctypes.data, pos.size))
+        return pos
+
+    def snp_counts(self, reset=False):
+        """(n_sites, 4) uint32: the adds of all align calls since the first enable or the last reset, A C G T.  Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_snp_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_uint64]
+        lib.salt_gpu_index_snp_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]
+        n = ctypes.c_uint32()
+        _gpu_check(lib.salt_gpu_index_snp_sites(self._ix, ctypes.byref(n), None, 0))
+        counts = np.zeros((n.value, 4), dtype=np.uint32)
+        _gpu_check(lib.salt_gpu_index_snp_counts(self._ix, counts.ctypes.data, counts.size, 1 if reset else 0))
+        return counts
 
     def counters(self):
         out = (ctypes.c_uint64 * len(CTR_NAMES))()

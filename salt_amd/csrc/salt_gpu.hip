@@ -38,6 +38,9 @@ struct salt_gpu_index {
     uint8_t *d_pac = nullptr; uint64_t l_pac = 0;      // 2-bit genome for the PE singleton rescue (not part of the image)
     uint4 *d_rctx = nullptr;                            // context records of the R rows (attach_r_ctx; not part of the image)
     int64_t *d_c_off = nullptr; uint32_t *d_c_name_off = nullptr; char *d_c_names = nullptr; int32_t n_contigs = 0;     // contig table for the SAM kernels
+    // salt_gpu_index_snp_enable: the site table (one record per 64 genome positions) and counts[snp_sites][4], built by the first enable (not
+    // part of the image); every workspace of the index adds into the one table while snp_on
+    SnpWin *d_snp_tab = nullptr; uint32_t *d_snp_counts = nullptr; uint64_t snp_win = 0; uint32_t snp_sites = 0, snp_min_mapq = 0; bool snp_on = false;
 };
 
 // A device buffer with its owner: p[0 .. cap) elements, freed with the owner.  alloc() gives it exactly n elements (what it held is freed
@@ -119,6 +122,7 @@ struct salt_gpu_ws {
     std::vector<hipEvent_t> ev;        // EV_PER_CALL per call: before k_pack, k_seed, k_light, k_heavy, k_gap, k_gapfin, k_cigar, after; paired end: after k_pair, k_sw, k_pe_final (+ its k_cigar)
     std::vector<uint8_t> ev_pe;        // the call was a paired-end one (its last three events are recorded)
     uint32_t n_timed = 0;
+    SnpCount snp_last{}; hipStream_t snp_last_st = nullptr;      // what the last align call counted (n_rec 0: nothing), for salt_gpu_ws_snp_uncount
 };
 static const uint32_t MAX_TIMED = 256, EV_PER_CALL = 12;
 
@@ -290,6 +294,7 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     if (ix->d_pac) { hipSetDevice(ix->device); hipFree(ix->d_pac); }
     if (ix->d_rctx) { hipSetDevice(ix->device); hipFree(ix->d_rctx); }
     if (ix->d_c_off) { hipSetDevice(ix->device); hipFree(ix->d_c_off); hipFree(ix->d_c_name_off); hipFree(ix->d_c_names); }
+    if (ix->d_snp_tab) { hipSetDevice(ix->device); hipFree(ix->d_snp_tab); hipFree(ix->d_snp_counts); }
     delete ix;
 }
 
@@ -444,6 +449,21 @@ static int check_opt(const salt_gpu_index *ix, const salt_aln_opt_t *o, uint32_t
 static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint32_t n_reads, uint32_t max_read_len,
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe);
 
+// The one launch behind the kernels that finish a batch's result rows, on the batch's stream: the rows' bases at the SNP sites into the
+// index's counts (k_snp_count).  With counting off nothing is launched.  Every entry point that leaves result rows passes here: single
+// end at the end of align_resident_impl, paired end at the end of pe_resident_impl (the rows are final only behind k_pe_final).
+static int snp_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
+{
+    const salt_gpu_index *ix = ws->ix;
+    if (!ix->snp_on) return SALT_OK;
+    SnpCount c{};
+    c.res = static_cast<const salt_result_t *>(d_results); c.seqs = static_cast<const uint8_t *>(d_seqs); c.offs = static_cast<const uint32_t *>(d_offs); c.n_rec = n_rec;
+    c.tab = ix->d_snp_tab; c.n_win = ix->snp_win; c.counts = ix->d_snp_counts; c.min_mapq = ix->snp_min_mapq; c.pe = pe; c.delta = 1u;
+    HIPCHK(launch_snp_count(c, st));
+    ws->snp_last = c; ws->snp_last_st = st;
+    return SALT_OK;
+}
+
 // ---- the workspace's buffer families: each is sized here and nowhere else ----
 // The seed-interval arrays and k_seed's walk queues, for `items` seeds.  d_sai_r is zeroed when allocated: no row of any epoch (sai_r_row,
 // salt_device.h).  settle: the zeroing is waited for, for a caller that does not know which stream the calls will use.  d_sai_c comes last:
@@ -484,6 +504,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe)
 {
     if (!ws || !o || !d_seqs || !d_offs || !d_results) return fail(SALT_E_INVAL, "null argument");
+    ws->snp_last.n_rec = 0;
     if (n_reads == 0) return SALT_OK;
     uint32_t spr = 0;
     int rc = check_opt(ws->ix, o, max_read_len, &spr);
@@ -528,6 +549,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                  gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr.p : nullptr, timed ? ev + 4 : nullptr, st);
     if (timed) { HIPCHK(hipEventRecord(ev[7], st)); ws->ev_pe[ws->n_timed] = 0; ++ws->n_timed; }
     HIPCHK(hipGetLastError());
+    if (!pe) return snp_hook(ws, n_reads, d_seqs, d_offs, d_results, 0, st);
     return SALT_OK;
 }
 
@@ -1070,6 +1092,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
 {
     const uint64_t n_src = n_bytes;
     if (d_src && add_newline) ++n_bytes;
+    ws->snp_last.n_rec = 0;
     salt_gpu_index *ix = ws->ix;
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
@@ -1127,7 +1150,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
 {
     if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
-    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0;
+    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->snp_last.n_rec = 0;
     if (n1 == 0 && n2 == 0) return SALT_OK;
     if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
     if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
@@ -1664,6 +1687,83 @@ extern "C" int salt_gpu_index_set_pac(salt_gpu_index_t *ix, const uint8_t *pac, 
     return attach_r_ctx(ix, R_CTX_RESERVE_PAC);      // an index attached without the room for its R context records gets them now, if the room is there
 }
 
+// ---- allele counts at the SNP sites ----
+// The first enable builds the site table from view.ref (k_snp_bits, a scan of the windows' popcounts, k_snp_rank) and the zeroed counts.
+extern "C" int salt_gpu_index_snp_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (min_mapq > 255) return fail(SALT_E_INVAL, "snp counts: min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
+    HIPCHK(hipSetDevice(ix->device));
+    if (on && !ix->d_snp_tab) {
+        const uint32_t ref_len = ix->view.ref_len;
+        if (ref_len == 0) return fail(SALT_E_INVAL, "snp counts: the index has an empty genome");
+        const uint64_t n_win = ((uint64_t)ref_len + 63) / 64;
+        DevBuf<uint32_t> cnt; DevBuf<uint8_t> tmp; DevBuf<SnpWin> tab;
+        const size_t tmp_bytes = snp_scan_bytes(n_win);
+        if (tab.alloc(n_win) != hipSuccess || cnt.alloc(n_win + 1) != hipSuccess || tmp.alloc(tmp_bytes ? tmp_bytes : 1) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SALT_E_NOMEM, "snp counts: no room for the site table: " + std::to_string(n_win * sizeof(SnpWin)) + " bytes (16 per 64 genome positions) and " +
+                                      std::to_string((n_win + 1) * 4 + tmp_bytes) + " bytes of scratch while it is built");
+        }
+        HIPCHK(launch_snp_table(ix->view.ref, ref_len, n_win, tab, cnt, tmp, tmp_bytes, nullptr));
+        uint32_t n_sites = 0;
+        HIPCHK(hipMemcpy(&n_sites, cnt + n_win, 4, hipMemcpyDeviceToHost));
+        uint32_t *counts = nullptr;
+        const uint64_t cbytes = ((uint64_t)n_sites + 1) * 16;                      // (one spare row: an index without sites still has a table)
+        if (hipMalloc((void **)&counts, cbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SALT_E_NOMEM, "snp counts: no room for the counts: " + std::to_string(cbytes) + " bytes (16 per site, " + std::to_string(n_sites) + " sites)");
+        }
+        const hipError_t e = hipMemset(counts, 0, cbytes);
+        if (e != hipSuccess) { hipFree(counts); return fail(SALT_E_HIP, std::string("hipMemset(snp counts): ") + hipGetErrorString(e)); }
+        ix->d_snp_tab = tab.p; tab.p = nullptr; tab.cap = 0;                        // the index owns it from here
+        ix->d_snp_counts = counts; ix->snp_win = n_win; ix->snp_sites = n_sites;
+    }
+    ix->snp_min_mapq = min_mapq; ix->snp_on = on != 0;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites, uint32_t *pos, uint64_t cap)
+{
+    if (!ix || !n_sites) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_snp_tab) return fail(SALT_E_INVAL, "snp counts: counting was never enabled on this index (salt_gpu_index_snp_enable)");
+    *n_sites = ix->snp_sites;
+    if (!pos || ix->snp_sites == 0) return SALT_OK;
+    if (cap < ix->snp_sites) return fail(SALT_E_INVAL, "snp counts: room for " + std::to_string(cap) + " positions, the index has " + std::to_string(ix->snp_sites) + " sites");
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf<uint32_t> d_pos;
+    if (d_pos.alloc(ix->snp_sites) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, "snp counts: no room for " + std::to_string((uint64_t)ix->snp_sites * 4) + " bytes of site positions"); }
+    HIPCHK(launch_snp_pos(ix->d_snp_tab, ix->snp_win, d_pos, nullptr));
+    HIPCHK(hipMemcpy(pos, d_pos, (uint64_t)ix->snp_sites * 4, hipMemcpyDeviceToHost));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts, uint64_t cap_words, int reset)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_snp_tab) return fail(SALT_E_INVAL, "snp counts: counting was never enabled on this index (salt_gpu_index_snp_enable)");
+    const uint64_t words = (uint64_t)ix->snp_sites * 4;
+    if (counts && cap_words < words) return fail(SALT_E_INVAL, "snp counts: room for " + std::to_string(cap_words) + " words, the table has " + std::to_string(words) + " (4 per site)");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (counts && words) HIPCHK(hipMemcpy(counts, ix->d_snp_counts, words * 4, hipMemcpyDeviceToHost));
+    if (reset && words) HIPCHK(hipMemset(ix->d_snp_counts, 0, words * 4));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (ws->snp_last.n_rec == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ws->ix->device));
+    SnpCount c = ws->snp_last;
+    c.delta = 0xFFFFFFFFu;                                                         // + (2^32 - 1) = - 1 in the counts' arithmetic
+    ws->snp_last.n_rec = 0;
+    HIPCHK(launch_snp_count(c, ws->snp_last_st));
+    HIPCHK(hipStreamSynchronize(ws->snp_last_st));
+    return SALT_OK;
+}
+
 extern "C" int salt_gpu_index_r_ctx(const salt_gpu_index_t *ix, void **dev_ptr, uint64_t *bytes)
 {
     if (!ix || !dev_ptr || !bytes) return fail(SALT_E_INVAL, "null argument");
@@ -1761,7 +1861,7 @@ static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sa
     }
 #endif
     HIPCHK(hipGetLastError());
-    return SALT_OK;
+    return snp_hook(ws, 2 * n_pairs, d_seqs, d_offs, d_results, 1, st);
 }
 
 extern "C" int salt_gpu_align_pe_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, uint32_t n_pairs,

@@ -247,6 +247,22 @@ hipError_t launch_bgzf_deflate(const uint8_t *text, uint64_t n, uint32_t *slots,
 hipError_t launch_bgzf_inflate(const uint8_t *members, const unsigned long long *c_off, const unsigned long long *u_off, uint32_t n_blocks,
                                uint8_t *text, uint32_t *status, hipStream_t st);
 
+// ---- allele counts at the SNP sites (salt_snp.hip) ----
+// One record per 64 genome positions: bit b set = position 64 w + b is a site (its mixRef mask lists two or more bases; nothing at or beyond
+// ref_len is one), rank = sites in front of the window.  16 bytes, so that a lookup is one request.
+struct SnpWin { unsigned long long bits; uint32_t rank, pad; };
+static_assert(sizeof(SnpWin) == 16, "one request per window");
+struct SnpCount {                                                              // what k_snp_count reads (by value)
+    const salt_result_t *res; const uint8_t *seqs; const uint32_t *offs; uint32_t n_rec;      // the batch: rows, codes as sequenced, offsets
+    const SnpWin *tab; uint64_t n_win; uint32_t *counts;                       // the index's site table and counts[n_sites][4] (A C G T)
+    uint32_t min_mapq; int32_t pe;                                             // pe: rows of a paired-end batch (reverse iff strand == 1, soft clips)
+    uint32_t delta;                                                            // 1; 0xFFFFFFFF takes a batch's adds back
+};
+size_t snp_scan_bytes(uint64_t n_win);
+hipError_t launch_snp_table(const uint32_t *ref, uint32_t ref_len, uint64_t n_win, SnpWin *tab, uint32_t *cnt, void *tmp, size_t tmp_bytes, hipStream_t st);
+hipError_t launch_snp_pos(const SnpWin *tab, uint64_t n_win, uint32_t *pos, hipStream_t st);
+hipError_t launch_snp_count(const SnpCount &c, hipStream_t st);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <cstdarg>
 #include <fstream>
+#include <mutex>
 #include <sstream>
 #include <algorithm>
 #include <string>
@@ -41,6 +42,7 @@ struct salt_index {
     int64_t l_pac = 0;
     int32_t seed_len = 0;
     salt_host_index_t view;
+    mutable std::vector<uint32_t> snp_pos; mutable std::once_flag snp_once;      // the SNP sites' genome positions, listed by the first salt_snp_* call
 };
 
 extern "C" const char *salt_host_last_error(void) { return g_err.c_str(); }
@@ -634,4 +636,97 @@ extern "C" int64_t salt_bam_from_sam(const salt_index_t *ix, const char *sam, si
     }
     if (n_records) *n_records = n_rec;
     return (int64_t)w;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Allele counts at the SNP sites: the host twin of the device's site table and k_snp_count (include/salt_gpu.h has the definition), written
+// from that definition over this program's own SAM record lines and without any code of the kernel's.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+const std::vector<uint32_t> &snp_positions(const salt_index *ix)
+{
+    std::call_once(ix->snp_once, [ix]() {
+        for (uint32_t g = 0; g < ix->view.ref_len; ++g) {
+            const uint32_t m = mask_at(ix, g);
+            if (m & (m - 1u)) ix->snp_pos.push_back(g);                // two or more bases listed (an N of the genome has mask 0)
+        }
+    });
+    return ix->snp_pos;
+}
+
+// one record line [l, e): its bases at the sites into counts; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with g_err set
+int snp_count_line(const salt_index *ix, const RefIds &ids, const std::vector<uint32_t> &sites, const char *l, const char *e, uint32_t min_mapq, uint32_t *counts)
+{
+    const char *f[12]; int nf = 0;
+    f[nf++] = l;
+    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
+    auto bad = [&](const char *why) { g_err = std::string("snp counts: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return -1; };
+    if (nf < 11) return bad("fewer than 11 fields");
+    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };
+    int64_t flag, pos1, mapq;
+    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
+        pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
+    if (flag & 4) return 0;                                            // unmapped, also a mate printed at its mate's place
+    if ((uint64_t)mapq < min_mapq) return 0;
+    const int32_t rid = ids.find(f[2], fe(2));
+    if (rid < 0) return bad("RNAME is no sequence of the index");
+    if (pos1 < 1) return bad("a mapped record without a position");
+    const char *seq = f[9]; const size_t l_seq = (size_t)(fe(9) - seq);
+    uint64_t g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)pos1 - 1;      // global position; the walk may run past the contig's end
+    size_t s = 0; uint64_t n = 0; bool digits = false, any = false;
+    for (const char *p = f[5]; p < fe(5); ++p) {
+        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
+        if (!digits) return bad("malformed CIGAR");
+        switch (*p) {
+        case 'M':
+            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
+            for (uint64_t k = 0; k < n; ++k, ++g, ++s) {
+                const auto it = std::lower_bound(sites.begin(), sites.end(), g);
+                if (g > 0xFFFFFFFFull || it == sites.end() || *it != g) continue;
+                int b;
+                switch (seq[s]) { case 'A': b = 0; break; case 'C': b = 1; break; case 'G': b = 2; break; case 'T': b = 3; break; default: b = -1; }
+                if (b >= 0) ++counts[(size_t)(it - sites.begin()) * 4 + (size_t)b];
+            }
+            break;
+        case 'I': case 'S':
+            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
+            s += n; break;
+        case 'D': g += n; break;
+        default: return bad("a CIGAR operation this program does not write");
+        }
+        n = 0; digits = false; any = true;
+    }
+    if (digits || !any) return bad("malformed CIGAR");
+    return 1;
+}
+
+} // namespace
+
+extern "C" int64_t salt_snp_sites(const salt_index_t *ix, uint32_t *pos, uint64_t cap)
+{
+    if (!ix) { g_err = "snp counts: null argument"; return -1; }
+    const std::vector<uint32_t> &sites = snp_positions(ix);
+    if (pos) memcpy(pos, sites.data(), (size_t)std::min<uint64_t>(cap, sites.size()) * 4);
+    return (int64_t)sites.size();
+}
+
+extern "C" int64_t salt_snp_count_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t *counts, uint64_t n_sites)
+{
+    if (!ix || (!sam && n) || !counts) { g_err = "snp counts: null argument"; return -1; }
+    const std::vector<uint32_t> &sites = snp_positions(ix);
+    if (n_sites != sites.size()) { g_err = "snp counts: counts for " + std::to_string(n_sites) + " sites, the index has " + std::to_string(sites.size()); return -1; }
+    const RefIds ids(ix);
+    int64_t n_rec = 0;
+    for (const char *l = sam, *end = sam + n; l < end; ) {
+        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
+        if (!e) e = end;
+        if (e > l && *l != '@') {                                      // (empty lines: a skipped read, the paired-end driver's; '@': a header line -- a read name
+            const int r = snp_count_line(ix, ids, sites, l, e, min_mapq, counts);      //  cannot start with '@', the FASTQ parsers drop it)
+            if (r < 0) return -1;
+            n_rec += r;
+        }
+        l = e + 1;
+    }
+    return n_rec;
 }

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cerrno>
 #include <ctime>
 #include <algorithm>
 #include <atomic>
@@ -60,6 +61,13 @@ extern "C" void salt_gpu_polish_close(salt_gpu_polish_t *p) __attribute__((weak)
 extern "C" int salt_gpu_polish_set_contigs(salt_gpu_polish_t *p, int32_t n, const int64_t *offsets, const char *const *names) __attribute__((weak));
 extern "C" int salt_gpu_polish_text(salt_gpu_polish_t *p, const salt_polish_opt_t *opt, const char *sam, uint64_t n_bytes,
                                     const char **out, uint64_t *out_bytes, uint32_t *n_records, int *stopped) __attribute__((weak));
+
+// Likewise the allele counts at the SNP sites (--snp-counts): without the device's table and kernel the counts come from the SAM lines,
+// through the host twin (salt_snp_count_sam).
+extern "C" int salt_gpu_index_snp_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq) __attribute__((weak));
+extern "C" int salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites, uint32_t *pos, uint64_t cap) __attribute__((weak));
+extern "C" int salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts, uint64_t cap_words, int reset) __attribute__((weak));
+extern "C" int salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
 namespace {
 
@@ -439,6 +447,30 @@ struct BamRun {
     const salt_index_t *ix = nullptr;
 } g_bam;
 
+// --snp-counts FILE: how many reads show which base at every SNP site of the index.  On the device the table belongs to each GPU's index
+// and every align call adds into it (salt_gpu_index_snp_enable); the tables are summed after the last block.  A block the text path has
+// aligned and then drops at a hand-over is taken back (salt_gpu_ws_snp_uncount): the host pipeline aligns those reads again.  Without
+// the device's symbols the SAM lines of every block and batch that is written go through salt_snp_count_sam, one caller at a time.
+struct SnpRun {
+    bool on = false, device = false; const char *fn = nullptr; FILE *fp = nullptr; uint32_t min_mapq = 0;
+    const salt_index_t *ix = nullptr; std::mutex mu; std::vector<uint32_t> host_counts; uint64_t n_sites = 0;
+    bool host() const { return on && !device; }
+} g_snp;
+
+// the host twin over SAM lines that are about to be written; false with the reason on stderr
+bool snp_host_add(const char *sam, size_t n)
+{
+    std::lock_guard<std::mutex> lk(g_snp.mu);
+    if (salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites) >= 0) return true;
+    fprintf(stderr, "[salt] %s\n", salt_host_last_error());
+    return false;
+}
+// a block the text path aligned and will not write: its adds leave the device's table
+void snp_drop_block(salt_gpu_ws_t *ws)
+{
+    if (g_snp.on && g_snp.device && salt_gpu_ws_snp_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
+}
+
 // SAM lines -> BAM records in `out`; false with the reason on stderr (a read name past the format's limit)
 bool bam_of_sam(const char *sam, size_t n, std::string &out)
 {
@@ -542,6 +574,9 @@ int usage()
             "                                        read names of up to 254 bytes) [False]\n"
             "               --polish[=lv|sw]         print the records `polish` (lv) or `polish -s` (sw) makes of the SAM lines, re-scored\n"
             "                                        on the GPU, no header; not with --bam [False]\n"
+            "               --snp-counts    <file>   write, per SNP site of the index, how many reads show A, C, G, T there (counted on\n"
+            "                                        the GPU; tab-separated, one line per site) [off]\n"
+            "               --snp-min-mapq  <int>    --snp-counts: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -984,8 +1019,11 @@ void SeWorker::run()
         }
         R.t_gpu = R.t_gpu + (now() - tg0);
         if (n_calls++ == 0) t_first = now() - tg0; else t_rest += now() - tg0;
+        const char *const lines = sam; const uint64_t lines_bytes = sam_bytes;      // (SAM lines whenever --snp-counts counts on the host)
         if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); R.fail(); break; }
-        if (!R.wait_turn(k) || !R.write_block(k, sam, sam_bytes, n_reads)) break;
+        if (!R.wait_turn(k)) { snp_drop_block(ws); break; }
+        if (g_snp.host() && !snp_host_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
+        if (!R.write_block(k, sam, sam_bytes, n_reads)) break;
     }
     if (trace) fprintf(stderr, "[salt] worker %d: started %.3f s after the clock, setup %.3f s, first device call %.3f s, %d later calls %.4f s each, done at %.3f s\n", wk,
                        tw_start - S.t0, t_setup, t_first, n_calls - 1, n_calls > 1 ? t_rest / (n_calls - 1) : 0.0, now() - S.t0);
@@ -1181,8 +1219,11 @@ static int run_pe_text(const char *fn1, const char *fn2, const std::vector<salt_
                 if (grc && !parser_refused(grc)) { R.fail_gpu(); break; }
                 if (grc) { fall_back(k, salt_gpu_last_error()); break; }
                 R.t_gpu = R.t_gpu + (now() - tg0);
+                const char *const lines = sam; const uint64_t lines_bytes = sam_bytes;
                 if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); R.fail(); break; }
-                if (!R.wait_turn(k) || !R.write_block(k, sam, sam_bytes, 2 * (long)n_pairs)) break;
+                if (!R.wait_turn(k)) { snp_drop_block(ws); break; }
+                if (g_snp.host() && !snp_host_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
+                if (!R.write_block(k, sam, sam_bytes, 2 * (long)n_pairs)) break;
             }
             salt_gpu_ws_destroy(ws);
         });
@@ -1234,7 +1275,8 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "threads", 1, 0, 't' }, { "num", 1, 0, 'n' }, { "help", 0, 0, 'h' }, { "pe", 0, 0, 'p' }, { "min_tlen", 1, 0, 'a' },
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
-        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 }, { 0, 0, 0, 0 } };
+        { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 },
+        { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1256,6 +1298,13 @@ static int parse_options(int argc, char **argv, Opts &o)
             else if (strcmp(optarg, "sw") == 0) g_polish = 2;
             else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
             break;
+        case 1004: g_snp.on = true; g_snp.fn = optarg; break;
+        case 1005: {
+            char *end = nullptr; const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --snp-min-mapq %s: a MAPQ is a number from 0 to 255\n", optarg); return 1; }
+            g_snp.min_mapq = (uint32_t)v;
+            break;
+        }
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1272,6 +1321,13 @@ static int parse_options(int argc, char **argv, Opts &o)
     // out of the device's SAM text are deflated there too
     g_bam.device = g_bam.on && salt_gpu_ws_set_sam_bam != nullptr && !(getenv("SALT_BAM_HOST") && atoi(getenv("SALT_BAM_HOST")));
     if (g_bam.on && !g_bam.device) g_bgzf.device = false;
+    if (g_snp.on) {
+        g_snp.device = salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount;
+        // counted on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
+        if (!g_snp.device && g_polish) { fprintf(stderr, "[opt_parse]: --snp-counts with --polish needs a libsalt_gpu that counts on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
+        if (!g_snp.device) g_bgzf.device = g_bam.device = false;
+        if (!(g_snp.fp = fopen(g_snp.fn, "w"))) { fprintf(stderr, "[opt_parse]: --snp-counts: cannot open %s for writing: %s\n", g_snp.fn, strerror(errno)); return 1; }
+    }
     return -1;
 }
 
@@ -1432,6 +1488,11 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
+                if (g_snp.host()) {
+                    bool good = true;
+                    for (const std::string &piece : b->sam) good = good && snp_host_add(piece.data(), piece.size());
+                    if (!good) { set_failed(); break; }
+                }
                 if (g_polish && !polish_batch(gp.get(), pe, *b)) { set_failed(); break; }
                 if (g_bgzf.on && !bgzf_batch(b->sam, pool)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); set_failed(); break; }
                 t_fmt = t_fmt + (now() - tf0);
@@ -1473,6 +1534,64 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
     if (fp2) gzclose(fp2);
     for (int i = 0; i < n_gpus * WPG; ++i) salt_gpu_ws_destroy(ws[(size_t)i]);
     return failed ? 1 : 0;
+}
+
+// --snp-counts, before the first block: the sites of the index; counting on on every GPU's index, or the host's table
+static bool snp_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_snp.on) return true;
+    g_snp.ix = ix;
+    const int64_t n = salt_snp_sites(ix, nullptr, 0);
+    if (n < 0) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+    g_snp.n_sites = (uint64_t)n;
+    if (!g_snp.device) { g_snp.host_counts.assign((size_t)n * 4, 0u); return true; }
+    for (salt_gpu_index_t *g : gix) {
+        uint32_t n_dev = 0;
+        if (salt_gpu_index_snp_enable(g, 1, g_snp.min_mapq) || salt_gpu_index_snp_sites(g, &n_dev, nullptr, 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+        if (n_dev != g_snp.n_sites) { fprintf(stderr, "[salt] --snp-counts: the device's site table has %u sites, the index %llu\n", n_dev, (unsigned long long)g_snp.n_sites); return false; }
+    }
+    return true;
+}
+
+// --snp-counts, after the last block of a run that succeeded: every GPU's counts summed in 64 bits, one line per site in genome order
+static bool snp_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_snp.on) return true;
+    const size_t n = (size_t)g_snp.n_sites;
+    std::vector<uint64_t> sum(n * 4, 0);
+    if (g_snp.device) {
+        std::vector<uint32_t> c(n * 4);
+        for (salt_gpu_index_t *g : gix) {
+            if (salt_gpu_index_snp_counts(g, c.data(), c.size(), 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+            for (size_t i = 0; i < c.size(); ++i) sum[i] += c[i];
+        }
+    } else for (size_t i = 0; i < sum.size(); ++i) sum[i] = g_snp.host_counts[i];
+    std::vector<uint32_t> pos(n);
+    salt_snp_sites(ix, pos.data(), n);
+    const salt_host_index_t *hv = salt_index_host_view(ix);
+    uint64_t l_pac = 0; const uint8_t *pac = salt_index_pac(ix, &l_pac);
+    FILE *f = g_snp.fp;
+    fprintf(f, "#contig\tpos\tref\talleles\tA\tC\tG\tT\n");
+    int32_t c = 0; const int32_t n_seqs = salt_index_n_seqs(ix);
+    int64_t c_off = 0; int32_t c_len = 0; const char *c_name = "*";
+    if (n_seqs > 0) salt_index_seq(ix, 0, &c_off, &c_len, &c_name);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t g = pos[i];
+        while (c + 1 < n_seqs && (int64_t)g >= c_off + c_len) salt_index_seq(ix, ++c, &c_off, &c_len, &c_name);
+        const uint32_t mask = (hv->ref[g >> 3] >> (4 * (g & 7u))) & 15u;
+        char alleles[5]; int na = 0;
+        for (int b = 0; b < 4; ++b) if (mask & (1u << b)) alleles[na++] = "ACGT"[b];
+        alleles[na] = 0;
+        const char ref = g < l_pac ? "ACGT"[(pac[g >> 2] >> ((~g & 3u) << 1)) & 3u] : 'N';
+        fprintf(f, "%s\t%lld\t%c\t%s\t%llu\t%llu\t%llu\t%llu\n", c_name, (long long)((int64_t)g - c_off + 1), ref, alleles,
+                (unsigned long long)sum[4 * i], (unsigned long long)sum[4 * i + 1], (unsigned long long)sum[4 * i + 2], (unsigned long long)sum[4 * i + 3]);
+    }
+    const bool ok = !ferror(f) && fclose(f) == 0;
+    g_snp.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --snp-counts: write error on %s\n", g_snp.fn); return false; }
+    fprintf(stderr, "[salt] SNP counts: %llu sites, %s, MAPQ >= %u -> %s\n", (unsigned long long)g_snp.n_sites, g_snp.device ? "counted on the device" : "counted on the host from the SAM lines",
+            g_snp.min_mapq, g_snp.fn);
+    return true;
 }
 
 } // namespace
@@ -1523,14 +1642,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
+    if (!snp_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !snp_finish(ix, gix) ? 1 : rc); }
         header_out = true;
     }
-    return leave(run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0));
+    const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
+    return leave(rc == 0 && !snp_finish(ix, gix) ? 1 : rc);
 }
