@@ -326,6 +326,19 @@ int  salt_gpu_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *va
 int  salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs,
                           const uint32_t *cand, const uint32_t *cand_offs, int mode, uint8_t *out);
 
+/* Unit entry of the rank primitives (salt_device.h) over an attached index: query i = queries[3i..] = (x, y, c), answered by every
+ * restatement of the rank query.  mode 0, the C index: x and y in {0xFFFFFFFF} or [0, c_seq_len], c in 0..3.  mode 1, the R index: x and
+ * y in [0, r_text_len + 1], c in 0..4 ('#' = 4).  Anything else: SALT_E_INVAL, and nothing is launched.  out[12i..]:
+ *   [0] Occ(x, c), [1] Occ(y, c)            by c_occ / r_occ
+ *   [2], [3] the same pair                  by c_occ2 / r_occ2, [6] the number of blocks it says it fetched
+ *   [4], [5] the same pair                  by c_occ2_addr + c_occ2_eval / r_occ2_addr + r_occ2_eval over exactly the blocks _addr
+ *                                           names (a half it does not name holds all ones), [7] _eval's block count, [8] the number
+ *                                           of blocks _addr named
+ *   [9] the BWT symbol of row x             by c_sym as the suffix-array expansion reads it (4: the '$' row, 0xFFFFFFFF) / r_bwt2nt
+ *                                           (5: x = r_text_len + 1, which is no row)
+ *   [10], [11] 0 */
+int  salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t n, const uint32_t *queries, uint32_t *out);
+
 /* Work-queue counters of the LAST batch (diagnostics): [0] reads k_light handed to k_heavy, [2] reads whose gapped pass
  * was deferred, [5] k_gap items (32 candidates each), [6] k_cigar items, [7] k_cigar's queue head; [1] / [3] the longest R / C list among
  * the 64 segments of the seed walk queues; [4] reads 0. */

@@ -149,6 +149,7 @@ def gpu_lib():
         lib.salt_gpu_ws_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)]
         lib.salt_gpu_diag_verify.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        lib.salt_gpu_diag_occ.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         assert lib.salt_gpu_result_size() == RESULT_DTYPE.itemsize
         _gpu = lib
     return _gpu
@@ -598,6 +599,13 @@ class GpuAligner:
         p, n = ctypes.c_void_p(), ctypes.c_uint64()
         _gpu_check(lib.salt_gpu_index_r_ctx(self._ix, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
+
+    def diag_occ(self, mode, queries):
+        """The rank primitives asked directly (salt_gpu_diag_occ): mode "C" or "R", queries (n, 3) uint32 rows (x, y, c) -> (n, 12) uint32."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, 3)
+        out = np.zeros((len(q), 12), dtype=np.uint32)
+        _gpu_check(gpu_lib().salt_gpu_diag_occ(self._ix, {"C": 0, "R": 1}[mode], len(q), q.ctypes.data, out.ctypes.data))
+        return out
 
     def epoch(self):
         """The epoch the workspace's next alignment call runs at."""

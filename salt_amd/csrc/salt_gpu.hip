@@ -1614,6 +1614,30 @@ extern "C" int salt_gpu_diag_rule(uint32_t n_cases, const uint32_t *pos, const u
     return SALT_OK;
 }
 
+// Unit entry of the rank primitives over an attached index (k_diag_occ): see include/salt_gpu.h
+extern "C" int salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t n, const uint32_t *queries, uint32_t *out)
+{
+    if (!ix || (n && (!queries || !out))) return fail(SALT_E_INVAL, "null argument");
+    if (mode != 0 && mode != 1) return fail(SALT_E_INVAL, "mode must be 0 (C) or 1 (R)");
+    if (n == 0) return SALT_OK;
+    const uint32_t hi = mode == 0 ? ix->hdr.c_seq_len : ix->hdr.r_text_len + 1, n_sym = mode == 0 ? 4u : 5u;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t *q = queries + 3 * (uint64_t)i;
+        for (int e = 0; e < 2; ++e) if (q[e] > hi && !(mode == 0 && q[e] == 0xFFFFFFFFu)) return fail(SALT_E_INVAL, "query " + std::to_string(i) + ": index outside the primitive's range");
+        if (q[2] >= n_sym) return fail(SALT_E_INVAL, "query " + std::to_string(i) + ": symbol outside the alphabet");
+    }
+    HIPCHK(hipSetDevice(ix->device));
+    uint32_t *d_q = nullptr, *d_out = nullptr;
+    auto done = [&](int rc) { hipFree(d_q); hipFree(d_out); return rc; };
+    DONECHK(hipMalloc((void **)&d_q, (uint64_t)n * 12)); DONECHK(hipMemcpy(d_q, queries, (uint64_t)n * 12, hipMemcpyHostToDevice));
+    DONECHK(hipMalloc((void **)&d_out, (uint64_t)n * 48));
+    launch_diag_occ(ix->view, mode, n, d_q, d_out, nullptr);
+    DONECHK(hipGetLastError());
+    DONECHK(hipDeviceSynchronize());
+    DONECHK(hipMemcpy(out, d_out, (uint64_t)n * 48, hipMemcpyDeviceToHost));
+    return done(SALT_OK);
+}
+
 // Unit entry of the candidate verifiers on a caller-supplied mixRef (see k_diag_verify): fault-free check of the guards that keep a
 // wrapped locate from being used as an address.
 extern "C" int salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs,

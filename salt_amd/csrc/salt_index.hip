@@ -245,4 +245,45 @@ void launch_build_r_pos(const IndexView &ix, const uint32_t *r_sa, uint32_t *out
     hipLaunchKernelGGL(k_build_r_pos, dim3(stride_grid(n)), dim3(256), 0, st, ix, r_sa, out);
 }
 
+// k_diag_occ: unit access to the rank primitives of salt_device.h (tests only; include/salt_gpu.h).  One thread per query (x, y, c), twelve
+// words out: the single query at either end, the pair by c_occ2 / r_occ2, the pair by _addr + _eval with exactly the blocks _addr names
+// loaded (a half it does not name stays all ones, so an _eval that reads it shows), the three block counts, the BWT symbol of row x.
+__global__ void __launch_bounds__(256)
+k_diag_occ(IndexView ix, int mode, uint32_t n, const uint32_t *__restrict__ q, uint4 *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = q[3 * i], y = q[3 * i + 1], c = q[3 * i + 2];
+    const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
+    uint4 o0, o1, o2 = make_uint4(0u, 0u, 0u, 0u);
+    if (mode == 0) {
+        o0.x = c_occ(ix, x, c); o0.y = c_occ(ix, y, c);
+        o1.z = c_occ2(ix, x, y, c, o0.z, o0.w);
+        const uint4 *pk, *pl;
+        c_occ2_addr(ix, x, y, pk, pl);
+        COcc2 r; r.cntk = r.plk = r.cntl = r.pll = ones;
+        if (pk) { r.cntk = pk[0]; r.plk = pk[1]; }
+        if (pl) { r.cntl = pl[0]; r.pll = pl[1]; }
+        o1.w = c_occ2_eval(ix, r, x, y, c, o1.x, o1.y);
+        o2.x = (pk ? 1u : 0u) + (pl ? 1u : 0u);
+        o2.y = x == 0xFFFFFFFFu || x == ix.c_primary ? 4u : c_sym(ix, x < ix.c_primary ? x : x - 1);      // as k_build_c_sa reads a row
+    } else {
+        o0.x = r_occ(ix, x, c); o0.y = r_occ(ix, y, c);
+        o1.z = r_occ2(ix, x, y, c, o0.z, o0.w);
+        const uint4 *pa, *pb;
+        r_occ2_addr(ix, x, y, pa, pb);
+        ROcc2 r; r.a.cnt = r.a.q0 = r.a.q1 = r.a.q2 = r.b.cnt = r.b.q0 = r.b.q1 = r.b.q2 = ones;
+        if (pa) { r.a.cnt = pa[0]; r.a.q0 = pa[1]; r.a.q1 = pa[2]; r.a.q2 = pa[3]; }
+        if (pb) { r.b.cnt = pb[0]; r.b.q0 = pb[1]; r.b.q1 = pb[2]; r.b.q2 = pb[3]; }
+        o1.w = r_occ2_eval(ix, r, x, y, c, o1.x, o1.y);
+        o2.x = (pa ? 1u : 0u) + (pb ? 1u : 0u);
+        o2.y = x > ix.r_text_len ? 5u : r_bwt2nt(ix, x);
+    }
+    out[3 * (uint64_t)i] = o0; out[3 * (uint64_t)i + 1] = o1; out[3 * (uint64_t)i + 2] = o2;
+}
+void launch_diag_occ(const IndexView &ix, int mode, uint32_t n, const uint32_t *q, uint32_t *out, hipStream_t st)
+{
+    if (n) hipLaunchKernelGGL(k_diag_occ, dim3((n + 255) / 256), dim3(256), 0, st, ix, mode, n, q, reinterpret_cast<uint4 *>(out));
+}
+
 } // namespace salt

@@ -273,5 +273,6 @@ void launch_build_c_sa(const IndexView &ix, const uint32_t *sa_sampled, uint32_t
 void launch_build_r_pos(const IndexView &ix, const uint32_t *r_sa, uint32_t *out, hipStream_t st);
 void launch_build_text(const IndexView &ix, uint32_t *out, hipStream_t st);
 void launch_build_wlkt(const IndexView &ix, uint32_t len, uint4 *out, hipStream_t st);
+void launch_diag_occ(const IndexView &ix, int mode, uint32_t n, const uint32_t *q, uint32_t *out, hipStream_t st);      // q: n x (x, y, c); out: n x 12 words
 
 } // namespace salt
