@@ -50,6 +50,9 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef const u32x4_t __attribute__((address_space(1))) *gp_u32x4;
 __device__ __forceinline__ gp_u32 as_global(const uint32_t *p) { return (gp_u32)p; }
 __device__ __forceinline__ gp_u32x4 as_global(const uint4 *p) { return (gp_u32x4)(const void *)p; }
+// ... and these that they point into the block's LDS (ds_read, lgkmcnt alone)
+typedef const uint32_t __attribute__((address_space(3))) *lds_u32;
+__device__ __forceinline__ lds_u32 as_lds(const uint32_t *p) { return (lds_u32)p; }
 
 // diagnostic phase clock: adds the cycles since the previous stamp to ctr[slot] (lane 0, only when counting)
 struct PhaseClock {                    // acc: a per-wave LDS array (flushed once per wave), or nullptr
@@ -647,14 +650,28 @@ template <int NS> struct SaiListsT { uint32_t sp[2][NS], ep[2][NS], off[2][NS]; 
 struct SaiLists { uint32_t *sp[2], *ep[2], *off[2]; };                                // the same lists by reference (the sort replica below)
 template <int NS> __device__ __forceinline__ SaiLists sai_ref(SaiListsT<NS> &a) { return SaiLists{ { a.sp[0], a.sp[1] }, { a.ep[0], a.ep[1] }, { a.off[0], a.off[1] } }; }
 struct LvTables { short L[LVK][64]; char A[LVK][64]; };
-// lane-parallel LV (one candidate per lane): nibble-packed text window per lane + two DP rows per lane
+// lane-parallel LV (one candidate per lane): nibble-packed text window per lane and the pattern, both zero-padded in LDS over every
+// word lv_lanes can ask for; the DP row lives in registers
 static constexpr int LLV_K = 12;                 // handles k <= 12 (reads up to 129 bp at k = L/10)
-static constexpr int LLV_TW = 22;                // words per lane: up to 168 text nibbles (+1 pad word): reads up to 164 bases
-static constexpr int LLV_W = 2 * LLV_K + 3;      // diagonals -k-1 .. k+1
+static constexpr int LLV_TW = 22;                // window words per lane + 1: up to 8 * (LLV_TW - 1) = 168 text nibbles, reads up to 164 bases
 static constexpr int LLV_N = 64;                 // candidates per round: one per lane
-struct LaneLv { uint32_t T[LLV_N * LLV_TW]; uint8_t rows[2][LLV_W][LLV_N]; };
+static constexpr int LLV_WIN = 4;                // the text window is LLV_WIN nibbles longer than the read (ed_diff, editdistance.c:174)
+// What lv_lanes indexes (plen = the read, tlen = plen + LLV_WIN <= 8 * (LLV_TW - 1), |d| <= k <= LLV_K):
+//   pattern nibble i with 0 <= i <= plen: a cell of a lane that is not done holds a value < plen, so best <= plen;
+//   text nibble d + i.  d + i >= 0: on a diagonal d < 0 every cell is >= -d (L[e][-e] = L[e-1][-e+1] + 1 >= e, and a cell never lies
+//   under its right neighbour + 1), on d >= 0 every reachable cell is >= 0.  d + i <= LLV_K + plen: the extension stops under
+//   min(plen, tlen - d), only the gate looks at best <= plen on d <= LLV_K.
+// Both are read eight nibbles at a time from any start, i.e. as the words (i >> 3) and (i >> 3) + 1: text words 0 .. LLV_TS - 1,
+// pattern words 0 .. LLV_PW - 1, staged with zeros behind the window / the read (lane_text, lane_pattern), so no load is predicated.
+static constexpr int LLV_TS = LLV_TW + 2;        // text words staged per lane
+static constexpr int LLV_PW = LLV_TW;            // pattern words staged
+static_assert(((8 * (LLV_TW - 1) - LLV_WIN + LLV_K) >> 3) + 2 <= LLV_TS, "text words of the longest window at the widest bound");
+static_assert(((8 * (LLV_TW - 1) - LLV_WIN) >> 3) + 2 <= LLV_PW, "pattern words of the longest read");
+// T is word-major, T[j * LLV_N + lane]: the LDS bank of a read is the lane's alone, whatever j each lane asks for (lane-major rows of
+// 22 words put 32 lanes on 16 banks).  P: the pattern all lanes share in k_gap and k_heavy (k_diag_lv gives every lane its own).
+struct LaneLv { uint32_t T[LLV_TS * LLV_N]; uint32_t P[LLV_PW]; };
 struct LvBytes { uint8_t T[MAXL + 4 + 64]; uint8_t P[MAXL + 64]; };
-// NS: seed slots per list the block can hold; LLV: with the lane-LV scratch (9 KB) for gapped passes finished inside the block.
+// NS: seed slots per list the block can hold; LLV: with the lane-LV scratch (6 KB) for gapped passes finished inside the block.
 // k_heavy's usual shape is <32, false> = 7.5 KB: its LDS is what decides how much of a CU it leaves to the kernels of the other
 // batches in flight (18.6 KB per block with 512 slots and the lane-LV scratch: 303-345 Mreads/s on the 4-stream step; 7.5 KB: 383-388)
 template <int NS, bool LLV>
@@ -1201,64 +1218,70 @@ __device__ __attribute__((noinline)) int lv_wave(const uint8_t *T, int tlen, con
 }
 
 // ---- Landau-Vishkin distance, one candidate per lane (computeEditDistance, LandauVishkin.c:19-122) ----
-// Text: the lane's (L+4)-base window of the mixRef, nibble-packed in LDS (zero beyond tlen, like the
-// reference's zero-padded byte buffer); pattern: the read's one-hot nibbles (N = 15), shared.
-// Returns e in 0..k, or 255 for "more than k" / inactive lanes.  The distance does not depend on the
-// diagonal order, so all lanes walk the (e, d) cells in the same order.
+// Text: the lane's (L+4)-base window of the mixRef, nibble-packed and word-major in s.T (lane_text: zero beyond tlen, like the
+// reference's zero-padded byte buffer); pattern: the read's one-hot nibbles (N = 15) behind pm, a per-lane LDS address that
+// lane_pattern filled (all lanes the same one in k_gap and k_heavy).  plen + LLV_WIN == tlen <= 8 * (LLV_TW - 1), k <= LLV_K.
+// Returns e in 0..k, or 255 for "more than k" / inactive lanes.  The distance does not depend on the diagonal order, so all lanes walk
+// the (e, d) cells in the same order: e and d are wave-uniform, the d loop is unrolled over -LLV_K .. LLV_K under a scalar |d| <= e
+// test, and the row of furthest-reaching values is LLV_W registers updated in place (cell d of level e needs cells d - 1, d, d + 1
+// of level e - 1: the old d - 1 is carried).  A step is one fetch of two pattern and two text words -- both operands are LDS-typed
+// and padded, so nothing is predicated -- which serves the equality gate (LandauVishkin.c:79) and the first eight bases of the extension.
 __device__ __attribute__((noinline)) uint32_t lv_lanes(LaneLv &s, const uint32_t *pm, int plen, int tlen, int k, bool active)
 {
+    constexpr int LLV_W = 2 * LLV_K + 1;                 // diagonals -LLV_K .. LLV_K
     const int lane = (int)lane_id() & (LLV_N - 1);      // callers pass active = false for lanes >= LLV_N
-    const uint32_t *T = s.T + lane * LLV_TW;
-    const int nwp = (plen + 7) >> 3;
-    // 8 nibbles starting at base i: pattern (zeros past plen) / text (zeros outside [0, tlen); i may be negative)
-    auto wP = [&](int i) -> uint32_t {
-        const int j = i >> 3;
-        const uint32_t lo = j < nwp ? pm[j] : 0u, hi = j + 1 < nwp ? pm[j + 1] : 0u;
-        return __funnelshift_r(lo, hi, 4u * (uint32_t)(i & 7));
+    const lds_u32 T = as_lds(s.T) + lane, P = as_lds(pm);
+    // 8 nibbles of the pattern from base i and of the text from base t
+    auto fetch = [&](int i, int t, uint32_t &p, uint32_t &x) {
+        const lds_u32 pp = P + (i >> 3), tt = T + (t >> 3) * LLV_N;
+        const uint32_t p0 = pp[0], p1 = pp[1], t0 = tt[0], t1 = tt[LLV_N];
+        p = __funnelshift_r(p0, p1, 4u * (uint32_t)(i & 7));
+        x = __funnelshift_r(t0, t1, 4u * (uint32_t)(t & 7));
     };
-    auto wT = [&](int i) -> uint32_t {
-        if (i < 0) return i <= -8 ? 0u : T[0] << (4 * -i);
-        const int j = i >> 3;
-        const uint32_t lo = j < LLV_TW ? T[j] : 0u, hi = j + 1 < LLV_TW ? T[j + 1] : 0u;
-        return __funnelshift_r(lo, hi, 4u * (uint32_t)(i & 7));
+    // leading bases that match among the 8 of p / x: a base matches when mask & one-hot != 0 (LandauVishkin.c:42-53,85-96)
+    auto run_of = [](uint32_t p, uint32_t x) -> int {
+        const uint32_t y = p & x;
+        const uint32_t z = ~(((y & 0x77777777u) + 0x77777777u) | y) & 0x88888888u;     // bit 3 of a nibble: no match there
+        return z ? __builtin_ctz(z) >> 2 : 8;
     };
-    // bases matching from i on diagonal d, 8 per step: a base matches when mask & one-hot != 0 (LandauVishkin.c:42-53,85-96)
-    auto extend = [&](int d, int i, int end) -> int {
-        while (i < end) {
-            const uint32_t y = wP(i) & wT(d + i);
-            const uint32_t z = ~(((y & 0x77777777u) + 0x77777777u) | y) & 0x88888888u;     // bit 3 of a nibble: no match there
-            const int run = z ? (__ffs((int)z) - 1) >> 2 : 8;
-            i += run;
-            if (run < 8) break;
-        }
-        return i < end ? i : end;
+    // the furthest base on diagonal d from `best`: behind the equality gate when `gated` (levels >= 1), min(end, first mismatch)
+    auto reach = [&](int d, int best, bool gated) -> int {
+        uint32_t p, x;
+        fetch(best, d + best, p, x);
+        const int end = plen < tlen - d ? plen : tlen - d;
+        const bool open = !gated || ((p ^ x) & 15u) == 0;
+        int run = run_of(p, x), i = best + run;
+        if (open && run == 8) while (i < end) { fetch(i, d + i, p, x); run = run_of(p, x); i += run; if (run < 8) break; }
+        i = i < end ? i : end;                            // best >= end included: the reference sets end there
+        return open ? i : best;
     };
-    auto RD = [&](int row, int d) -> int { return (int)s.rows[row][d + LLV_K + 1][lane] - 2; };
-    auto WR = [&](int row, int d, int v) { s.rows[row][d + LLV_K + 1][lane] = (uint8_t)(v + 2); };
-    for (int row = 0; row < 2; ++row) for (int d = 0; d < LLV_W; ++d) s.rows[row][d][lane] = 0;      // -2 everywhere
+    int row[LLV_W];
+#pragma unroll
+    for (int j = 0; j < LLV_W; ++j) row[j] = -2;
     const int end0 = plen < tlen ? plen : tlen;
     uint32_t result = 255;
     bool done = !active;
     if (active) {
-        const int i = extend(0, 0, end0);
-        WR(0, 0, i);
+        const int i = reach(0, 0, false);
+        row[LLV_K] = i;
         if (i == end0) { result = (uint32_t)(plen > end0 ? plen - end0 : 0); done = true; }
     }
     for (int e = 1; e <= k; ++e) {
         if (__ballot(!done) == 0) break;
-        const int cur = e & 1, prev = cur ^ 1;
-        for (int d = -e; d <= e; ++d) {
-            if (done) continue;
-            int best = RD(prev, d) + 1;
-            const int left = RD(prev, d - 1), right = RD(prev, d + 1) + 1;
-            if (left > best) best = left;
-            if (right > best) best = right;
-            if ((wP(best) & 15u) == (wT(d + best) & 15u)) {               // equality gate (LandauVishkin.c:79)
-                const int end = plen < tlen - d ? plen : tlen - d;
-                best = best >= end ? end : extend(d, best, end);
+        int carry = -2;                                   // cell d - 1 of the level before
+#pragma unroll
+        for (int d = -LLV_K; d <= LLV_K; ++d) {
+            if ((d < 0 ? -d : d) > e) continue;
+            const int mid = row[d + LLV_K], right = d < LLV_K ? row[d + LLV_K + 1] : -2;
+            int best = mid + 1;
+            if (carry > best) best = carry;
+            if (right + 1 > best) best = right + 1;
+            carry = mid;
+            if (!done) {
+                best = reach(d, best, true);
+                if (best == plen) { result = (uint32_t)e; done = true; }
+                else row[d + LLV_K] = best;
             }
-            if (best == plen) { result = (uint32_t)e; done = true; }
-            else WR(cur, d, best);
         }
     }
     return result;
@@ -1506,10 +1529,11 @@ __device__ __attribute__((noinline)) void lv_cigar(const uint32_t *ref, W &w, Lv
 // ---------------------------------------------------------------------------------------------
 // k_align
 // ---------------------------------------------------------------------------------------------
-// the text window of one candidate for lv_lanes: tl reference masks from pos, nibble-packed, zero past the end
+// the text window of one candidate for lv_lanes: tl reference masks from pos, nibble-packed, into the lane's column of the word-major
+// T (T = LaneLv::T + lane); zero past the end, over every word lv_lanes can ask for at this tl (see LLV_TS)
 __device__ __forceinline__ void lane_text(const uint32_t *__restrict__ ref, uint32_t *T, uint32_t pos, uint32_t tl)
 {
-    const uint32_t w0 = pos >> 3, sh = (pos & 7u) * 4u, nwt = (tl + 7) >> 3;
+    const uint32_t w0 = pos >> 3, sh = (pos & 7u) * 4u, nwt = (tl + 7) >> 3, nst = ((tl - LLV_WIN + LLV_K) >> 3) + 2;
     // every word of the window is asked for before the first is used (one load, one wait, one store per word was 22 memory round trips
     // in a row per candidate)
     uint32_t wv[LLV_TW + 1];
@@ -1523,8 +1547,17 @@ __device__ __forceinline__ void lane_text(const uint32_t *__restrict__ ref, uint
             const uint32_t rem = tl - (uint32_t)j * 8;
             if (rem < 8) word &= (1u << (4 * rem)) - 1u;
         }
-        T[j] = word;
+        if ((uint32_t)j < nst) T[j * LLV_N] = word;
     }
+#pragma unroll
+    for (int j = LLV_TW; j < LLV_TS; ++j) if ((uint32_t)j < nst) T[j * LLV_N] = 0u;
+}
+// the pattern for lv_lanes: words j = first, first + step, ... of P are word(j) for j < nw and zero up to what lv_lanes can ask for
+// (see LLV_PW).  The lanes of a wave share the words of one pattern (first = lane, step = 64) or a lane fills its own (0, 1).
+template <class F>
+__device__ __forceinline__ void lane_pattern(uint32_t *P, uint32_t nw, uint32_t first, uint32_t step, F word)
+{
+    for (uint32_t j = first; j < (uint32_t)LLV_PW; j += step) P[j] = j < nw ? word(j) : 0u;
 }
 
 // A read without a gap-free hit needs Landau-Vishkin over all its candidates plus LV tracebacks for its CIGARs:
@@ -1719,6 +1752,8 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
             const bool lanes_ok = lanes_fit && W::HAS_LLV;
             if constexpr (W::HAS_LLV) if (lanes_ok) {
                 const int k0 = gap_k0;
+                WSYNC();
+                lane_pattern(w.u.llv.P, (L + 7) >> 3, lane, 64u, [&](uint32_t j) { return w.pm[strand][j]; });
                 for (uint32_t b = 0; b < n_cand; b += LLV_N) {
                     WSYNC();
                     const uint32_t i = b + lane;
@@ -1726,9 +1761,9 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
                     if (lane < LLV_N && i < n_cand) {
                         const uint32_t pos = loci[i];
                         act = !(pos > ix.ref_len || pos + L + 4 > ix.ref_len);           // ed_diff guard (editdistance.c:178)
-                        if (act) lane_text(ix.ref, w.u.llv.T + lane * LLV_TW, pos, L + 4);
+                        if (act) lane_text(ix.ref, w.u.llv.T + lane, pos, L + 4);
                     }
-                    const uint32_t e = lv_lanes(w.u.llv, w.pm[strand], (int)L, (int)L + 4, k0, act);
+                    const uint32_t e = lv_lanes(w.u.llv, w.u.llv.P, (int)L, (int)L + 4, k0, act);
                     if (lane < LLV_N && i < n_cand) cand_e[i] = (uint8_t)e;
                 }
                 WSYNC();
@@ -1928,11 +1963,10 @@ HEAVY_KERNEL(k_heavy_glob, false, true, WaveLds)    // single end with -m above 
 
 // k_gap: one item = 32 candidates of one strand of one queued read: their Landau-Vishkin distances at the bound L/10
 // (ed_diff -> computeEditDistance, editdistance.c:174-232, LandauVishkin.c:19-122), one candidate per lane
-struct GapLds { LaneLv llv; uint32_t pm[MAXL / 8]; };
 __global__ void __launch_bounds__(64)
 k_gap(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, GapBufs g)
 {
-    __shared__ GapLds s;
+    __shared__ LaneLv s;
     __shared__ uint32_t s_item;
     const uint32_t lane = lane_id();
     const uint32_t n_items = g.gctl->gap_items < g.items_cap ? g.gctl->gap_items : g.items_cap;
@@ -1947,17 +1981,17 @@ k_gap(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, GapBufs g)
         const uint32_t r = g.gq[slot];
         const uint32_t *rec = pm + (uint64_t)r * ap.pg.pm_stride;
         const uint32_t L = rec[2 * ap.pg.nw8], nw = (L + 7) >> 3;
-        for (uint32_t t = lane; t < nw; t += 64) s.pm[t] = rec[strand * ap.pg.nw8 + t];
+        lane_pattern(s.P, nw, lane, 64u, [&](uint32_t j) { return rec[strand * ap.pg.nw8 + j]; });
         const uint32_t n = g.gn[2 * slot + strand], i = chunk * LLV_N + lane;
         const size_t row = g.goff[2 * slot + strand];
         bool act = false;
         if (lane < LLV_N && i < n) {
             const uint32_t pos = g.gloci[row + i];
             act = !(pos > ix.ref_len || pos + L + 4 > ix.ref_len);               // ed_diff guard (editdistance.c:178)
-            if (act) lane_text(ix.ref, s.llv.T + lane * LLV_TW, pos, L + 4);
+            if (act) lane_text(ix.ref, s.T + lane, pos, L + 4);
         }
         WSYNC();
-        const uint32_t e = lv_lanes(s.llv, s.pm, (int)L, (int)L + 4, ap.pe ? 3 : (int)(L / 10), act);   // alnse.c:1090 / 1016-1028
+        const uint32_t e = lv_lanes(s, s.P, (int)L, (int)L + 4, ap.pe ? 3 : (int)(L / 10), act);   // alnse.c:1090 / 1016-1028
         if (lane < LLV_N && i < n) g.ge[row + i] = (uint8_t)e;
         WSYNC();
     }
@@ -2755,7 +2789,7 @@ k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, cons
           uint16_t *__restrict__ cig_out /* [n][64] */, LvTables *__restrict__ lvtab)
 {
     __shared__ WaveLds w;
-    __shared__ uint32_t lane_pm[LLV_N][LLV_TW];
+    __shared__ uint32_t lane_pm[LLV_N][LLV_PW];
     const uint32_t c = blockIdx.x, lane = lane_id();
     if (c >= n_cases) return;
     const uint32_t off = offs[c], L = offs[c + 1] - off, p = pos[c];
@@ -2784,9 +2818,9 @@ k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, cons
     const uint32_t gn = fit ? lane_n[c] : 0u;
     if (gn) {                                                             // gn is 1 or LLV_N
         const uint32_t m = lane_case[lane_first[c] + lane % gn], mo = offs[m], mp = pos[m];      // same L and k as case c
-        for (uint32_t j = 0; j < nw; ++j) lane_pm[lane][j] = pm_word(mo, j);
+        lane_pattern(lane_pm[lane], nw, 0u, 1u, [&](uint32_t j) { return pm_word(mo, j); });
         const bool act = !(mp > ix.ref_len || mp + L + 4 > ix.ref_len);   // ed_diff guard, as k_gap has it
-        if (act) lane_text(ix.ref, w.u.llv.T + lane * LLV_TW, mp, L + 4);
+        if (act) lane_text(ix.ref, w.u.llv.T + lane, mp, L + 4);
         WSYNC();
         const uint32_t el = lv_lanes(w.u.llv, lane_pm[lane], (int)L, (int)L + 4, k, act);
         if (lane < gn) out[(size_t)m * 4 + 2] = el == 255 ? -1 : (int32_t)el;

@@ -396,8 +396,9 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
         // (pop_ranged, salt_align.hip) it follows the waves again (profiles/r03/ab_heavy_ranged_pops.log)
         if (const char *e2 = getenv("SALT_GPU_HEAVY_PER_CU")) { int v = atoi(e2); if (v > 0 && (uint32_t)v <= heavy_blocks_per_cu()) per_cu = (uint32_t)v; }
         ws->heavy_blocks = (uint32_t)prop.multiProcessorCount * per_cu;    // persistent one-wave blocks
-        // k_gap's items (64 candidates' Landau-Vishkin distances, ~70 us each) are independent and need no table of their own: its grid is
-        // what its 9.3 KB of LDS admit per CU (16), not k_heavy's (13 079 items per 10^6 GRCh38-scale reads: 0.54 ms on 2 048 waves, 0.31 on 4 096)
+        // k_gap's items (64 candidates' Landau-Vishkin distances, tens of microseconds each) are independent and need no table of their own: its grid is
+        // 16 per CU, not k_heavy's (13 079 items per 10^6 GRCh38-scale reads: 0.54 ms on 2 048 waves, 0.31 on 4 096, with the 9.3 KB of LDS a block
+        // held then; at 6.2 KB and 98 VGPRs sixteen is what the registers admit, and 8 / 12 / 16 were taken again: profiles/r13/ab_gap_grid.log)
         uint32_t gap_per_cu = 16;
         if (const char *e2 = getenv("SALT_GPU_GAP_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) gap_per_cu = (uint32_t)v; }
         ws->gap_blocks = (uint32_t)prop.multiProcessorCount * gap_per_cu;
