@@ -313,14 +313,16 @@ int  salt_gpu_buffer_equal(int device, const void *a, const void *b, uint64_t by
 /* Unit entry of the candidate rule the kernels evaluate on UNSORTED lists: case i has candidates
  * pos/val[offs[i]..offs[i+1]) (val > vmax = no candidate) and the incoming bound bound_in[i].  mode 0: gap-free rule
  * (code_kmismatch, alnse.c:348-369; distances 0..3, range filter pos < ref_len) by rule_unsorted; 1: the same by
- * rule_sparse; 2: gapped rule (code_kdiff, alnse.c:371-393; distances 0..12, filter !(pos + L + 4 >= ref_len)).
+ * rule_sparse; 2: gapped rule (code_kdiff, alnse.c:371-393; distances 0..12, filter !(pos + L + 4 >= ref_len)); 3: as 1 by
+ * rule_sparse on half-waves (32 lanes, what k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b.
  * out[i][18] = found, best_pos, best_dist, n_hits, a0, bound_out, then 6 x (hit_pos, hit_dist) in position order. */
 int  salt_gpu_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *val, const uint32_t *offs, const uint32_t *bound_in,
                         uint32_t L, uint32_t ref_len, int mode, uint32_t *out);
 
 /* Unit entry of the candidate verifiers (tests): case i = read seqs[offs[i]..offs[i+1]) against candidates
  * cand[cand_offs[i]..cand_offs[i+1]) (<= 256) on the 4-bit mixRef `ref_words`; mode 0 = one candidate per lane, 1 / 2 = four / eight lanes
- * per candidate (reads <= 120 / 248 bases), 3 / 4 = the two-strand variants of 1 / 2.  out[j] = masked Hamming distance 0..3 of candidate
+ * per candidate (reads <= 120 / 248 bases), 3 / 4 = the two-strand variants of 1 / 2, 5 / 6 = 3 / 4 on half-waves (32 lanes, what
+ * k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b.  out[j] = masked Hamming distance 0..3 of candidate
  * j or 255 (more, or a candidate at or beyond ref_len -- a locate that wrapped below 0, alnse.c:672-673,762 -- which must never be
  * dereferenced).  Mirrors ed_mismatch (editdistance.c:88-163) under code_kmismatch's cap (alnse.c:348-369). */
 int  salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs,

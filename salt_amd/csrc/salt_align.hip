@@ -11,6 +11,7 @@
 //             query.c:270-333, LandauVishkin.c:19-122,176-470, editdistance.c:88-284)
 //
 // All arithmetic is integer; outputs are bit-exact with the reference CPU path.
+#include <type_traits>
 #include "salt_device.h"
 #include "salt_kernels.h"
 
@@ -1128,15 +1129,51 @@ __device__ __forceinline__ void verify_two_phase(const uint32_t *__restrict__ re
     }
 }
 
-// Both strands of one read in the same trips (k_light): candidates c0[0..n0) use pm0, c1[0..n1) use pm1.
-template <int LN = 4>
+// ---- lane groups ------------------------------------------------------------------------------
+// The light kernels give a read a whole wave (GW = 64) or one of its halves (GW = 32: two reads per wave, each on its own).  What
+// such a group asks of its lanes, all of it settled at compile time: the lane inside the group; a ballot over the group (64: the
+// wave's mask; 32: this half's 32 bits of it, by a select and not a 64-bit shift); a broadcast from a group lane (64: v_readlane, the
+// index is wave-uniform; 32: a shuffle from the half's base); the lanes-below mask; the group-wide add.
+__device__ __forceinline__ uint32_t popc(uint32_t m) { return (uint32_t)__popc(m); }
+__device__ __forceinline__ uint32_t popc(uint64_t m) { return (uint32_t)__popcll(m); }
+__device__ __forceinline__ int first_bit(uint32_t m) { return __ffs((int)m) - 1; }
+__device__ __forceinline__ int first_bit(uint64_t m) { return __ffsll((long long)m) - 1; }
+template <int GW> struct LaneGroup {
+    static_assert(GW == 64 || GW == 32, "a wave or half of one");
+    typedef std::conditional_t<GW == 64, uint64_t, uint32_t> mask_t;
+    static __device__ __forceinline__ uint32_t lane() { return lane_id() & (uint32_t)(GW - 1); }
+    static __device__ __forceinline__ mask_t ballot(bool x)
+    {
+        const uint64_t m = __ballot(x);
+        if constexpr (GW == 64) return m; else return (lane_id() & 32u) ? (uint32_t)(m >> 32) : (uint32_t)m;
+    }
+    static __device__ __forceinline__ uint32_t bcast(uint32_t v, int src)
+    {
+        if constexpr (GW == 64) return (uint32_t)__builtin_amdgcn_readlane((int)v, src);
+        else return (uint32_t)__shfl((int)v, (int)(lane_id() & 32u) + src);
+    }
+    static __device__ __forceinline__ mask_t below() { return ((mask_t)1 << lane()) - (mask_t)1; }
+    static __device__ __forceinline__ uint32_t sum(uint32_t v)
+    {
+        for (int o = GW / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+        return v;
+    }
+};
+
+// Both strands of one read in the same trips (the light kernels): candidates c0[0..n0) use pm0, c1[0..n1) use pm1.  A group of GW
+// lanes works on them, GW / LN rows per group of loads, four groups of loads in flight.
+template <int LN = 4, int GW = 64>
 __device__ __forceinline__ void verify_quads_2(const uint32_t *__restrict__ ref, uint32_t ref_len, const uint32_t *pm0, const uint32_t *pm1, uint32_t L,
                                                const uint32_t *c0, uint32_t n0, const uint32_t *c1, uint32_t n1, uint8_t *o0, uint8_t *o1)
 {
-    constexpr uint32_t CPW = 64u / LN;
-    const uint32_t lane = lane_id(), sub = lane & (uint32_t)(LN - 1), q = lane / (uint32_t)LN;
+    constexpr uint32_t CPW = (uint32_t)GW / LN;
+    const uint32_t lane = LaneGroup<GW>::lane(), sub = lane & (uint32_t)(LN - 1), q = lane / (uint32_t)LN;
     const uint32_t nw = (L + 7) >> 3, n = n0 + n1;
     const uint32_t nvalid = L > 32u * sub ? (L - 32u * sub < 32u ? L - 32u * sub : 32u) : 0u;
+    // A lane whose words lie behind the window fetches nothing.  Its pattern words are zero, so the counts are the same with and without
+    // this, at either width; it stays with the one instantiation that had it (two 150-base reads a wave), so that the others compile to
+    // what they were.
+    const bool behind = LN == 8 && GW == 32 && !(4u * sub < nw + 1u);
     uint32_t pa[4], pb[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) { const bool in = (4 * sub + t) < nw; pa[t] = in ? pm0[4 * sub + t] : 0u; pb[t] = in ? pm1[4 * sub + t] : 0u; }
@@ -1148,8 +1185,9 @@ __device__ __forceinline__ void verify_quads_2(const uint32_t *__restrict__ ref,
             const uint32_t c = b + CPW * g + q;
             act[g] = c < n; rev[g] = c >= n0;
             pos[g] = act[g] ? (rev[g] ? c1[c - n0] : c0[c]) : 0u;
-            if (pos[g] >= ref_len) pos[g] = 0xFFFFFFFFu;
-            x[g] = *reinterpret_cast<const u32x4_a4 *>(ref + ((pos[g] == 0xFFFFFFFFu ? 0u : pos[g]) >> 3) + 4 * sub);
+            if (pos[g] >= ref_len) pos[g] = 0xFFFFFFFFu;                 // wrapped below 0 (see mismatch_capped): no load, INF
+            if (behind) x[g] = u32x4_a4{ 0u, 0u, 0u, 0u };
+            else x[g] = *reinterpret_cast<const u32x4_a4 *>(ref + ((pos[g] == 0xFFFFFFFFu ? 0u : pos[g]) >> 3) + 4 * sub);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -1386,45 +1424,48 @@ __device__ __forceinline__ void rule_unsorted(const uint32_t *pos, const uint8_t
     bound = best_v < bound ? best_v : bound;
 }
 
-// rule_unsorted for short lists with few candidates inside the bound (k_light): the reductions walk the set bits of a
-// ballot with v_readlane, i.e. they cost scalar instructions per candidate instead of six cross-lane steps per value.
-template <int VMAX, bool GAPF>
+// rule_unsorted for short lists with few candidates inside the bound (the light kernels), on a group of GW lanes: lane i of the group
+// holds candidates i, i + GW, ...  The reductions walk the set bits of a ballot with a broadcast each, i.e. they cost scalar
+// instructions per candidate instead of six cross-lane steps per value.
+template <int VMAX, bool GAPF, int GW = 64>
 __device__ __forceinline__ void rule_sparse(const uint32_t *pos, const uint8_t *val, const uint32_t n, const uint32_t L, const uint32_t ref_len,
                                             uint32_t &bound, bool &any, uint32_t &best_pos, uint32_t &best_v,
                                             uint32_t &n_hits, uint32_t &a0, uint32_t *hit_pos, uint8_t *hit_nd)
 {
-    const uint32_t lane = lane_id();
+    typedef LaneGroup<GW> G;
+    typedef typename G::mask_t mask_t;
+    const uint32_t lane = G::lane();
     const uint32_t NONE = 0xFFFFFFFFu;
     auto in_range = [&](uint32_t p) -> bool { return GAPF ? !(p + L + 4 >= ref_len) : p < ref_len; };
-    uint32_t mp[VMAX + 1];
-#pragma unroll
-    for (int t = 0; t <= VMAX; ++t) mp[t] = NONE;
     any = false; n_hits = 0;
     if (n == 0) return;
-    if (n <= 64) {                                            // the usual case: every candidate inside the bound is the same locus
+    if (n <= (uint32_t)GW) {                                  // the usual case: every candidate inside the bound is the same locus
         uint32_t p = 0, v = NONE;
         if (lane < n) { p = pos[lane]; v = val[lane]; }
         const bool ok = v <= bound && in_range(p);
-        const uint64_t m = __ballot(ok);
+        const mask_t m = G::ballot(ok);
         if (m == 0) return;
-        const int l0 = __ffsll((long long)m) - 1;
-        const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)p, l0);
-        if (__ballot(ok && p != p0) == 0) {
-            const uint32_t v0 = (uint32_t)__builtin_amdgcn_readlane((int)v, l0);
+        const int l0 = first_bit(m);
+        const uint32_t p0 = G::bcast(p, l0);
+        if (G::ballot(ok && p != p0) == 0) {
+            const uint32_t v0 = G::bcast(v, l0);
             any = true; best_pos = p0; best_v = v0; n_hits = 1; a0 = v0;
             if (lane == 0) { hit_pos[0] = p0; hit_nd[0] = (uint8_t)v0; }
             bound = v0 < bound ? v0 : bound;
             return;
         }
     }
-    for (uint32_t b = 0; b < n; b += 64) {
+    uint32_t mp[VMAX + 1];
+#pragma unroll
+    for (int t = 0; t <= VMAX; ++t) mp[t] = NONE;
+    for (uint32_t b = 0; b < n; b += GW) {
         const uint32_t i = b + lane;
         uint32_t p = 0, v = NONE;
         if (i < n) { p = pos[i]; v = val[i]; }
-        uint64_t m = __ballot(v <= bound && in_range(p));
+        mask_t m = G::ballot(v <= bound && in_range(p));
         while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)p, l), vl = (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+            const int l = first_bit(m);
+            const uint32_t pl = G::bcast(p, l), vl = G::bcast(v, l);
 #pragma unroll
             for (int t = 0; t <= VMAX; ++t) if (vl == (uint32_t)t && pl < mp[t]) mp[t] = pl;
             m &= m - 1;
@@ -1440,18 +1481,18 @@ __device__ __forceinline__ void rule_sparse(const uint32_t *pos, const uint8_t *
     uint32_t last_p = 0;
     for (uint32_t h = 0; h < (uint32_t)NHIT; ++h) {
         uint32_t cur_p = NONE, cur_v = 0;
-        for (uint32_t b = 0; b < n; b += 64) {
+        for (uint32_t b = 0; b < n; b += GW) {
             const uint32_t i = b + lane;
             uint32_t p = 0, v = NONE;
             if (i < n) { p = pos[i]; v = val[i]; }
             uint32_t lim = NONE;
 #pragma unroll
             for (int t = 1; t <= VMAX; ++t) if (v == (uint32_t)t) lim = before[t];
-            uint64_t m = __ballot(v <= bound && in_range(p) && p < lim && (h == 0 || p > last_p));
+            mask_t m = G::ballot(v <= bound && in_range(p) && p < lim && (h == 0 || p > last_p));
             while (m) {
-                const int l = __ffsll((long long)m) - 1;
-                const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)p, l);
-                if (pl < cur_p) { cur_p = pl; cur_v = (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+                const int l = first_bit(m);
+                const uint32_t pl = G::bcast(p, l);
+                if (pl < cur_p) { cur_p = pl; cur_v = G::bcast(v, l); }
                 m &= m - 1;
             }
         }
@@ -2118,9 +2159,10 @@ k_cigar(IndexView ix, PackGeom pg, const uint32_t *__restrict__ pm, salt_result_
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_light: one wave per read, the common case in three memory round trips.
+// The light kernels (k_light, k_light2): one body, light_read, at two widths -- a wave per read, or half a wave.  The common case in
+// three memory round trips.
 //
-// A read stays here when (a) it is short enough for the small LDS image (L <= 160, <= 16 seed slots),
+// A read stays here when (a) it is short enough for the small LDS image (a wave: L <= 160, <= 16 seed slots; a half: 120 / 248, <= 8),
 // (b) each of its four seed lists (C/R x strand) enumerates at most 64 suffix-array rows, so that the
 // max_locate cap (>= 128) can never bite and locate order is irrelevant once the loci are sorted, and
 // (c) a gap-free hit exists.  Everything else is queued for k_heavy, which replays the reference's
@@ -2151,37 +2193,45 @@ k_queue_pack(const uint32_t *__restrict__ qseg, const QueueRange *__restrict__ r
     for (uint32_t i = threadIdx.x; i < cnt_s; i += 256) queue[base_s + i] = src[i];
 }
 
-static constexpr int LT_SLOTS = 16;      // seed slots per list handled here
 static constexpr int LT_LOCI = 128;      // loci per strand handled here
-static constexpr int LT_MAXL = 160;
+static constexpr int LT_MAXL = 160;      // longest read that gets a whole wave here
+static constexpr int L2_SLOTS = 8;       // seed slots per list of a read that gets a half-wave
 
-struct LightLds {
-    uint32_t pm[2][LT_MAXL / 8];
-    uint32_t sp[4][LT_SLOTS], off[4][LT_SLOTS];
-    uint32_t pre[4][LT_SLOTS + 1];       // rows enumerated before slot i of list l
+// A read's LDS record: SLOTS seed slots per list (a quarter of the group's lanes), PMW one-hot words per strand
+template <int SLOTS, int PMW> struct LightRec {
+    uint32_t pm[2][PMW];
+    uint32_t sp[4][SLOTS], off[4][SLOTS];
+    uint32_t pre[4][SLOTS + 1];          // rows enumerated before slot i of list l
     uint32_t loci[2][LT_LOCI];
     uint32_t hit_pos[2][NHIT];
     uint8_t  hit_nd[2][NHIT];
     uint8_t  val[2][LT_LOCI];
 };
+// a wave's read: 16 slots, 160 bases; a half-wave's: 8 slots, 32 words (reads up to 120 bases use 15 a strand, up to 248 bases 31)
+template <int GW> using LightLds = LightRec<GW / 4, GW == 64 ? LT_MAXL / 8 : 32>;
 
-static constexpr int LT_WAVES = 2;       // independent reads (waves) per workgroup: half the workgroups to dispatch (as k_light2)
-__global__ void __launch_bounds__(64 * LT_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
-k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
-        const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
-        uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges, unsigned long long *__restrict__ ctr)
+// The body of both light kernels: read r on a group of GW lanes (LaneGroup), every ballot / shuffle inside the group.
+// LN: lanes per located row in the window check: 4 cover reads up to 120 bases, 8 up to 248; 0 = picked by the read's length.
+// INSTR: the access counters and phase stamps behind `ctr`, and the diagnostics build's early exits (ap.dbg_stop); without it none of
+// that is compiled.
+template <int GW, int LN, bool INSTR>
+__device__ __forceinline__ void light_read(const IndexView &ix, const AlignParams &ap, const uint32_t *__restrict__ pm,
+                                           const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
+                                           uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges,
+                                           unsigned long long *__restrict__ ctr, LightLds<GW> &w, const uint32_t r)
 {
-    __shared__ LightLds w_all[LT_WAVES];
-    LightLds &w = w_all[threadIdx.x >> 6];
-    const uint32_t lane = lane_id();
-    const uint64_t lt = (1ull << lane) - 1ull;
-    const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * LT_WAVES + (threadIdx.x >> 6));
-    if (r >= ap.n_reads) return;
+    typedef LaneGroup<GW> G;
+    typedef typename G::mask_t mask_t;
+    constexpr uint32_t SLOTS = GW / 4, HALF = GW / 2;
+    constexpr uint32_t LMAX = LN == 4 ? 120u : LN == 8 ? 248u : (uint32_t)LT_MAXL;
+    static_assert(LMAX <= 8 * sizeof(w.pm[0]) / 4 && (LN != 0 || LMAX <= 248u), "the read fits the record and the window check");
+    const uint32_t lane = G::lane();
+    const mask_t lt = G::below();
     const uint32_t *rec = pm + (uint64_t)r * ap.pg.pm_stride;               // k_pack's one-hot words of this read, both strands
     const uint32_t L = rec[2 * ap.pg.nw8];
-    bool heavy = L > LT_MAXL || L < (uint32_t)ap.l_seed || ap.spr > LT_SLOTS || ap.max_locate < 2 * 64;
-    uint32_t c_sa_c = 0, c_sa_r = 0, c_verify = 0, c_vwords = 0, c_loci = 0;
-    const bool prof = ctr && (r & 127u) == 0;                                // phase clock of every 128th read
+    bool heavy = L > LMAX || L < (uint32_t)ap.l_seed || ap.spr > SLOTS || ap.max_locate < 2 * 64;
+    uint32_t c_sa_c = 0, c_sa_r = 0, c_verify = 0, c_loci = 0;
+    const bool prof = INSTR && ctr && (r & 127u) == 0;                       // phase clock of every 128th read
     uint64_t tp = prof ? __builtin_amdgcn_s_memtime() : 0;
     auto stamp = [&](int slot) {
         if (!prof) return;
@@ -2189,43 +2239,51 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
         if (lane == 0) atomicAdd(ctr + slot, (unsigned long long)(n - tp));
         tp = n;
     };
+    // a suffix-array row of list l (or, with bit 31 of `of`, a genome position) less the seed's offset, and whether alnse_locate_alt
+    // keeps it (alnse.c:672-673,715-717)
+    auto locate = [&](uint32_t l, uint32_t j, uint32_t of, uint32_t &p) -> bool {
+        p = ((of >> 31) ? j : (l & 1) ? ix.r_pos[j] : ix.c_sa[j]) - (of & 0x7FFFFFFFu);
+        return (l & 1) ? !(p > ix.ref_len || p + L > ix.ref_len) : !(p + L > ix.ref_len);
+    };
 
     if (!heavy) {
         // ---- round trip 1: the read (as one-hot nibble words, both strands) and its seeds ----
         const uint32_t nw = (L + 7) >> 3;
+        __builtin_assume(nw <= (LMAX + 7) / 8);
         uint32_t n_amb = 0;
-        if (lane < 2 * nw) {
-            const uint32_t s = lane >= nw, j = s ? lane - nw : lane;
+        for (uint32_t x = lane; x < 2 * nw; x += GW) {                      // (one trip unless 150-base reads share a wave)
+            const uint32_t s = x >= nw, j = s ? x - nw : x;
             const uint32_t word = rec[s * ap.pg.nw8 + j];
             w.pm[s][j] = word;
-            if (!s) n_amb = (uint32_t)__popc(word & (word >> 1) & (word >> 2) & (word >> 3) & 0x11111111u);   // N = all four bits
+            if (!s) n_amb += popc(word & (word >> 1) & (word >> 2) & (word >> 3) & 0x11111111u);   // N = all four bits
         }
-        if (ap.max_amb < L)                                                 // (uniform) otherwise the limit cannot be passed
-            for (int o = 32; o > 0; o >>= 1) n_amb += (uint32_t)__shfl_xor((int)n_amb, o);
-        if (n_amb > ap.max_amb) {                                           // alnse.c:1328 / alnpe.c:495: record left untouched
-            if (lane == 0) {
-                salt_result_t *out = results + r;
-                out->pos = 0xFFFFFFFFu; out->strand = 3; out->n_diff = 255; out->is_gap = 255; out->mapq = 0;
-                out->b0 = -1; out->b1 = -1; out->seq_start = 0; out->seq_end = (uint16_t)(L - 1);
-                out->n_hits[0] = out->n_hits[1] = 0; out->n_cigar = 0; out->skipped = 1;
+        if (ap.max_amb < L) {                                               // (uniform) otherwise the limit cannot be passed
+            n_amb = G::sum(n_amb);
+            if (n_amb > ap.max_amb) {                                       // alnse.c:1328 / alnpe.c:495: record left untouched
+                if (lane == 0) {
+                    salt_result_t *out = results + r;
+                    out->pos = 0xFFFFFFFFu; out->strand = 3; out->n_diff = 255; out->is_gap = 255; out->mapq = 0;
+                    out->b0 = -1; out->b1 = -1; out->seq_start = 0; out->seq_end = (uint16_t)(L - 1);
+                    out->n_hits[0] = out->n_hits[1] = 0; out->n_cigar = 0; out->skipped = 1;
+                }
+                return;
             }
-            return;
         }
-        uint32_t tot[4] = { 0, 0, 0, 0 };
-        bool small = false;
+        uint32_t tot[4];
+        bool small;
         {
             // lane = (list, slot); list: 0 C/fwd 1 R/fwd 2 C/rev 3 R/rev.  The reference orders each list by
             // interval size (alnse.c:307-308), which only decides what is located first when the max_locate
             // cap bites; here it cannot (<= 64 rows per list), and the loci are sorted afterwards anyway.
-            const uint32_t l = lane >> 4, slot = lane & 15u;
+            const uint32_t l = lane / SLOTS, slot = lane % SLOTS;
             uint4 v = make_uint4(1, 0, 0, 0);
             if (slot < ap.spr) { v = ((l & 1) ? sai_r : sai_c)[((uint64_t)r * 2u + (l >> 1)) * ap.spr + slot]; if (l & 1) v = sai_r_row(v, ap.epoch); }
             uint32_t sz = v.w ? v.y - v.x + 1u : 0u;
             if (sz > 65u) sz = 65u;                                         // keeps the sums below from wrapping
-            uint32_t inc = sz;                                              // inclusive prefix sum within the 16-lane row
-            for (int o = 1; o < 16; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, o, 16); if (slot >= (uint32_t)o) inc += t; }
-            for (int q = 0; q < 4; ++q) tot[q] = (uint32_t)__builtin_amdgcn_readlane((int)inc, 16 * q + 15);
-            small = tot[0] <= 16 && tot[1] <= 16 && tot[2] <= 16 && tot[3] <= 16;       // (uniform) the usual case
+            uint32_t inc = sz;                                              // inclusive prefix sum within the list's row of lanes
+            for (int o = 1; o < (int)SLOTS; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, o, SLOTS); if (slot >= (uint32_t)o) inc += t; }
+            for (int q = 0; q < 4; ++q) tot[q] = G::bcast(inc, (int)SLOTS * q + (int)SLOTS - 1);
+            small = tot[0] <= SLOTS && tot[1] <= SLOTS && tot[2] <= SLOTS && tot[3] <= SLOTS;      // (uniform) the usual case
             if (small) {
                 // every seed writes the suffix-array rows of its interval where the row lanes of its list will look them up
                 for (uint32_t k2 = 0; k2 < sz; ++k2) { w.sp[l][inc - sz + k2] = v.x + k2; w.off[l][inc - sz + k2] = v.z | (v.w == 2 ? 0x80000000u : 0u); }
@@ -2238,79 +2296,85 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
         WSYNC();
         stamp(SALT_CTR_LT_SEEDS);
         for (int l = 0; l < 4; ++l) heavy |= tot[l] > 64;
-        if (ap.dbg_stop == 1) { if (lane == 0) results[r].pos = tot[0] + tot[1] + tot[2] + tot[3] + w.pm[0][0] + w.pm[1][1]; return; }
+        if (INSTR && ap.dbg_stop == 1) { if (lane == 0) results[r].pos = tot[0] + tot[1] + tot[2] + tot[3] + w.pm[0][0] + w.pm[1][1]; return; }
         if (!heavy) {
-            // ---- round trip 2: every suffix-array row of the four lists at once ----
-            uint32_t n_s[2];
+            // ---- round trip 2: the suffix-array rows of the four lists ----
+            uint32_t n_s[2] = { 0, 0 };
             if (small) {
-                // lane = (list, row): at most 16 rows per list, so one lane per row covers all four lists in one go
-                const uint32_t l = lane >> 4, x = lane & 15u;
+                // lane = (list, row): at most SLOTS rows per list, so one lane per row covers all four lists in one go
+                const uint32_t l = lane / SLOTS, x = lane % SLOTS;
                 const uint32_t tl = l == 0 ? tot[0] : l == 1 ? tot[1] : l == 2 ? tot[2] : tot[3];
                 bool keep = false; uint32_t p = 0;
-                if (x < tl) {
-                    const uint32_t j = w.sp[l][x], of = w.off[l][x];
-                    p = ((of >> 31) ? j : (l & 1) ? ix.r_pos[j] : ix.c_sa[j]) - (of & 0x7FFFFFFFu);
-                    keep = (l & 1) ? !(p > ix.ref_len || p + L > ix.ref_len) : !(p + L > ix.ref_len);       // alnse.c:672-673,715-717
-                }
+                if (x < tl) keep = locate(l, w.sp[l][x], w.off[l][x], p);
                 stamp(SALT_CTR_LT_LOCATE);
-                if (ap.dbg_stop == 2) { if (__ballot(p == 12345u) == 1) results[r].pos = p; return; }
-                const uint64_t km = __ballot(keep);
-                const uint32_t s = lane >> 5, ms = (uint32_t)(km >> (32 * s));
-                WSYNC();                                                    // the row table aliases nothing below, but keep LDS ordered
-                if (keep) w.loci[s][(uint32_t)__popc(ms & ((1u << (lane & 31u)) - 1u))] = p;
-                n_s[0] = (uint32_t)__popc((uint32_t)km); n_s[1] = (uint32_t)__popc((uint32_t)(km >> 32));
-                c_sa_c += tot[0] + tot[2]; c_sa_r += tot[1] + tot[3]; c_loci += n_s[0] + n_s[1];
+                if (INSTR && ap.dbg_stop == 2) { if (__ballot(p == 12345u) == 1) results[r].pos = p; return; }
+                const mask_t km = G::ballot(keep);                          // a strand's two lists are one half of it
+                const uint32_t k0 = (uint32_t)(km & (((mask_t)1 << HALF) - 1)), k1 = (uint32_t)(km >> HALF), s = lane / HALF;
+                if (keep) w.loci[s][popc((s ? k1 : k0) & ((1u << (lane % HALF)) - 1u))] = p;
+                n_s[0] = popc(k0); n_s[1] = popc(k1);
+                c_sa_c += tot[0] + tot[2]; c_sa_r += tot[1] + tot[3];
             } else {
-            uint32_t pos4[4]; bool keep4[4];
-            for (int l = 0; l < 4; ++l) {
-                keep4[l] = false; pos4[l] = 0;
-                if (lane < tot[l]) {
+                // row x of list l: its seed slot by the prefix sums (empty slots, with equal sums, are skipped), then as above
+                auto locate_row = [&](uint32_t l, uint32_t x, uint32_t &p) -> bool {
                     uint32_t i = 0;
-                    while (w.pre[l][i + 1] <= lane) ++i;                   // skips empty slots (equal prefix sums)
-                    const uint32_t j = w.sp[l][i] + (lane - w.pre[l][i]), of = w.off[l][i];
-                    const uint32_t p = ((of >> 31) ? j : (l & 1) ? ix.r_pos[j] : ix.c_sa[j]) - (of & 0x7FFFFFFFu);
-                    pos4[l] = p;
-                    keep4[l] = (l & 1) ? !(p > ix.ref_len || p + L > ix.ref_len) : !(p + L > ix.ref_len);   // alnse.c:672-673,715-717
+                    while (w.pre[l][i + 1] <= x) ++i;
+                    return locate(l, w.sp[l][i] + (x - w.pre[l][i]), w.off[l][i], p);
+                };
+                if constexpr (GW == 64) {
+                    // A list has at most 64 rows, one a lane: the loads of all four lists are in flight before the first ballot.
+                    uint32_t pos4[4]; bool keep4[4];
+                    for (int l = 0; l < 4; ++l) {
+                        keep4[l] = false; pos4[l] = 0;
+                        if (lane < tot[l]) keep4[l] = locate_row(l, lane, pos4[l]);
+                    }
+                    stamp(SALT_CTR_LT_LOCATE);
+                    if (INSTR && ap.dbg_stop == 2) { const uint32_t x = pos4[0] + pos4[1] + pos4[2] + pos4[3]; if (__ballot(x == 12345u) == 1) results[r].pos = x; return; }
+                    for (int s = 0; s < 2; ++s) {                           // both lists of a strand, as located (no order, duplicates stay)
+                        const mask_t mc = G::ballot(keep4[2 * s]), mr = G::ballot(keep4[2 * s + 1]);
+                        const uint32_t nc = popc(mc);
+                        if (keep4[2 * s]) w.loci[s][popc(mc & lt)] = pos4[2 * s];
+                        if (keep4[2 * s + 1]) w.loci[s][nc + popc(mr & lt)] = pos4[2 * s + 1];
+                        n_s[s] = nc + popc(mr);
+                    }
+                } else {
+                    // Half a wave needs two trips for such a list, and eight rows a lane in flight do not fit the 64 registers that 8
+                    // waves a SIMD leave (58 - 60 are in use): list by list, a trip at a time, as this kernel always went.  Neither
+                    // width was measured with the other's order.
+                    for (int l = 0; l < 4; ++l) {
+                        const int s = l >> 1;
+                        for (uint32_t x = lane; x - lane < tot[l]; x += GW) {     // (x - lane) is the same for the whole group: a uniform trip count
+                            bool keep = false; uint32_t p = 0;
+                            if (x < tot[l]) keep = locate_row(l, x, p);
+                            const mask_t km = G::ballot(keep);
+                            if (keep) w.loci[s][n_s[s] + popc(km & lt)] = p;
+                            n_s[s] += popc(km);
+                        }
+                    }
                 }
+                c_sa_c += tot[0] + tot[2]; c_sa_r += tot[1] + tot[3];
             }
-            stamp(SALT_CTR_LT_LOCATE);
-            if (ap.dbg_stop == 2) { const uint32_t x = pos4[0] + pos4[1] + pos4[2] + pos4[3]; if (__ballot(x == 12345u) == 1) results[r].pos = x; return; }
-            for (int s = 0; s < 2; ++s) {                                   // both lists of a strand, as located (no order, duplicates stay)
-                const uint64_t mc = __ballot(keep4[2 * s]), mr = __ballot(keep4[2 * s + 1]);
-                const uint32_t nc = (uint32_t)__popcll(mc);
-                if (keep4[2 * s]) w.loci[s][(uint32_t)__popcll(mc & lt)] = pos4[2 * s];
-                if (keep4[2 * s + 1]) w.loci[s][nc + (uint32_t)__popcll(mr & lt)] = pos4[2 * s + 1];
-                n_s[s] = nc + (uint32_t)__popcll(mr);
-                c_sa_c += tot[2 * s]; c_sa_r += tot[2 * s + 1]; c_loci += n_s[s];
-            }
-            }
+            c_loci += n_s[0] + n_s[1];
             WSYNC();
             stamp(SALT_CTR_LT_SORT);
-            if (ap.dbg_stop == 3) { if (lane == 0) results[r].pos = w.loci[0][0] + w.loci[1][0] + n_s[0] + n_s[1]; return; }
-            // ---- round trip 3: masked Hamming distance of every located row of both strands ----
+            if (INSTR && ap.dbg_stop == 3) { if (lane == 0) results[r].pos = w.loci[0][0] + w.loci[1][0] + n_s[0] + n_s[1]; return; }
+            // ---- round trip 3: masked Hamming distance of every located row of both strands, 4 or 8 lanes per row ----
+            if (LN == 4 || (LN == 0 && L <= 120)) verify_quads_2<4, GW>(ix.ref, ix.ref_len, w.pm[0], w.pm[1], L, w.loci[0], n_s[0], w.loci[1], n_s[1], w.val[0], w.val[1]);
+            else verify_quads_2<8, GW>(ix.ref, ix.ref_len, w.pm[0], w.pm[1], L, w.loci[0], n_s[0], w.loci[1], n_s[1], w.val[0], w.val[1]);
+            WSYNC();
+            stamp(SALT_CTR_LT_VERIFY);
+            if (INSTR && ap.dbg_stop == 4) { if (__ballot(w.val[0][0] + w.val[1][0] == 12345u) == 1) results[r].pos = w.val[0][0]; return; }
+            c_verify += n_s[0] + n_s[1];
+            // ---- the sequential best/first-hit rule (alnse.c:348-369, 1079-1083) on the unsorted rows: rule_sparse ----
             uint32_t bound = 3, q_pos = 0xFFFFFFFFu, q_strand = 3, q_ndiff = 255;
             uint32_t n_hits_s[2] = { 0, 0 }, a0[2] = { 0, 0 };
             bool found[2] = { false, false };
-            {
-                if (L <= 120) verify_quads_2(ix.ref, ix.ref_len, w.pm[0], w.pm[1], L, w.loci[0], n_s[0], w.loci[1], n_s[1], w.val[0], w.val[1]);
-                else if (L <= 248) verify_quads_2<8>(ix.ref, ix.ref_len, w.pm[0], w.pm[1], L, w.loci[0], n_s[0], w.loci[1], n_s[1], w.val[0], w.val[1]);
-                else
-                    for (int s = 0; s < 2; ++s)
-                        for (uint32_t i = lane; i < n_s[s]; i += 64) w.val[s][i] = (uint8_t)mismatch_capped(ix, w.pm[s], L, w.loci[s][i]);
-                WSYNC();
-                stamp(SALT_CTR_LT_VERIFY);
-                if (ap.dbg_stop == 4) { if (__ballot(w.val[0][0] + w.val[1][0] == 12345u) == 1) results[r].pos = w.val[0][0]; return; }
-                c_verify += n_s[0] + n_s[1];
-                // ---- the sequential best/first-hit rule (alnse.c:348-369, 1079-1083) on the unsorted rows: rule_unsorted ----
-                for (int s = 0; s < 2; ++s) {
-                    bool any = false; uint32_t bp = 0, bv = 0;
-                    rule_sparse<3, false>(w.loci[s], w.val[s], n_s[s], L, ix.ref_len, bound, any, bp, bv, n_hits_s[s], a0[s], w.hit_pos[s], w.hit_nd[s]);
-                    if (any) { found[s] = true; q_pos = bp; q_ndiff = bv; q_strand = (uint32_t)s; }
-                }
+            for (int s = 0; s < 2; ++s) {
+                bool any = false; uint32_t bp = 0, bv = 0;
+                rule_sparse<3, false, GW>(w.loci[s], w.val[s], n_s[s], L, ix.ref_len, bound, any, bp, bv, n_hits_s[s], a0[s], w.hit_pos[s], w.hit_nd[s]);
+                if (any) { found[s] = true; q_pos = bp; q_ndiff = bv; q_strand = (uint32_t)s; }
             }
-            if (ap.dbg_stop == 5) { if (lane == 0) results[r].pos = q_pos + n_hits_s[0] + n_hits_s[1] + a0[0] + a0[1]; return; }
-            if (!heavy && !found[0] && !found[1]) heavy = true;             // needs the gapped pass
-            if (heavy) { }
+            if (INSTR && ap.dbg_stop == 5) { if (lane == 0) results[r].pos = q_pos + n_hits_s[0] + n_hits_s[1] + a0[0] + a0[1]; return; }
+            if (!found[0] && !found[1]) heavy = true;                       // needs the gapped pass
             else {
                 WSYNC();
                 // ---- query_set_hits / gen_mapq (query.c:270-333): lane t < 2*NHIT looks at recorded hit (t / NHIT, t % NHIT);
@@ -2322,10 +2386,10 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
                     hp = w.hit_pos[hs][hj]; hn = w.hit_nd[hs][hj];
                     cand = hp != 0xFFFFFFFFu && hp != q_pos && (hs ? a0[1] : a0[0]) <= q_ndiff;
                 }
-                const uint64_t cm = __ballot(cand);
-                const bool sel = cand && (uint32_t)__popcll(cm & lt) < (uint32_t)ap.max_hits;
-                const uint64_t sm = __ballot(sel);
-                const uint32_t nh0 = (uint32_t)__popcll(sm & ((1ull << NHIT) - 1ull)), nh1 = (uint32_t)__popcll(sm >> NHIT);
+                const mask_t cm = G::ballot(cand);
+                const bool sel = cand && popc(cm & lt) < (uint32_t)ap.max_hits;
+                const mask_t sm = G::ballot(sel);
+                const uint32_t nh0 = popc(sm & (((mask_t)1 << NHIT) - 1)), nh1 = popc(sm >> NHIT);
                 const int b0 = (int)q_ndiff;
                 int b1 = 100000;
                 if (nh0) b1 = (int)a0[0];
@@ -2338,20 +2402,23 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
                 }
                 salt_result_t *out = results + r;
                 if (sel) {                                                  // one 8-byte store per kept hit, all in one instruction
-                    const uint32_t hidx = (uint32_t)__popcll(sm & lt);
+                    const uint32_t hidx = popc(sm & lt);
                     salt_hit_t hv; hv.pos = hp; hv.n_diff = (uint8_t)hn; hv.is_gap = 0; hv.strand = (uint16_t)hs;
                     out->hits[hs][hs ? hidx - nh0 : hidx] = hv;
                     out->hit_n_cigar[hidx] = 0;
                 }
-                if (lane < 6) {                                             // the 24 header bytes as six dwords
-                    const uint32_t d = lane == 0 ? q_pos
-                                     : lane == 1 ? (q_strand | (q_ndiff << 8) | (mapq << 24))             // strand, n_diff, is_gap = 0, mapq
-                                     : lane == 2 ? (uint32_t)b0
-                                     : lane == 3 ? (uint32_t)b1
-                                     : lane == 4 ? ((L - 1) << 16)                                        // seq_start = 0, seq_end
+                // the 24 header bytes as six dwords, by lanes 0..5 of a wave and 16..21 of a half-wave: where each kernel had them when
+                // it was last timed; the other place was not measured
+                const uint32_t t = lane - (GW == 64 ? 0u : 16u);
+                if (t < 6) {
+                    const uint32_t d = t == 0 ? q_pos
+                                     : t == 1 ? (q_strand | (q_ndiff << 8) | (mapq << 24))                // strand, n_diff, is_gap = 0, mapq
+                                     : t == 2 ? (uint32_t)b0
+                                     : t == 3 ? (uint32_t)b1
+                                     : t == 4 ? ((L - 1) << 16)                                           // seq_start = 0, seq_end
                                      : (nh0 | (nh1 << 8) | (1u << 16));                                   // n_hits[2], n_cigar = 1, skipped = 0
-                    reinterpret_cast<uint32_t *>(out)[lane] = d;
-                } else if (lane == 6) out->cigar[0] = (uint16_t)((L << 4) | 0u);
+                    reinterpret_cast<uint32_t *>(out)[t] = d;
+                } else if (t == 6) out->cigar[0] = (uint16_t)((L << 4) | 0u);
             }
         }
     }
@@ -2359,300 +2426,49 @@ k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
         if (lane == 0) queue_push(queue, ranges, ap.n_reads, r);
         return;                                                             // k_heavy does (and counts) all of it
     }
-    stamp(SALT_CTR_LT_OUT);
-    if (prof && lane == 0) atomicAdd(ctr + SALT_CTR_LT_SAMPLES, 1ull);
-    if (ctr) {
-        for (int o = 32; o > 0; o >>= 1) c_vwords += __shfl_down(c_vwords, o);
-        if (lane == 0) {
+    if constexpr (INSTR) {
+        stamp(SALT_CTR_LT_OUT);
+        if (prof && lane == 0) atomicAdd(ctr + SALT_CTR_LT_SAMPLES, 1ull);
+        if (ctr && lane == 0) {
             atomicAdd(ctr + SALT_CTR_SA_C, c_sa_c); atomicAdd(ctr + SALT_CTR_SA_R, c_sa_r);
-            atomicAdd(ctr + SALT_CTR_VERIFY, c_verify); atomicAdd(ctr + SALT_CTR_VERIFY_WORDS, c_vwords);
+            atomicAdd(ctr + SALT_CTR_VERIFY, c_verify);
             atomicAdd(ctr + SALT_CTR_READS, 1ull); atomicAdd(ctr + SALT_CTR_BASES, L); atomicAdd(ctr + SALT_CTR_LOCI, c_loci);
             atomicAdd(ctr + SALT_CTR_D_SA_LIGHT, c_sa_c + c_sa_r);
-            atomicAdd(ctr + SALT_CTR_D_VERIFY_LIGHT, c_verify * (L <= 120 ? 4u : L <= 248 ? 8u : (((L + 7) >> 3) + 4u) / 4u));
+            atomicAdd(ctr + SALT_CTR_D_VERIFY_LIGHT, c_verify * (L <= 120 ? 4u : 8u));
             atomicAdd(ctr + SALT_CTR_D_OUT_LIGHT, 40u);                     // 24-byte header + CIGAR word + (typically one) 8-byte hit
         }
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_light2: k_light with TWO reads per wave (32 lanes each) for reads with few seed slots (spr <= 8; L <= 120 with four lanes per
-// located row: the 100-bp single-end case; L <= 248 with eight: 150-base reads and mates).  k_light is bound by instruction issue and by the dispatch of one workgroup per read; with
-// two reads per wave both halve.  Same steps, same results; every ballot / shuffle stays inside the read's half-wave.
-// ---------------------------------------------------------------------------------------------
-static constexpr int L2_SLOTS = 8;       // seed slots per list
-struct LightLds2 {
-    uint32_t pm[2][32];                  // (reads up to 120 bases use 15 words per strand, up to 248 bases 31)
-    uint32_t sp[4][L2_SLOTS], off[4][L2_SLOTS];
-    uint32_t pre[4][L2_SLOTS + 1];
-    uint32_t loci[2][LT_LOCI];
-    uint32_t hit_pos[2][NHIT];
-    uint8_t  hit_nd[2][NHIT];
-    uint8_t  val[2][LT_LOCI];
-};
-
-// rule_sparse on a half-wave: n candidates, lane hl of the half holds candidates hl, hl + 32, ...
-__device__ __forceinline__ void rule_sparse_h(const uint32_t *pos, const uint8_t *val, const uint32_t n, const uint32_t ref_len,
-                                              uint32_t &bound, bool &any, uint32_t &best_pos, uint32_t &best_v,
-                                              uint32_t &n_hits, uint32_t &a0, uint32_t *hit_pos, uint8_t *hit_nd)
+// k_light: LT_WAVES independent reads (waves) per workgroup: half the workgroups to dispatch.  It takes what k_light2 does not: paired-end
+// mates, reads above 120 / 248 bases or with more than 8 seed slots, and every step with the access counters on.
+static constexpr int LT_WAVES = 2;
+__global__ void __launch_bounds__(64 * LT_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
+k_light(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
+        const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
+        uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges, unsigned long long *__restrict__ ctr)
 {
-    const uint32_t lane = lane_id(), hl = lane & 31u, hb = lane & 32u;
-    const uint32_t NONE = 0xFFFFFFFFu;
-    auto HB = [&](bool x) -> uint32_t { const uint64_t m = __ballot(x); return hb ? (uint32_t)(m >> 32) : (uint32_t)m; };   // this half's 32 bits (a select, not a 64-bit shift)
-    auto SHF = [&](uint32_t v, int src) -> uint32_t { return (uint32_t)__shfl((int)v, (int)hb + src); };
-    any = false; n_hits = 0;
-    if (n == 0) return;
-    if (n <= 32) {                                            // the usual case: every candidate inside the bound is the same locus
-        uint32_t p = 0, v = NONE;
-        if (hl < n) { p = pos[hl]; v = val[hl]; }
-        const bool ok = v <= bound && p < ref_len;
-        const uint32_t m = HB(ok);
-        if (m == 0) return;
-        const int l0 = __ffs((int)m) - 1;
-        const uint32_t p0 = SHF(p, l0);
-        if (HB(ok && p != p0) == 0) {
-            const uint32_t v0 = SHF(v, l0);
-            any = true; best_pos = p0; best_v = v0; n_hits = 1; a0 = v0;
-            if (hl == 0) { hit_pos[0] = p0; hit_nd[0] = (uint8_t)v0; }
-            bound = v0 < bound ? v0 : bound;
-            return;
-        }
-    }
-    uint32_t mp[4] = { NONE, NONE, NONE, NONE };
-    for (uint32_t b = 0; b < n; b += 32) {
-        const uint32_t i = b + hl;
-        uint32_t p = 0, v = NONE;
-        if (i < n) { p = pos[i]; v = val[i]; }
-        uint32_t m = HB(v <= bound && p < ref_len);
-        while (m) {
-            const int l = __ffs((int)m) - 1;
-            const uint32_t pl = SHF(p, l), vl = SHF(v, l);
-#pragma unroll
-            for (int t = 0; t <= 3; ++t) if (vl == (uint32_t)t && pl < mp[t]) mp[t] = pl;
-            m &= m - 1;
-        }
-    }
-    uint32_t before[4];
-    before[0] = NONE;
-#pragma unroll
-    for (int t = 1; t <= 3; ++t) before[t] = mp[t - 1] < before[t - 1] ? mp[t - 1] : before[t - 1];
-#pragma unroll
-    for (int t = 3; t >= 0; --t) if (mp[t] != NONE) { any = true; best_v = (uint32_t)t; best_pos = mp[t]; }
-    if (!any) return;
-    uint32_t last_p = 0;
-    for (uint32_t h = 0; h < (uint32_t)NHIT; ++h) {
-        uint32_t cur_p = NONE, cur_v = 0;
-        for (uint32_t b = 0; b < n; b += 32) {
-            const uint32_t i = b + hl;
-            uint32_t p = 0, v = NONE;
-            if (i < n) { p = pos[i]; v = val[i]; }
-            const uint32_t lim = v == 1 ? before[1] : v == 2 ? before[2] : v == 3 ? before[3] : NONE;
-            uint32_t m = HB(v <= bound && p < ref_len && p < lim && (h == 0 || p > last_p));
-            while (m) {
-                const int l = __ffs((int)m) - 1;
-                const uint32_t pl = SHF(p, l);
-                if (pl < cur_p) { cur_p = pl; cur_v = SHF(v, l); }
-                m &= m - 1;
-            }
-        }
-        if (cur_p == NONE) break;
-        if (hl == 0) { hit_pos[h] = cur_p; hit_nd[h] = (uint8_t)cur_v; }
-        if (h == 0) a0 = cur_v;
-        last_p = cur_p; ++n_hits;
-    }
-    bound = best_v < bound ? best_v : bound;
+    __shared__ LightLds<64> w[LT_WAVES];
+    const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * LT_WAVES + (threadIdx.x >> 6));
+    if (r < ap.n_reads) light_read<64, 0, true>(ix, ap, pm, sai_c, sai_r, results, queue, ranges, ctr, w[threadIdx.x >> 6], r);
 }
 
+// k_light2: TWO reads per wave (32 lanes each) for reads with few seed slots (spr <= 8; L <= 120 with LN = 4 lanes per located row: the
+// 100-bp single-end case; L <= 248 with 8: 150-base reads).  The light pass is bound by instruction issue and by the dispatch of its
+// workgroups; with two reads per wave both halve.  Same steps, same results.
 // L2_WAVES waves per workgroup; each wave still works alone on its two reads (no block-level synchronisation).  Two waves per
 // workgroup halve the number of workgroups the dispatcher has to place (5 x 10^5 -> 2.5 x 10^5 per batch): the kernel alone takes
 // the same 0.48 ms, but with other batches' kernels on the GPU the step rate rises ~6 %; four are slower again.
-// LN: lanes per located row in the window check: 4 cover reads up to 120 bases, 8 up to 248 (150-base mates and reads; the seed slots
-// bound the length before that: spr <= 8)
 template <int L2_WAVES, int LN = 4>
 __global__ void __launch_bounds__(64 * L2_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_light2(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
          const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
          uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges)
 {
-    __shared__ LightLds2 w2[2 * L2_WAVES];
-    const uint32_t lane = lane_id(), hl = lane & 31u, hb = lane & 32u, half = lane >> 5;
-    LightLds2 &w = w2[2u * (threadIdx.x >> 6) + half];
-    const uint32_t lt = (1u << hl) - 1u;
-    auto HB = [&](bool x) -> uint32_t { const uint64_t m = __ballot(x); return hb ? (uint32_t)(m >> 32) : (uint32_t)m; };   // this half's 32 bits (a select, not a 64-bit shift)
-    auto SHF = [&](uint32_t v, int src) -> uint32_t { return (uint32_t)__shfl((int)v, (int)hb + src); };
-    const uint32_t r = 2u * (blockIdx.x * (uint32_t)L2_WAVES + (threadIdx.x >> 6)) + half;
-    if (r >= ap.n_reads) return;
-    const uint32_t *rec = pm + (uint64_t)r * ap.pg.pm_stride;
-    const uint32_t L = rec[2 * ap.pg.nw8];
-    bool heavy = L > (LN == 8 ? 248u : 120u) || L < (uint32_t)ap.l_seed || ap.spr > (uint32_t)L2_SLOTS || ap.max_locate < 2 * 64;
-    if (!heavy) {
-        // ---- round trip 1: the read (one-hot nibble words, both strands) and its seeds ----
-        const uint32_t nw = (L + 7) >> 3;                                   // <= 15 (LN = 4) / <= 31 (LN = 8)
-        uint32_t n_amb = 0;
-        for (uint32_t x = hl; x < 2 * nw; x += 32) {                        // (one trip for reads up to 128 bases)
-            const uint32_t s = x >= nw, j = s ? x - nw : x;
-            const uint32_t word = rec[s * ap.pg.nw8 + j];
-            w.pm[s][j] = word;
-            if (!s) n_amb += (uint32_t)__popc(word & (word >> 1) & (word >> 2) & (word >> 3) & 0x11111111u);
-        }
-        if (ap.max_amb < L) {
-            for (int o = 16; o > 0; o >>= 1) n_amb += (uint32_t)__shfl_xor((int)n_amb, o);
-            if (n_amb > ap.max_amb) {                                       // alnse.c:1328 / alnpe.c:495: record left untouched
-                if (hl == 0) {
-                    salt_result_t *out = results + r;
-                    out->pos = 0xFFFFFFFFu; out->strand = 3; out->n_diff = 255; out->is_gap = 255; out->mapq = 0;
-                    out->b0 = -1; out->b1 = -1; out->seq_start = 0; out->seq_end = (uint16_t)(L - 1);
-                    out->n_hits[0] = out->n_hits[1] = 0; out->n_cigar = 0; out->skipped = 1;
-                }
-                return;
-            }
-        }
-        uint32_t tot[4];
-        bool small;
-        {
-            // half-lane = (list, slot); list: 0 C/fwd 1 R/fwd 2 C/rev 3 R/rev (see k_light)
-            const uint32_t l = hl >> 3, slot = hl & 7u;
-            uint4 v = make_uint4(1, 0, 0, 0);
-            if (slot < ap.spr) { v = ((l & 1) ? sai_r : sai_c)[((uint64_t)r * 2u + (l >> 1)) * ap.spr + slot]; if (l & 1) v = sai_r_row(v, ap.epoch); }
-            uint32_t sz = v.w ? v.y - v.x + 1u : 0u;
-            if (sz > 65u) sz = 65u;
-            uint32_t inc = sz;                                              // inclusive prefix sum within the 8-lane row
-            for (int o = 1; o < 8; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, o, 8); if (slot >= (uint32_t)o) inc += t; }
-            for (int q = 0; q < 4; ++q) tot[q] = SHF(inc, 8 * q + 7);
-            small = tot[0] <= 8 && tot[1] <= 8 && tot[2] <= 8 && tot[3] <= 8;
-            if (small) {
-                for (uint32_t k2 = 0; k2 < sz; ++k2) { w.sp[l][inc - sz + k2] = v.x + k2; w.off[l][inc - sz + k2] = v.z | (v.w == 2 ? 0x80000000u : 0u); }
-            } else {
-                w.sp[l][slot] = v.x; w.off[l][slot] = v.z | (v.w == 2 ? 0x80000000u : 0u);        // bit 31: .x is a genome position already
-                w.pre[l][slot + 1] = inc;
-                if (slot == 0) w.pre[l][0] = 0;
-            }
-        }
-        WSYNC();
-        for (int l = 0; l < 4; ++l) heavy |= tot[l] > 64;
-        if (!heavy) {
-            // ---- round trip 2: the suffix-array rows of the four lists ----
-            uint32_t n_s[2] = { 0, 0 };
-            if (small) {
-                const uint32_t l = hl >> 3, x = hl & 7u;
-                const uint32_t tl = l == 0 ? tot[0] : l == 1 ? tot[1] : l == 2 ? tot[2] : tot[3];
-                bool keep = false; uint32_t p = 0;
-                if (x < tl) {
-                    const uint32_t j = w.sp[l][x], of = w.off[l][x];
-                    p = ((of >> 31) ? j : (l & 1) ? ix.r_pos[j] : ix.c_sa[j]) - (of & 0x7FFFFFFFu);
-                    keep = (l & 1) ? !(p > ix.ref_len || p + L > ix.ref_len) : !(p + L > ix.ref_len);       // alnse.c:672-673,715-717
-                }
-                const uint32_t km = HB(keep);
-                const uint32_t s = hl >> 4, ms = (km >> (16 * s)) & 0xFFFFu;
-                if (keep) w.loci[s][(uint32_t)__popc(ms & ((1u << (hl & 15u)) - 1u))] = p;
-                n_s[0] = (uint32_t)__popc(km & 0xFFFFu); n_s[1] = (uint32_t)__popc(km >> 16);
-            } else {
-                for (int l = 0; l < 4; ++l) {
-                    const int s = l >> 1;
-                    for (uint32_t x = hl; x - hl < tot[l]; x += 32) {         // (x - hl) is the same for the whole half: a uniform trip count
-                        bool keep = false; uint32_t p = 0;
-                        if (x < tot[l]) {
-                            uint32_t i = 0;
-                            while (w.pre[l][i + 1] <= x) ++i;
-                            const uint32_t j = w.sp[l][i] + (x - w.pre[l][i]), of = w.off[l][i];
-                            p = ((of >> 31) ? j : (l & 1) ? ix.r_pos[j] : ix.c_sa[j]) - (of & 0x7FFFFFFFu);
-                            keep = (l & 1) ? !(p > ix.ref_len || p + L > ix.ref_len) : !(p + L > ix.ref_len);
-                        }
-                        const uint32_t km = HB(keep);
-                        if (keep) w.loci[s][n_s[s] + (uint32_t)__popc(km & lt)] = p;
-                        n_s[s] += (uint32_t)__popc(km);
-                    }
-                }
-            }
-            WSYNC();
-            // ---- round trip 3: masked Hamming distance of every located row of both strands, LN lanes per row ----
-            {
-                constexpr uint32_t RPG = 32u / LN;                           // rows of one group of loads per half-wave
-                const uint32_t sub = hl & (uint32_t)(LN - 1), q = hl / (uint32_t)LN, n = n_s[0] + n_s[1];
-                const uint32_t nvalid = L > 32u * sub ? (L - 32u * sub < 32u ? L - 32u * sub : 32u) : 0u;
-                uint32_t pa[4], pb[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { const bool in = (4 * sub + t) < nw; pa[t] = in ? w.pm[0][4 * sub + t] : 0u; pb[t] = in ? w.pm[1][4 * sub + t] : 0u; }
-                for (uint32_t b = 0; b < n; b += 4u * RPG) {                // 4 groups of RPG rows per trip
-                    uint32_t pos[4]; u32x4_a4 x[4]; bool act[4], rev[4];
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        if (b + RPG * g >= n) break;
-                        const uint32_t c = b + RPG * g + q;
-                        act[g] = c < n; rev[g] = c >= n_s[0];
-                        pos[g] = act[g] ? (rev[g] ? w.loci[1][c - n_s[0]] : w.loci[0][c]) : 0u;
-                        if (pos[g] >= ix.ref_len) pos[g] = 0xFFFFFFFFu;      // wrapped below 0 (see mismatch_capped): no load, INF
-                        if (LN == 8 && !(4u * sub < nw + 1u)) x[g] = u32x4_a4{ 0u, 0u, 0u, 0u };       // this lane's words lie behind the window: never fetched
-                        else x[g] = *reinterpret_cast<const u32x4_a4 *>(ix.ref + ((pos[g] == 0xFFFFFFFFu ? 0u : pos[g]) >> 3) + 4 * sub);
-                    }
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        if (b + RPG * g >= n) break;
-                        const uint32_t pw[4] = { rev[g] ? pb[0] : pa[0], rev[g] ? pb[1] : pa[1], rev[g] ? pb[2] : pa[2], rev[g] ? pb[3] : pa[3] };
-                        const uint32_t mism = quad_mismatch<LN>(x[g], pos[g], pw, nvalid);
-                        if (act[g] && sub == 0) {
-                            const uint32_t c = b + RPG * g + q;
-                            const uint8_t v = (uint8_t)((mism > 3 || pos[g] == 0xFFFFFFFFu) ? INF : mism);
-                            if (rev[g]) w.val[1][c - n_s[0]] = v; else w.val[0][c] = v;
-                        }
-                    }
-                }
-            }
-            WSYNC();
-            // ---- the sequential best/first-hit rule on the unsorted rows ----
-            uint32_t bound = 3, q_pos = 0xFFFFFFFFu, q_strand = 3, q_ndiff = 255;
-            uint32_t n_hits_s[2] = { 0, 0 }, a0[2] = { 0, 0 };
-            bool found[2] = { false, false };
-            for (int s = 0; s < 2; ++s) {
-                bool any = false; uint32_t bp = 0, bv = 0;
-                rule_sparse_h(w.loci[s], w.val[s], n_s[s], ix.ref_len, bound, any, bp, bv, n_hits_s[s], a0[s], w.hit_pos[s], w.hit_nd[s]);
-                if (any) { found[s] = true; q_pos = bp; q_ndiff = bv; q_strand = (uint32_t)s; }
-            }
-            if (!found[0] && !found[1]) heavy = true;                       // needs the gapped pass
-            else {
-                WSYNC();
-                // ---- query_set_hits / gen_mapq (query.c:270-333), see k_light ----
-                const uint32_t hs = hl >= (uint32_t)NHIT, hj = hl - hs * NHIT;
-                uint32_t hp = 0xFFFFFFFFu, hn = 0;
-                bool cand = false;
-                if (hl < 2u * NHIT && hj < (hs ? n_hits_s[1] : n_hits_s[0])) {
-                    hp = w.hit_pos[hs][hj]; hn = w.hit_nd[hs][hj];
-                    cand = hp != 0xFFFFFFFFu && hp != q_pos && (hs ? a0[1] : a0[0]) <= q_ndiff;
-                }
-                const uint32_t cm = HB(cand);
-                const bool sel = cand && (uint32_t)__popc(cm & lt) < (uint32_t)ap.max_hits;
-                const uint32_t sm = HB(sel);
-                const uint32_t nh0 = (uint32_t)__popc(sm & ((1u << NHIT) - 1u)), nh1 = (uint32_t)__popc(sm >> NHIT);
-                const int b0 = (int)q_ndiff;
-                int b1 = 100000;
-                if (nh0) b1 = (int)a0[0];
-                if (nh1 && (int)a0[1] <= b1) b1 = (int)a0[1];
-                uint32_t mapq = 0;
-                if (b0 != 0) {
-                    const uint32_t x = (uint32_t)(b0 > b1 ? b0 - b1 : b1 - b0);
-                    const uint64_t qq = mapq_quot(x, (uint32_t)b0);
-                    mapq = qq < 254 ? (uint32_t)qq : 254u;
-                }
-                salt_result_t *out = results + r;
-                if (sel) {
-                    const uint32_t hidx = (uint32_t)__popc(sm & lt);
-                    salt_hit_t hv; hv.pos = hp; hv.n_diff = (uint8_t)hn; hv.is_gap = 0; hv.strand = (uint16_t)hs;
-                    out->hits[hs][hs ? hidx - nh0 : hidx] = hv;
-                    out->hit_n_cigar[hidx] = 0;
-                }
-                if (hl >= 16 && hl < 22) {                                  // the 24 header bytes as six dwords
-                    const uint32_t t = hl - 16;
-                    const uint32_t d = t == 0 ? q_pos
-                                     : t == 1 ? (q_strand | (q_ndiff << 8) | (mapq << 24))
-                                     : t == 2 ? (uint32_t)b0
-                                     : t == 3 ? (uint32_t)b1
-                                     : t == 4 ? ((L - 1) << 16)
-                                     : (nh0 | (nh1 << 8) | (1u << 16));
-                    reinterpret_cast<uint32_t *>(out)[t] = d;
-                } else if (hl == 22) out->cigar[0] = (uint16_t)((L << 4) | 0u);
-            }
-        }
-    }
-    if (heavy && hl == 0) queue_push(queue, ranges, ap.n_reads, r);            // k_heavy does all of it
+    __shared__ LightLds<32> w[2 * L2_WAVES];
+    const uint32_t h = 2u * (threadIdx.x >> 6) + (lane_id() >> 5);        // this half-wave among the workgroup's
+    const uint32_t r = 2u * blockIdx.x * (uint32_t)L2_WAVES + h;
+    if (r < ap.n_reads) light_read<32, LN, false>(ix, ap, pm, sai_c, sai_r, results, queue, ranges, nullptr, w[h], r);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2741,16 +2557,21 @@ size_t queue_words(uint32_t max_reads) { return (size_t)max_reads * 2 + (size_t)
 
 // ---------------------------------------------------------------------------------------------
 // k_diag_rule: unit access to rule_unsorted / rule_sparse (tests only).  One wave per case; out[case] = any, best_pos,
-// best_v, n_hits, a0, bound_out, then NHIT x (hit_pos, hit_nd)
+// best_v, n_hits, a0, bound_out, then NHIT x (hit_pos, hit_nd).  mode 0: rule_unsorted<3, false>, 1: rule_sparse<3, false>,
+// 2: rule_unsorted<LLV_K, true>, 3: rule_sparse<3, false, 32> as k_light2 runs it -- two cases per wave, 2b and 2b + 1 in the halves
+// of block b, each half with its own hit arrays
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
 k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *__restrict__ val, const uint32_t *__restrict__ offs,
             const uint32_t *__restrict__ bound_in, uint32_t L, uint32_t ref_len, int mode, uint32_t *__restrict__ out)
 {
-    __shared__ uint32_t hit_pos[NHIT];
-    __shared__ uint8_t hit_nd[NHIT];
-    const uint32_t c = blockIdx.x, lane = lane_id();
+    __shared__ uint32_t hit_pos_s[2][NHIT];
+    __shared__ uint8_t hit_nd_s[2][NHIT];
+    const uint32_t half = mode == 3 ? lane_id() >> 5 : 0u, lane = mode == 3 ? lane_id() & 31u : lane_id();
+    const uint32_t c = mode == 3 ? 2u * blockIdx.x + half : blockIdx.x;
     if (c >= n_cases) return;
+    uint32_t *hit_pos = hit_pos_s[half];
+    uint8_t *hit_nd = hit_nd_s[half];
     const uint32_t o = offs[c], n = offs[c + 1] - o;
     uint32_t bound = bound_in[c], bp = 0, bv = 0, nh = 0, a0 = 0;
     bool any = false;
@@ -2758,6 +2579,7 @@ k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *_
     WSYNC();
     if (mode == 0) rule_unsorted<3, false>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else if (mode == 1) rule_sparse<3, false>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
+    else if (mode == 3) rule_sparse<3, false, 32>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else rule_unsorted<LLV_K, true>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     WSYNC();
     uint32_t *w = out + (size_t)c * (6 + 2 * NHIT);
@@ -2768,7 +2590,8 @@ k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *_
 void launch_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *val, const uint32_t *offs, const uint32_t *bound_in,
                       uint32_t L, uint32_t ref_len, int mode, uint32_t *out, hipStream_t st)
 {
-    if (n_cases) hipLaunchKernelGGL(k_diag_rule, dim3(n_cases), dim3(64), 0, st, n_cases, pos, val, offs, bound_in, L, ref_len, mode, out);
+    const uint32_t blocks = mode == 3 ? (n_cases + 1) / 2 : n_cases;
+    if (n_cases) hipLaunchKernelGGL(k_diag_rule, dim3(blocks), dim3(64), 0, st, n_cases, pos, val, offs, bound_in, L, ref_len, mode, out);
 }
 uint32_t diag_rule_words() { return 6 + 2 * NHIT; }
 
@@ -2850,22 +2673,27 @@ void launch_diag_lv(const IndexView &ix, uint32_t n, const uint32_t *pos, const 
 // k_diag_verify: unit access to the candidate verifiers (tests only).  One wave per case: the read seqs[offs[c]..offs[c+1]) against
 // candidates cand[coffs[c]..coffs[c+1]) (at most 256) on the caller's mixRef.  mode 0: mismatch_capped per lane, 1: verify_quads<8>
 // (4 lanes per candidate, L <= 120), 2: verify_quads<8, 8> (L <= 248), 3 / 4: verify_quads_2<4> / <8> with the list split between the
-// "strands" (both use the same read).  out[i] = 0..3 or 255.  Candidates >= ref_len (a locate that wrapped below 0, alnse.c:672-673) must
-// come back 255 WITHOUT being used as an address: the test's mixRef is a few KB, so a regression reads far outside of it only by value.
+// "strands" (both use the same read), 5 / 6: verify_quads_2<4, 32> / <8, 32> as k_light2 runs them -- two cases per wave, 2b and 2b + 1
+// in the halves of block b, each set up like a case of modes 3 / 4.  out[i] = 0..3 or 255.  Candidates >= ref_len (a locate that wrapped
+// below 0, alnse.c:672-673) must come back 255 WITHOUT being used as an address: the test's mixRef is a few KB, so a regression reads
+// far outside of it only by value.
 __global__ void __launch_bounds__(64)
 k_diag_verify(const uint32_t *__restrict__ ref, uint32_t ref_len, uint32_t n_cases, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
               const uint32_t *__restrict__ cand, const uint32_t *__restrict__ coffs, int mode, uint8_t *__restrict__ out)
 {
-    __shared__ uint32_t pm[64];
-    __shared__ uint32_t loci[256];
-    __shared__ uint8_t val[256];
-    const uint32_t c = blockIdx.x, lane = lane_id();
+    __shared__ uint32_t pm_s[2][64];
+    __shared__ uint32_t loci_s[2][256];
+    __shared__ uint8_t val_s[2][256];
+    const uint32_t gw = mode >= 5 ? 32u : 64u, half = mode >= 5 ? lane_id() >> 5 : 0u, lane = lane_id() & (gw - 1u);
+    const uint32_t c = mode >= 5 ? 2u * blockIdx.x + half : blockIdx.x;
     if (c >= n_cases) return;
+    uint32_t *pm = pm_s[half], *loci = loci_s[half];
+    uint8_t *val = val_s[half];
     const uint32_t off = offs[c], L = offs[c + 1] - off, c0 = coffs[c];
     uint32_t n = coffs[c + 1] - c0;
     if (n > 256) n = 256;
     const uint32_t nw = (L + 7) >> 3;
-    for (uint32_t j = lane; j < 64; j += 64) {
+    for (uint32_t j = lane; j < 64; j += gw) {
         uint32_t word = 0;
         for (uint32_t q = 0; q < 8 && j < nw; ++q) {
             const uint32_t i = j * 8 + q, cc = i < L ? seqs[off + i] : 5u;
@@ -2873,21 +2701,24 @@ k_diag_verify(const uint32_t *__restrict__ ref, uint32_t ref_len, uint32_t n_cas
         }
         pm[j] = word;
     }
-    for (uint32_t i = lane; i < n; i += 64) { loci[i] = cand[c0 + i]; val[i] = 77; }
+    for (uint32_t i = lane; i < n; i += gw) { loci[i] = cand[c0 + i]; val[i] = 77; }
     WSYNC();
     IndexView ix; ix.ref = ref; ix.ref_len = ref_len;
     if (mode == 0) { for (uint32_t i = lane; i < n; i += 64) val[i] = (uint8_t)mismatch_capped(ix, pm, L, loci[i]); }
     else if (mode == 1) verify_quads<8>(ref, ref_len, pm, L, loci, n, val);
     else if (mode == 2) verify_quads<8, 8>(ref, ref_len, pm, L, loci, n, val);
     else if (mode == 3) verify_quads_2(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
-    else verify_quads_2<8>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
+    else if (mode == 4) verify_quads_2<8>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
+    else if (mode == 5) verify_quads_2<4, 32>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
+    else verify_quads_2<8, 32>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
     WSYNC();
-    for (uint32_t i = lane; i < n; i += 64) out[c0 + i] = val[i];
+    for (uint32_t i = lane; i < n; i += gw) out[c0 + i] = val[i];
 }
 void launch_diag_verify(const uint32_t *ref, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs, const uint32_t *cand,
                         const uint32_t *coffs, int mode, uint8_t *out, hipStream_t st)
 {
-    if (n_cases) hipLaunchKernelGGL(k_diag_verify, dim3(n_cases), dim3(64), 0, st, ref, ref_len, n_cases, seqs, offs, cand, coffs, mode, out);
+    const uint32_t blocks = mode >= 5 ? (n_cases + 1) / 2 : n_cases;
+    if (n_cases) hipLaunchKernelGGL(k_diag_verify, dim3(blocks), dim3(64), 0, st, ref, ref_len, n_cases, seqs, offs, cand, coffs, mode, out);
 }
 
 // ---------------------------------------------------------------------------------------------

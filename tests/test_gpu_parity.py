@@ -238,12 +238,13 @@ def test_gpu_one_workspace_takes_batches_of_growing_read_length():
     ora.close(); aln.close(); idx.destroy()
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4, 5, 6])
 def test_gpu_verifiers_never_dereference_a_wrapped_locate(mode):
     """Candidates at or beyond mixRef.l -- `pos - offset` that wrapped below 0 passes the reference's range check (alnse.c:672-673)
     and is only dropped by the candidate rule (alnse.c:762) -- must come back as "no hit" from every verifier without being used as an
     address.  Fault-free: the mixRef here is 4 KB and the wild values are 0xFFFFFFF0-style, so a regression shows as a wrong byte (or
-    a fault), a correct build as 255; in-range candidates must still give the masked Hamming distance."""
+    a fault), a correct build as 255; in-range candidates must still give the masked Hamming distance.  Modes 5 / 6 are modes 3 / 4 on
+    half-waves, two cases a wave: neighbouring cases differ in length, so the halves of a wave do not run in step."""
     import ctypes
     from salt_amd import api
     lib = api.gpu_lib()
@@ -256,7 +257,7 @@ def test_gpu_verifiers_never_dereference_a_wrapped_locate(mode):
     for q in range(8):
         m = masks[q::8]
         words[:len(m)] |= m << np.uint32(4 * q)
-    Ls = [100, 120, 37, 8, 64] if mode in (0, 1, 3) else [150, 248, 121]
+    Ls = [100, 120, 37, 8, 64] if mode in (0, 1, 3, 5) else [150, 248, 121]
     if mode == 0:
         Ls += [300]
     reads, cands, coffs, want = [], [], [0], []
@@ -343,18 +344,19 @@ def _sequential_rule(pos, val, bound, vmax, in_range):
     return found, best_pos, best_v, hits, a0, bound
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
 def test_gpu_rule_on_unsorted_lists_equals_the_sequential_rule(mode):
     """rule_unsorted / rule_sparse (no sort, duplicates allowed) against the sequential loop over the sorted unique list, on
     3000 random lists: lengths 0..300, few distinct loci or many, duplicates, loci at and beyond the reference end, every
-    incoming bound."""
+    incoming bound.  Mode 3 is rule_sparse on half-waves, two lists a wave: neighbouring lists differ in length, so a half that
+    leaked into the other would show."""
     import ctypes
     import salt_amd
     lib = salt_amd.gpu_lib()
     lib.salt_gpu_diag_rule.argtypes = [ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
     rng = np.random.Generator(np.random.PCG64(100 + mode))
-    L, ref_len, vmax = 100, 1000000, (3 if mode < 2 else 12)
-    in_range = (lambda p: p < ref_len) if mode < 2 else (lambda p: not ((p + L + 4) & 0xFFFFFFFF >= ref_len))
+    L, ref_len, vmax = 100, 1000000, (3 if mode != 2 else 12)
+    in_range = (lambda p: p < ref_len) if mode != 2 else (lambda p: not ((p + L + 4) & 0xFFFFFFFF >= ref_len))
     pos, val, offs, bounds = [], [], [0], []
     for c in range(3000):
         n = int(rng.choice([0, 1, 2, 5, 17, 63, 64, 65, 128, 300]))
