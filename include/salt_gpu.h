@@ -203,6 +203,56 @@ int  salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites, uint32_t 
 int  salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts, uint64_t cap_words, int reset);
 int  salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws);
 
+/* ---- coverage: per-base and windowed depth (`salt --depth`) ---------------------------------------------------------------
+ * Which records contribute is the rule of the SNP counts: the row is mapped (pos != 0xFFFFFFFF), not skipped, and mapq >= min_mapq; only
+ * the primary alignment counts, never an alternative (XA) hit; an unmapped mate printed at its mate's position does not count.
+ * The difference array: diff is uint32[ref_len + 1] in the concatenated coordinate of salt_result_t.pos, arithmetic mod 2^32.  The CIGAR is
+ * walked as the SAM / BAM writers lay it out (a paired-end row's leading soft clip seq_start advances the read only) from g = pos.  Every
+ * M run [g, g + len) is cut to [g, min(g + len, ref_len)); when that is not empty, diff[g] += 1 and diff[end] -= 1.  D advances g and is
+ * no coverage (samtools depth's default), I and S advance the read only.  A read across a contig boundary counts at the global positions
+ * it covers.
+ * Depth: depth[g] = sum of diff[x], x <= g, mod 2^32, for 0 <= g < ref_len: exact while fewer than 2^32 records cover one position.  diff
+ * is a sum of integers: it does not depend on batch order, stream, workspace or GPU, and the arrays of several GPUs add word by word.
+ * Per-base text (window 0): bedGraph, "contig\tstart\tend\tdepth\n", start and end 0-based, half-open and contig-relative; one line per
+ * maximal run of equal depth inside one contig, runs of depth 0 included, ascending in genome order, no header.  The lines of a contig
+ * tile it from 0 to its length; a run never crosses a contig end, also when the depth is the same on both sides.  The contigs are those of
+ * salt_gpu_index_set_contigs (<P>.C.ann); position ref_len is the last contig's end.
+ * Window text (window W >= 1): every contig has the windows [k W, min((k + 1) W, contig_len)); the line is "contig\tstart\tend\tmean\n";
+ * with sum the 64-bit sum of depth over the window and len its length, h = (100 sum + len / 2) / len by integer division and the field is
+ * h / 100, a dot, h % 100 as two digits.  No floating point anywhere.
+ * While depth is on, every entry point that leaves result rows adds its batch behind the kernels that finish the rows, on the same stream
+ * (k_depth_mark: about two atomics a read).  The array belongs to the device index and is shared by its workspaces and forks; it lies
+ * outside the image (4 bytes a genome position).  With depth off no kernel is launched; before the first enable nothing is allocated, and
+ * every other call below fails with SALT_E_INVAL "never enabled".
+ *   salt_gpu_index_depth_enable    the first enable allocates and zeroes diff (SALT_E_NOMEM names the size); on = 0 stops and keeps it;
+ *                                  min_mapq 0 .. 255 (above: SALT_E_INVAL).  Call with no align call in flight, like the three below.
+ *   salt_gpu_index_depth_reset     diff = 0
+ *   salt_gpu_index_depth_fetch     out[0 .. n) = diff[first .. first + n); synchronises the device
+ *   salt_gpu_index_depth_add       diff[first .. first + n) += in[0 .. n), by a kernel: how the arrays of several GPUs are summed, chunk
+ *                                  by chunk, and how any array can be put in front of the text kernels.  A range that leaves
+ *                                  [0, ref_len] is SALT_E_INVAL with the range in the message, for both.
+ *   salt_gpu_index_depth_text_begin  starts the text of the array as it stands: window 0 = per base; tile_positions = genome positions
+ *                                  scanned at a time, 0 = the default (the text does not depend on it); bgzf != 0: whole BGZF blocks
+ *                                  instead of text, deflated on the device, without the end-of-file block.  Needs the contig table.
+ *                                  An array of window sums that does not fit is SALT_E_NOMEM naming its size.
+ *   salt_gpu_index_depth_text_next   the next piece, in genome order: *data points into a buffer the index owns, valid until the next
+ *                                  call on the index; *n_bytes == 0: the text is complete.  diff is never written by these two: the
+ *                                  text can be made twice with the same bytes, and counting can go on afterwards.
+ *   salt_gpu_ws_depth_uncount      takes back what the workspace's LAST successful align call added (delta 2^32 - 1), as
+ *                                  salt_gpu_ws_snp_uncount does.  Nothing to take back: SALT_OK. */
+typedef struct {
+    uint32_t window;            /* 0: per-base runs; W >= 1: mean depth of every window of W positions */
+    uint32_t tile_positions;    /* 0: default */
+    int32_t  bgzf;              /* the pieces are BGZF blocks */
+} salt_depth_text_opt_t;
+int  salt_gpu_index_depth_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq);
+int  salt_gpu_index_depth_reset(salt_gpu_index_t *ix);
+int  salt_gpu_index_depth_fetch(salt_gpu_index_t *ix, uint64_t first, uint64_t n, uint32_t *out);
+int  salt_gpu_index_depth_add(salt_gpu_index_t *ix, uint64_t first, uint64_t n, const uint32_t *in);
+int  salt_gpu_index_depth_text_begin(salt_gpu_index_t *ix, const salt_depth_text_opt_t *opt);
+int  salt_gpu_index_depth_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes);
+int  salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws);
+
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,
  * strict 4-line FASTQ records: the block is parsed, aligned and formatted on the device; the host only hands over the text and

@@ -87,6 +87,21 @@ int64_t salt_bam_from_sam(const salt_index_t *ix, const char *sam, size_t n, uin
 int64_t salt_snp_sites(const salt_index_t *ix, uint32_t *pos, uint64_t cap);
 int64_t salt_snp_count_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t *counts, uint64_t n_sites);
 
+/* Coverage (`salt --depth`): the host twins of the device's difference array and text kernels, written from the definition in salt_gpu.h
+ * without any code of the kernels'.  They are the model the device is compared with, and what `salt` uses when its libsalt_gpu has no
+ * salt_gpu_index_depth_enable.  diff is uint32[n_words], n_words = ref_len + 1 (anything else is an error).
+ *   salt_depth_add_sam  diff += the M runs of the record lines of this program's own SAM text: a record counts iff FLAG bit 4 is clear and
+ *                       MAPQ >= min_mapq; global position = contig offset + POS - 1; every M run [g, g + len) is cut at ref_len and, when
+ *                       something is left, adds 1 at g and takes 1 at its end; D advances on the genome, I and S in the read.  Header
+ *                       lines ('@') and empty lines are skipped; any other line that is no SAM record is an error, and nothing of that
+ *                       line is added.  Returns the records that counted.
+ *   salt_depth_text     the text of the array: window == 0 the per-base bedGraph (one line per maximal run of equal depth inside a contig),
+ *                       else one line per window of `window` positions with the mean as h / 100 '.' h % 100.  Returns the bytes the text
+ *                       takes; the first min(cap, that) of them are in out (out may be NULL with cap 0: the size only).
+ * Both return -1 with salt_host_last_error() set on failure. */
+int64_t salt_depth_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t *diff, uint64_t n_words);
+int64_t salt_depth_text(const salt_index_t *ix, const uint32_t *diff, uint64_t n_words, uint32_t window, char *out, uint64_t cap);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

@@ -239,6 +239,11 @@ class Index:
     def l_seed(self):
         return host_lib().salt_index_seed_len(self._h)
 
+    @property
+    def ref_len(self):
+        """positions of the concatenated genome (the length of <P>.ref)"""
+        return int(self.view.contents.ref_len)
+
     def destroy(self):
         if self._h:
             host_lib().salt_index_free(self._h)
@@ -470,6 +475,44 @@ def snp_count_sam(index, sam, min_mapq=0, counts=None):
     if h.salt_snp_count_sam(index._h, sam, len(sam), int(min_mapq), counts.ctypes.data, n_sites) < 0:
         raise SaltError(h.salt_host_last_error().decode())
     return counts
+
+
+def depth_add_sam(index, sam, min_mapq=0, diff=None):
+    """The coverage difference array of this program's own SAM text: uint32[ref_len + 1], +1 where an M run begins and -1 where it ends
+    (salt_depth_add_sam, the host twin of the device's k_depth_mark).  diff: an array of an earlier call to add into.  Returns
+    (diff, records that counted)."""
+    h = host_lib()
+    h.salt_depth_add_sam.restype = ctypes.c_int64
+    h.salt_depth_add_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    sam = bytes(sam)
+    if diff is None:
+        diff = np.zeros(index.ref_len + 1, dtype=np.uint32)
+    if diff.dtype != np.uint32 or diff.ndim != 1 or not diff.flags.c_contiguous:
+        raise SaltError("depth_add_sam: diff must be a contiguous uint32 array of ref_len + 1 words")
+    n = h.salt_depth_add_sam(index._h, sam, len(sam), int(min_mapq), diff.ctypes.data, diff.size)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    return diff, int(n)
+
+
+def depth_text(index, diff, window=0):
+    """The text of a difference array (salt_depth_text, the host twin of the device's text kernels): window 0 = per-base bedGraph, one
+    line per run of equal depth inside a contig; window W = the mean depth of every window of W positions.  bytes."""
+    h = host_lib()
+    h.salt_depth_text.restype = ctypes.c_int64
+    h.salt_depth_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    diff = np.ascontiguousarray(diff, dtype=np.uint32)
+    n = h.salt_depth_text(index._h, diff.ctypes.data, diff.size, int(window), None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_depth_text(index._h, diff.ctypes.data, diff.size, int(window), out, n) != n:
+        raise SaltError("depth_text: the size of the text changed between two calls")
+    return out.raw[:n]
+
+
+class _DepthTextOpt(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_uint32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
 
 class _TextOpt(ctypes.Structure):
@@ -713,6 +756,57 @@ class GpuAligner:
         counts = np.zeros((n.value, 4), dtype=np.uint32)
         _gpu_check(lib.salt_gpu_index_snp_counts(self._ix, counts.ctypes.data, counts.size, 1 if reset else 0))
         return counts
+
+    def depth_enable(self, on=True, min_mapq=0):
+        """Mark, from now on, the M runs of every align call on this aligner's device index (its forks included) in the index's coverage
+        difference array; records below min_mapq do not count.  The first enable allocates and zeroes the array (4 bytes a genome
+        position); on=False stops and keeps it."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_depth_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_depth_enable(self._ix, 1 if on else 0, int(min_mapq)))
+
+    def depth_reset(self):
+        lib = gpu_lib()
+        lib.salt_gpu_index_depth_reset.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_index_depth_reset(self._ix))
+
+    def depth_fetch(self, first, n):
+        """diff[first .. first + n) of the device's difference array (ref_len + 1 words in all): uint32 array.  Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_depth_fetch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        out = np.zeros(max(int(n), 0), dtype=np.uint32)
+        _gpu_check(lib.salt_gpu_index_depth_fetch(self._ix, int(first), int(n), out.ctypes.data))
+        return out
+
+    def depth_add(self, first, words):
+        """diff[first .. first + len(words)) += words, on the device: how the arrays of several GPUs are summed."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_depth_add.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        _gpu_check(lib.salt_gpu_index_depth_add(self._ix, int(first), words.size, words.ctypes.data))
+
+    def depth_uncount(self):
+        """Takes back what this aligner's last align call marked."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_depth_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_ws_depth_uncount(self._ws))
+
+    def depth_text(self, window=0, tile_positions=0, bgzf=False, pieces=False):
+        """The text of the difference array as it stands, made on the device: per-base bedGraph (window 0) or window means; with bgzf
+        whole BGZF blocks (no end-of-file block).  pieces=True: the list of pieces as they left the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_depth_text_begin.argtypes = [ctypes.c_void_p, ctypes.POINTER(_DepthTextOpt)]
+        lib.salt_gpu_index_depth_text_next.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        opt = _DepthTextOpt(int(window), int(tile_positions), 1 if bgzf else 0)
+        _gpu_check(lib.salt_gpu_index_depth_text_begin(self._ix, ctypes.byref(opt)))
+        out = []
+        while True:
+            p, n = ctypes.c_void_p(), ctypes.c_uint64()
+            _gpu_check(lib.salt_gpu_index_depth_text_next(self._ix, ctypes.byref(p), ctypes.byref(n)))
+            if n.value == 0:
+                break
+            out.append(ctypes.string_at(p.value, n.value))
+        return out if pieces else b"".join(out)
 
     def counters(self):
         out = (ctypes.c_uint64 * len(CTR_NAMES))()

@@ -41,6 +41,10 @@ struct salt_gpu_index {
     // salt_gpu_index_snp_enable: the site table (one record per 64 genome positions) and counts[snp_sites][4], built by the first enable (not
     // part of the image); every workspace of the index adds into the one table while snp_on
     SnpWin *d_snp_tab = nullptr; uint32_t *d_snp_counts = nullptr; uint64_t snp_win = 0; uint32_t snp_sites = 0, snp_min_mapq = 0; bool snp_on = false;
+    // salt_gpu_index_depth_enable: the difference array of ref_len + 1 words, allocated by the first enable (not part of the image) and shared
+    // by every workspace of the index while depth_on; the text state and its buffers come with the first salt_gpu_index_depth_text_begin
+    uint32_t *d_depth = nullptr; uint32_t depth_min_mapq = 0; bool depth_on = false; DepthText *depth_text = nullptr;
+    std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
 };
 
 // A device buffer with its owner: p[0 .. cap) elements, freed with the owner.  alloc() gives it exactly n elements (what it held is freed
@@ -123,6 +127,7 @@ struct salt_gpu_ws {
     std::vector<uint8_t> ev_pe;        // the call was a paired-end one (its last three events are recorded)
     uint32_t n_timed = 0;
     SnpCount snp_last{}; hipStream_t snp_last_st = nullptr;      // what the last align call counted (n_rec 0: nothing), for salt_gpu_ws_snp_uncount
+    DepthMark depth_last{}; hipStream_t depth_last_st = nullptr; // likewise what it marked in the depth array, for salt_gpu_ws_depth_uncount
 };
 static const uint32_t MAX_TIMED = 256, EV_PER_CALL = 12;
 
@@ -295,6 +300,7 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     if (ix->d_rctx) { hipSetDevice(ix->device); hipFree(ix->d_rctx); }
     if (ix->d_c_off) { hipSetDevice(ix->device); hipFree(ix->d_c_off); hipFree(ix->d_c_name_off); hipFree(ix->d_c_names); }
     if (ix->d_snp_tab) { hipSetDevice(ix->device); hipFree(ix->d_snp_tab); hipFree(ix->d_snp_counts); }
+    if (ix->d_depth || ix->depth_text) { hipSetDevice(ix->device); hipFree(ix->d_depth); depth_text_free(ix->depth_text); }
     delete ix;
 }
 
@@ -465,6 +471,26 @@ static int snp_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const
     return SALT_OK;
 }
 
+// Its sibling for the coverage, at the same two places: the rows' M runs into the index's difference array (k_depth_mark).  With depth
+// off nothing is launched.
+static int depth_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_results, hipStream_t st)
+{
+    const salt_gpu_index *ix = ws->ix;
+    if (!ix->depth_on) return SALT_OK;
+    DepthMark c{};
+    c.res = static_cast<const salt_result_t *>(d_results); c.n_rec = n_rec; c.diff = ix->d_depth; c.ref_len = ix->view.ref_len;
+    c.min_mapq = ix->depth_min_mapq; c.delta = 1u;
+    HIPCHK(launch_depth_mark(c, st));
+    ws->depth_last = c; ws->depth_last_st = st;
+    return SALT_OK;
+}
+// both, behind the kernels that finish a batch's rows
+static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
+{
+    const int rc = snp_hook(ws, n_rec, d_seqs, d_offs, d_results, pe, st);
+    return rc ? rc : depth_hook(ws, n_rec, d_results, st);
+}
+
 // ---- the workspace's buffer families: each is sized here and nowhere else ----
 // The seed-interval arrays and k_seed's walk queues, for `items` seeds.  d_sai_r is zeroed when allocated: no row of any epoch (sai_r_row,
 // salt_device.h).  settle: the zeroing is waited for, for a caller that does not know which stream the calls will use.  d_sai_c comes last:
@@ -505,7 +531,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe)
 {
     if (!ws || !o || !d_seqs || !d_offs || !d_results) return fail(SALT_E_INVAL, "null argument");
-    ws->snp_last.n_rec = 0;
+    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0;
     if (n_reads == 0) return SALT_OK;
     uint32_t spr = 0;
     int rc = check_opt(ws->ix, o, max_read_len, &spr);
@@ -550,7 +576,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                  gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr.p : nullptr, timed ? ev + 4 : nullptr, st);
     if (timed) { HIPCHK(hipEventRecord(ev[7], st)); ws->ev_pe[ws->n_timed] = 0; ++ws->n_timed; }
     HIPCHK(hipGetLastError());
-    if (!pe) return snp_hook(ws, n_reads, d_seqs, d_offs, d_results, 0, st);
+    if (!pe) return rows_hooks(ws, n_reads, d_seqs, d_offs, d_results, 0, st);
     return SALT_OK;
 }
 
@@ -640,6 +666,8 @@ extern "C" int salt_gpu_index_set_contigs(salt_gpu_index_t *ix, int32_t n, const
     HIPCHK(hipMemcpy(ix->d_c_name_off, noff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ix->d_c_names, blob.data(), blob.size(), hipMemcpyHostToDevice));
     ix->n_contigs = n;
+    ix->h_c_off.assign(offsets, offsets + n); ix->c_name_max = 0;
+    for (int i = 0; i < n; ++i) ix->c_name_max = std::max<uint32_t>(ix->c_name_max, noff[(size_t)i + 1] - noff[(size_t)i]);
     HIPCHK(text_warm());                                     // the text kernels' code object is loaded now, not inside the first block's call
     return SALT_OK;
 }
@@ -1093,7 +1121,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
 {
     const uint64_t n_src = n_bytes;
     if (d_src && add_newline) ++n_bytes;
-    ws->snp_last.n_rec = 0;
+    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0;
     salt_gpu_index *ix = ws->ix;
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
@@ -1151,7 +1179,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
 {
     if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
-    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->snp_last.n_rec = 0;
+    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0;
     if (n1 == 0 && n2 == 0) return SALT_OK;
     if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
     if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
@@ -1789,6 +1817,115 @@ extern "C" int salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws)
     return SALT_OK;
 }
 
+// ---- coverage ----
+static const char *const DEPTH_NEVER = "depth: depth was never enabled on this index (salt_gpu_index_depth_enable)";
+
+extern "C" int salt_gpu_index_depth_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (min_mapq > 255) return fail(SALT_E_INVAL, "depth: min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
+    HIPCHK(hipSetDevice(ix->device));
+    if (on && !ix->d_depth) {
+        if (ix->view.ref_len == 0) return fail(SALT_E_INVAL, "depth: the index has an empty genome");
+        const uint64_t bytes = ((uint64_t)ix->view.ref_len + 1) * 4;
+        uint32_t *d = nullptr;
+        if (hipMalloc((void **)&d, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SALT_E_NOMEM, "depth: no room for the difference array: " + std::to_string(bytes) + " bytes (4 per genome position)");
+        }
+        const hipError_t e = hipMemset(d, 0, bytes);
+        if (e != hipSuccess) { hipFree(d); return fail(SALT_E_HIP, std::string("hipMemset(depth): ") + hipGetErrorString(e)); }
+        ix->d_depth = d;
+    }
+    ix->depth_min_mapq = min_mapq; ix->depth_on = on != 0;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_depth_reset(salt_gpu_index_t *ix)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemset(ix->d_depth, 0, ((uint64_t)ix->view.ref_len + 1) * 4));
+    return SALT_OK;
+}
+
+// first + n words inside the array, or the message that names the range
+static int depth_range(const salt_gpu_index *ix, const char *what, uint64_t first, uint64_t n)
+{
+    const uint64_t words = (uint64_t)ix->view.ref_len + 1;
+    if (first > words || n > words - first)
+        return fail(SALT_E_INVAL, std::string("depth ") + what + ": words [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") leave the array's [0, " +
+                                  std::to_string(ix->view.ref_len) + "]");
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_depth_fetch(salt_gpu_index_t *ix, uint64_t first, uint64_t n, uint32_t *out)
+{
+    if (!ix || (!out && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
+    if (const int rc = depth_range(ix, "fetch", first, n)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (n) HIPCHK(hipMemcpy(out, ix->d_depth + first, n * 4, hipMemcpyDeviceToHost));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_depth_add(salt_gpu_index_t *ix, uint64_t first, uint64_t n, const uint32_t *in)
+{
+    if (!ix || (!in && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
+    if (const int rc = depth_range(ix, "add", first, n)) return rc;
+    if (n == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf<uint32_t> d_in;
+    if (d_in.alloc(n) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, "depth add: no room for " + std::to_string(n * 4) + " bytes of words to add"); }
+    HIPCHK(hipMemcpy(d_in, in, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_depth_add(ix->d_depth + first, d_in, n, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_depth_text_begin(salt_gpu_index_t *ix, const salt_depth_text_opt_t *opt)
+{
+    if (!ix || !opt) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
+    if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "depth text needs the contig table: call salt_gpu_index_set_contigs first");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!ix->depth_text) ix->depth_text = depth_text_new();
+    std::string err;
+    const int rc = depth_text_begin(ix->depth_text, ix->d_depth, ix->view.ref_len, ix->d_c_off, ix->d_c_name_off, ix->d_c_names, ix->h_c_off, ix->c_name_max,
+                                    opt->window, opt->tile_positions, opt->bgzf, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_index_depth_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes)
+{
+    if (!ix || !data || !n_bytes) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
+    if (!ix->depth_text) return fail(SALT_E_INVAL, "depth text: no text was begun (salt_gpu_index_depth_text_begin)");
+    HIPCHK(hipSetDevice(ix->device));
+    std::string err;
+    const int rc = depth_text_next(ix->depth_text, data, n_bytes, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (!ws->ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
+    if (ws->depth_last.n_rec == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ws->ix->device));
+    DepthMark c = ws->depth_last;
+    c.delta = 0xFFFFFFFFu;                                                         // + (2^32 - 1) = - 1 in the array's arithmetic
+    ws->depth_last.n_rec = 0;
+    HIPCHK(launch_depth_mark(c, ws->depth_last_st));
+    HIPCHK(hipStreamSynchronize(ws->depth_last_st));
+    return SALT_OK;
+}
+
 extern "C" int salt_gpu_index_r_ctx(const salt_gpu_index_t *ix, void **dev_ptr, uint64_t *bytes)
 {
     if (!ix || !dev_ptr || !bytes) return fail(SALT_E_INVAL, "null argument");
@@ -1886,7 +2023,7 @@ static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sa
     }
 #endif
     HIPCHK(hipGetLastError());
-    return snp_hook(ws, 2 * n_pairs, d_seqs, d_offs, d_results, 1, st);
+    return rows_hooks(ws, 2 * n_pairs, d_seqs, d_offs, d_results, 1, st);
 }
 
 extern "C" int salt_gpu_align_pe_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, uint32_t n_pairs,

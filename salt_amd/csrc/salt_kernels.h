@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <string>
+#include <vector>
 #include "../../include/salt_gpu.h"
 #include "salt_device.h"
 
@@ -262,6 +263,24 @@ size_t snp_scan_bytes(uint64_t n_win);
 hipError_t launch_snp_table(const uint32_t *ref, uint32_t ref_len, uint64_t n_win, SnpWin *tab, uint32_t *cnt, void *tmp, size_t tmp_bytes, hipStream_t st);
 hipError_t launch_snp_pos(const SnpWin *tab, uint64_t n_win, uint32_t *pos, hipStream_t st);
 hipError_t launch_snp_count(const SnpCount &c, hipStream_t st);
+
+// ---- coverage (salt_depth.hip) ----
+struct DepthMark {                                                             // what k_depth_mark reads (by value)
+    const salt_result_t *res; uint32_t n_rec;                                  // the batch's rows
+    uint32_t *diff; uint32_t ref_len;                                          // the index's difference array, ref_len + 1 words
+    uint32_t min_mapq;
+    uint32_t delta;                                                            // 1; 0xFFFFFFFF takes a batch's marks back
+};
+hipError_t launch_depth_mark(const DepthMark &c, hipStream_t st);
+hipError_t launch_depth_add(uint32_t *diff, const uint32_t *in, uint64_t n, hipStream_t st);      // diff[i] += in[i]
+// The text of a difference array, piece by piece (salt_gpu_index_depth_text_begin / _next): its device and page-locked buffers and where it
+// stands.  Both return SALT_OK or an error code with the message in err.  h_c_off: the contigs' offsets as set_contigs got them.
+struct DepthText;
+DepthText *depth_text_new();
+void depth_text_free(DepthText *t);
+int depth_text_begin(DepthText *t, const uint32_t *d_diff, uint32_t ref_len, const int64_t *d_c_off, const uint32_t *d_c_name_off, const char *d_c_names,
+                     const std::vector<int64_t> &h_c_off, uint32_t max_name, uint32_t window, uint32_t tile_positions, int bgzf, std::string &err);
+int depth_text_next(DepthText *t, const char **data, uint64_t *n_bytes, std::string &err);
 
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);

@@ -730,3 +730,121 @@ extern "C" int64_t salt_snp_count_sam(const salt_index_t *ix, const char *sam, s
     }
     return n_rec;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Coverage: the host twin of the device's difference array and text kernels (k_depth_mark, salt_depth.hip; include/salt_gpu.h has the
+// definition), written from that definition over this program's own SAM record lines and without any code of the kernels'.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// one record line [l, e): its M runs into diff; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with g_err set
+int depth_add_line(const salt_index *ix, const RefIds &ids, const char *l, const char *e, uint32_t min_mapq, uint32_t *diff)
+{
+    const char *f[12]; int nf = 0;
+    f[nf++] = l;
+    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
+    auto bad = [&](const char *why) { g_err = std::string("depth: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return -1; };
+    if (nf < 11) return bad("fewer than 11 fields");
+    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };
+    int64_t flag, pos1, mapq;
+    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
+        pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
+    if (flag & 4) return 0;                                            // unmapped, also a mate printed at its mate's place
+    if ((uint64_t)mapq < min_mapq) return 0;
+    const int32_t rid = ids.find(f[2], fe(2));
+    if (rid < 0) return bad("RNAME is no sequence of the index");
+    if (pos1 < 1) return bad("a mapped record without a position");
+    const size_t l_seq = (size_t)(fe(9) - f[9]);
+    const uint64_t ref_len = ix->view.ref_len;
+    // the line is checked whole before anything is added: a refused line leaves diff as it was
+    uint64_t runs[2 * 64]; int n_runs = 0;
+    uint64_t g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)pos1 - 1;      // global position; the walk may run past the contig's end
+    size_t s = 0; uint64_t n = 0; bool digits = false, any = false;
+    for (const char *p = f[5]; p < fe(5); ++p) {
+        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
+        if (!digits) return bad("malformed CIGAR");
+        switch (*p) {
+        case 'M':
+            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
+            if (n_runs == 64) return bad("more M runs than a record of this program has");
+            runs[2 * n_runs] = g; runs[2 * n_runs + 1] = g + n; ++n_runs;
+            g += n; s += n; break;
+        case 'I': case 'S':
+            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
+            s += n; break;
+        case 'D': g += n; break;
+        default: return bad("a CIGAR operation this program does not write");
+        }
+        n = 0; digits = false; any = true;
+    }
+    if (digits || !any) return bad("malformed CIGAR");
+    for (int k = 0; k < n_runs; ++k) {
+        const uint64_t a = runs[2 * k], b = std::min(runs[2 * k + 1], ref_len);      // cut at the genome's end: not wrapped, not refused
+        if (a < b) { diff[a] += 1u; diff[b] -= 1u; }
+    }
+    return 1;
+}
+
+struct DepthOut {                                                      // counts every byte, keeps those that fit
+    char *p; uint64_t cap, n = 0;
+    void put(char c) { if (n < cap) p[n] = c; ++n; }
+    void puts(const std::string &s) { for (char c : s) put(c); }
+    void putu(uint64_t v) { char b[24]; int k = 0; do { b[k++] = (char)('0' + v % 10); v /= 10; } while (v); while (k) put(b[--k]); }
+};
+
+} // namespace
+
+extern "C" int64_t salt_depth_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t *diff, uint64_t n_words)
+{
+    if (!ix || (!sam && n) || !diff) { g_err = "depth: null argument"; return -1; }
+    if (n_words != (uint64_t)ix->view.ref_len + 1) { g_err = "depth: an array of " + std::to_string(n_words) + " words, the index needs " + std::to_string((uint64_t)ix->view.ref_len + 1) + " (ref_len + 1)"; return -1; }
+    const RefIds ids(ix);
+    int64_t n_rec = 0;
+    for (const char *l = sam, *end = sam + n; l < end; ) {
+        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
+        if (!e) e = end;
+        if (e > l && *l != '@') {                                      // (empty lines: a skipped read; '@': a header line)
+            const int r = depth_add_line(ix, ids, l, e, min_mapq, diff);
+            if (r < 0) return -1;
+            n_rec += r;
+        }
+        l = e + 1;
+    }
+    return n_rec;
+}
+
+extern "C" int64_t salt_depth_text(const salt_index_t *ix, const uint32_t *diff, uint64_t n_words, uint32_t window, char *out, uint64_t cap)
+{
+    if (!ix || !diff || (!out && cap)) { g_err = "depth: null argument"; return -1; }
+    const uint64_t ref_len = ix->view.ref_len;
+    if (n_words != ref_len + 1) { g_err = "depth: an array of " + std::to_string(n_words) + " words, the index needs " + std::to_string(ref_len + 1) + " (ref_len + 1)"; return -1; }
+    DepthOut o{ out, cap };
+    uint32_t depth = 0;                                                // depth[g - 1] in front of position g, mod 2^32
+    for (size_t c = 0; c < ix->anns.size(); ++c) {
+        const uint64_t c0 = (uint64_t)ix->anns[c].offset, c1 = c + 1 < ix->anns.size() ? std::min<uint64_t>((uint64_t)ix->anns[c + 1].offset, ref_len) : ref_len;
+        const std::string &name = ix->anns[c].name;
+        if (c0 >= c1) continue;
+        if (window == 0) {
+            uint64_t start = c0; uint32_t d_run = depth + diff[c0];
+            for (uint64_t g = c0; g < c1; ++g) {
+                depth += diff[g];
+                if (depth != d_run) {
+                    o.puts(name); o.put('\t'); o.putu(start - c0); o.put('\t'); o.putu(g - c0); o.put('\t'); o.putu(d_run); o.put('\n');
+                    start = g; d_run = depth;
+                }
+            }
+            o.puts(name); o.put('\t'); o.putu(start - c0); o.put('\t'); o.putu(c1 - c0); o.put('\t'); o.putu(d_run); o.put('\n');
+        } else {
+            for (uint64_t w0 = c0; w0 < c1; w0 += window) {
+                const uint64_t w1 = std::min<uint64_t>(w0 + window, c1), len = w1 - w0;
+                uint64_t sum = 0;
+                for (uint64_t g = w0; g < w1; ++g) { depth += diff[g]; sum += depth; }
+                // h = (100 sum + len / 2) / len without leaving 64 bits: sum = q len + r gives 100 q + (100 r + len / 2) / len
+                const uint64_t h = 100u * (sum / len) + (100u * (sum % len) + len / 2) / len;
+                o.puts(name); o.put('\t'); o.putu(w0 - c0); o.put('\t'); o.putu(w1 - c0); o.put('\t'); o.putu((uint64_t)(h / 100u)); o.put('.');
+                o.put((char)('0' + (int)(h % 100u) / 10)); o.put((char)('0' + (int)(h % 100u) % 10)); o.put('\n');
+            }
+        }
+    }
+    return (int64_t)o.n;
+}

@@ -69,6 +69,15 @@ extern "C" int salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites,
 extern "C" int salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts, uint64_t cap_words, int reset) __attribute__((weak));
 extern "C" int salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
+// And the coverage (--depth): without the device's difference array and text kernels it is summed from the SAM lines and printed by the
+// host twins (salt_depth_add_sam, salt_depth_text).
+extern "C" int salt_gpu_index_depth_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq) __attribute__((weak));
+extern "C" int salt_gpu_index_depth_fetch(salt_gpu_index_t *ix, uint64_t first, uint64_t n, uint32_t *out) __attribute__((weak));
+extern "C" int salt_gpu_index_depth_add(salt_gpu_index_t *ix, uint64_t first, uint64_t n, const uint32_t *in) __attribute__((weak));
+extern "C" int salt_gpu_index_depth_text_begin(salt_gpu_index_t *ix, const salt_depth_text_opt_t *opt) __attribute__((weak));
+extern "C" int salt_gpu_index_depth_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
+extern "C" int salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
+
 namespace {
 
 const int N_SEQS = 100000;
@@ -471,6 +480,35 @@ void snp_drop_block(salt_gpu_ws_t *ws)
     if (g_snp.on && g_snp.device && salt_gpu_ws_snp_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
 }
 
+// --depth FILE: coverage along the genome, per base or per window.  On the device every GPU's index holds a difference array that every
+// align call marks (salt_gpu_index_depth_enable); after the last block the arrays are added into the first GPU's and its text kernels
+// print the file.  A block the text path has aligned and then drops at a hand-over is taken back (salt_gpu_ws_depth_uncount).  Without the
+// device's symbols the SAM lines of every block and batch that is written go through salt_depth_add_sam, one caller at a time.
+struct DepthRun {
+    bool on = false, device = false, gz = false; const char *fn = nullptr; FILE *fp = nullptr; uint32_t min_mapq = 0, window = 0;
+    const salt_index_t *ix = nullptr; std::mutex mu; std::vector<uint32_t> host_diff;
+    bool host() const { return on && !device; }
+} g_depth;
+
+bool depth_host_add(const char *sam, size_t n)
+{
+    std::lock_guard<std::mutex> lk(g_depth.mu);
+    if (salt_depth_add_sam(g_depth.ix, sam, n, g_depth.min_mapq, g_depth.host_diff.data(), g_depth.host_diff.size()) >= 0) return true;
+    fprintf(stderr, "[salt] %s\n", salt_host_last_error());
+    return false;
+}
+// the SAM lines of a block or batch that is about to be written, through every host twin that is on
+bool host_twins_add(const char *sam, size_t n)
+{
+    return (!g_snp.host() || snp_host_add(sam, n)) && (!g_depth.host() || depth_host_add(sam, n));
+}
+// a block the text path aligned and will not write leaves the device's tables
+void drop_block(salt_gpu_ws_t *ws)
+{
+    snp_drop_block(ws);
+    if (g_depth.on && g_depth.device && salt_gpu_ws_depth_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
+}
+
 // SAM lines -> BAM records in `out`; false with the reason on stderr (a read name past the format's limit)
 bool bam_of_sam(const char *sam, size_t n, std::string &out)
 {
@@ -577,6 +615,10 @@ int usage()
             "               --snp-counts    <file>   write, per SNP site of the index, how many reads show A, C, G, T there (counted on\n"
             "                                        the GPU; tab-separated, one line per site) [off]\n"
             "               --snp-min-mapq  <int>    --snp-counts: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
+            "               --depth         <file>   write the coverage along the genome (made on the GPU): bedGraph, one line per run\n"
+            "                                        of equal depth; a name ending in .gz is written as BGZF [off]\n"
+            "               --depth-min-mapq <int>   --depth: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
+            "               --depth-window  <int>    --depth: the mean depth of every window of <int> positions instead [per base]\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -1021,8 +1063,8 @@ void SeWorker::run()
         if (n_calls++ == 0) t_first = now() - tg0; else t_rest += now() - tg0;
         const char *const lines = sam; const uint64_t lines_bytes = sam_bytes;      // (SAM lines whenever --snp-counts counts on the host)
         if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); R.fail(); break; }
-        if (!R.wait_turn(k)) { snp_drop_block(ws); break; }
-        if (g_snp.host() && !snp_host_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
+        if (!R.wait_turn(k)) { drop_block(ws); break; }
+        if (!host_twins_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
         if (!R.write_block(k, sam, sam_bytes, n_reads)) break;
     }
     if (trace) fprintf(stderr, "[salt] worker %d: started %.3f s after the clock, setup %.3f s, first device call %.3f s, %d later calls %.4f s each, done at %.3f s\n", wk,
@@ -1221,8 +1263,8 @@ static int run_pe_text(const char *fn1, const char *fn2, const std::vector<salt_
                 R.t_gpu = R.t_gpu + (now() - tg0);
                 const char *const lines = sam; const uint64_t lines_bytes = sam_bytes;
                 if (g_bgzf.on && !bgzf_text_block(sam, sam_bytes, zbuf)) { fprintf(stderr, "[salt] no BGZF blocks for a block of the output\n"); R.fail(); break; }
-                if (!R.wait_turn(k)) { snp_drop_block(ws); break; }
-                if (g_snp.host() && !snp_host_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
+                if (!R.wait_turn(k)) { drop_block(ws); break; }
+                if (!host_twins_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
                 if (!R.write_block(k, sam, sam_bytes, 2 * (long)n_pairs)) break;
             }
             salt_gpu_ws_destroy(ws);
@@ -1276,7 +1318,7 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
         { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 },
-        { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { 0, 0, 0, 0 } };
+        { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { "depth", 1, 0, 1006 }, { "depth-min-mapq", 1, 0, 1007 }, { "depth-window", 1, 0, 1008 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1305,6 +1347,19 @@ static int parse_options(int argc, char **argv, Opts &o)
             g_snp.min_mapq = (uint32_t)v;
             break;
         }
+        case 1006: g_depth.on = true; g_depth.fn = optarg; break;
+        case 1007: {
+            char *end = nullptr; const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --depth-min-mapq %s: a MAPQ is a number from 0 to 255\n", optarg); return 1; }
+            g_depth.min_mapq = (uint32_t)v;
+            break;
+        }
+        case 1008: {
+            char *end = nullptr; errno = 0; const long long v = strtoll(optarg, &end, 10);
+            if (end == optarg || *end || errno || v < 1 || v > 0xFFFFFFFFll) { fprintf(stderr, "[opt_parse]: --depth-window %s: a window is a number of positions from 1 to 4294967295\n", optarg); return 1; }
+            g_depth.window = (uint32_t)v;
+            break;
+        }
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1327,6 +1382,16 @@ static int parse_options(int argc, char **argv, Opts &o)
         if (!g_snp.device && g_polish) { fprintf(stderr, "[opt_parse]: --snp-counts with --polish needs a libsalt_gpu that counts on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
         if (!g_snp.device) g_bgzf.device = g_bam.device = false;
         if (!(g_snp.fp = fopen(g_snp.fn, "w"))) { fprintf(stderr, "[opt_parse]: --snp-counts: cannot open %s for writing: %s\n", g_snp.fn, strerror(errno)); return 1; }
+    }
+    if (g_depth.on) {
+        g_depth.device = salt_gpu_index_depth_enable && salt_gpu_index_depth_fetch && salt_gpu_index_depth_add && salt_gpu_index_depth_text_begin &&
+                         salt_gpu_index_depth_text_next && salt_gpu_ws_depth_uncount;
+        // summed on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
+        if (!g_depth.device && g_polish) { fprintf(stderr, "[opt_parse]: --depth with --polish needs a libsalt_gpu that marks the coverage on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
+        if (!g_depth.device) g_bgzf.device = g_bam.device = false;
+        const size_t l = strlen(g_depth.fn);
+        g_depth.gz = l > 3 && strcmp(g_depth.fn + l - 3, ".gz") == 0;
+        if (!(g_depth.fp = fopen(g_depth.fn, "wb"))) { fprintf(stderr, "[opt_parse]: --depth: cannot open %s for writing: %s\n", g_depth.fn, strerror(errno)); return 1; }
     }
     return -1;
 }
@@ -1488,9 +1553,9 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
-                if (g_snp.host()) {
+                if (g_snp.host() || g_depth.host()) {
                     bool good = true;
-                    for (const std::string &piece : b->sam) good = good && snp_host_add(piece.data(), piece.size());
+                    for (const std::string &piece : b->sam) good = good && host_twins_add(piece.data(), piece.size());
                     if (!good) { set_failed(); break; }
                 }
                 if (g_polish && !polish_batch(gp.get(), pe, *b)) { set_failed(); break; }
@@ -1594,6 +1659,74 @@ static bool snp_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_
     return true;
 }
 
+// --depth, before the first block: marking on on every GPU's index, or the host's array
+static bool depth_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_depth.on) return true;
+    g_depth.ix = ix;
+    if (!g_depth.device) { g_depth.host_diff.assign((size_t)salt_index_host_view(ix)->ref_len + 1, 0u); return true; }
+    for (salt_gpu_index_t *g : gix)
+        if (salt_gpu_index_depth_enable(g, 1, g_depth.min_mapq)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    return true;
+}
+
+// --depth, after the last block of a run that succeeded: the arrays of the other GPUs are added into the first one's, in chunks through a
+// page-locked buffer, and its text kernels print the file piece by piece; on the host the twin prints it.  A .gz file ends with the BGZF
+// end-of-file block.
+static bool depth_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &C)
+{
+    if (!g_depth.on) return true;
+    FILE *f = g_depth.fp;
+    uint64_t text_bytes = 0, file_bytes = 0;
+    bool ok = true;
+    if (g_depth.device) {
+        const uint64_t words = (uint64_t)salt_index_host_view(ix)->ref_len + 1, chunk = std::min<uint64_t>(words, 16u << 20);
+        auto gpu_fail = [&]() { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; };
+        if (gix.size() > 1) {
+            uint32_t *buf = nullptr;
+            if (salt_gpu_host_alloc(chunk * 4, (void **)&buf)) return gpu_fail();
+            for (size_t k = 1; k < gix.size() && ok; ++k)
+                for (uint64_t at = 0; at < words && ok; at += chunk) {
+                    const uint64_t n = std::min(chunk, words - at);
+                    ok = salt_gpu_index_depth_fetch(gix[k], at, n, buf) == 0 && salt_gpu_index_depth_add(gix[0], at, n, buf) == 0;
+                }
+            if (!ok) gpu_fail();
+            salt_gpu_host_free(buf);
+            if (!ok) return false;
+        }
+        salt_depth_text_opt_t to; to.window = g_depth.window; to.tile_positions = 0; to.bgzf = g_depth.gz ? 1 : 0;
+        if (salt_gpu_index_depth_enable(gix[0], 0, g_depth.min_mapq) || salt_gpu_index_set_contigs(gix[0], C.n(), C.off.data(), C.nm.data()) ||
+            salt_gpu_index_depth_text_begin(gix[0], &to)) return gpu_fail();
+        for (;;) {
+            const char *data = nullptr; uint64_t n = 0;
+            if (salt_gpu_index_depth_text_next(gix[0], &data, &n)) return gpu_fail();
+            if (n == 0) break;
+            ok = ok && fwrite(data, 1, (size_t)n, f) == n;
+            file_bytes += n; text_bytes += g_depth.gz ? bgzf_text_bytes(data, n) : n;
+        }
+    } else {
+        const int64_t need = salt_depth_text(ix, g_depth.host_diff.data(), g_depth.host_diff.size(), g_depth.window, nullptr, 0);
+        std::string text(need > 0 ? (size_t)need : 0, '\0'), z;
+        if (need < 0 || salt_depth_text(ix, g_depth.host_diff.data(), g_depth.host_diff.size(), g_depth.window, &text[0], (uint64_t)need) != need) {
+            fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false;
+        }
+        if (g_depth.gz && !bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] --depth: no BGZF blocks for the text\n"); return false; }
+        const std::string &out = g_depth.gz ? z : text;
+        ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+        text_bytes = text.size(); file_bytes = out.size();
+    }
+    if (g_depth.gz) { ok = ok && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, f) == sizeof BGZF_EOF; file_bytes += sizeof BGZF_EOF; }
+    ok = !ferror(f) && fclose(f) == 0 && ok;
+    g_depth.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --depth: write error on %s\n", g_depth.fn); return false; }
+    char what[64];
+    if (g_depth.window) snprintf(what, sizeof what, "windows of %u", g_depth.window); else snprintf(what, sizeof what, "per base");
+    fprintf(stderr, "[salt] depth: %s, %s, MAPQ >= %u, %llu bytes of text -> %s (%llu bytes)\n", what,
+            g_depth.device ? "marked and printed on the device" : "summed on the host from the SAM lines", g_depth.min_mapq, (unsigned long long)text_bytes, g_depth.fn,
+            (unsigned long long)file_bytes);
+    return true;
+}
+
 } // namespace
 
 // options; choice of path (TextPlan); index load and attach; header; text path; host pipeline
@@ -1642,16 +1775,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
-    if (!snp_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
+    if (!snp_begin(ix, gix) || !depth_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !snp_finish(ix, gix) ? 1 : rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs)) ? 1 : rc); }
         header_out = true;
     }
     const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
-    return leave(rc == 0 && !snp_finish(ix, gix) ? 1 : rc);
+    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs)) ? 1 : rc);
 }
