@@ -364,7 +364,8 @@ int  salt_gpu_buffer_equal(int device, const void *a, const void *b, uint64_t by
  * pos/val[offs[i]..offs[i+1]) (val > vmax = no candidate) and the incoming bound bound_in[i].  mode 0: gap-free rule
  * (code_kmismatch, alnse.c:348-369; distances 0..3, range filter pos < ref_len) by rule_unsorted; 1: the same by
  * rule_sparse; 2: gapped rule (code_kdiff, alnse.c:371-393; distances 0..12, filter !(pos + L + 4 >= ref_len)); 3: as 1 by
- * rule_sparse on half-waves (32 lanes, what k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b.
+ * rule_sparse on half-waves (32 lanes, what k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b; 4: as 1 on
+ * quarters of a wave (16 lanes, what k_light4 runs), cases 4b .. 4b + 3 side by side in the quarters of wave b.
  * out[i][18] = found, best_pos, best_dist, n_hits, a0, bound_out, then 6 x (hit_pos, hit_dist) in position order. */
 int  salt_gpu_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *val, const uint32_t *offs, const uint32_t *bound_in,
                         uint32_t L, uint32_t ref_len, int mode, uint32_t *out);
@@ -372,7 +373,8 @@ int  salt_gpu_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *va
 /* Unit entry of the candidate verifiers (tests): case i = read seqs[offs[i]..offs[i+1]) against candidates
  * cand[cand_offs[i]..cand_offs[i+1]) (<= 256) on the 4-bit mixRef `ref_words`; mode 0 = one candidate per lane, 1 / 2 = four / eight lanes
  * per candidate (reads <= 120 / 248 bases), 3 / 4 = the two-strand variants of 1 / 2, 5 / 6 = 3 / 4 on half-waves (32 lanes, what
- * k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b.  out[j] = masked Hamming distance 0..3 of candidate
+ * k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b, 7 = 3 on quarters of a wave (16 lanes, what k_light4
+ * runs), cases 4b .. 4b + 3 side by side in the quarters of wave b.  out[j] = masked Hamming distance 0..3 of candidate
  * j or 255 (more, or a candidate at or beyond ref_len -- a locate that wrapped below 0, alnse.c:672-673,762 -- which must never be
  * dereferenced).  Mirrors ed_mismatch (editdistance.c:88-163) under code_kmismatch's cap (alnse.c:348-369). */
 int  salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs,
@@ -393,7 +395,9 @@ int  salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t n, const u
 
 /* Work-queue counters of the LAST batch (diagnostics): [0] reads k_light handed to k_heavy, [2] reads whose gapped pass
  * was deferred, [5] k_gap items (32 candidates each), [6] k_cigar items, [7] k_cigar's queue head; [1] / [3] the longest R / C list among
- * the 64 segments of the seed walk queues; [4] reads 0. */
+ * the 64 segments of the seed walk queues; [4] reads the quarter-wave light kernel (k_light4: four reads a wave, for reads of at most 120
+ * bases with at most 4 seed slots a strand) left to its retry launch because one of their seed lists has more than 16 rows; 0 when
+ * another shape of the light pass ran. */
 int  salt_gpu_ws_queue_counts(salt_gpu_ws_t *ws, uint32_t out[8]);
 
 /* counters of the last batch(es) since the previous call; resets them */

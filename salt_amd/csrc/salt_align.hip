@@ -1130,27 +1130,32 @@ __device__ __forceinline__ void verify_two_phase(const uint32_t *__restrict__ re
 }
 
 // ---- lane groups ------------------------------------------------------------------------------
-// The light kernels give a read a whole wave (GW = 64) or one of its halves (GW = 32: two reads per wave, each on its own).  What
-// such a group asks of its lanes, all of it settled at compile time: the lane inside the group; a ballot over the group (64: the
-// wave's mask; 32: this half's 32 bits of it, by a select and not a 64-bit shift); a broadcast from a group lane (64: v_readlane, the
-// index is wave-uniform; 32: a shuffle from the half's base); the lanes-below mask; the group-wide add.
+// The light kernels give a read a whole wave (GW = 64), one of its halves (GW = 32: two reads per wave, each on its own) or one of
+// its quarters (GW = 16: four).  What such a group asks of its lanes, all of it settled at compile time: the lane inside the group; a
+// ballot over the group (64: the wave's mask; 32: this half's 32 bits of it, by a select and not a 64-bit shift; 16: this quarter's
+// 16 bits of that half); a broadcast from a group lane (64: v_readlane, the index is wave-uniform; 32 / 16: a shuffle from the
+// group's base); the lanes-below mask; the group-wide add.
 __device__ __forceinline__ uint32_t popc(uint32_t m) { return (uint32_t)__popc(m); }
 __device__ __forceinline__ uint32_t popc(uint64_t m) { return (uint32_t)__popcll(m); }
 __device__ __forceinline__ int first_bit(uint32_t m) { return __ffs((int)m) - 1; }
 __device__ __forceinline__ int first_bit(uint64_t m) { return __ffsll((long long)m) - 1; }
 template <int GW> struct LaneGroup {
-    static_assert(GW == 64 || GW == 32, "a wave or half of one");
+    static_assert(GW == 64 || GW == 32 || GW == 16, "a wave, half of one or a quarter");
     typedef std::conditional_t<GW == 64, uint64_t, uint32_t> mask_t;
     static __device__ __forceinline__ uint32_t lane() { return lane_id() & (uint32_t)(GW - 1); }
     static __device__ __forceinline__ mask_t ballot(bool x)
     {
         const uint64_t m = __ballot(x);
-        if constexpr (GW == 64) return m; else return (lane_id() & 32u) ? (uint32_t)(m >> 32) : (uint32_t)m;
+        if constexpr (GW == 64) return m;
+        else {
+            const uint32_t h = (lane_id() & 32u) ? (uint32_t)(m >> 32) : (uint32_t)m;
+            if constexpr (GW == 32) return h; else return (h >> (lane_id() & 16u)) & 0xFFFFu;
+        }
     }
     static __device__ __forceinline__ uint32_t bcast(uint32_t v, int src)
     {
         if constexpr (GW == 64) return (uint32_t)__builtin_amdgcn_readlane((int)v, src);
-        else return (uint32_t)__shfl((int)v, (int)(lane_id() & 32u) + src);
+        else return (uint32_t)__shfl((int)v, (int)(lane_id() & (uint32_t)(64 - GW)) + src);
     }
     static __device__ __forceinline__ mask_t below() { return ((mask_t)1 << lane()) - (mask_t)1; }
     static __device__ __forceinline__ uint32_t sum(uint32_t v)
@@ -2159,10 +2164,11 @@ k_cigar(IndexView ix, PackGeom pg, const uint32_t *__restrict__ pm, salt_result_
 }
 
 // ---------------------------------------------------------------------------------------------
-// The light kernels (k_light, k_light2): one body, light_read, at two widths -- a wave per read, or half a wave.  The common case in
-// three memory round trips.
+// The light kernels (k_light, k_light2, k_light4): one body, light_read, at three widths -- a wave per read, half a wave, or a quarter.
+// The common case in three memory round trips.
 //
-// A read stays here when (a) it is short enough for the small LDS image (a wave: L <= 160, <= 16 seed slots; a half: 120 / 248, <= 8),
+// A read stays here when (a) it is short enough for the small LDS image (a wave: L <= 160, <= 16 seed slots; a half: 120 / 248, <= 8;
+// a quarter: 120, <= 4),
 // (b) each of its four seed lists (C/R x strand) enumerates at most 64 suffix-array rows, so that the
 // max_locate cap (>= 128) can never bite and locate order is irrelevant once the loci are sorted, and
 // (c) a gap-free hit exists.  Everything else is queued for k_heavy, which replays the reference's
@@ -2177,6 +2183,14 @@ __device__ __forceinline__ void queue_push(uint32_t *__restrict__ qseg, QueueRan
 {
     const uint32_t s = (r >> 2) & (QUEUE_RANGES - 1u);
     qseg[(size_t)s * qseg_cap(n_reads) + atomicAdd(&ranges[s].push, 1u)] = r;
+}
+// The reads a quarter of a wave cannot hold (k_light4: a list above L4_ROWS rows, none above 64) wait in segments of their own behind
+// k_heavy's, built the same way (QueueRange::retry), for k_light_retry.
+__device__ __forceinline__ uint32_t *retry_segs(uint32_t *qseg, uint32_t n_reads) { return qseg + (size_t)QUEUE_RANGES * qseg_cap(n_reads); }
+__device__ __forceinline__ void retry_push(uint32_t *__restrict__ qseg, QueueRange *__restrict__ ranges, uint32_t n_reads, uint32_t r)
+{
+    const uint32_t s = (r >> 2) & (QUEUE_RANGES - 1u);
+    retry_segs(qseg, n_reads)[(size_t)s * qseg_cap(n_reads) + atomicAdd(&ranges[s].retry, 1u)] = r;
 }
 __global__ void __launch_bounds__(256)
 k_queue_pack(const uint32_t *__restrict__ qseg, const QueueRange *__restrict__ ranges, uint32_t n_reads, uint32_t *__restrict__ queue, SeCtl *__restrict__ ctl)
@@ -2196,21 +2210,28 @@ k_queue_pack(const uint32_t *__restrict__ qseg, const QueueRange *__restrict__ r
 static constexpr int LT_LOCI = 128;      // loci per strand handled here
 static constexpr int LT_MAXL = 160;      // longest read that gets a whole wave here
 static constexpr int L2_SLOTS = 8;       // seed slots per list of a read that gets a half-wave
+static constexpr int L4_SLOTS = 4;       // ... of a read that gets a quarter
+#ifndef SALT_L4_ROWS
+#define SALT_L4_ROWS 16
+#endif
+static constexpr int L4_ROWS = SALT_L4_ROWS;     // rows per list a quarter's record holds; a read with a longer list (up to 64) goes to the retry launch
 
-// A read's LDS record: SLOTS seed slots per list (a quarter of the group's lanes), PMW one-hot words per strand
-template <int SLOTS, int PMW> struct LightRec {
+// A read's LDS record: SLOTS seed slots per list (a quarter of the group's lanes), PMW one-hot words per strand, LOCI located rows per strand
+template <int SLOTS, int PMW, int LOCI> struct LightRec {
     uint32_t pm[2][PMW];
     uint32_t sp[4][SLOTS], off[4][SLOTS];
     uint32_t pre[4][SLOTS + 1];          // rows enumerated before slot i of list l
-    uint32_t loci[2][LT_LOCI];
+    uint32_t loci[2][LOCI];
     uint32_t hit_pos[2][NHIT];
     uint8_t  hit_nd[2][NHIT];
-    uint8_t  val[2][LT_LOCI];
+    uint8_t  val[2][LOCI];
 };
-// a wave's read: 16 slots, 160 bases; a half-wave's: 8 slots, 32 words (reads up to 120 bases use 15 a strand, up to 248 bases 31)
-template <int GW> using LightLds = LightRec<GW / 4, GW == 64 ? LT_MAXL / 8 : 32>;
+// a wave's read: 16 slots, 160 bases; a half-wave's: 8 slots, 32 words (reads up to 120 bases use 15 a strand, up to 248 bases 31);
+// a quarter's: 4 slots, 16 words (120 bases), L4_ROWS rows a list
+template <int GW> using LightLds = LightRec<GW / 4, GW == 64 ? LT_MAXL / 8 : GW == 32 ? 32 : 16, GW == 16 ? 2 * L4_ROWS : LT_LOCI>;
+static_assert(sizeof(LightLds<32>) == 1996 && 8 * sizeof(LightLds<16>) <= 4 * sizeof(LightLds<32>), "eight quarter records in the LDS of four half-wave ones");
 
-// The body of both light kernels: read r on a group of GW lanes (LaneGroup), every ballot / shuffle inside the group.
+// The body of the light kernels: read r on a group of GW lanes (LaneGroup), every ballot / shuffle inside the group.
 // LN: lanes per located row in the window check: 4 cover reads up to 120 bases, 8 up to 248; 0 = picked by the read's length.
 // INSTR: the access counters and phase stamps behind `ctr`, and the diagnostics build's early exits (ap.dbg_stop); without it none of
 // that is compiled.
@@ -2296,6 +2317,13 @@ __device__ __forceinline__ void light_read(const IndexView &ix, const AlignParam
         WSYNC();
         stamp(SALT_CTR_LT_SEEDS);
         for (int l = 0; l < 4; ++l) heavy |= tot[l] > 64;
+        if constexpr (GW == 16) {
+            // a list the record cannot hold: the half-wave body takes the read (k_light_retry), which also decides whether it is heavy
+            if (!heavy && (tot[0] > (uint32_t)L4_ROWS || tot[1] > (uint32_t)L4_ROWS || tot[2] > (uint32_t)L4_ROWS || tot[3] > (uint32_t)L4_ROWS)) {
+                if (lane == 0) retry_push(queue, ranges, ap.n_reads, r);
+                return;
+            }
+        }
         if (INSTR && ap.dbg_stop == 1) { if (lane == 0) results[r].pos = tot[0] + tot[1] + tot[2] + tot[3] + w.pm[0][0] + w.pm[1][1]; return; }
         if (!heavy) {
             // ---- round trip 2: the suffix-array rows of the four lists ----
@@ -2320,8 +2348,9 @@ __device__ __forceinline__ void light_read(const IndexView &ix, const AlignParam
                     while (w.pre[l][i + 1] <= x) ++i;
                     return locate(l, w.sp[l][i] + (x - w.pre[l][i]), w.off[l][i], p);
                 };
-                if constexpr (GW == 64) {
-                    // A list has at most 64 rows, one a lane: the loads of all four lists are in flight before the first ballot.
+                if constexpr (GW == 64 || (GW == 16 && L4_ROWS <= 16)) {
+                    // A list has at most 64 rows (a quarter's: L4_ROWS), one a lane: the loads of all four lists are in flight before the
+                    // first ballot.
                     uint32_t pos4[4]; bool keep4[4];
                     for (int l = 0; l < 4; ++l) {
                         keep4[l] = false; pos4[l] = 0;
@@ -2407,9 +2436,9 @@ __device__ __forceinline__ void light_read(const IndexView &ix, const AlignParam
                     out->hits[hs][hs ? hidx - nh0 : hidx] = hv;
                     out->hit_n_cigar[hidx] = 0;
                 }
-                // the 24 header bytes as six dwords, by lanes 0..5 of a wave and 16..21 of a half-wave: where each kernel had them when
-                // it was last timed; the other place was not measured
-                const uint32_t t = lane - (GW == 64 ? 0u : 16u);
+                // the 24 header bytes as six dwords, by lanes 0..5 of a wave or a quarter and 16..21 of a half-wave: where each kernel
+                // had them when it was last timed; the other place was not measured
+                const uint32_t t = lane - (GW == 32 ? 16u : 0u);
                 if (t < 6) {
                     const uint32_t d = t == 0 ? q_pos
                                      : t == 1 ? (q_strand | (q_ndiff << 8) | (mapq << 24))                // strand, n_diff, is_gap = 0, mapq
@@ -2469,6 +2498,42 @@ k_light2(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
     const uint32_t h = 2u * (threadIdx.x >> 6) + (lane_id() >> 5);        // this half-wave among the workgroup's
     const uint32_t r = 2u * blockIdx.x * (uint32_t)L2_WAVES + h;
     if (r < ap.n_reads) light_read<32, LN, false>(ix, ap, pm, sai_c, sai_r, results, queue, ranges, nullptr, w[h], r);
+}
+
+// k_light4: FOUR reads per wave (16 lanes each) for reads with at most 4 seed slots and 120 bases: the 100-base single-end case at the
+// default stride.  Such a read's seeds fill 16 lanes, its usual 4 - 6 located rows 16 - 24 lanes of the window check, its hits 12, its
+// header 7; the instruction stream of a wave now serves four of them.  Each quarter works alone and takes its own path (skipped,
+// queued, small, general).  A read with a list above L4_ROWS rows (and none above 64) is left to k_light_retry.
+template <int L4_WAVES>
+__global__ void __launch_bounds__(64 * L4_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
+k_light4(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
+         const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
+         uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges)
+{
+    __shared__ LightLds<16> w[4 * L4_WAVES];
+    const uint32_t q = 4u * (threadIdx.x >> 6) + (lane_id() >> 4);        // this quarter among the workgroup's
+    const uint32_t r = 4u * blockIdx.x * (uint32_t)L4_WAVES + q;
+    if (r < ap.n_reads) light_read<16, 4, false>(ix, ap, pm, sai_c, sai_r, results, queue, ranges, nullptr, w[q], r);
+}
+
+// k_light_retry: the half-wave body over the reads k_light4 left (retry_push), right behind it.  A fixed grid, a multiple of QUEUE_RANGES
+// blocks of four half-waves: block b takes every (gridDim / QUEUE_RANGES)-th group of four of segment b % QUEUE_RANGES, and leaves at
+// once when there is none.  The loop around the body keeps a few more registers alive than k_light2's 59; with the 64 of 8 waves a
+// SIMD it spills, so this small launch is left to the compiler's own budget.
+__global__ void __launch_bounds__(128)
+k_light_retry(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm,
+              const uint4 *__restrict__ sai_c, const uint4 *__restrict__ sai_r, salt_result_t *__restrict__ results,
+              uint32_t *__restrict__ queue /* the segments */, QueueRange *__restrict__ ranges)
+{
+    __shared__ LightLds<32> w[4];
+    const uint32_t h = 2u * (threadIdx.x >> 6) + (lane_id() >> 5);
+    const uint32_t seg = blockIdx.x & (QUEUE_RANGES - 1u), step = 4u * (gridDim.x / QUEUE_RANGES);
+    const uint32_t cnt = __hip_atomic_load(&ranges[seg].retry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t *src = retry_segs(queue, ap.n_reads) + (size_t)seg * qseg_cap(ap.n_reads);
+    for (uint32_t i = 4u * (blockIdx.x / QUEUE_RANGES) + h; i < cnt; i += step) {
+        light_read<32, 4, false>(ix, ap, pm, sai_c, sai_r, results, queue, ranges, nullptr, w[h], src[i]);
+        WSYNC();
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2544,7 +2609,22 @@ void launch_light(const IndexView &ix, const AlignParams &ap, const uint32_t *pm
 {
     if (!ap.n_reads) return;
     static const bool no_half = getenv("SALT_GPU_NO_LIGHT2") && atoi(getenv("SALT_GPU_NO_LIGHT2"));
-    if (!no_half && !ctr && !SALT_DIAG_VAL(ap.dbg_stop) && ap.spr <= (uint32_t)L2_SLOTS && ap.pg.nw8 <= 31) {          // reads of at most 120 / 248 bases with at most 8 seed slots: two per wave
+    static const bool no_quarter = getenv("SALT_GPU_NO_LIGHT4") && atoi(getenv("SALT_GPU_NO_LIGHT4"));
+    if (!no_half && !no_quarter && !ctr && !SALT_DIAG_VAL(ap.dbg_stop) && ap.spr <= (uint32_t)L4_SLOTS && ap.pg.nw8 <= 15) {  // at most 120 bases and 4 seed slots: four per wave
+        static const int wv = getenv("SALT_GPU_L4_WAVES") ? atoi(getenv("SALT_GPU_L4_WAVES")) : 2;
+        if (wv == 1) hipLaunchKernelGGL(k_light4<1>, dim3((ap.n_reads + 3) / 4), dim3(64), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
+        else if (wv == 4) hipLaunchKernelGGL(k_light4<4>, dim3((ap.n_reads + 15) / 16), dim3(256), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
+        else hipLaunchKernelGGL(k_light4<2>, dim3((ap.n_reads + 7) / 8), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
+        // the reads with a list a quarter cannot hold (3 % of the GRCh38-scale batches): as many blocks a CU as its registers let a CU
+        // hold at once (8; SALT_GPU_L4_RETRY_PER_CU for measurements), rounded up to whole rounds over the segments
+        static const uint32_t retry_blocks = [] {
+            int dev = 0, cus = 0, per_cu = getenv("SALT_GPU_L4_RETRY_PER_CU") ? atoi(getenv("SALT_GPU_L4_RETRY_PER_CU")) : 8;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = (int)QUEUE_RANGES;
+            if (per_cu < 1 || per_cu > 64) per_cu = 8;
+            return ((uint32_t)(cus * per_cu) + QUEUE_RANGES - 1u) / QUEUE_RANGES * QUEUE_RANGES;
+        }();
+        hipLaunchKernelGGL(k_light_retry, dim3(retry_blocks), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
+    } else if (!no_half && !ctr && !SALT_DIAG_VAL(ap.dbg_stop) && ap.spr <= (uint32_t)L2_SLOTS && ap.pg.nw8 <= 31) {          // reads of at most 120 / 248 bases with at most 8 seed slots: two per wave
         static const int wv = getenv("SALT_GPU_L2_WAVES") ? atoi(getenv("SALT_GPU_L2_WAVES")) : 2;
         if (ap.pg.nw8 > 15) hipLaunchKernelGGL((k_light2<2, 8>), dim3((ap.n_reads + 3) / 4), dim3(128), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
         else if (wv == 1) hipLaunchKernelGGL(k_light2<1>, dim3((ap.n_reads + 1) / 2), dim3(64), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges);
@@ -2553,22 +2633,23 @@ void launch_light(const IndexView &ix, const AlignParams &ap, const uint32_t *pm
         hipLaunchKernelGGL(k_light, dim3((ap.n_reads + LT_WAVES - 1) / LT_WAVES), dim3(64 * LT_WAVES), 0, st, ix, ap, pm, sai_c, sai_r, results, qseg, ranges, ctr);
     hipLaunchKernelGGL(k_queue_pack, dim3(QUEUE_RANGES), dim3(256), 0, st, qseg, ranges, ap.n_reads, queue, ctl);
 }
-size_t queue_words(uint32_t max_reads) { return (size_t)max_reads * 2 + (size_t)QUEUE_RANGES * qseg_cap(max_reads); }     // flat queue | overflow queue | segments
+size_t queue_words(uint32_t max_reads) { return (size_t)max_reads * 2 + (size_t)2 * QUEUE_RANGES * qseg_cap(max_reads); }     // flat queue | overflow queue | segments | retry segments
 
 // ---------------------------------------------------------------------------------------------
 // k_diag_rule: unit access to rule_unsorted / rule_sparse (tests only).  One wave per case; out[case] = any, best_pos,
 // best_v, n_hits, a0, bound_out, then NHIT x (hit_pos, hit_nd).  mode 0: rule_unsorted<3, false>, 1: rule_sparse<3, false>,
 // 2: rule_unsorted<LLV_K, true>, 3: rule_sparse<3, false, 32> as k_light2 runs it -- two cases per wave, 2b and 2b + 1 in the halves
-// of block b, each half with its own hit arrays
+// of block b, each half with its own hit arrays, 4: rule_sparse<3, false, 16> as k_light4 runs it -- four cases per wave, 4b .. 4b + 3
+// in the quarters of block b, each quarter with its own hit arrays
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
 k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *__restrict__ val, const uint32_t *__restrict__ offs,
             const uint32_t *__restrict__ bound_in, uint32_t L, uint32_t ref_len, int mode, uint32_t *__restrict__ out)
 {
-    __shared__ uint32_t hit_pos_s[2][NHIT];
-    __shared__ uint8_t hit_nd_s[2][NHIT];
-    const uint32_t half = mode == 3 ? lane_id() >> 5 : 0u, lane = mode == 3 ? lane_id() & 31u : lane_id();
-    const uint32_t c = mode == 3 ? 2u * blockIdx.x + half : blockIdx.x;
+    __shared__ uint32_t hit_pos_s[4][NHIT];
+    __shared__ uint8_t hit_nd_s[4][NHIT];
+    const uint32_t gw = mode == 3 ? 32u : mode == 4 ? 16u : 64u, half = lane_id() / gw, lane = lane_id() & (gw - 1u);
+    const uint32_t c = (64u / gw) * blockIdx.x + half;
     if (c >= n_cases) return;
     uint32_t *hit_pos = hit_pos_s[half];
     uint8_t *hit_nd = hit_nd_s[half];
@@ -2580,6 +2661,7 @@ k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *_
     if (mode == 0) rule_unsorted<3, false>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else if (mode == 1) rule_sparse<3, false>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else if (mode == 3) rule_sparse<3, false, 32>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
+    else if (mode == 4) rule_sparse<3, false, 16>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else rule_unsorted<LLV_K, true>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     WSYNC();
     uint32_t *w = out + (size_t)c * (6 + 2 * NHIT);
@@ -2590,7 +2672,7 @@ k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *_
 void launch_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *val, const uint32_t *offs, const uint32_t *bound_in,
                       uint32_t L, uint32_t ref_len, int mode, uint32_t *out, hipStream_t st)
 {
-    const uint32_t blocks = mode == 3 ? (n_cases + 1) / 2 : n_cases;
+    const uint32_t blocks = mode == 3 ? (n_cases + 1) / 2 : mode == 4 ? (n_cases + 3) / 4 : n_cases;
     if (n_cases) hipLaunchKernelGGL(k_diag_rule, dim3(blocks), dim3(64), 0, st, n_cases, pos, val, offs, bound_in, L, ref_len, mode, out);
 }
 uint32_t diag_rule_words() { return 6 + 2 * NHIT; }
@@ -2674,18 +2756,19 @@ void launch_diag_lv(const IndexView &ix, uint32_t n, const uint32_t *pos, const 
 // candidates cand[coffs[c]..coffs[c+1]) (at most 256) on the caller's mixRef.  mode 0: mismatch_capped per lane, 1: verify_quads<8>
 // (4 lanes per candidate, L <= 120), 2: verify_quads<8, 8> (L <= 248), 3 / 4: verify_quads_2<4> / <8> with the list split between the
 // "strands" (both use the same read), 5 / 6: verify_quads_2<4, 32> / <8, 32> as k_light2 runs them -- two cases per wave, 2b and 2b + 1
-// in the halves of block b, each set up like a case of modes 3 / 4.  out[i] = 0..3 or 255.  Candidates >= ref_len (a locate that wrapped
+// in the halves of block b, each set up like a case of modes 3 / 4; 7: verify_quads_2<4, 16> as k_light4 runs it -- four cases per
+// wave, in the quarters of block b.  out[i] = 0..3 or 255.  Candidates >= ref_len (a locate that wrapped
 // below 0, alnse.c:672-673) must come back 255 WITHOUT being used as an address: the test's mixRef is a few KB, so a regression reads
 // far outside of it only by value.
 __global__ void __launch_bounds__(64)
 k_diag_verify(const uint32_t *__restrict__ ref, uint32_t ref_len, uint32_t n_cases, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
               const uint32_t *__restrict__ cand, const uint32_t *__restrict__ coffs, int mode, uint8_t *__restrict__ out)
 {
-    __shared__ uint32_t pm_s[2][64];
-    __shared__ uint32_t loci_s[2][256];
-    __shared__ uint8_t val_s[2][256];
-    const uint32_t gw = mode >= 5 ? 32u : 64u, half = mode >= 5 ? lane_id() >> 5 : 0u, lane = lane_id() & (gw - 1u);
-    const uint32_t c = mode >= 5 ? 2u * blockIdx.x + half : blockIdx.x;
+    __shared__ uint32_t pm_s[4][64];
+    __shared__ uint32_t loci_s[4][256];
+    __shared__ uint8_t val_s[4][256];
+    const uint32_t gw = mode == 7 ? 16u : mode >= 5 ? 32u : 64u, half = lane_id() / gw, lane = lane_id() & (gw - 1u);
+    const uint32_t c = (64u / gw) * blockIdx.x + half;
     if (c >= n_cases) return;
     uint32_t *pm = pm_s[half], *loci = loci_s[half];
     uint8_t *val = val_s[half];
@@ -2710,14 +2793,15 @@ k_diag_verify(const uint32_t *__restrict__ ref, uint32_t ref_len, uint32_t n_cas
     else if (mode == 3) verify_quads_2(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
     else if (mode == 4) verify_quads_2<8>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
     else if (mode == 5) verify_quads_2<4, 32>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
-    else verify_quads_2<8, 32>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
+    else if (mode == 6) verify_quads_2<8, 32>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
+    else verify_quads_2<4, 16>(ref, ref_len, pm, pm, L, loci, n / 2, loci + n / 2, n - n / 2, val, val + n / 2);
     WSYNC();
     for (uint32_t i = lane; i < n; i += gw) out[c0 + i] = val[i];
 }
 void launch_diag_verify(const uint32_t *ref, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs, const uint32_t *cand,
                         const uint32_t *coffs, int mode, uint8_t *out, hipStream_t st)
 {
-    const uint32_t blocks = mode >= 5 ? (n_cases + 1) / 2 : n_cases;
+    const uint32_t blocks = mode == 7 ? (n_cases + 3) / 4 : mode >= 5 ? (n_cases + 1) / 2 : n_cases;
     if (n_cases) hipLaunchKernelGGL(k_diag_verify, dim3(blocks), dim3(64), 0, st, ref, ref_len, n_cases, seqs, offs, cand, coffs, mode, out);
 }
 

@@ -1673,14 +1673,14 @@ extern "C" int salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len,
                                     const uint32_t *cand, const uint32_t *cand_offs, int mode, uint8_t *out)
 {
     if (!ref_words || !seqs || !offs || !cand || !cand_offs || !out) return fail(SALT_E_INVAL, "null argument");
-    if (mode < 0 || mode > 6) return fail(SALT_E_INVAL, "mode must be 0..6");
+    if (mode < 0 || mode > 7) return fail(SALT_E_INVAL, "mode must be 0..7");
     if (n_cases == 0) return SALT_OK;
     int n_dev = 0;
     HIPCHK(hipGetDeviceCount(&n_dev));
     if (n_dev <= 0) return fail(SALT_E_HIP, "no HIP device visible");
     for (uint32_t i = 0; i < n_cases; ++i) {
         const uint32_t L = offs[i + 1] - offs[i];
-        if (L == 0 || L > SALT_MAX_READ_LEN || ((mode == 1 || mode == 3 || mode == 5) && L > 120) || ((mode == 2 || mode == 4 || mode == 6) && L > 248)) return fail(SALT_E_INVAL, "read length outside the verifier's range");
+        if (L == 0 || L > SALT_MAX_READ_LEN || ((mode == 1 || mode == 3 || mode == 5 || mode == 7) && L > 120) || ((mode == 2 || mode == 4 || mode == 6) && L > 248)) return fail(SALT_E_INVAL, "read length outside the verifier's range");
         if (cand_offs[i + 1] - cand_offs[i] > 256) return fail(SALT_E_INVAL, "at most 256 candidates per case");
     }
     const uint64_t nw = ((uint64_t)ref_len + 7) / 8 + 36, bases = offs[n_cases], nc = cand_offs[n_cases];
@@ -1708,6 +1708,11 @@ extern "C" int salt_gpu_ws_queue_counts(salt_gpu_ws_t *ws, uint32_t out[8])
     SeCtl c; HIPCHK(hipMemcpy(&c, ws->d_qctl, sizeof c, hipMemcpyDeviceToHost));
     memset(out, 0, 32);
     out[0] = c.light_queued; out[2] = c.gap_slots; out[5] = c.gap_items; out[6] = c.cigar_items; out[7] = c.cigar_head;
+    {   // the reads k_light4 left to k_light_retry
+        std::vector<QueueRange> qr(QUEUE_RANGES);
+        HIPCHK(hipMemcpy(qr.data(), ws->d_ranges, qr.size() * sizeof(QueueRange), hipMemcpyDeviceToHost));
+        for (const QueueRange &q : qr) out[4] += q.retry;
+    }
     {   // the longest R list and the longest C list among the segments of k_seed's walk queues
         std::vector<uint32_t> wc(seed_wq_cnt_words());
         HIPCHK(hipMemcpy(wc.data(), ws->d_wq_cnt, wc.size() * 4, hipMemcpyDeviceToHost));

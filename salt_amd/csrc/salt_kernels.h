@@ -91,16 +91,17 @@ struct SeCtl {
 };
 static_assert(sizeof(SeCtl) == 8 * 128 && alignof(SeCtl) == 128, "one control word per 128-byte line");
 // One range of k_heavy's queue, 256 bytes: the counter k_light's reads of that range are pushed through, and the heads k_heavy, k_gap and
-// k_gapfin pull the range's items from (pop_ranged), a 128-byte line apart from the counter.  QUEUE_RANGES of them, zeroed per batch.
+// k_gapfin pull the range's items from (pop_ranged), a 128-byte line apart from the counter; behind the heads the counter of the reads
+// k_light4 leaves to k_light_retry (nobody pulls while they push).  QUEUE_RANGES of them, zeroed per batch.
 static const uint32_t QUEUE_RANGES = 64;
 struct QueueRange {
     enum { HEAVY, GAP, GAPFIN };            // heads[]: k_heavy's, k_gap's, k_gapfin's
-    uint32_t push, pad0[31], heads[3], pad1[29];
+    uint32_t push, pad0[31], heads[3], retry, pad1[28];
 };
 static_assert(sizeof(QueueRange) == 256 && offsetof(QueueRange, push) == 0 && offsetof(QueueRange, heads) == 128, "k_light's counter, then the heads");
 void launch_light(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint8_t *seqs, const uint32_t *offs, const uint4 *sai_c,
                   const uint4 *sai_r, salt_result_t *results, uint32_t *queue, SeCtl *ctl, uint32_t *qseg, QueueRange *ranges, unsigned long long *ctr, hipStream_t st);
-size_t queue_words(uint32_t max_reads);                      // d_queue: the flat queue, k_heavy's overflow queue, k_light's segments
+size_t queue_words(uint32_t max_reads);                      // d_queue: the flat queue, k_heavy's overflow queue, k_light's segments, k_light4's retry segments
 // Deferred gapped passes (k_heavy -> k_gap -> k_gapfin -> k_cigar), `cap` slots; gctl = the workspace's control words
 struct GapBufs {
     uint32_t *gq;        // [cap] read index of the slot (0xFFFFFFFF: not used after all)
