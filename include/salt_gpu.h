@@ -253,6 +253,47 @@ int  salt_gpu_index_depth_text_begin(salt_gpu_index_t *ix, const salt_depth_text
 int  salt_gpu_index_depth_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes);
 int  salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws);
 
+/* ---- the error profile: mismatches by cycle, quality and substitution, SNP sites masked (`salt --error-profile`) ----------
+ * Which records contribute is the rule of the SNP counts: the row is mapped (pos != 0xFFFFFFFF), not skipped, and mapq >= min_mapq; only
+ * the primary alignment counts, never an alternative (XA) hit.
+ * The walk is k_snp_count's: a paired-end row's leading soft clip is seq_start; g = pos, s the index in SEQ as printed (reverse iff
+ * strand != 0 single end, strand == 1 paired end); I and S advance s, D advances g; ops beyond SALT_MAX_CIGAR_OPS are ignored.
+ * One base event is an M column with g < ref_len and s < L (L the read's length) for which (1) the mixRef mask at g has exactly one bit
+ * set -- sites (two or more bits) and N (mask 0) count nowhere -- and (2) the read's code there is 0 .. 3: a read's N counts nowhere.
+ * Its coordinates are the sequencer's, not the SAM's:
+ *   cycle = rev ? L - 1 - s : s                  0 .. 511
+ *   read  = the code as sequenced, seqs[offs[i] + cycle]
+ *   ref   = the index of the mask's bit (bit c = base code c), complemented (3 - c) when rev
+ *   q     = the FASTQ quality byte at `cycle` minus 33 when the byte is in 33 .. 126; otherwise, and when the call has no qualities, 94 ("none")
+ *   mate  = 0 single end and read 2i of a pair, 1 for read 2i + 1
+ * Tables, all uint64, owned by the device index and shared by its workspaces and forks, outside the image:
+ *   E[2][512][95][4][4]  indexed [mate][cycle][q][ref][read]: SALT_ERRPROF_CELLS cells, 12.45 MB
+ *   R[2][8]              per mate: records seen, skipped, unmapped, below min_mapq, counted, counted and reverse, counted with any I, D or
+ *                        S op, 0.  Skipped, unmapped and below min_mapq are exclusive and tested in that order; counted is the rest.
+ * The sums do not depend on batch order, stream, workspace or GPU, and the cells are 64-bit: nothing wraps silently.  (k_errprof sums
+ * per workgroup in 32-bit LDS cells that it flushes behind every tile of 16 cycles; such a cell never passes the workgroup's 1 024 reads.)
+ * While the profile is on, every entry point that leaves result rows adds its batch behind the kernels that finish the rows, on the same
+ * stream.  The text entry points take the qualities from the raw block on the device; the host-buffer and resident entry points count in
+ * q = 94 unless salt_gpu_ws_set_quals was called.  With the profile off no kernel is launched and nothing is copied; before the first
+ * enable nothing is allocated.
+ *   salt_gpu_index_errprof_enable  the first enable allocates and zeroes the tables (SALT_E_NOMEM names the size); on = 0 stops and keeps
+ *                                  them; min_mapq 0 .. 255 (above: SALT_E_INVAL).  Call with no align call in flight, like fetch.
+ *   salt_gpu_index_errprof_fetch   synchronises the device; cells (SALT_ERRPROF_CELLS of them) may be NULL (reset only), cap_cells too small
+ *                                  is SALT_E_INVAL with the number in the message; rec (may be NULL) gets R; reset != 0 zeroes both
+ *                                  afterwards.  Never enabled: SALT_E_INVAL.
+ *   salt_gpu_ws_errprof_uncount    takes back what the workspace's LAST successful align call added (the same kernel with delta 2^64 - 1
+ *                                  and that call's quality source; the call's buffers must be untouched since).  Nothing to take back: SALT_OK.
+ *   salt_gpu_ws_set_quals          quality bytes parallel to seqs, at the same offs, in FASTQ order (Phred + 33), for the NEXT host-buffer
+ *                                  or resident align call on this workspace, which consumes them; on_device != 0: a device pointer (a
+ *                                  host pointer cannot serve a resident call: SALT_E_INVAL there).  The bytes must stay valid until that
+ *                                  call returns (host) or its stream has run and no uncount is wanted any more (device).  NULL: none. */
+#define SALT_ERRPROF_Q      95                    /* q 0 .. 93 and "none" */
+#define SALT_ERRPROF_CELLS  (2u * SALT_MAX_READ_LEN * SALT_ERRPROF_Q * 16u)
+int  salt_gpu_index_errprof_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq);
+int  salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t rec[16], int reset);
+int  salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws);
+int  salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device);
+
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,
  * strict 4-line FASTQ records: the block is parsed, aligned and formatted on the device; the host only hands over the text and

@@ -102,6 +102,28 @@ int64_t salt_snp_count_sam(const salt_index_t *ix, const char *sam, size_t n, ui
 int64_t salt_depth_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t *diff, uint64_t n_words);
 int64_t salt_depth_text(const salt_index_t *ix, const uint32_t *diff, uint64_t n_words, uint32_t window, char *out, uint64_t cap);
 
+/* The error profile (`salt --error-profile`): the host twins of the device's k_errprof and the one printer of the file, written from the
+ * definition in salt_gpu.h without any code of the kernel's.  cells is uint64[n_cells], n_cells = 2 x 512 x 95 x 4 x 4 = 1 556 480 (anything
+ * else is an error), indexed [mate][cycle][q][ref][read]; rec is uint64[16], R[2][8] of salt_gpu.h.
+ *   salt_errprof_add_sam  cells and rec += the base events of the record lines of this program's own SAM text: mate from FLAG 0x80, reverse
+ *                         from 0x10, unmapped from 0x4; a record counts iff it is mapped and MAPQ >= min_mapq; global position = contig
+ *                         offset + POS - 1; q = QUAL[s] as printed, minus 33 when the byte is in 33 .. 126, else 94; QUAL `*` gives 94
+ *                         everywhere; SEQ letters are complemented back for reverse reads, cycle = L - 1 - s there.  Header lines ('@')
+ *                         and empty lines are skipped; any other line that is no SAM record of at most 512 bases is an error, and nothing
+ *                         of that line is added.  A skipped read prints as an empty line, so rec[1] and rec[9] ("skipped") stay 0 here and
+ *                         "seen" does not count such reads: the device's seen - skipped is this function's seen.  Returns the records
+ *                         that counted.
+ *   salt_errprof_text     the bytes of the file: tab-separated, '\n' line ends; "#salt-error-profile v1 min_mapq=<n>", then the sections
+ *                         R (per mate the seven counters), Q (mate, q 0 .. 93 then "none", bases, mismatches, empirical = -10 log10((mismatches
+ *                         + 1) / (bases + 2)) as %.2f), C (mate, cycle from 1, bases, mismatches), S (mate, ref, read as letters, count: 16
+ *                         rows a mate) and, with full != 0, E (mate, cycle, q, ref, read, count: the non-zero cells), each behind its '#'
+ *                         header line and ascending in its keys.  Only mates with records seen are printed; Q and C rows without bases are
+ *                         left out.  Returns the bytes the text takes; the first min(cap, that) of them are in out (out may be NULL with
+ *                         cap 0: the size only).  Both paths of `salt` print through this function.
+ * Both return -1 with salt_host_last_error() set on failure. */
+int64_t salt_errprof_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint64_t *cells, uint64_t n_cells, uint64_t rec[16]);
+int64_t salt_errprof_text(const uint64_t *cells, const uint64_t rec[16], uint32_t min_mapq, int full, char *out, uint64_t cap);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

@@ -511,6 +511,45 @@ def depth_text(index, diff, window=0):
     return out.raw[:n]
 
 
+ERRPROF_SHAPE = (2, 512, 95, 4, 4)       # E[mate][cycle][q][ref][read]; q 94 = "none"
+
+
+def errprof_add_sam(index, sam, min_mapq=0, tables=None):
+    """The error profile of this program's own SAM text (salt_errprof_add_sam, the host twin of the device's k_errprof): base events by
+    mate, cycle, quality, genome base and read base, the index's SNP sites and N left out.  tables: the (E, R) of an earlier call to add
+    into.  Returns (E uint64 (2, 512, 95, 4, 4), R uint64 (2, 8), records that counted)."""
+    h = host_lib()
+    h.salt_errprof_add_sam.restype = ctypes.c_int64
+    h.salt_errprof_add_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    sam = bytes(sam)
+    E, R = tables if tables is not None else (np.zeros(ERRPROF_SHAPE, dtype=np.uint64), np.zeros((2, 8), dtype=np.uint64))
+    for a, shape in ((E, ERRPROF_SHAPE), (R, (2, 8))):
+        if a.dtype != np.uint64 or a.shape != shape or not a.flags.c_contiguous:
+            raise SaltError("errprof_add_sam: tables must be contiguous uint64 arrays of shapes (2, 512, 95, 4, 4) and (2, 8)")
+    n = h.salt_errprof_add_sam(index._h, sam, len(sam), int(min_mapq), E.ctypes.data, E.size, R.ctypes.data)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    return E, R, int(n)
+
+
+def errprof_text(E, R, min_mapq=0, full=False):
+    """The bytes of `salt --error-profile`'s file for the tables (salt_errprof_text)."""
+    h = host_lib()
+    h.salt_errprof_text.restype = ctypes.c_int64
+    h.salt_errprof_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64]
+    E = np.ascontiguousarray(E, dtype=np.uint64)
+    R = np.ascontiguousarray(R, dtype=np.uint64)
+    if E.shape != ERRPROF_SHAPE or R.shape != (2, 8):
+        raise SaltError("errprof_text: tables of shapes (2, 512, 95, 4, 4) and (2, 8)")
+    n = h.salt_errprof_text(E.ctypes.data, R.ctypes.data, int(min_mapq), 1 if full else 0, None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_errprof_text(E.ctypes.data, R.ctypes.data, int(min_mapq), 1 if full else 0, out, n) != n:
+        raise SaltError("errprof_text: the size of the text changed between two calls")
+    return out.raw[:n]
+
+
 class _DepthTextOpt(ctypes.Structure):
     _fields_ = [("window", ctypes.c_uint32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
@@ -603,9 +642,11 @@ class GpuAligner:
                 m //= 2
             o = (offs[done:done + m + 1] - offs[done]).astype(np.uint32)
             s = seqs[int(offs[done]):int(offs[done + m])]
+            self._quals_for(int(offs[done]), int(offs[done + m]))
             _gpu_check(gpu_lib().salt_gpu_align_se(self._ws, ctypes.byref(co), m, s.ctypes.data, o.ctypes.data,
                                                    res[done:].ctypes.data))
             done += m
+        self._quals = None
         return res
 
     def alnpe_core1(self, opt, index, seqs, offs):
@@ -630,9 +671,11 @@ class GpuAligner:
                 m = (m // 2) & ~1
             o = (offs[done:done + m + 1] - offs[done]).astype(np.uint32)
             s = seqs[int(offs[done]):int(offs[done + m])]
+            self._quals_for(int(offs[done]), int(offs[done + m]))
             _gpu_check(lib.salt_gpu_align_pe(self._ws, ctypes.byref(co), ctypes.byref(pe), m // 2, s.ctypes.data,
                                              o.ctypes.data, res[done:].ctypes.data))
             done += m
+        self._quals = None
         return res
 
     def r_ctx(self):
@@ -807,6 +850,52 @@ class GpuAligner:
                 break
             out.append(ctypes.string_at(p.value, n.value))
         return out if pieces else b"".join(out)
+
+    def errprof_enable(self, on=True, min_mapq=0):
+        """Add, from now on, the base events of every align call on this aligner's device index (its forks included) to the index's error
+        profile; records below min_mapq do not count.  The first enable allocates and zeroes the tables (12.45 MB); on=False stops and
+        keeps them."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_errprof_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_errprof_enable(self._ix, 1 if on else 0, int(min_mapq)))
+
+    def errprof_table(self, reset=False):
+        """(E uint64 (2, 512, 95, 4, 4) indexed [mate][cycle][q][ref][read], R uint64 (2, 8)): the adds of all align calls since the
+        first enable or the last reset.  Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_errprof_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+        E = np.zeros(ERRPROF_SHAPE, dtype=np.uint64)
+        R = np.zeros((2, 8), dtype=np.uint64)
+        _gpu_check(lib.salt_gpu_index_errprof_fetch(self._ix, E.ctypes.data, E.size, R.ctypes.data, 1 if reset else 0))
+        return E, R
+
+    def errprof_uncount(self):
+        """Takes back what this aligner's last align call added to the error profile."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_errprof_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_ws_errprof_uncount(self._ws))
+
+    def set_quals(self, quals, on_device=False):
+        """Quality bytes (Phred + 33, FASTQ order) parallel to the bases of the NEXT alnse_core1 / alnpe_core1 (a uint8 array or bytes) or,
+        with on_device, of the next align_resident / align_pe_resident (a device pointer).  That call consumes them; None: none."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_set_quals.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        self._quals = None
+        if quals is None or on_device:
+            _gpu_check(lib.salt_gpu_ws_set_quals(self._ws, quals, 1 if on_device else 0))
+        else:
+            _gpu_check(lib.salt_gpu_ws_set_quals(self._ws, None, 0))
+            self._quals = np.ascontiguousarray(np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals, dtype=np.uint8)
+
+    def _quals_for(self, lo, hi):
+        """hands the pending host qualities of bases [lo, hi) to the batch that is about to be aligned"""
+        q = getattr(self, "_quals", None)
+        if q is None:
+            return
+        if len(q) < hi:
+            raise SaltError("set_quals: %d quality bytes for %d bases" % (len(q), hi))
+        self._qslice = np.ascontiguousarray(q[lo:hi])
+        _gpu_check(gpu_lib().salt_gpu_ws_set_quals(self._ws, self._qslice.ctypes.data, 0))
 
     def counters(self):
         out = (ctypes.c_uint64 * len(CTR_NAMES))()

@@ -45,6 +45,9 @@ struct salt_gpu_index {
     // by every workspace of the index while depth_on; the text state and its buffers come with the first salt_gpu_index_depth_text_begin
     uint32_t *d_depth = nullptr; uint32_t depth_min_mapq = 0; bool depth_on = false; DepthText *depth_text = nullptr;
     std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
+    // salt_gpu_index_errprof_enable: E[2][512][95][4][4] and R[2][8] behind it, uint64, allocated by the first enable (not part of the image)
+    // and shared by every workspace of the index while errprof_on
+    unsigned long long *d_errprof = nullptr; uint32_t errprof_min_mapq = 0; bool errprof_on = false;
 };
 
 // A device buffer with its owner: p[0 .. cap) elements, freed with the owner.  alloc() gives it exactly n elements (what it held is freed
@@ -128,6 +131,12 @@ struct salt_gpu_ws {
     uint32_t n_timed = 0;
     SnpCount snp_last{}; hipStream_t snp_last_st = nullptr;      // what the last align call counted (n_rec 0: nothing), for salt_gpu_ws_snp_uncount
     DepthMark depth_last{}; hipStream_t depth_last_st = nullptr; // likewise what it marked in the depth array, for salt_gpu_ws_depth_uncount
+    ErrProf ep_last{}; hipStream_t ep_last_st = nullptr;         // and what it added to the error profile, with its quality source, for salt_gpu_ws_errprof_uncount
+    // the error profile's quality bytes: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
+    // q_cur is the source of the call that is being queued (the text entry points set it to their raw block); d_quals holds a host call's bytes
+    const uint8_t *q_next = nullptr; bool q_next_dev = false;
+    struct { const uint8_t *quals = nullptr; const FqRec *rec = nullptr; uint64_t bytes = 0; } q_cur;
+    DevBuf<uint8_t> d_quals;
 };
 static const uint32_t MAX_TIMED = 256, EV_PER_CALL = 12;
 
@@ -301,6 +310,7 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     if (ix->d_c_off) { hipSetDevice(ix->device); hipFree(ix->d_c_off); hipFree(ix->d_c_name_off); hipFree(ix->d_c_names); }
     if (ix->d_snp_tab) { hipSetDevice(ix->device); hipFree(ix->d_snp_tab); hipFree(ix->d_snp_counts); }
     if (ix->d_depth || ix->depth_text) { hipSetDevice(ix->device); hipFree(ix->d_depth); depth_text_free(ix->depth_text); }
+    if (ix->d_errprof) { hipSetDevice(ix->device); hipFree(ix->d_errprof); }
     delete ix;
 }
 
@@ -484,11 +494,47 @@ static int depth_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_results, 
     ws->depth_last = c; ws->depth_last_st = st;
     return SALT_OK;
 }
-// both, behind the kernels that finish a batch's rows
+// The third: the rows' base events into the index's error profile (k_errprof), with the qualities of the call's source (ws->q_cur: the
+// text block, salt_gpu_ws_set_quals' bytes, or none).  With the profile off nothing is launched.
+static int errprof_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
+{
+    const salt_gpu_index *ix = ws->ix;
+    if (!ix->errprof_on) return SALT_OK;
+    ErrProf c{};
+    c.res = static_cast<const salt_result_t *>(d_results); c.seqs = static_cast<const uint8_t *>(d_seqs); c.offs = static_cast<const uint32_t *>(d_offs); c.n_rec = n_rec;
+    c.quals = ws->q_cur.quals; c.rec = ws->q_cur.rec; c.q_bytes = ws->q_cur.bytes;
+    c.ref = ix->view.ref; c.ref_len = ix->view.ref_len; c.cells = ix->d_errprof; c.min_mapq = ix->errprof_min_mapq; c.pe = pe; c.delta = 1ull;
+    HIPCHK(launch_errprof(c, st));
+    ws->ep_last = c; ws->ep_last_st = st;
+    return SALT_OK;
+}
+// all three, behind the kernels that finish a batch's rows
 static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
 {
-    const int rc = snp_hook(ws, n_rec, d_seqs, d_offs, d_results, pe, st);
-    return rc ? rc : depth_hook(ws, n_rec, d_results, st);
+    int rc = snp_hook(ws, n_rec, d_seqs, d_offs, d_results, pe, st);
+    if (!rc) rc = depth_hook(ws, n_rec, d_results, st);
+    return rc ? rc : errprof_hook(ws, n_rec, d_seqs, d_offs, d_results, pe, st);
+}
+// salt_gpu_ws_set_quals' bytes on their way into a call.  A host-buffer call copies host bytes up beside its bases (quals_upload; with the
+// profile off nothing is copied and they are dropped); every host-buffer or resident call then consumes the pointer (quals_take).
+static int quals_upload(salt_gpu_ws_t *ws, uint64_t bases, hipStream_t st)
+{
+    if (!ws->q_next || ws->q_next_dev) return SALT_OK;
+    if (!ws->ix->errprof_on) { ws->q_next = nullptr; return SALT_OK; }
+    if (int rc = ws->d_quals.reserve(bases + 64, st)) { ws->q_next = nullptr; return rc; }
+    const hipError_t e = hipMemcpyAsync(ws->d_quals, ws->q_next, bases, hipMemcpyHostToDevice, st);
+    ws->q_next = ws->d_quals; ws->q_next_dev = true;
+    if (e != hipSuccess) { ws->q_next = nullptr; return fail(SALT_E_HIP, std::string("hipMemcpyAsync(quality bytes): ") + hipGetErrorString(e)); }
+    return SALT_OK;
+}
+static int quals_take(salt_gpu_ws_t *ws)
+{
+    ws->q_cur = {};
+    const uint8_t *q = ws->q_next; ws->q_next = nullptr;
+    if (!q) return SALT_OK;
+    if (!ws->q_next_dev) return fail(SALT_E_INVAL, "salt_gpu_ws_set_quals: host quality bytes cannot serve a resident call (pass a device pointer, on_device = 1)");
+    ws->q_cur.quals = q; ws->q_cur.bytes = ~0ull;
+    return SALT_OK;
 }
 
 // ---- the workspace's buffer families: each is sized here and nowhere else ----
@@ -524,6 +570,8 @@ static int reserve_pack(salt_gpu_ws_t *ws, uint32_t n_reads, const PackGeom &pg,
 extern "C" int salt_gpu_align_se_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint32_t n_reads, uint32_t max_read_len,
                                           const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream)
 {
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (int rc = quals_take(ws)) return rc;
     return align_resident_impl(ws, o, n_reads, max_read_len, d_seqs, d_offs, d_results, hip_stream, 0);
 }
 
@@ -531,7 +579,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe)
 {
     if (!ws || !o || !d_seqs || !d_offs || !d_results) return fail(SALT_E_INVAL, "null argument");
-    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0;
+    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0; ws->ep_last.n_rec = 0;
     if (n_reads == 0) return SALT_OK;
     uint32_t spr = 0;
     int rc = check_opt(ws->ix, o, max_read_len, &spr);
@@ -644,6 +692,7 @@ extern "C" int salt_gpu_align_se(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uin
     HIPCHK(hipSetDevice(ws->ix->device));
     HIPCHK(hipMemcpyAsync(ws->d_seqs, seqs, bases, hipMemcpyHostToDevice, ws->stream));
     HIPCHK(hipMemcpyAsync(ws->d_offs, offs, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice, ws->stream));
+    if (int rc2 = quals_upload(ws, bases, ws->stream)) return rc2;
     int rc = salt_gpu_align_se_resident(ws, o, n_reads, max_len, ws->d_seqs, ws->d_offs, ws->d_results, ws->stream);
     if (rc) return rc;
     return fetch_results(ws, n_reads, results, ws->stream);
@@ -1121,7 +1170,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
 {
     const uint64_t n_src = n_bytes;
     if (d_src && add_newline) ++n_bytes;
-    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0;
+    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0; ws->ep_last.n_rec = 0;
     salt_gpu_index *ix = ws->ix;
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
@@ -1158,6 +1207,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
     if ((rc = text_codes(ws, n_rec, "block", st, &max_len))) return rc;
     // ---- align ----
     tr.mark();
+    ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = n_bytes;      // the error profile reads the qualities where they lie
     if ((rc = align_resident_impl(ws, o, n_rec, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st, 0))) return rc;
     tr.mark();
     // ---- SAM text ----
@@ -1179,7 +1229,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
 {
     if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
-    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0;
+    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0; ws->ep_last.n_rec = 0;
     if (n1 == 0 && n2 == 0) return SALT_OK;
     if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
     if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
@@ -1219,6 +1269,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->d_scan.cap, st));
     uint32_t max_len = 0;
     if ((rc = text_codes(ws, n_rec, "blocks", st, &max_len))) return rc;
+    ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = b2 + n2;      // both blocks; a mate's qual_off counts from d_raw
     if ((rc = pe_resident_impl(ws, o, pe, n, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st))) return rc;
     TextTrace tr;                                               // off: the stage clocks are single end's
     if ((rc = text_emit(ws, to, pe, n_rec, max_len, st, tr, sam, sam_bytes))) return rc;
@@ -1931,6 +1982,65 @@ extern "C" int salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws)
     return SALT_OK;
 }
 
+// ---- the error profile ----
+static const char *const ERRPROF_NEVER = "error profile: the profile was never enabled on this index (salt_gpu_index_errprof_enable)";
+static const uint64_t ERRPROF_ALL = (uint64_t)SALT_ERRPROF_CELLS + 16;      // E, then R
+
+extern "C" int salt_gpu_index_errprof_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (min_mapq > 255) return fail(SALT_E_INVAL, "error profile: min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
+    HIPCHK(hipSetDevice(ix->device));
+    if (on && !ix->d_errprof) {
+        const uint64_t bytes = ERRPROF_ALL * 8;
+        unsigned long long *d = nullptr;
+        if (hipMalloc((void **)&d, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SALT_E_NOMEM, "error profile: no room for the tables: " + std::to_string(bytes) + " bytes (8 per cell of E[2][512][95][4][4] and R[2][8])");
+        }
+        const hipError_t e = hipMemset(d, 0, bytes);
+        if (e != hipSuccess) { hipFree(d); return fail(SALT_E_HIP, std::string("hipMemset(error profile): ") + hipGetErrorString(e)); }
+        ix->d_errprof = d;
+    }
+    ix->errprof_min_mapq = min_mapq; ix->errprof_on = on != 0;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t rec[16], int reset)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_errprof) return fail(SALT_E_INVAL, ERRPROF_NEVER);
+    if (cells && cap_cells < SALT_ERRPROF_CELLS)
+        return fail(SALT_E_INVAL, "error profile: room for " + std::to_string(cap_cells) + " cells, the table has " + std::to_string((uint64_t)SALT_ERRPROF_CELLS) + " (2 x 512 x 95 x 4 x 4)");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (cells) HIPCHK(hipMemcpy(cells, ix->d_errprof, (uint64_t)SALT_ERRPROF_CELLS * 8, hipMemcpyDeviceToHost));
+    if (rec) HIPCHK(hipMemcpy(rec, ix->d_errprof + SALT_ERRPROF_CELLS, 16 * 8, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ix->d_errprof, 0, ERRPROF_ALL * 8));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (!ws->ix->d_errprof) return fail(SALT_E_INVAL, ERRPROF_NEVER);
+    if (ws->ep_last.n_rec == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ws->ix->device));
+    ErrProf c = ws->ep_last;
+    c.delta = ~0ull;                                                               // + (2^64 - 1) = - 1 in the cells' arithmetic
+    ws->ep_last.n_rec = 0;
+    HIPCHK(launch_errprof(c, ws->ep_last_st));
+    HIPCHK(hipStreamSynchronize(ws->ep_last_st));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    ws->q_next = quals; ws->q_next_dev = quals && on_device != 0;
+    return SALT_OK;
+}
+
 extern "C" int salt_gpu_index_r_ctx(const salt_gpu_index_t *ix, void **dev_ptr, uint64_t *bytes)
 {
     if (!ix || !dev_ptr || !bytes) return fail(SALT_E_INVAL, "null argument");
@@ -2039,6 +2149,7 @@ extern "C" int salt_gpu_align_pe_resident(salt_gpu_ws_t *ws, const salt_aln_opt_
     if (2ull * n_pairs > ws->max_reads) return fail(SALT_E_CAPACITY, "more mates than the workspace holds");
     if (!ws->ix->d_pac) return fail(SALT_E_INVAL, "paired end needs the 2-bit genome: call salt_gpu_index_set_pac first");
     HIPCHK(hipSetDevice(ws->ix->device));
+    if (int rc = quals_take(ws)) return rc;
     return pe_resident_impl(ws, o, pe, n_pairs, max_read_len, d_seqs, d_offs, d_results, static_cast<hipStream_t>(hip_stream));
 }
 
@@ -2063,7 +2174,10 @@ extern "C" int salt_gpu_align_pe(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, con
     hipStream_t st = ws->stream;
     HIPCHK(hipMemcpyAsync(ws->d_seqs, seqs, bases, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ws->d_offs, offs, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice, st));
-    int rc = pe_resident_impl(ws, o, pe, n_pairs, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st);
+    int rc = quals_upload(ws, bases, st);
+    if (!rc) rc = quals_take(ws);
+    if (rc) return rc;
+    rc = pe_resident_impl(ws, o, pe, n_pairs, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st);
     if (rc) return rc;
     rc = fetch_results(ws, n_reads, results, st);
     if (rc) return rc;

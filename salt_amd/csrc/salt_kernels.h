@@ -283,6 +283,20 @@ int depth_text_begin(DepthText *t, const uint32_t *d_diff, uint32_t ref_len, con
                      const std::vector<int64_t> &h_c_off, uint32_t max_name, uint32_t window, uint32_t tile_positions, int bgzf, std::string &err);
 int depth_text_next(DepthText *t, const char **data, uint64_t *n_bytes, std::string &err);
 
+// ---- the error profile (salt_errprof.hip) ----
+static constexpr uint32_t SALT_EP_CHUNK = 1024;                                // reads (of one mate) a workgroup of k_errprof owns, a lane each
+struct ErrProf {                                                               // what k_errprof reads (by value)
+    const salt_result_t *res; const uint8_t *seqs; const uint32_t *offs; uint32_t n_rec;      // the batch: rows, codes as sequenced, offsets
+    // the quality bytes (Phred + 33, FASTQ order): null = none (q 94); rec null: read i's lie at quals + offs[i] (parallel to seqs), else at
+    // quals + rec[i].qual_off (the text path's raw block); q_bytes: the bytes behind quals, a read whose range leaves them counts in q 94
+    const uint8_t *quals; const FqRec *rec; uint64_t q_bytes;
+    const uint32_t *ref; uint32_t ref_len;                                     // the 4-bit mixRef
+    unsigned long long *cells;                                                 // E[2][512][95][4][4], then R[2][8]
+    uint32_t min_mapq; int32_t pe;                                             // pe: rows of a paired-end batch (reverse iff strand == 1, soft clips, mate = i & 1)
+    unsigned long long delta;                                                  // 1; 2^64 - 1 takes a batch's adds back
+};
+hipError_t launch_errprof(const ErrProf &c, hipStream_t st);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstdarg>
+#include <cmath>
 #include <fstream>
 #include <mutex>
 #include <sstream>
@@ -845,6 +846,152 @@ extern "C" int64_t salt_depth_text(const salt_index_t *ix, const uint32_t *diff,
                 o.put((char)('0' + (int)(h % 100u) / 10)); o.put((char)('0' + (int)(h % 100u) % 10)); o.put('\n');
             }
         }
+    }
+    return (int64_t)o.n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The error profile: the host twin of k_errprof (salt_errprof.hip; include/salt_gpu.h has the definition), written from that definition
+// over this program's own SAM record lines and without any code of the kernel's, and the printer of the file.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+const uint64_t EP_CYCLES = 512, EP_Q = 95, EP_CELLS = 2 * EP_CYCLES * EP_Q * 16;
+
+// one record line [l, e): its base events into cells, its fate into rec; 1 it counted, 0 it did not (unmapped, below min_mapq), -1 with g_err set
+int errprof_add_line(const salt_index *ix, const RefIds &ids, const char *l, const char *e, uint32_t min_mapq, uint64_t *cells, uint64_t *rec)
+{
+    const char *f[12]; int nf = 0;
+    f[nf++] = l;
+    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
+    auto bad = [&](const char *why) { g_err = std::string("error profile: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return -1; };
+    if (nf < 11) return bad("fewer than 11 fields");
+    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };
+    int64_t flag, pos1, mapq;
+    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
+        pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
+    uint64_t *r = rec + ((flag & 0x80) ? 8 : 0);
+    const uint64_t mate = (flag & 0x80) ? 1 : 0;
+    if (flag & 4) { ++r[0]; ++r[2]; return 0; }                        // unmapped, also a mate printed at its mate's place
+    if ((uint64_t)mapq < min_mapq) { ++r[0]; ++r[3]; return 0; }
+    const bool rev = (flag & 0x10) != 0;
+    const int32_t rid = ids.find(f[2], fe(2));
+    if (rid < 0) return bad("RNAME is no sequence of the index");
+    if (pos1 < 1) return bad("a mapped record without a position");
+    const char *seq = f[9], *qual = f[10]; const size_t l_seq = (size_t)(fe(9) - seq), l_qual = (size_t)(fe(10) - qual);
+    if (l_seq == 0 || l_seq > EP_CYCLES) return bad("SEQ is empty or longer than 512 bases");
+    const bool no_qual = l_qual == 1 && qual[0] == '*' && l_seq != 1;
+    if (!no_qual && l_qual != l_seq) return bad("QUAL is neither * nor as long as SEQ");
+    const uint64_t ref_len = ix->view.ref_len;
+    // the line is checked whole before anything is added: a refused line leaves the tables as they were
+    uint32_t ev[EP_CYCLES]; size_t n_ev = 0;
+    uint64_t g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)pos1 - 1;      // global position; the walk may run past the contig's end
+    size_t s = 0; uint64_t n = 0; bool digits = false, any = false, gapped = false;
+    for (const char *p = f[5]; p < fe(5); ++p) {
+        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
+        if (!digits) return bad("malformed CIGAR");
+        switch (*p) {
+        case 'M':
+            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
+            for (uint64_t k = 0; k < n; ++k, ++g, ++s) {
+                if (g >= ref_len) continue;
+                const uint32_t m = mask_at(ix, (uint32_t)g);
+                if (m == 0 || (m & (m - 1u)) != 0) continue;                   // N of the genome; a site
+                int b;
+                switch (seq[s]) { case 'A': b = 0; break; case 'C': b = 1; break; case 'G': b = 2; break; case 'T': b = 3; break; default: b = -1; }
+                if (b < 0) continue;                                           // a read's N
+                int c = 0; while (!((m >> c) & 1u)) ++c;
+                const uint32_t q = no_qual ? 94u : ((uint8_t)qual[s] >= 33 && (uint8_t)qual[s] <= 126 ? (uint32_t)(uint8_t)qual[s] - 33u : 94u);
+                const uint64_t cycle = rev ? l_seq - 1 - s : s;
+                ev[n_ev++] = (uint32_t)(((mate * EP_CYCLES + cycle) * EP_Q + q) * 16 + (uint64_t)(rev ? 3 - c : c) * 4 + (uint64_t)(rev ? 3 - b : b));
+            }
+            break;
+        case 'I': case 'S':
+            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
+            s += n; gapped = true; break;
+        case 'D': g += n; gapped = true; break;
+        default: return bad("a CIGAR operation this program does not write");
+        }
+        n = 0; digits = false; any = true;
+    }
+    if (digits || !any) return bad("malformed CIGAR");
+    for (size_t k = 0; k < n_ev; ++k) ++cells[ev[k]];
+    ++r[0]; ++r[4];
+    if (rev) ++r[5];
+    if (gapped) ++r[6];
+    return 1;
+}
+
+} // namespace
+
+extern "C" int64_t salt_errprof_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint64_t *cells, uint64_t n_cells, uint64_t rec[16])
+{
+    if (!ix || (!sam && n) || !cells || !rec) { g_err = "error profile: null argument"; return -1; }
+    if (n_cells != EP_CELLS) { g_err = "error profile: a table of " + std::to_string(n_cells) + " cells, the profile has " + std::to_string(EP_CELLS) + " (2 x 512 x 95 x 4 x 4)"; return -1; }
+    const RefIds ids(ix);
+    int64_t n_rec = 0;
+    for (const char *l = sam, *end = sam + n; l < end; ) {
+        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
+        if (!e) e = end;
+        if (e > l && *l != '@') {                                      // (empty lines: a skipped read, the paired-end driver's; '@': a header line)
+            const int r = errprof_add_line(ix, ids, l, e, min_mapq, cells, rec);
+            if (r < 0) return -1;
+            n_rec += r;
+        }
+        l = e + 1;
+    }
+    return n_rec;
+}
+
+extern "C" int64_t salt_errprof_text(const uint64_t *cells, const uint64_t rec[16], uint32_t min_mapq, int full, char *out, uint64_t cap)
+{
+    if (!cells || !rec || (!out && cap)) { g_err = "error profile: null argument"; return -1; }
+    DepthOut o{ out, cap };
+    static const char NT[] = "ACGT";
+    auto cell = [&](uint64_t mate, uint64_t cyc, uint64_t q, uint64_t rr) { return cells[((mate * EP_CYCLES + cyc) * EP_Q + q) * 16 + rr]; };
+    auto row = [&](char tag, uint64_t mate) { o.put(tag); o.put('\t'); o.putu(mate); };
+    auto num = [&](uint64_t v) { o.put('\t'); o.putu(v); };
+    const bool show[2] = { rec[0] != 0, rec[8] != 0 };
+    o.puts("#salt-error-profile\tv1\tmin_mapq="); o.putu(min_mapq); o.put('\n');
+    o.puts("#R\tmate\tseen\tskipped\tunmapped\tlow_mapq\tcounted\treverse\tgapped\n");
+    for (uint64_t m = 0; m < 2; ++m) if (show[m]) { row('R', m); for (int k = 0; k < 7; ++k) num(rec[m * 8 + (uint64_t)k]); o.put('\n'); }
+    o.puts("#Q\tmate\tq\tbases\tmismatches\tempirical\n");
+    for (uint64_t m = 0; m < 2; ++m) if (show[m])
+        for (uint64_t q = 0; q < EP_Q; ++q) {
+            uint64_t bases = 0, mm = 0;
+            for (uint64_t c = 0; c < EP_CYCLES; ++c) for (uint64_t rr = 0; rr < 16; ++rr) { const uint64_t v = cell(m, c, q, rr); bases += v; if ((rr >> 2) != (rr & 3)) mm += v; }
+            if (!bases) continue;
+            row('Q', m); o.put('\t');
+            if (q == EP_Q - 1) o.puts("none"); else o.putu(q);
+            num(bases); num(mm);
+            char b[64]; snprintf(b, sizeof b, "\t%.2f\n", -10.0 * log10(((double)mm + 1.0) / ((double)bases + 2.0)));
+            o.puts(b);
+        }
+    o.puts("#C\tmate\tcycle\tbases\tmismatches\n");
+    for (uint64_t m = 0; m < 2; ++m) if (show[m])
+        for (uint64_t c = 0; c < EP_CYCLES; ++c) {
+            uint64_t bases = 0, mm = 0;
+            for (uint64_t q = 0; q < EP_Q; ++q) for (uint64_t rr = 0; rr < 16; ++rr) { const uint64_t v = cell(m, c, q, rr); bases += v; if ((rr >> 2) != (rr & 3)) mm += v; }
+            if (!bases) continue;
+            row('C', m); num(c + 1); num(bases); num(mm); o.put('\n');
+        }
+    o.puts("#S\tmate\tref\tread\tcount\n");
+    for (uint64_t m = 0; m < 2; ++m) if (show[m])
+        for (uint64_t rr = 0; rr < 16; ++rr) {
+            uint64_t v = 0;
+            for (uint64_t c = 0; c < EP_CYCLES; ++c) for (uint64_t q = 0; q < EP_Q; ++q) v += cell(m, c, q, rr);
+            row('S', m); o.put('\t'); o.put(NT[rr >> 2]); o.put('\t'); o.put(NT[rr & 3]); num(v); o.put('\n');
+        }
+    if (full) {
+        o.puts("#E\tmate\tcycle\tq\tref\tread\tcount\n");
+        for (uint64_t m = 0; m < 2; ++m) if (show[m])
+            for (uint64_t c = 0; c < EP_CYCLES; ++c) for (uint64_t q = 0; q < EP_Q; ++q) for (uint64_t rr = 0; rr < 16; ++rr) {
+                const uint64_t v = cell(m, c, q, rr);
+                if (!v) continue;
+                row('E', m); num(c + 1); o.put('\t');
+                if (q == EP_Q - 1) o.puts("none"); else o.putu(q);
+                o.put('\t'); o.put(NT[rr >> 2]); o.put('\t'); o.put(NT[rr & 3]); num(v); o.put('\n');
+            }
     }
     return (int64_t)o.n;
 }

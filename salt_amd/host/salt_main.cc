@@ -78,6 +78,13 @@ extern "C" int salt_gpu_index_depth_text_begin(salt_gpu_index_t *ix, const salt_
 extern "C" int salt_gpu_index_depth_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
 extern "C" int salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
+// And the error profile (--error-profile): without the device's tables and kernel it is summed from the SAM lines by the host twin
+// (salt_errprof_add_sam); the file is printed by salt_errprof_text either way.
+extern "C" int salt_gpu_index_errprof_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq) __attribute__((weak));
+extern "C" int salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t rec[16], int reset) __attribute__((weak));
+extern "C" int salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
+extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device) __attribute__((weak));
+
 namespace {
 
 const int N_SEQS = 100000;
@@ -497,16 +504,36 @@ bool depth_host_add(const char *sam, size_t n)
     fprintf(stderr, "[salt] %s\n", salt_host_last_error());
     return false;
 }
+// --error-profile FILE: mismatches by cycle, quality and substitution, the index's SNP sites masked.  On the device every GPU's index holds
+// the tables that every align call adds to (salt_gpu_index_errprof_enable; the host pipeline hands its batches' qualities over with
+// salt_gpu_ws_set_quals); after the last block they are fetched and summed on the host.  A block the text path has aligned and then drops
+// at a hand-over is taken back (salt_gpu_ws_errprof_uncount).  Without the device's symbols the SAM lines of every block and batch that
+// is written go through salt_errprof_add_sam, one caller at a time.  salt_errprof_text prints the file on both paths.
+const size_t ERRPROF_CELLS = 2u * 512u * 95u * 16u;
+struct ErrprofRun {
+    bool on = false, device = false, full = false; const char *fn = nullptr; FILE *fp = nullptr; uint32_t min_mapq = 0;
+    const salt_index_t *ix = nullptr; std::mutex mu; std::vector<uint64_t> cells; uint64_t rec[16] = { 0 };
+    bool host() const { return on && !device; }
+} g_errprof;
+
+bool errprof_host_add(const char *sam, size_t n)
+{
+    std::lock_guard<std::mutex> lk(g_errprof.mu);
+    if (salt_errprof_add_sam(g_errprof.ix, sam, n, g_errprof.min_mapq, g_errprof.cells.data(), g_errprof.cells.size(), g_errprof.rec) >= 0) return true;
+    fprintf(stderr, "[salt] %s\n", salt_host_last_error());
+    return false;
+}
 // the SAM lines of a block or batch that is about to be written, through every host twin that is on
 bool host_twins_add(const char *sam, size_t n)
 {
-    return (!g_snp.host() || snp_host_add(sam, n)) && (!g_depth.host() || depth_host_add(sam, n));
+    return (!g_snp.host() || snp_host_add(sam, n)) && (!g_depth.host() || depth_host_add(sam, n)) && (!g_errprof.host() || errprof_host_add(sam, n));
 }
 // a block the text path aligned and will not write leaves the device's tables
 void drop_block(salt_gpu_ws_t *ws)
 {
     snp_drop_block(ws);
     if (g_depth.on && g_depth.device && salt_gpu_ws_depth_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
+    if (g_errprof.on && g_errprof.device && salt_gpu_ws_errprof_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
 }
 
 // SAM lines -> BAM records in `out`; false with the reason on stderr (a read name past the format's limit)
@@ -619,6 +646,10 @@ int usage()
             "                                        of equal depth; a name ending in .gz is written as BGZF [off]\n"
             "               --depth-min-mapq <int>   --depth: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
             "               --depth-window  <int>    --depth: the mean depth of every window of <int> positions instead [per base]\n"
+            "               --error-profile <file>   write how often a sequenced base disagrees with the genome, by cycle, base quality and\n"
+            "                                        substitution, the index's SNP sites left out (counted on the GPU; tab-separated) [off]\n"
+            "               --error-profile-min-mapq <int>  --error-profile: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
+            "               --error-profile-full     --error-profile: also every non-zero cell (mate, cycle, quality, ref, read)\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -1301,6 +1332,20 @@ static void interleave_mates(const Batch &b, const Batch &m, std::vector<uint8_t
         memcpy(iseq.data() + ioff[2 * i + 1], m.seqs.data() + m.offs[i], l1); ioff[2 * i + 2] = ioff[2 * i + 1] + l1;
     }
 }
+// the quality bytes of a parsed batch in the layout of the bases handed to the device: read i's at offs[i], mates interleaved as interleave_mates does
+static void batch_quals(const Batch &b, const Batch *m, std::vector<uint8_t> &q)
+{
+    const size_t n = (size_t)b.n();
+    q.resize(b.seqs.size() + (m ? m->seqs.size() : 0));
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t l0 = b.offs[i + 1] - b.offs[i];
+        memcpy(q.data() + at, b.raw.data() + b.qual[i], l0); at += l0;
+        if (!m) continue;
+        const uint32_t l1 = m->offs[i + 1] - m->offs[i];
+        memcpy(q.data() + at, m->raw.data() + m->qual[i], l1); at += l1;
+    }
+}
 struct Opts {
     int n_threads = 1, n_gpus = 1, overlap = -1, pe = 0;
     salt_aln_opt_t ao{}; salt_sam_opt_t so{};
@@ -1318,7 +1363,8 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "max_tlen", 1, 0, 'b' }, { "group", 1, 0, 'g' }, { "sw", 0, 0, 'e' }, { "max_locate", 1, 0, 'm' }, { "max_seed", 1, 0, 's' },
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
         { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 },
-        { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { "depth", 1, 0, 1006 }, { "depth-min-mapq", 1, 0, 1007 }, { "depth-window", 1, 0, 1008 }, { 0, 0, 0, 0 } };
+        { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { "depth", 1, 0, 1006 }, { "depth-min-mapq", 1, 0, 1007 }, { "depth-window", 1, 0, 1008 },
+        { "error-profile", 1, 0, 1009 }, { "error-profile-min-mapq", 1, 0, 1010 }, { "error-profile-full", 0, 0, 1011 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1360,6 +1406,14 @@ static int parse_options(int argc, char **argv, Opts &o)
             g_depth.window = (uint32_t)v;
             break;
         }
+        case 1009: g_errprof.on = true; g_errprof.fn = optarg; break;
+        case 1010: {
+            char *end = nullptr; const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --error-profile-min-mapq %s: a MAPQ is a number from 0 to 255\n", optarg); return 1; }
+            g_errprof.min_mapq = (uint32_t)v;
+            break;
+        }
+        case 1011: g_errprof.full = true; break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1392,6 +1446,13 @@ static int parse_options(int argc, char **argv, Opts &o)
         const size_t l = strlen(g_depth.fn);
         g_depth.gz = l > 3 && strcmp(g_depth.fn + l - 3, ".gz") == 0;
         if (!(g_depth.fp = fopen(g_depth.fn, "wb"))) { fprintf(stderr, "[opt_parse]: --depth: cannot open %s for writing: %s\n", g_depth.fn, strerror(errno)); return 1; }
+    }
+    if (g_errprof.on) {
+        g_errprof.device = salt_gpu_index_errprof_enable && salt_gpu_index_errprof_fetch && salt_gpu_ws_errprof_uncount && salt_gpu_ws_set_quals;
+        // summed on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
+        if (!g_errprof.device && g_polish) { fprintf(stderr, "[opt_parse]: --error-profile with --polish needs a libsalt_gpu that makes the profile on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
+        if (!g_errprof.device) g_bgzf.device = g_bam.device = false;
+        if (!(g_errprof.fp = fopen(g_errprof.fn, "w"))) { fprintf(stderr, "[opt_parse]: --error-profile: cannot open %s for writing: %s\n", g_errprof.fn, strerror(errno)); return 1; }
     }
     return -1;
 }
@@ -1547,13 +1608,18 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (b->n() == 0) { std::unique_lock<std::mutex> lk(mu); done.push_back(std::move(b)); cv.notify_all(); continue; }
                 b->res.resize((size_t)b->n() * (pe ? 2 : 1));
                 double tg0 = now();
+                std::vector<uint8_t> iqual;                      // --error-profile on the device: the batch's qualities, parallel to the bases
+                if (g_errprof.on && g_errprof.device) {
+                    batch_quals(*b, pe ? b->mate.get() : nullptr, iqual);
+                    if (salt_gpu_ws_set_quals(ws[(size_t)g], iqual.data(), 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
+                }
                 int grc = pe ? salt_gpu_align_pe(ws[(size_t)g], &o.ao, &o.po, (uint32_t)b->n(), iseq.data(), ioff.data(), b->res.data())
                              : salt_gpu_align_se(ws[(size_t)g], &o.ao, (uint32_t)b->n(), b->seqs.data(), b->offs.data(), b->res.data());
                 t_gpu = t_gpu + (now() - tg0);
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
-                if (g_snp.host() || g_depth.host()) {
+                if (g_snp.host() || g_depth.host() || g_errprof.host()) {
                     bool good = true;
                     for (const std::string &piece : b->sam) good = good && host_twins_add(piece.data(), piece.size());
                     if (!good) { set_failed(); break; }
@@ -1656,6 +1722,49 @@ static bool snp_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_
     if (!ok) { fprintf(stderr, "[salt] --snp-counts: write error on %s\n", g_snp.fn); return false; }
     fprintf(stderr, "[salt] SNP counts: %llu sites, %s, MAPQ >= %u -> %s\n", (unsigned long long)g_snp.n_sites, g_snp.device ? "counted on the device" : "counted on the host from the SAM lines",
             g_snp.min_mapq, g_snp.fn);
+    return true;
+}
+
+// --error-profile, before the first block: the profile on on every GPU's index, or the host's tables
+static bool errprof_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_errprof.on) return true;
+    g_errprof.ix = ix;
+    g_errprof.cells.assign(ERRPROF_CELLS, 0);
+    if (!g_errprof.device) return true;
+    for (salt_gpu_index_t *g : gix)
+        if (salt_gpu_index_errprof_enable(g, 1, g_errprof.min_mapq)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    return true;
+}
+
+// --error-profile, after the last block of a run that succeeded: every GPU's tables are fetched and summed on the host, and the file is printed
+static bool errprof_finish(const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_errprof.on) return true;
+    if (g_errprof.device) {
+        std::vector<uint64_t> one(ERRPROF_CELLS);
+        for (salt_gpu_index_t *g : gix) {
+            uint64_t rec[16];
+            if (salt_gpu_index_errprof_fetch(g, one.data(), one.size(), rec, 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+            for (size_t i = 0; i < one.size(); ++i) g_errprof.cells[i] += one[i];
+            for (int i = 0; i < 16; ++i) g_errprof.rec[i] += rec[i];
+        }
+    }
+    const int64_t need = salt_errprof_text(g_errprof.cells.data(), g_errprof.rec, g_errprof.min_mapq, g_errprof.full ? 1 : 0, nullptr, 0);
+    std::string text(need > 0 ? (size_t)need : 0, '\0');
+    if (need < 0 || salt_errprof_text(g_errprof.cells.data(), g_errprof.rec, g_errprof.min_mapq, g_errprof.full ? 1 : 0, &text[0], (uint64_t)need) != need) {
+        fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false;
+    }
+    FILE *f = g_errprof.fp;
+    bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    ok = !ferror(f) && fclose(f) == 0 && ok;
+    g_errprof.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --error-profile: write error on %s\n", g_errprof.fn); return false; }
+    uint64_t bases = 0;
+    for (uint64_t v : g_errprof.cells) bases += v;
+    fprintf(stderr, "[salt] error profile: %llu records, %llu bases, %s, MAPQ >= %u -> %s (%llu bytes)\n", (unsigned long long)(g_errprof.rec[4] + g_errprof.rec[12]),
+            (unsigned long long)bases, g_errprof.device ? "counted on the device" : "counted on the host from the SAM lines", g_errprof.min_mapq, g_errprof.fn,
+            (unsigned long long)text.size());
     return true;
 }
 
@@ -1775,16 +1884,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
-    if (!snp_begin(ix, gix) || !depth_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
+    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs)) ? 1 : rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix)) ? 1 : rc); }
         header_out = true;
     }
     const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
-    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs)) ? 1 : rc);
+    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix)) ? 1 : rc);
 }
