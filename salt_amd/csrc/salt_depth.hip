@@ -19,10 +19,9 @@
 #include <vector>
 #include "salt_device.h"
 #include "salt_kernels.h"
+#include "salt_tally.h"
 
 namespace salt {
-
-static inline uint32_t dgrid(uint64_t n) { uint64_t b = (n + 255) / 256; if (b > (1u << 16)) b = 1u << 16; return b ? (uint32_t)b : 1u; }
 
 // One thread per record.  Loads: the row's first 24 bytes (a 16-byte and an 8-byte request) and its CIGAR words one at a time (most rows
 // have one); per M run two atomics.  An index is at most ref_len and no more than SALT_MAX_CIGAR_OPS words are read: a row the align
@@ -31,20 +30,12 @@ __global__ void __launch_bounds__(256) k_depth_mark(DepthMark c)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.n_rec; i += (uint64_t)gridDim.x * blockDim.x) {
         const salt_result_t *q = c.res + i;
-        const uint4 h0 = *reinterpret_cast<const uint4 *>(q);                      // pos | strand n_diff is_gap mapq | b0 | b1
-        const uint2 h1 = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(q) + 16);      // seq_start seq_end | n_hits[2] n_cigar skipped
-        const uint32_t pos = h0.x, mapq = h0.y >> 24, n_cigar = (h1.y >> 16) & 0xFFu, skipped = h1.y >> 24;
-        if (pos == 0xFFFFFFFFu || skipped || mapq < c.min_mapq) continue;
-        uint64_t g = pos;                                                          // (a leading soft clip moves in the read only)
-        const uint32_t n_ops = n_cigar < SALT_MAX_CIGAR_OPS ? n_cigar : SALT_MAX_CIGAR_OPS;
-        for (uint32_t k = 0; k < n_ops; ++k) {
-            const uint32_t op = q->cigar[k], len = op >> 4, what = op & 15u;
-            if (what == 2u) { g += len; continue; }
-            if (what != 0u) continue;                                              // I: the read only
+        const TallyRow r = tally_row(q, 0, c.min_mapq);                            // (a leading soft clip moves in the read only)
+        if (r.fate != TALLY_COUNTED) continue;
+        tally_m_runs(q, r, [&](uint64_t g, uint32_t, uint32_t len) {
             const uint64_t end = g + len < c.ref_len ? g + len : (uint64_t)c.ref_len;      // cut at the genome's end
             if (g < end) { atomicAdd(c.diff + g, c.delta); atomicAdd(c.diff + end, 0u - c.delta); }
-            g += len;
-        }
+        });
     }
 }
 
@@ -56,13 +47,13 @@ __global__ void __launch_bounds__(256) k_depth_add(uint32_t *__restrict__ diff, 
 hipError_t launch_depth_mark(const DepthMark &c, hipStream_t st)
 {
     if (c.n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_depth_mark, dim3(dgrid(c.n_rec)), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(k_depth_mark, dim3(tally_grid(c.n_rec)), dim3(256), 0, st, c);
     return hipGetLastError();
 }
 hipError_t launch_depth_add(uint32_t *diff, const uint32_t *in, uint64_t n, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_depth_add, dim3(dgrid(n)), dim3(256), 0, st, diff, in, n);
+    hipLaunchKernelGGL(k_depth_add, dim3(tally_grid(n)), dim3(256), 0, st, diff, in, n);
     return hipGetLastError();
 }
 
@@ -283,7 +274,7 @@ static int depth_lines_measure(DepthText *t, std::string &err)
     DepthJob &j = t->job;
     t->lines_pending = false; t->line_at = 0; t->h_off.clear();
     if (j.n_lines == 0) return SALT_OK;
-    hipLaunchKernelGGL(k_depth_len, dim3(dgrid(j.n_lines)), dim3(256), 0, nullptr, j, t->len.p);
+    hipLaunchKernelGGL(k_depth_len, dim3(tally_grid(j.n_lines)), dim3(256), 0, nullptr, j, t->len.p);
     DT_HIP(hipGetLastError());
     DT_HIP(rocprim::exclusive_scan(t->tmp.p, t->tmp_bytes, t->len.p, t->len.p, 0ull, (size_t)j.n_lines + 1, rocprim::plus<unsigned long long>(), nullptr));
     unsigned long long total = 0;
@@ -309,7 +300,7 @@ static int depth_lines_piece(DepthText *t, const char **data, uint64_t *n_bytes,
         if (i1 == i0) { err = "depth text: a line longer than the text buffer"; return SALT_E_HIP; }
         bytes = t->h_off[(size_t)i1] - t->h_off[(size_t)i0];
     }
-    hipLaunchKernelGGL(k_depth_write, dim3(dgrid(i1 - i0)), dim3(256), 0, nullptr, j, t->len.p, i0, i1, reinterpret_cast<char *>(t->text.p));
+    hipLaunchKernelGGL(k_depth_write, dim3(tally_grid(i1 - i0)), dim3(256), 0, nullptr, j, t->len.p, i0, i1, reinterpret_cast<char *>(t->text.p));
     DT_HIP(hipGetLastError());
     t->line_at = i1;
     if (i1 == j.n_lines) t->lines_pending = false;
@@ -335,16 +326,16 @@ static int depth_tile(DepthText *t, std::string &err)
     const uint32_t n = (uint32_t)std::min<uint64_t>(t->tile, (uint64_t)t->ref_len - t->g0);
     j.t0 = (uint32_t)t->g0; j.n = n; j.carry = t->carry; j.n_lines = 0;
     DT_HIP(rocprim::inclusive_scan(t->tmp.p, t->tmp_bytes, t->diff + t->g0, t->dep.p, (size_t)n, rocprim::plus<uint32_t>(), nullptr));
-    hipLaunchKernelGGL(k_depth_flags, dim3(dgrid(n)), dim3(256), 0, nullptr, j);
+    hipLaunchKernelGGL(k_depth_flags, dim3(tally_grid(n)), dim3(256), 0, nullptr, j);
     DT_HIP(hipGetLastError());
     uint32_t carry_out = 0;
     const bool last = t->g0 + n == t->ref_len;
     if (t->window) {
-        hipLaunchKernelGGL(k_depth_win_sum, dim3(dgrid(((uint64_t)n + 63) / 64)), dim3(256), 0, nullptr, j);
+        hipLaunchKernelGGL(k_depth_win_sum, dim3(tally_grid(((uint64_t)n + 63) / 64)), dim3(256), 0, nullptr, j);
         DT_HIP(hipGetLastError());
         DT_HIP(hipMemcpy(&carry_out, t->dep.p + (n - 1), 4, hipMemcpyDeviceToHost));
     } else {
-        hipLaunchKernelGGL(k_depth_contig_flags, dim3(dgrid((uint64_t)j.n_contigs)), dim3(256), 0, nullptr, j);
+        hipLaunchKernelGGL(k_depth_contig_flags, dim3(tally_grid((uint64_t)j.n_contigs)), dim3(256), 0, nullptr, j);
         DT_HIP(hipGetLastError());
         const uint32_t lead = t->have_open ? 1u : 0u;
         DT_HIP(rocprim::select(t->tmp.p, t->tmp_bytes, rocprim::counting_iterator<uint32_t>(j.t0), t->flag.p, t->start.p + lead, t->cnt.p, (size_t)n, (hipStream_t) nullptr));

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "salt_device.h"
 #include "salt_kernels.h"
+#include "salt_tally.h"
 
 namespace salt {
 
@@ -73,21 +74,16 @@ __global__ void __launch_bounds__(EP_THREADS) k_errprof(ErrProf c)
     const salt_result_t *row = nullptr;
     if (i < c.n_rec) {
         row = c.res + i;
-        const uint4 h0 = *reinterpret_cast<const uint4 *>(row);                        // pos | strand n_diff is_gap mapq | b0 | b1
-        const uint2 h1 = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(row) + 16);      // seq_start seq_end | n_hits[2] n_cigar skipped
-        const uint32_t strand = h0.y & 0xFFu, mapq = h0.y >> 24, n_cigar = (h1.y >> 16) & 0xFFu, skipped = h1.y >> 24;
+        const TallyRow h = tally_row(row, c.pe, c.min_mapq);
         atomicAdd(&rcnt[0], 1u);
-        if (skipped) atomicAdd(&rcnt[1], 1u);
-        else if (h0.x == 0xFFFFFFFFu) atomicAdd(&rcnt[2], 1u);
-        else if (mapq < c.min_mapq) atomicAdd(&rcnt[3], 1u);
+        if (h.fate != TALLY_COUNTED) atomicAdd(&rcnt[h.fate], 1u);                     // R 1 .. 3: skipped, unmapped, below the floor
         else {
             const uint32_t o0 = c.offs[i], l_read = c.offs[i + 1] - o0;
             L = l_read < SALT_MAX_READ_LEN ? l_read : SALT_MAX_READ_LEN;
-            pos = h0.x; rev = c.pe ? strand == 1u : strand != 0u;
+            pos = h.pos; rev = h.rev;
             sq = c.seqs + o0;
-            s_lead = c.pe ? (h1.x & 0xFFFFu) : 0u;
-            n_ops = n_cigar < SALT_MAX_CIGAR_OPS ? n_cigar : SALT_MAX_CIGAR_OPS;
-            bool gapped = c.pe && (s_lead != 0u || (h1.x >> 16) != l_read - 1u);      // the soft clips the SAM / BAM writers print
+            s_lead = h.s_lead; n_ops = h.n_ops;
+            bool gapped = c.pe && (s_lead != 0u || h.seq_end != l_read - 1u);      // the soft clips the SAM / BAM writers print
             const uint32_t op0 = n_ops ? row->cigar[0] : 0u;
             if (n_ops == 1u && (op0 & 3u) == 0u) m_len = op0 >> 4;
             else {

@@ -28,28 +28,6 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 // the same in a function that frees its buffers in a lambda done(rc) on every return
 #define DONECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(SALT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_))); } while (0)
 
-struct salt_gpu_index {
-    int device = 0;
-    uint8_t *image = nullptr;      // device
-    uint64_t bytes = 0;
-    bool owns = true;
-    ImageHeader hdr;               // host copy
-    IndexView view;
-    uint8_t *d_pac = nullptr; uint64_t l_pac = 0;      // 2-bit genome for the PE singleton rescue (not part of the image)
-    uint4 *d_rctx = nullptr;                            // context records of the R rows (attach_r_ctx; not part of the image)
-    int64_t *d_c_off = nullptr; uint32_t *d_c_name_off = nullptr; char *d_c_names = nullptr; int32_t n_contigs = 0;     // contig table for the SAM kernels
-    // salt_gpu_index_snp_enable: the site table (one record per 64 genome positions) and counts[snp_sites][4], built by the first enable (not
-    // part of the image); every workspace of the index adds into the one table while snp_on
-    SnpWin *d_snp_tab = nullptr; uint32_t *d_snp_counts = nullptr; uint64_t snp_win = 0; uint32_t snp_sites = 0, snp_min_mapq = 0; bool snp_on = false;
-    // salt_gpu_index_depth_enable: the difference array of ref_len + 1 words, allocated by the first enable (not part of the image) and shared
-    // by every workspace of the index while depth_on; the text state and its buffers come with the first salt_gpu_index_depth_text_begin
-    uint32_t *d_depth = nullptr; uint32_t depth_min_mapq = 0; bool depth_on = false; DepthText *depth_text = nullptr;
-    std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
-    // salt_gpu_index_errprof_enable: E[2][512][95][4][4] and R[2][8] behind it, uint64, allocated by the first enable (not part of the image)
-    // and shared by every workspace of the index while errprof_on
-    unsigned long long *d_errprof = nullptr; uint32_t errprof_min_mapq = 0; bool errprof_on = false;
-};
-
 // A device buffer with its owner: p[0 .. cap) elements, freed with the owner.  alloc() gives it exactly n elements (what it held is freed
 // first, so a failed call leaves it empty); reserve() is the grow-on-demand rule of every buffer a call may find too small: nothing when it is
 // large enough, else the stream is drained (kernels queued on it may still read the old one) and it gets a quarter more than asked for.
@@ -60,6 +38,7 @@ template <class T> struct DevBuf {
     operator T *() const { return p; }
     T *operator->() const { return p; }
     void release() { hipFree(p); p = nullptr; cap = 0; }
+    void take(DevBuf &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
     hipError_t alloc(uint64_t n) { release(); const hipError_t e = hipMalloc((void **)&p, n * sizeof(T)); if (e == hipSuccess) cap = n; else p = nullptr; return e; }
     int reserve(uint64_t need, hipStream_t st)
     {
@@ -78,6 +57,27 @@ template <class T> struct PinBuf {
     void release() { if (p && owned) hipHostFree(p); p = nullptr; cap = 0; owned = true; }
     void adopt(T *q, uint64_t n) { release(); p = q; cap = n; owned = false; }
     hipError_t alloc(uint64_t n) { release(); const hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault); if (e == hipSuccess) cap = n; else p = nullptr; return e; }
+};
+
+struct salt_gpu_index {
+    int device = 0;
+    uint8_t *image = nullptr;      // device
+    uint64_t bytes = 0;
+    bool owns = true;
+    ImageHeader hdr;               // host copy
+    IndexView view;
+    uint8_t *d_pac = nullptr; uint64_t l_pac = 0;      // 2-bit genome for the PE singleton rescue (not part of the image)
+    uint4 *d_rctx = nullptr;                            // context records of the R rows (attach_r_ctx; not part of the image)
+    int64_t *d_c_off = nullptr; uint32_t *d_c_name_off = nullptr; char *d_c_names = nullptr; int32_t n_contigs = 0;     // contig table for the SAM kernels
+    // The row tallies (in front of 4.6): each table is allocated by its first enable (not part of the image) and shared by every workspace of
+    // the index while its gate is on.  snp: the site table (one record per 64 genome positions) and counts[snp_sites][4]; depth: the
+    // difference array of ref_len + 1 words (the text state and its buffers come with the first salt_gpu_index_depth_text_begin);
+    // errprof: E[2][512][95][4][4] and R[2][8] behind it, uint64.
+    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof;
+    DevBuf<SnpWin> d_snp_tab; DevBuf<uint32_t> d_snp_counts; uint64_t snp_win = 0; uint32_t snp_sites = 0;
+    DevBuf<uint32_t> d_depth; DepthText *depth_text = nullptr;
+    std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
+    DevBuf<unsigned long long> d_errprof;
 };
 
 // Every allocation below is a DevBuf / PinBuf: a new buffer is one field here and one reserve() or alloc() where it is sized.  Buffers that
@@ -129,9 +129,11 @@ struct salt_gpu_ws {
     std::vector<hipEvent_t> ev;        // EV_PER_CALL per call: before k_pack, k_seed, k_light, k_heavy, k_gap, k_gapfin, k_cigar, after; paired end: after k_pair, k_sw, k_pe_final (+ its k_cigar)
     std::vector<uint8_t> ev_pe;        // the call was a paired-end one (its last three events are recorded)
     uint32_t n_timed = 0;
-    SnpCount snp_last{}; hipStream_t snp_last_st = nullptr;      // what the last align call counted (n_rec 0: nothing), for salt_gpu_ws_snp_uncount
-    DepthMark depth_last{}; hipStream_t depth_last_st = nullptr; // likewise what it marked in the depth array, for salt_gpu_ws_depth_uncount
-    ErrProf ep_last{}; hipStream_t ep_last_st = nullptr;         // and what it added to the error profile, with its quality source, for salt_gpu_ws_errprof_uncount
+    // what the last align call added to each tally (n_rec 0: nothing) and on which stream, for the salt_gpu_ws_*_uncount calls; the error
+    // profile's job carries its quality source
+    template <class Job> struct LastJob { Job job{}; hipStream_t st = nullptr; };
+    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last;
+    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; }
     // the error profile's quality bytes: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
     // q_cur is the source of the call that is being queued (the text entry points set it to their raw block); d_quals holds a host call's bytes
     const uint8_t *q_next = nullptr; bool q_next_dev = false;
@@ -308,9 +310,8 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     if (ix->d_pac) { hipSetDevice(ix->device); hipFree(ix->d_pac); }
     if (ix->d_rctx) { hipSetDevice(ix->device); hipFree(ix->d_rctx); }
     if (ix->d_c_off) { hipSetDevice(ix->device); hipFree(ix->d_c_off); hipFree(ix->d_c_name_off); hipFree(ix->d_c_names); }
-    if (ix->d_snp_tab) { hipSetDevice(ix->device); hipFree(ix->d_snp_tab); hipFree(ix->d_snp_counts); }
-    if (ix->d_depth || ix->depth_text) { hipSetDevice(ix->device); hipFree(ix->d_depth); depth_text_free(ix->depth_text); }
-    if (ix->d_errprof) { hipSetDevice(ix->device); hipFree(ix->d_errprof); }
+    hipSetDevice(ix->device);                                  // the tallies' DevBufs go with the index
+    depth_text_free(ix->depth_text);
     delete ix;
 }
 
@@ -466,61 +467,49 @@ static int check_opt(const salt_gpu_index *ix, const salt_aln_opt_t *o, uint32_t
 static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint32_t n_reads, uint32_t max_read_len,
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe);
 
-// The one launch behind the kernels that finish a batch's result rows, on the batch's stream: the rows' bases at the SNP sites into the
-// index's counts (k_snp_count).  With counting off nothing is launched.  Every entry point that leaves result rows passes here: single
-// end at the end of align_resident_impl, paired end at the end of pe_resident_impl (the rows are final only behind k_pe_final).
-static int snp_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
+// A tally's launch, recorded as the workspace's last one.
+template <class Job> static int tally_launch(salt_gpu_ws::LastJob<Job> &last, hipError_t (*launch)(const Job &, hipStream_t), const Job &c, hipStream_t st)
 {
-    const salt_gpu_index *ix = ws->ix;
-    if (!ix->snp_on) return SALT_OK;
-    SnpCount c{};
-    c.res = static_cast<const salt_result_t *>(d_results); c.seqs = static_cast<const uint8_t *>(d_seqs); c.offs = static_cast<const uint32_t *>(d_offs); c.n_rec = n_rec;
-    c.tab = ix->d_snp_tab; c.n_win = ix->snp_win; c.counts = ix->d_snp_counts; c.min_mapq = ix->snp_min_mapq; c.pe = pe; c.delta = 1u;
-    HIPCHK(launch_snp_count(c, st));
-    ws->snp_last = c; ws->snp_last_st = st;
+    HIPCHK(launch(c, st));
+    last.job = c; last.st = st;
     return SALT_OK;
 }
-
-// Its sibling for the coverage, at the same two places: the rows' M runs into the index's difference array (k_depth_mark).  With depth
-// off nothing is launched.
-static int depth_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_results, hipStream_t st)
-{
-    const salt_gpu_index *ix = ws->ix;
-    if (!ix->depth_on) return SALT_OK;
-    DepthMark c{};
-    c.res = static_cast<const salt_result_t *>(d_results); c.n_rec = n_rec; c.diff = ix->d_depth; c.ref_len = ix->view.ref_len;
-    c.min_mapq = ix->depth_min_mapq; c.delta = 1u;
-    HIPCHK(launch_depth_mark(c, st));
-    ws->depth_last = c; ws->depth_last_st = st;
-    return SALT_OK;
-}
-// The third: the rows' base events into the index's error profile (k_errprof), with the qualities of the call's source (ws->q_cur: the
-// text block, salt_gpu_ws_set_quals' bytes, or none).  With the profile off nothing is launched.
-static int errprof_hook(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
-{
-    const salt_gpu_index *ix = ws->ix;
-    if (!ix->errprof_on) return SALT_OK;
-    ErrProf c{};
-    c.res = static_cast<const salt_result_t *>(d_results); c.seqs = static_cast<const uint8_t *>(d_seqs); c.offs = static_cast<const uint32_t *>(d_offs); c.n_rec = n_rec;
-    c.quals = ws->q_cur.quals; c.rec = ws->q_cur.rec; c.q_bytes = ws->q_cur.bytes;
-    c.ref = ix->view.ref; c.ref_len = ix->view.ref_len; c.cells = ix->d_errprof; c.min_mapq = ix->errprof_min_mapq; c.pe = pe; c.delta = 1ull;
-    HIPCHK(launch_errprof(c, st));
-    ws->ep_last = c; ws->ep_last_st = st;
-    return SALT_OK;
-}
-// all three, behind the kernels that finish a batch's rows
+// The launches behind the kernels that finish a batch's result rows, on the batch's stream, one per tally that is on: the rows' bases at the
+// SNP sites into the index's counts (k_snp_count), their M runs into its difference array (k_depth_mark), their base events into its error
+// profile (k_errprof), the last with the qualities of the call's source (ws->q_cur: the text block, salt_gpu_ws_set_quals' bytes, or
+// none).  Every entry point that leaves result rows passes here: single end at the end of align_resident_impl, paired end at the end of
+// pe_resident_impl (the rows are final only behind k_pe_final).
 static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
 {
-    int rc = snp_hook(ws, n_rec, d_seqs, d_offs, d_results, pe, st);
-    if (!rc) rc = depth_hook(ws, n_rec, d_results, st);
-    return rc ? rc : errprof_hook(ws, n_rec, d_seqs, d_offs, d_results, pe, st);
+    const salt_gpu_index *ix = ws->ix;
+    const salt_result_t *res = static_cast<const salt_result_t *>(d_results);
+    const uint8_t *seqs = static_cast<const uint8_t *>(d_seqs); const uint32_t *offs = static_cast<const uint32_t *>(d_offs);
+    if (ix->snp.on) {
+        SnpCount c{};
+        c.res = res; c.seqs = seqs; c.offs = offs; c.n_rec = n_rec;
+        c.tab = ix->d_snp_tab; c.n_win = ix->snp_win; c.counts = ix->d_snp_counts; c.min_mapq = ix->snp.min_mapq; c.pe = pe; c.delta = 1u;
+        if (const int rc = tally_launch(ws->snp_last, launch_snp_count, c, st)) return rc;
+    }
+    if (ix->depth.on) {
+        DepthMark c{};
+        c.res = res; c.n_rec = n_rec; c.diff = ix->d_depth; c.ref_len = ix->view.ref_len; c.min_mapq = ix->depth.min_mapq; c.delta = 1u;
+        if (const int rc = tally_launch(ws->depth_last, launch_depth_mark, c, st)) return rc;
+    }
+    if (ix->errprof.on) {
+        ErrProf c{};
+        c.res = res; c.seqs = seqs; c.offs = offs; c.n_rec = n_rec;
+        c.quals = ws->q_cur.quals; c.rec = ws->q_cur.rec; c.q_bytes = ws->q_cur.bytes;
+        c.ref = ix->view.ref; c.ref_len = ix->view.ref_len; c.cells = ix->d_errprof; c.min_mapq = ix->errprof.min_mapq; c.pe = pe; c.delta = 1ull;
+        if (const int rc = tally_launch(ws->ep_last, launch_errprof, c, st)) return rc;
+    }
+    return SALT_OK;
 }
 // salt_gpu_ws_set_quals' bytes on their way into a call.  A host-buffer call copies host bytes up beside its bases (quals_upload; with the
 // profile off nothing is copied and they are dropped); every host-buffer or resident call then consumes the pointer (quals_take).
 static int quals_upload(salt_gpu_ws_t *ws, uint64_t bases, hipStream_t st)
 {
     if (!ws->q_next || ws->q_next_dev) return SALT_OK;
-    if (!ws->ix->errprof_on) { ws->q_next = nullptr; return SALT_OK; }
+    if (!ws->ix->errprof.on) { ws->q_next = nullptr; return SALT_OK; }
     if (int rc = ws->d_quals.reserve(bases + 64, st)) { ws->q_next = nullptr; return rc; }
     const hipError_t e = hipMemcpyAsync(ws->d_quals, ws->q_next, bases, hipMemcpyHostToDevice, st);
     ws->q_next = ws->d_quals; ws->q_next_dev = true;
@@ -579,7 +568,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                                const void *d_seqs, const void *d_offs, void *d_results, void *hip_stream, int pe)
 {
     if (!ws || !o || !d_seqs || !d_offs || !d_results) return fail(SALT_E_INVAL, "null argument");
-    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0; ws->ep_last.n_rec = 0;
+    ws->forget_last();
     if (n_reads == 0) return SALT_OK;
     uint32_t spr = 0;
     int rc = check_opt(ws->ix, o, max_read_len, &spr);
@@ -1170,7 +1159,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
 {
     const uint64_t n_src = n_bytes;
     if (d_src && add_newline) ++n_bytes;
-    ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0; ws->ep_last.n_rec = 0;
+    ws->forget_last();
     salt_gpu_index *ix = ws->ix;
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
@@ -1229,7 +1218,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
 {
     if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
-    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->snp_last.n_rec = 0; ws->depth_last.n_rec = 0; ws->ep_last.n_rec = 0;
+    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->forget_last();
     if (n1 == 0 && n2 == 0) return SALT_OK;
     if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
     if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
@@ -1796,18 +1785,54 @@ extern "C" int salt_gpu_index_set_pac(salt_gpu_index_t *ix, const uint8_t *pac, 
     return attach_r_ctx(ix, R_CTX_RESERVE_PAC);      // an index attached without the room for its R context records gets them now, if the room is there
 }
 
+// ---- the row tallies (in front of 4.6): what enabling one and taking a call's adds back share ----
+// The null check, the MAPQ check under the tally's prefix, the device, `first` when the tally has no table yet, then the gate.
+template <class First> static int tally_enable(salt_gpu_index_t *ix, salt_gpu_index::Tally salt_gpu_index::*gate, const char *prefix, int on, uint32_t min_mapq, First first)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (min_mapq > 255) return fail(SALT_E_INVAL, std::string(prefix) + ": min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
+    HIPCHK(hipSetDevice(ix->device));
+    if (on) if (const int rc = first()) return rc;
+    (ix->*gate).min_mapq = min_mapq; (ix->*gate).on = on != 0;
+    return SALT_OK;
+}
+// n zeroed elements, or the tally's own message and an empty buffer
+template <class T> static int alloc_zeroed(DevBuf<T> &b, uint64_t n, const char *prefix, const std::string &no_room)
+{
+    if (b.alloc(n) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, std::string(prefix) + ": no room for " + no_room); }
+    const hipError_t e = hipMemset(b.p, 0, n * sizeof(T));
+    if (e != hipSuccess) { b.release(); return fail(SALT_E_HIP, std::string("hipMemset(") + prefix + "): " + hipGetErrorString(e)); }
+    return SALT_OK;
+}
+// The workspace's last job once more with the job's "minus one" as delta: + (2^32 - 1) or + (2^64 - 1) = - 1 in the table's arithmetic.
+// never: the message for an index whose `table` was never allocated; null: such an index has nothing to take back.
+template <class Job, class Delta, class T>
+static int tally_uncount(salt_gpu_ws_t *ws, salt_gpu_ws::LastJob<Job> salt_gpu_ws::*last_of, hipError_t (*launch)(const Job &, hipStream_t), Delta minus_one,
+                         DevBuf<T> salt_gpu_index::*table, const char *never)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    if (never && !(ws->ix->*table).p) return fail(SALT_E_INVAL, never);
+    salt_gpu_ws::LastJob<Job> &last = ws->*last_of;
+    if (last.job.n_rec == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ws->ix->device));
+    Job c = last.job;
+    c.delta = minus_one;
+    last.job.n_rec = 0;
+    HIPCHK(launch(c, last.st));
+    HIPCHK(hipStreamSynchronize(last.st));
+    return SALT_OK;
+}
+
 // ---- allele counts at the SNP sites ----
 // The first enable builds the site table from view.ref (k_snp_bits, a scan of the windows' popcounts, k_snp_rank) and the zeroed counts.
 extern "C" int salt_gpu_index_snp_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
 {
-    if (!ix) return fail(SALT_E_INVAL, "null argument");
-    if (min_mapq > 255) return fail(SALT_E_INVAL, "snp counts: min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
-    HIPCHK(hipSetDevice(ix->device));
-    if (on && !ix->d_snp_tab) {
+    return tally_enable(ix, &salt_gpu_index::snp, "snp counts", on, min_mapq, [&]() -> int {
+        if (ix->d_snp_tab) return SALT_OK;
         const uint32_t ref_len = ix->view.ref_len;
         if (ref_len == 0) return fail(SALT_E_INVAL, "snp counts: the index has an empty genome");
         const uint64_t n_win = ((uint64_t)ref_len + 63) / 64;
-        DevBuf<uint32_t> cnt; DevBuf<uint8_t> tmp; DevBuf<SnpWin> tab;
+        DevBuf<uint32_t> cnt, counts; DevBuf<uint8_t> tmp; DevBuf<SnpWin> tab;
         const size_t tmp_bytes = snp_scan_bytes(n_win);
         if (tab.alloc(n_win) != hipSuccess || cnt.alloc(n_win + 1) != hipSuccess || tmp.alloc(tmp_bytes ? tmp_bytes : 1) != hipSuccess) {
             (void)hipGetLastError();
@@ -1817,19 +1842,12 @@ extern "C" int salt_gpu_index_snp_enable(salt_gpu_index_t *ix, int on, uint32_t 
         HIPCHK(launch_snp_table(ix->view.ref, ref_len, n_win, tab, cnt, tmp, tmp_bytes, nullptr));
         uint32_t n_sites = 0;
         HIPCHK(hipMemcpy(&n_sites, cnt + n_win, 4, hipMemcpyDeviceToHost));
-        uint32_t *counts = nullptr;
-        const uint64_t cbytes = ((uint64_t)n_sites + 1) * 16;                      // (one spare row: an index without sites still has a table)
-        if (hipMalloc((void **)&counts, cbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SALT_E_NOMEM, "snp counts: no room for the counts: " + std::to_string(cbytes) + " bytes (16 per site, " + std::to_string(n_sites) + " sites)");
-        }
-        const hipError_t e = hipMemset(counts, 0, cbytes);
-        if (e != hipSuccess) { hipFree(counts); return fail(SALT_E_HIP, std::string("hipMemset(snp counts): ") + hipGetErrorString(e)); }
-        ix->d_snp_tab = tab.p; tab.p = nullptr; tab.cap = 0;                        // the index owns it from here
-        ix->d_snp_counts = counts; ix->snp_win = n_win; ix->snp_sites = n_sites;
-    }
-    ix->snp_min_mapq = min_mapq; ix->snp_on = on != 0;
-    return SALT_OK;
+        const uint64_t rows = (uint64_t)n_sites + 1;                                // (one spare row: an index without sites still has a table)
+        if (const int rc = alloc_zeroed(counts, rows * 4, "snp counts", "the counts: " + std::to_string(rows * 16) + " bytes (16 per site, " + std::to_string(n_sites) + " sites)")) return rc;
+        ix->d_snp_tab.take(tab); ix->d_snp_counts.take(counts);                    // the index owns them from here
+        ix->snp_win = n_win; ix->snp_sites = n_sites;
+        return SALT_OK;
+    });
 }
 
 extern "C" int salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites, uint32_t *pos, uint64_t cap)
@@ -1862,15 +1880,7 @@ extern "C" int salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts,
 
 extern "C" int salt_gpu_ws_snp_uncount(salt_gpu_ws_t *ws)
 {
-    if (!ws) return fail(SALT_E_INVAL, "null argument");
-    if (ws->snp_last.n_rec == 0) return SALT_OK;
-    HIPCHK(hipSetDevice(ws->ix->device));
-    SnpCount c = ws->snp_last;
-    c.delta = 0xFFFFFFFFu;                                                         // + (2^32 - 1) = - 1 in the counts' arithmetic
-    ws->snp_last.n_rec = 0;
-    HIPCHK(launch_snp_count(c, ws->snp_last_st));
-    HIPCHK(hipStreamSynchronize(ws->snp_last_st));
-    return SALT_OK;
+    return tally_uncount(ws, &salt_gpu_ws::snp_last, launch_snp_count, 0xFFFFFFFFu, &salt_gpu_index::d_snp_counts, nullptr);
 }
 
 // ---- coverage ----
@@ -1878,23 +1888,12 @@ static const char *const DEPTH_NEVER = "depth: depth was never enabled on this i
 
 extern "C" int salt_gpu_index_depth_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
 {
-    if (!ix) return fail(SALT_E_INVAL, "null argument");
-    if (min_mapq > 255) return fail(SALT_E_INVAL, "depth: min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
-    HIPCHK(hipSetDevice(ix->device));
-    if (on && !ix->d_depth) {
+    return tally_enable(ix, &salt_gpu_index::depth, "depth", on, min_mapq, [&]() -> int {
+        if (ix->d_depth) return SALT_OK;
         if (ix->view.ref_len == 0) return fail(SALT_E_INVAL, "depth: the index has an empty genome");
-        const uint64_t bytes = ((uint64_t)ix->view.ref_len + 1) * 4;
-        uint32_t *d = nullptr;
-        if (hipMalloc((void **)&d, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SALT_E_NOMEM, "depth: no room for the difference array: " + std::to_string(bytes) + " bytes (4 per genome position)");
-        }
-        const hipError_t e = hipMemset(d, 0, bytes);
-        if (e != hipSuccess) { hipFree(d); return fail(SALT_E_HIP, std::string("hipMemset(depth): ") + hipGetErrorString(e)); }
-        ix->d_depth = d;
-    }
-    ix->depth_min_mapq = min_mapq; ix->depth_on = on != 0;
-    return SALT_OK;
+        const uint64_t words = (uint64_t)ix->view.ref_len + 1;
+        return alloc_zeroed(ix->d_depth, words, "depth", "the difference array: " + std::to_string(words * 4) + " bytes (4 per genome position)");
+    });
 }
 
 extern "C" int salt_gpu_index_depth_reset(salt_gpu_index_t *ix)
@@ -1970,16 +1969,7 @@ extern "C" int salt_gpu_index_depth_text_next(salt_gpu_index_t *ix, const char *
 
 extern "C" int salt_gpu_ws_depth_uncount(salt_gpu_ws_t *ws)
 {
-    if (!ws) return fail(SALT_E_INVAL, "null argument");
-    if (!ws->ix->d_depth) return fail(SALT_E_INVAL, DEPTH_NEVER);
-    if (ws->depth_last.n_rec == 0) return SALT_OK;
-    HIPCHK(hipSetDevice(ws->ix->device));
-    DepthMark c = ws->depth_last;
-    c.delta = 0xFFFFFFFFu;                                                         // + (2^32 - 1) = - 1 in the array's arithmetic
-    ws->depth_last.n_rec = 0;
-    HIPCHK(launch_depth_mark(c, ws->depth_last_st));
-    HIPCHK(hipStreamSynchronize(ws->depth_last_st));
-    return SALT_OK;
+    return tally_uncount(ws, &salt_gpu_ws::depth_last, launch_depth_mark, 0xFFFFFFFFu, &salt_gpu_index::d_depth, DEPTH_NEVER);
 }
 
 // ---- the error profile ----
@@ -1988,22 +1978,10 @@ static const uint64_t ERRPROF_ALL = (uint64_t)SALT_ERRPROF_CELLS + 16;      // E
 
 extern "C" int salt_gpu_index_errprof_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
 {
-    if (!ix) return fail(SALT_E_INVAL, "null argument");
-    if (min_mapq > 255) return fail(SALT_E_INVAL, "error profile: min_mapq " + std::to_string(min_mapq) + " is above 255, the largest MAPQ");
-    HIPCHK(hipSetDevice(ix->device));
-    if (on && !ix->d_errprof) {
-        const uint64_t bytes = ERRPROF_ALL * 8;
-        unsigned long long *d = nullptr;
-        if (hipMalloc((void **)&d, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SALT_E_NOMEM, "error profile: no room for the tables: " + std::to_string(bytes) + " bytes (8 per cell of E[2][512][95][4][4] and R[2][8])");
-        }
-        const hipError_t e = hipMemset(d, 0, bytes);
-        if (e != hipSuccess) { hipFree(d); return fail(SALT_E_HIP, std::string("hipMemset(error profile): ") + hipGetErrorString(e)); }
-        ix->d_errprof = d;
-    }
-    ix->errprof_min_mapq = min_mapq; ix->errprof_on = on != 0;
-    return SALT_OK;
+    return tally_enable(ix, &salt_gpu_index::errprof, "error profile", on, min_mapq, [&]() -> int {
+        if (ix->d_errprof) return SALT_OK;
+        return alloc_zeroed(ix->d_errprof, ERRPROF_ALL, "error profile", "the tables: " + std::to_string(ERRPROF_ALL * 8) + " bytes (8 per cell of E[2][512][95][4][4] and R[2][8])");
+    });
 }
 
 extern "C" int salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t rec[16], int reset)
@@ -2022,16 +2000,7 @@ extern "C" int salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cell
 
 extern "C" int salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws)
 {
-    if (!ws) return fail(SALT_E_INVAL, "null argument");
-    if (!ws->ix->d_errprof) return fail(SALT_E_INVAL, ERRPROF_NEVER);
-    if (ws->ep_last.n_rec == 0) return SALT_OK;
-    HIPCHK(hipSetDevice(ws->ix->device));
-    ErrProf c = ws->ep_last;
-    c.delta = ~0ull;                                                               // + (2^64 - 1) = - 1 in the cells' arithmetic
-    ws->ep_last.n_rec = 0;
-    HIPCHK(launch_errprof(c, ws->ep_last_st));
-    HIPCHK(hipStreamSynchronize(ws->ep_last_st));
-    return SALT_OK;
+    return tally_uncount(ws, &salt_gpu_ws::ep_last, launch_errprof, ~0ull, &salt_gpu_index::d_errprof, ERRPROF_NEVER);
 }
 
 extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device)

@@ -10,10 +10,9 @@
 #include <rocprim/functional.hpp>
 #include "salt_device.h"
 #include "salt_kernels.h"
+#include "salt_tally.h"
 
 namespace salt {
-
-static inline uint32_t sgrid(uint64_t n) { uint64_t b = (n + 255) / 256; if (b > (1u << 16)) b = 1u << 16; return b ? (uint32_t)b : 1u; }
 
 // window w = positions [64 w, 64 w + 64): eight words of the 4-bit mixRef.  A position at or beyond ref_len is no site, whatever the
 // words' padding holds; a word beyond the array is not read.
@@ -62,25 +61,16 @@ __global__ void __launch_bounds__(256) k_snp_count(SnpCount c)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.n_rec; i += (uint64_t)gridDim.x * blockDim.x) {
         const salt_result_t *q = c.res + i;
-        const uint4 h0 = *reinterpret_cast<const uint4 *>(q);                      // pos | strand n_diff is_gap mapq | b0 | b1
-        const uint2 h1 = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(q) + 16);      // seq_start seq_end | n_hits[2] n_cigar skipped
-        const uint32_t pos = h0.x, strand = h0.y & 0xFFu, mapq = h0.y >> 24, n_cigar = (h1.y >> 16) & 0xFFu, skipped = h1.y >> 24;
-        if (pos == 0xFFFFFFFFu || skipped || mapq < c.min_mapq) continue;
-        const bool rev = c.pe ? strand == 1u : strand != 0u;
+        const TallyRow r = tally_row(q, c.pe, c.min_mapq);
+        if (r.fate != TALLY_COUNTED) continue;
+        const bool rev = r.rev;
         const uint32_t o0 = c.offs[i], L = c.offs[i + 1] - o0;
         const uint8_t *sq = c.seqs + o0;
-        uint64_t g = pos;
-        uint32_t s = c.pe ? (h1.x & 0xFFFFu) : 0u;                                // the leading soft clip of a rescued mate
-        const uint32_t n_ops = n_cigar < SALT_MAX_CIGAR_OPS ? n_cigar : SALT_MAX_CIGAR_OPS;
-        for (uint32_t k = 0; k < n_ops; ++k) {
-            const uint32_t op = q->cigar[k], len = op >> 4, what = op & 3u;
-            if (what == 1u) { s += len; continue; }
-            if (what == 2u) { g += len; continue; }
-            if (what != 0u) continue;
+        tally_m_runs(q, r, [&](uint64_t g, uint32_t s, uint32_t len) {
             const uint64_t g_end = g + len;                                        // the run covers [g, g_end), read bases s + (x - g)
             for (uint64_t w = g >> 6; w < c.n_win && (w << 6) < g_end; ++w) {
-                const SnpWin r = c.tab[w];
-                unsigned long long bits = r.bits;
+                const SnpWin t = c.tab[w];
+                unsigned long long bits = t.bits;
                 if ((w << 6) < g) bits &= ~0ull << (g & 63u);
                 if (g_end < (w << 6) + 64) bits &= ~(~0ull << (g_end & 63u));
                 for (; bits; bits &= bits - 1) {
@@ -90,12 +80,11 @@ __global__ void __launch_bounds__(256) k_snp_count(SnpCount c)
                     uint32_t code = sq[rev ? L - 1u - (uint32_t)j : (uint32_t)j];
                     if (code > 3u) continue;                                       // N counts nowhere
                     if (rev) code = 3u - code;
-                    const uint64_t site = (uint64_t)r.rank + (uint32_t)__popcll(r.bits & ((1ull << b) - 1ull));
+                    const uint64_t site = (uint64_t)t.rank + (uint32_t)__popcll(t.bits & ((1ull << b) - 1ull));
                     atomicAdd(c.counts + site * 4 + code, c.delta);
                 }
             }
-            g = g_end; s += len;
-        }
+        });
     }
 }
 
@@ -109,23 +98,23 @@ size_t snp_scan_bytes(uint64_t n_win)
 // tab[0 .. n_win) from the mixRef; cnt: n_win + 1 words of scratch, cnt[n_win] = the number of sites afterwards
 hipError_t launch_snp_table(const uint32_t *ref, uint32_t ref_len, uint64_t n_win, SnpWin *tab, uint32_t *cnt, void *tmp, size_t tmp_bytes, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_snp_bits, dim3(sgrid(n_win)), dim3(256), 0, st, ref, ref_len, n_win, tab, cnt);
+    hipLaunchKernelGGL(k_snp_bits, dim3(tally_grid(n_win)), dim3(256), 0, st, ref, ref_len, n_win, tab, cnt);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rocprim::exclusive_scan(tmp, tmp_bytes, cnt, cnt, 0u, (size_t)n_win + 1, rocprim::plus<uint32_t>(), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_snp_rank, dim3(sgrid(n_win)), dim3(256), 0, st, cnt, n_win, tab);
+    hipLaunchKernelGGL(k_snp_rank, dim3(tally_grid(n_win)), dim3(256), 0, st, cnt, n_win, tab);
     return hipGetLastError();
 }
 hipError_t launch_snp_pos(const SnpWin *tab, uint64_t n_win, uint32_t *pos, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_snp_pos, dim3(sgrid(n_win)), dim3(256), 0, st, tab, n_win, pos);
+    hipLaunchKernelGGL(k_snp_pos, dim3(tally_grid(n_win)), dim3(256), 0, st, tab, n_win, pos);
     return hipGetLastError();
 }
 hipError_t launch_snp_count(const SnpCount &c, hipStream_t st)
 {
     if (c.n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_snp_count, dim3(sgrid(c.n_rec)), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(k_snp_count, dim3(tally_grid(c.n_rec)), dim3(256), 0, st, c);
     return hipGetLastError();
 }
 

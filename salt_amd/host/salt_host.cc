@@ -501,26 +501,70 @@ struct RefIds {
     }
 };
 
-// one line [l, e) without its newline -> one record appended to o; false with g_err set
+// A SAM record line [l, e) without its newline, split at its tabs: what the BAM encoder and the three host twins below read first.  Every
+// refusal is g_err = prefix + why + the line's first 80 bytes, and false.
+struct SamLine {
+    const char *prefix, *l, *e;
+    const char *f[12]; int nf;                                     // starts of the 11 mandatory fields and of the tags
+    int64_t flag, pos1, mapq;                                      // set and range-checked by numbers()
+    const char *fe(int k) const { return k + 1 < nf ? f[k + 1] - 1 : e; }      // end of field k (the tags: all of them)
+    size_t len(int k) const { return (size_t)(fe(k) - f[k]); }
+    bool is(int k, char c) const { return len(k) == 1 && *f[k] == c; }
+    bool bad(const char *why) const { g_err = std::string(prefix) + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return false; }
+    bool split(const char *prefix_, const char *l_, const char *e_)
+    {
+        prefix = prefix_; l = l_; e = e_; nf = 0;
+        f[nf++] = l;
+        for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
+        return nf < 11 ? bad("fewer than 11 fields") : true;
+    }
+    bool numbers()
+    {
+        if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
+            pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
+        return true;
+    }
+    bool parse(const char *prefix_, const char *l_, const char *e_) { return split(prefix_, l_, e_) && numbers(); }
+};
+
+// f(l, e) for every record line of sam[0 .. n): not empty (a skipped read, the paired-end driver's blank lines) and, with skip_headers, no
+// '@' line (a read name cannot start with '@': the FASTQ parsers drop it).  The sum of what f returned, or its first negative value.
+template <class F> int64_t for_record_lines(const char *sam, size_t n, bool skip_headers, F f)
+{
+    int64_t sum = 0;
+    for (const char *l = sam, *end = sam + n; l < end; ) {
+        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
+        if (!e) e = end;
+        if (e > l && !(skip_headers && *l == '@')) {
+            const int64_t r = f(l, e);
+            if (r < 0) return r;
+            sum += r;
+        }
+        l = e + 1;
+    }
+    return sum;
+}
+
+// one line -> one record appended to o; false with g_err set.  The read name is checked in front of the numbers.
 bool bam_record_of_line(const RefIds &ids, const char *l, const char *e, Bytes &o)
 {
-    const char *f[12]; int nf = 0;                                 // starts of the 11 mandatory fields and of the tags
-    f[nf++] = l;
-    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
-    auto bad = [&](const char *why) { g_err = std::string("BAM: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return false; };
-    if (nf < 11) return bad("fewer than 11 fields");
-    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };      // end of field k (the tags: all of them)
-    const size_t l_name = (size_t)(fe(0) - f[0]);
+    SamLine L;
+    if (!L.split("BAM: ", l, e)) return false;
+    const char *const *f = L.f; const int nf = L.nf;
+    auto bad = [&](const char *why) { return L.bad(why); };
+    auto fe = [&](int k) { return L.fe(k); };
+    const size_t l_name = L.len(0);
     if (l_name == 0) return bad("empty read name");
     if (l_name > SALT_BAM_MAX_NAME) {
         g_err = "BAM: read name of " + std::to_string(l_name) + " bytes ('" + std::string(l, 40) + "...'): a BAM read name holds at most " +
                 std::to_string(SALT_BAM_MAX_NAME) + " bytes";
         return false;
     }
-    int64_t flag, pos1, mapq, pnext1, tlen;
-    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || !field_int(f[7], fe(7), &pnext1) ||
-        !field_int(f[8], fe(8), &tlen) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 || pos1 < 0 || pos1 > 0x7FFFFFFF || pnext1 < 0 || pnext1 > 0x7FFFFFFF ||
-        tlen < INT32_MIN || tlen > INT32_MAX) return bad("a numeric field is no number of its range");
+    if (!L.numbers()) return false;
+    const int64_t flag = L.flag, pos1 = L.pos1, mapq = L.mapq;
+    int64_t pnext1, tlen;
+    if (!field_int(f[7], fe(7), &pnext1) || !field_int(f[8], fe(8), &tlen) || pnext1 < 0 || pnext1 > 0x7FFFFFFF || tlen < INT32_MIN || tlen > INT32_MAX)
+        return bad("a numeric field is no number of its range");
     int32_t rid = -1, nrid = -1;
     if (!(fe(2) - f[2] == 1 && *f[2] == '*') && (rid = ids.find(f[2], fe(2))) < -1) return bad("RNAME is no sequence of the index");
     if (fe(6) - f[6] == 1 && *f[6] == '=') nrid = rid;
@@ -622,20 +666,17 @@ extern "C" int64_t salt_bam_from_sam(const salt_index_t *ix, const char *sam, si
     if (!ix || (!sam && n) || (!out && cap)) { g_err = "BAM: null argument"; return SALT_BAM_E_INVAL; }
     const RefIds ids(ix);
     Bytes rec;
-    size_t w = 0; uint64_t n_rec = 0;
-    for (const char *l = sam, *end = sam + n; l < end; ) {
-        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
-        if (!e) e = end;
-        if (e > l) {                                               // (a skipped read's empty line, the paired-end driver's blank lines: no record)
-            rec.b.clear();
-            if (!bam_record_of_line(ids, l, e, rec)) return SALT_BAM_E_INVAL;
-            if (w + rec.b.size() > cap) return SALT_BAM_E_CAP;
-            memcpy(out + w, rec.b.data(), rec.b.size());
-            w += rec.b.size(); ++n_rec;
-        }
-        l = e + 1;
-    }
-    if (n_records) *n_records = n_rec;
+    size_t w = 0;
+    const int64_t n_rec = for_record_lines(sam, n, false, [&](const char *l, const char *e) -> int64_t {
+        rec.b.clear();
+        if (!bam_record_of_line(ids, l, e, rec)) return SALT_BAM_E_INVAL;
+        if (w + rec.b.size() > cap) return SALT_BAM_E_CAP;
+        memcpy(out + w, rec.b.data(), rec.b.size());
+        w += rec.b.size();
+        return 1;
+    });
+    if (n_rec < 0) return n_rec;
+    if (n_records) *n_records = (uint64_t)n_rec;
     return (int64_t)w;
 }
 
@@ -656,49 +697,63 @@ const std::vector<uint32_t> &snp_positions(const salt_index *ix)
     return ix->snp_pos;
 }
 
-// one record line [l, e): its bases at the sites into counts; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with g_err set
-int snp_count_line(const salt_index *ix, const RefIds &ids, const std::vector<uint32_t> &sites, const char *l, const char *e, uint32_t min_mapq, uint32_t *counts)
+// ---- what the three twins share (with each other, and with nothing under csrc/) ----
+// The M runs of a counted record line: genome positions [g, g + len), bases [s, s + len) of SEQ; gapped: the CIGAR has an I, S or D.
+struct MRuns { uint64_t g[64], len[64]; size_t s[64]; int n = 0; bool gapped = false; };
+
+// The line's head: 1 it counts and *g is its global position, 0 it does not (unmapped, also a mate printed at its mate's place: flag & 4;
+// else below min_mapq), -1 with g_err set.
+int twin_head(const salt_index *ix, const RefIds &ids, SamLine &L, const char *prefix, const char *l, const char *e, uint32_t min_mapq, uint64_t *g)
 {
-    const char *f[12]; int nf = 0;
-    f[nf++] = l;
-    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
-    auto bad = [&](const char *why) { g_err = std::string("snp counts: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return -1; };
-    if (nf < 11) return bad("fewer than 11 fields");
-    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };
-    int64_t flag, pos1, mapq;
-    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
-        pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
-    if (flag & 4) return 0;                                            // unmapped, also a mate printed at its mate's place
-    if ((uint64_t)mapq < min_mapq) return 0;
-    const int32_t rid = ids.find(f[2], fe(2));
-    if (rid < 0) return bad("RNAME is no sequence of the index");
-    if (pos1 < 1) return bad("a mapped record without a position");
-    const char *seq = f[9]; const size_t l_seq = (size_t)(fe(9) - seq);
-    uint64_t g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)pos1 - 1;      // global position; the walk may run past the contig's end
+    if (!L.parse(prefix, l, e)) return -1;
+    if ((L.flag & 4) || (uint64_t)L.mapq < min_mapq) return 0;
+    const int32_t rid = ids.find(L.f[2], L.fe(2));
+    if (rid < 0) return L.bad("RNAME is no sequence of the index"), -1;
+    if (L.pos1 < 1) return L.bad("a mapped record without a position"), -1;
+    *g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)L.pos1 - 1;            // the walk may run past the contig's end
+    return 1;
+}
+// The line's CIGAR, checked whole against SEQ before the caller adds anything: a refused line leaves the caller's table as it was.
+bool twin_cigar(const SamLine &L, uint64_t g, MRuns &m)
+{
+    const size_t l_seq = L.len(9);
     size_t s = 0; uint64_t n = 0; bool digits = false, any = false;
-    for (const char *p = f[5]; p < fe(5); ++p) {
-        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
-        if (!digits) return bad("malformed CIGAR");
+    for (const char *p = L.f[5]; p < L.fe(5); ++p) {
+        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return L.bad("CIGAR length of 2^28 or more"); continue; }
+        if (!digits) return L.bad("malformed CIGAR");
         switch (*p) {
         case 'M':
-            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
-            for (uint64_t k = 0; k < n; ++k, ++g, ++s) {
-                const auto it = std::lower_bound(sites.begin(), sites.end(), g);
-                if (g > 0xFFFFFFFFull || it == sites.end() || *it != g) continue;
-                int b;
-                switch (seq[s]) { case 'A': b = 0; break; case 'C': b = 1; break; case 'G': b = 2; break; case 'T': b = 3; break; default: b = -1; }
-                if (b >= 0) ++counts[(size_t)(it - sites.begin()) * 4 + (size_t)b];
-            }
-            break;
+            if (s + n > l_seq) return L.bad("the CIGAR is longer than SEQ");
+            if (m.n == 64) return L.bad("more M runs than a record of this program has");
+            m.g[m.n] = g; m.s[m.n] = s; m.len[m.n] = n; ++m.n;
+            g += n; s += n; break;
         case 'I': case 'S':
-            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
-            s += n; break;
-        case 'D': g += n; break;
-        default: return bad("a CIGAR operation this program does not write");
+            if (s + n > l_seq) return L.bad("the CIGAR is longer than SEQ");
+            s += n; m.gapped = true; break;
+        case 'D': g += n; m.gapped = true; break;
+        default: return L.bad("a CIGAR operation this program does not write");
         }
         n = 0; digits = false; any = true;
     }
-    if (digits || !any) return bad("malformed CIGAR");
+    return digits || !any ? L.bad("malformed CIGAR") : true;
+}
+inline int base_code(char c) { switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; } }
+
+// one record line [l, e): its bases at the sites into counts; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with g_err set
+int snp_count_line(const salt_index *ix, const RefIds &ids, const std::vector<uint32_t> &sites, const char *l, const char *e, uint32_t min_mapq, uint32_t *counts)
+{
+    SamLine L; MRuns m; uint64_t g0;
+    const int h = twin_head(ix, ids, L, "snp counts: ", l, e, min_mapq, &g0);
+    if (h != 1) return h;
+    if (!twin_cigar(L, g0, m)) return -1;
+    for (int r = 0; r < m.n; ++r)
+        for (uint64_t k = 0; k < m.len[r]; ++k) {
+            const uint64_t g = m.g[r] + k;
+            const auto it = std::lower_bound(sites.begin(), sites.end(), g);
+            if (g > 0xFFFFFFFFull || it == sites.end() || *it != g) continue;
+            const int b = base_code(L.f[9][m.s[r] + k]);
+            if (b >= 0) ++counts[(size_t)(it - sites.begin()) * 4 + (size_t)b];
+        }
     return 1;
 }
 
@@ -718,18 +773,7 @@ extern "C" int64_t salt_snp_count_sam(const salt_index_t *ix, const char *sam, s
     const std::vector<uint32_t> &sites = snp_positions(ix);
     if (n_sites != sites.size()) { g_err = "snp counts: counts for " + std::to_string(n_sites) + " sites, the index has " + std::to_string(sites.size()); return -1; }
     const RefIds ids(ix);
-    int64_t n_rec = 0;
-    for (const char *l = sam, *end = sam + n; l < end; ) {
-        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
-        if (!e) e = end;
-        if (e > l && *l != '@') {                                      // (empty lines: a skipped read, the paired-end driver's; '@': a header line -- a read name
-            const int r = snp_count_line(ix, ids, sites, l, e, min_mapq, counts);      //  cannot start with '@', the FASTQ parsers drop it)
-            if (r < 0) return -1;
-            n_rec += r;
-        }
-        l = e + 1;
-    }
-    return n_rec;
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return snp_count_line(ix, ids, sites, l, e, min_mapq, counts); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -741,46 +785,12 @@ namespace {
 // one record line [l, e): its M runs into diff; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with g_err set
 int depth_add_line(const salt_index *ix, const RefIds &ids, const char *l, const char *e, uint32_t min_mapq, uint32_t *diff)
 {
-    const char *f[12]; int nf = 0;
-    f[nf++] = l;
-    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
-    auto bad = [&](const char *why) { g_err = std::string("depth: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return -1; };
-    if (nf < 11) return bad("fewer than 11 fields");
-    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };
-    int64_t flag, pos1, mapq;
-    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
-        pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
-    if (flag & 4) return 0;                                            // unmapped, also a mate printed at its mate's place
-    if ((uint64_t)mapq < min_mapq) return 0;
-    const int32_t rid = ids.find(f[2], fe(2));
-    if (rid < 0) return bad("RNAME is no sequence of the index");
-    if (pos1 < 1) return bad("a mapped record without a position");
-    const size_t l_seq = (size_t)(fe(9) - f[9]);
-    const uint64_t ref_len = ix->view.ref_len;
-    // the line is checked whole before anything is added: a refused line leaves diff as it was
-    uint64_t runs[2 * 64]; int n_runs = 0;
-    uint64_t g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)pos1 - 1;      // global position; the walk may run past the contig's end
-    size_t s = 0; uint64_t n = 0; bool digits = false, any = false;
-    for (const char *p = f[5]; p < fe(5); ++p) {
-        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
-        if (!digits) return bad("malformed CIGAR");
-        switch (*p) {
-        case 'M':
-            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
-            if (n_runs == 64) return bad("more M runs than a record of this program has");
-            runs[2 * n_runs] = g; runs[2 * n_runs + 1] = g + n; ++n_runs;
-            g += n; s += n; break;
-        case 'I': case 'S':
-            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
-            s += n; break;
-        case 'D': g += n; break;
-        default: return bad("a CIGAR operation this program does not write");
-        }
-        n = 0; digits = false; any = true;
-    }
-    if (digits || !any) return bad("malformed CIGAR");
-    for (int k = 0; k < n_runs; ++k) {
-        const uint64_t a = runs[2 * k], b = std::min(runs[2 * k + 1], ref_len);      // cut at the genome's end: not wrapped, not refused
+    SamLine L; MRuns m; uint64_t g0;
+    const int h = twin_head(ix, ids, L, "depth: ", l, e, min_mapq, &g0);
+    if (h != 1) return h;
+    if (!twin_cigar(L, g0, m)) return -1;
+    for (int k = 0; k < m.n; ++k) {
+        const uint64_t a = m.g[k], b = std::min<uint64_t>(a + m.len[k], ix->view.ref_len);      // cut at the genome's end: not wrapped, not refused
         if (a < b) { diff[a] += 1u; diff[b] -= 1u; }
     }
     return 1;
@@ -800,18 +810,7 @@ extern "C" int64_t salt_depth_add_sam(const salt_index_t *ix, const char *sam, s
     if (!ix || (!sam && n) || !diff) { g_err = "depth: null argument"; return -1; }
     if (n_words != (uint64_t)ix->view.ref_len + 1) { g_err = "depth: an array of " + std::to_string(n_words) + " words, the index needs " + std::to_string((uint64_t)ix->view.ref_len + 1) + " (ref_len + 1)"; return -1; }
     const RefIds ids(ix);
-    int64_t n_rec = 0;
-    for (const char *l = sam, *end = sam + n; l < end; ) {
-        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
-        if (!e) e = end;
-        if (e > l && *l != '@') {                                      // (empty lines: a skipped read; '@': a header line)
-            const int r = depth_add_line(ix, ids, l, e, min_mapq, diff);
-            if (r < 0) return -1;
-            n_rec += r;
-        }
-        l = e + 1;
-    }
-    return n_rec;
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return depth_add_line(ix, ids, l, e, min_mapq, diff); });
 }
 
 extern "C" int64_t salt_depth_text(const salt_index_t *ix, const uint32_t *diff, uint64_t n_words, uint32_t window, char *out, uint64_t cap)
@@ -861,64 +860,34 @@ const uint64_t EP_CYCLES = 512, EP_Q = 95, EP_CELLS = 2 * EP_CYCLES * EP_Q * 16;
 // one record line [l, e): its base events into cells, its fate into rec; 1 it counted, 0 it did not (unmapped, below min_mapq), -1 with g_err set
 int errprof_add_line(const salt_index *ix, const RefIds &ids, const char *l, const char *e, uint32_t min_mapq, uint64_t *cells, uint64_t *rec)
 {
-    const char *f[12]; int nf = 0;
-    f[nf++] = l;
-    for (const char *p = l; p < e && nf < 12; ++p) if (*p == '\t') f[nf++] = p + 1;
-    auto bad = [&](const char *why) { g_err = std::string("error profile: ") + why + " in SAM line '" + std::string(l, std::min<size_t>((size_t)(e - l), 80)) + "'"; return -1; };
-    if (nf < 11) return bad("fewer than 11 fields");
-    auto fe = [&](int k) { return k + 1 < nf ? f[k + 1] - 1 : e; };
-    int64_t flag, pos1, mapq;
-    if (!field_int(f[1], fe(1), &flag) || !field_int(f[3], fe(3), &pos1) || !field_int(f[4], fe(4), &mapq) || flag < 0 || flag > 0xFFFF || mapq < 0 || mapq > 255 ||
-        pos1 < 0 || pos1 > 0x7FFFFFFF) return bad("a numeric field is no number of its range");
-    uint64_t *r = rec + ((flag & 0x80) ? 8 : 0);
-    const uint64_t mate = (flag & 0x80) ? 1 : 0;
-    if (flag & 4) { ++r[0]; ++r[2]; return 0; }                        // unmapped, also a mate printed at its mate's place
-    if ((uint64_t)mapq < min_mapq) { ++r[0]; ++r[3]; return 0; }
-    const bool rev = (flag & 0x10) != 0;
-    const int32_t rid = ids.find(f[2], fe(2));
-    if (rid < 0) return bad("RNAME is no sequence of the index");
-    if (pos1 < 1) return bad("a mapped record without a position");
-    const char *seq = f[9], *qual = f[10]; const size_t l_seq = (size_t)(fe(9) - seq), l_qual = (size_t)(fe(10) - qual);
-    if (l_seq == 0 || l_seq > EP_CYCLES) return bad("SEQ is empty or longer than 512 bases");
+    SamLine L; MRuns m; uint64_t g0;
+    const int h = twin_head(ix, ids, L, "error profile: ", l, e, min_mapq, &g0);
+    if (h < 0) return h;
+    uint64_t *r = rec + ((L.flag & 0x80) ? 8 : 0);
+    const uint64_t mate = (L.flag & 0x80) ? 1 : 0;
+    if (h == 0) { ++r[0]; ++r[(L.flag & 4) ? 2 : 3]; return 0; }
+    const bool rev = (L.flag & 0x10) != 0;
+    const char *seq = L.f[9], *qual = L.f[10]; const size_t l_seq = L.len(9), l_qual = L.len(10);
+    if (l_seq == 0 || l_seq > EP_CYCLES) return L.bad("SEQ is empty or longer than 512 bases"), -1;
     const bool no_qual = l_qual == 1 && qual[0] == '*' && l_seq != 1;
-    if (!no_qual && l_qual != l_seq) return bad("QUAL is neither * nor as long as SEQ");
-    const uint64_t ref_len = ix->view.ref_len;
-    // the line is checked whole before anything is added: a refused line leaves the tables as they were
-    uint32_t ev[EP_CYCLES]; size_t n_ev = 0;
-    uint64_t g = (uint64_t)ix->anns[(size_t)rid].offset + (uint64_t)pos1 - 1;      // global position; the walk may run past the contig's end
-    size_t s = 0; uint64_t n = 0; bool digits = false, any = false, gapped = false;
-    for (const char *p = f[5]; p < fe(5); ++p) {
-        if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); digits = true; if (n >= (1u << 28)) return bad("CIGAR length of 2^28 or more"); continue; }
-        if (!digits) return bad("malformed CIGAR");
-        switch (*p) {
-        case 'M':
-            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
-            for (uint64_t k = 0; k < n; ++k, ++g, ++s) {
-                if (g >= ref_len) continue;
-                const uint32_t m = mask_at(ix, (uint32_t)g);
-                if (m == 0 || (m & (m - 1u)) != 0) continue;                   // N of the genome; a site
-                int b;
-                switch (seq[s]) { case 'A': b = 0; break; case 'C': b = 1; break; case 'G': b = 2; break; case 'T': b = 3; break; default: b = -1; }
-                if (b < 0) continue;                                           // a read's N
-                int c = 0; while (!((m >> c) & 1u)) ++c;
-                const uint32_t q = no_qual ? 94u : ((uint8_t)qual[s] >= 33 && (uint8_t)qual[s] <= 126 ? (uint32_t)(uint8_t)qual[s] - 33u : 94u);
-                const uint64_t cycle = rev ? l_seq - 1 - s : s;
-                ev[n_ev++] = (uint32_t)(((mate * EP_CYCLES + cycle) * EP_Q + q) * 16 + (uint64_t)(rev ? 3 - c : c) * 4 + (uint64_t)(rev ? 3 - b : b));
-            }
-            break;
-        case 'I': case 'S':
-            if (s + n > l_seq) return bad("the CIGAR is longer than SEQ");
-            s += n; gapped = true; break;
-        case 'D': g += n; gapped = true; break;
-        default: return bad("a CIGAR operation this program does not write");
+    if (!no_qual && l_qual != l_seq) return L.bad("QUAL is neither * nor as long as SEQ"), -1;
+    if (!twin_cigar(L, g0, m)) return -1;
+    for (int k = 0; k < m.n; ++k)
+        for (uint64_t j = 0; j < m.len[k]; ++j) {
+            const uint64_t g = m.g[k] + j; const size_t s = m.s[k] + j;
+            if (g >= ix->view.ref_len) continue;
+            const uint32_t mk = mask_at(ix, (uint32_t)g);
+            if (mk == 0 || (mk & (mk - 1u)) != 0) continue;                    // N of the genome; a site
+            const int b = base_code(seq[s]);
+            if (b < 0) continue;                                               // a read's N
+            int c = 0; while (!((mk >> c) & 1u)) ++c;
+            const uint32_t q = no_qual ? 94u : ((uint8_t)qual[s] >= 33 && (uint8_t)qual[s] <= 126 ? (uint32_t)(uint8_t)qual[s] - 33u : 94u);
+            const uint64_t cycle = rev ? l_seq - 1 - s : s;
+            ++cells[((mate * EP_CYCLES + cycle) * EP_Q + q) * 16 + (uint64_t)(rev ? 3 - c : c) * 4 + (uint64_t)(rev ? 3 - b : b)];
         }
-        n = 0; digits = false; any = true;
-    }
-    if (digits || !any) return bad("malformed CIGAR");
-    for (size_t k = 0; k < n_ev; ++k) ++cells[ev[k]];
     ++r[0]; ++r[4];
     if (rev) ++r[5];
-    if (gapped) ++r[6];
+    if (m.gapped) ++r[6];
     return 1;
 }
 
@@ -929,18 +898,7 @@ extern "C" int64_t salt_errprof_add_sam(const salt_index_t *ix, const char *sam,
     if (!ix || (!sam && n) || !cells || !rec) { g_err = "error profile: null argument"; return -1; }
     if (n_cells != EP_CELLS) { g_err = "error profile: a table of " + std::to_string(n_cells) + " cells, the profile has " + std::to_string(EP_CELLS) + " (2 x 512 x 95 x 4 x 4)"; return -1; }
     const RefIds ids(ix);
-    int64_t n_rec = 0;
-    for (const char *l = sam, *end = sam + n; l < end; ) {
-        const char *e = (const char *)memchr(l, '\n', (size_t)(end - l));
-        if (!e) e = end;
-        if (e > l && *l != '@') {                                      // (empty lines: a skipped read, the paired-end driver's; '@': a header line)
-            const int r = errprof_add_line(ix, ids, l, e, min_mapq, cells, rec);
-            if (r < 0) return -1;
-            n_rec += r;
-        }
-        l = e + 1;
-    }
-    return n_rec;
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return errprof_add_line(ix, ids, l, e, min_mapq, cells, rec); });
 }
 
 extern "C" int64_t salt_errprof_text(const uint64_t *cells, const uint64_t rec[16], uint32_t min_mapq, int full, char *out, uint64_t cap)

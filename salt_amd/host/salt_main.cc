@@ -463,77 +463,60 @@ struct BamRun {
     const salt_index_t *ix = nullptr;
 } g_bam;
 
-// --snp-counts FILE: how many reads show which base at every SNP site of the index.  On the device the table belongs to each GPU's index
-// and every align call adds into it (salt_gpu_index_snp_enable); the tables are summed after the last block.  A block the text path has
-// aligned and then drops at a hand-over is taken back (salt_gpu_ws_snp_uncount): the host pipeline aligns those reads again.  Without
-// the device's symbols the SAM lines of every block and batch that is written go through salt_snp_count_sam, one caller at a time.
-struct SnpRun {
+// The three row tallies (--snp-counts, --depth, --error-profile) run alike.  On the device the table belongs to each GPU's index and every
+// align call adds into it (salt_gpu_index_*_enable); a block the text path has aligned and then drops at a hand-over is taken back
+// (salt_gpu_ws_*_uncount): the host pipeline aligns those reads again.  Without the device's symbols the SAM lines of every block and
+// batch that is written go through the tally's host twin, one caller at a time.
+struct TallyRun {
     bool on = false, device = false; const char *fn = nullptr; FILE *fp = nullptr; uint32_t min_mapq = 0;
-    const salt_index_t *ix = nullptr; std::mutex mu; std::vector<uint32_t> host_counts; uint64_t n_sites = 0;
+    const salt_index_t *ix = nullptr; std::mutex mu;
     bool host() const { return on && !device; }
-} g_snp;
-
-// the host twin over SAM lines that are about to be written; false with the reason on stderr
-bool snp_host_add(const char *sam, size_t n)
-{
-    std::lock_guard<std::mutex> lk(g_snp.mu);
-    if (salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites) >= 0) return true;
-    fprintf(stderr, "[salt] %s\n", salt_host_last_error());
-    return false;
-}
-// a block the text path aligned and will not write: its adds leave the device's table
-void snp_drop_block(salt_gpu_ws_t *ws)
-{
-    if (g_snp.on && g_snp.device && salt_gpu_ws_snp_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
-}
-
-// --depth FILE: coverage along the genome, per base or per window.  On the device every GPU's index holds a difference array that every
-// align call marks (salt_gpu_index_depth_enable); after the last block the arrays are added into the first GPU's and its text kernels
-// print the file.  A block the text path has aligned and then drops at a hand-over is taken back (salt_gpu_ws_depth_uncount).  Without the
-// device's symbols the SAM lines of every block and batch that is written go through salt_depth_add_sam, one caller at a time.
-struct DepthRun {
-    bool on = false, device = false, gz = false; const char *fn = nullptr; FILE *fp = nullptr; uint32_t min_mapq = 0, window = 0;
-    const salt_index_t *ix = nullptr; std::mutex mu; std::vector<uint32_t> host_diff;
-    bool host() const { return on && !device; }
-} g_depth;
-
-bool depth_host_add(const char *sam, size_t n)
-{
-    std::lock_guard<std::mutex> lk(g_depth.mu);
-    if (salt_depth_add_sam(g_depth.ix, sam, n, g_depth.min_mapq, g_depth.host_diff.data(), g_depth.host_diff.size()) >= 0) return true;
-    fprintf(stderr, "[salt] %s\n", salt_host_last_error());
-    return false;
-}
-// --error-profile FILE: mismatches by cycle, quality and substitution, the index's SNP sites masked.  On the device every GPU's index holds
-// the tables that every align call adds to (salt_gpu_index_errprof_enable; the host pipeline hands its batches' qualities over with
-// salt_gpu_ws_set_quals); after the last block they are fetched and summed on the host.  A block the text path has aligned and then drops
-// at a hand-over is taken back (salt_gpu_ws_errprof_uncount).  Without the device's symbols the SAM lines of every block and batch that
-// is written go through salt_errprof_add_sam, one caller at a time.  salt_errprof_text prints the file on both paths.
+};
+// --snp-counts FILE: how many reads show which base at every SNP site of the index; the GPUs' tables are summed after the last block.
+struct SnpRun : TallyRun { std::vector<uint32_t> host_counts; uint64_t n_sites = 0; } g_snp;
+// --depth FILE: coverage along the genome, per base or per window.  After the last block the GPUs' difference arrays are added into the first
+// GPU's and its text kernels print the file.
+struct DepthRun : TallyRun { bool gz = false; uint32_t window = 0; std::vector<uint32_t> host_diff; } g_depth;
+// --error-profile FILE: mismatches by cycle, quality and substitution, the index's SNP sites masked.  The host pipeline hands its batches'
+// qualities over with salt_gpu_ws_set_quals; after the last block the GPUs' tables are fetched and summed on the host.  salt_errprof_text
+// prints the file on both paths.
 const size_t ERRPROF_CELLS = 2u * 512u * 95u * 16u;
-struct ErrprofRun {
-    bool on = false, device = false, full = false; const char *fn = nullptr; FILE *fp = nullptr; uint32_t min_mapq = 0;
-    const salt_index_t *ix = nullptr; std::mutex mu; std::vector<uint64_t> cells; uint64_t rec[16] = { 0 };
-    bool host() const { return on && !device; }
-} g_errprof;
+struct ErrprofRun : TallyRun { bool full = false; std::vector<uint64_t> cells; uint64_t rec[16] = { 0 }; } g_errprof;
 
-bool errprof_host_add(const char *sam, size_t n)
-{
-    std::lock_guard<std::mutex> lk(g_errprof.mu);
-    if (salt_errprof_add_sam(g_errprof.ix, sam, n, g_errprof.min_mapq, g_errprof.cells.data(), g_errprof.cells.size(), g_errprof.rec) >= 0) return true;
-    fprintf(stderr, "[salt] %s\n", salt_host_last_error());
-    return false;
-}
-// the SAM lines of a block or batch that is about to be written, through every host twin that is on
+// What differs between them where they run alike, in the order snp, depth, error profile.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
+// how the file is opened; does: what a libsalt_gpu without the symbols does not do (the --polish refusal); symbols: this libsalt_gpu has
+// the device side; host_add: the twin over SAM lines (< 0: refused); uncount: the last align call's adds leave the device's table.
+struct Tally {
+    TallyRun *run; const char *opt, *stem, *mode, *does;
+    bool (*symbols)(); int64_t (*host_add)(const char *sam, size_t n); int (*uncount)(salt_gpu_ws_t *ws);
+};
+const Tally TALLIES[3] = {
+    { &g_snp, "snp-counts", "snp", "w", "counts",
+      [] { return salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount; },
+      [](const char *sam, size_t n) { return salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites); }, salt_gpu_ws_snp_uncount },
+    { &g_depth, "depth", "depth", "wb", "marks the coverage",
+      [] { return salt_gpu_index_depth_enable && salt_gpu_index_depth_fetch && salt_gpu_index_depth_add && salt_gpu_index_depth_text_begin && salt_gpu_index_depth_text_next && salt_gpu_ws_depth_uncount; },
+      [](const char *sam, size_t n) { return salt_depth_add_sam(g_depth.ix, sam, n, g_depth.min_mapq, g_depth.host_diff.data(), g_depth.host_diff.size()); }, salt_gpu_ws_depth_uncount },
+    { &g_errprof, "error-profile", "error-profile", "w", "makes the profile",
+      [] { return salt_gpu_index_errprof_enable && salt_gpu_index_errprof_fetch && salt_gpu_ws_errprof_uncount && salt_gpu_ws_set_quals; },
+      [](const char *sam, size_t n) { return salt_errprof_add_sam(g_errprof.ix, sam, n, g_errprof.min_mapq, g_errprof.cells.data(), g_errprof.cells.size(), g_errprof.rec); }, salt_gpu_ws_errprof_uncount },
+};
+
+// the SAM lines of a block or batch that is about to be written, through every host twin that is on; false with the reason on stderr
 bool host_twins_add(const char *sam, size_t n)
 {
-    return (!g_snp.host() || snp_host_add(sam, n)) && (!g_depth.host() || depth_host_add(sam, n)) && (!g_errprof.host() || errprof_host_add(sam, n));
+    for (const Tally &t : TALLIES) {
+        if (!t.run->host()) continue;
+        std::lock_guard<std::mutex> lk(t.run->mu);
+        if (t.host_add(sam, n) < 0) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+    }
+    return true;
 }
 // a block the text path aligned and will not write leaves the device's tables
 void drop_block(salt_gpu_ws_t *ws)
 {
-    snp_drop_block(ws);
-    if (g_depth.on && g_depth.device && salt_gpu_ws_depth_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
-    if (g_errprof.on && g_errprof.device && salt_gpu_ws_errprof_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
+    for (const Tally &t : TALLIES)
+        if (t.run->on && t.run->device && t.uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
 }
 
 // SAM lines -> BAM records in `out`; false with the reason on stderr (a read name past the format's limit)
@@ -1387,19 +1370,14 @@ static int parse_options(int argc, char **argv, Opts &o)
             else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
             break;
         case 1004: g_snp.on = true; g_snp.fn = optarg; break;
-        case 1005: {
+        case 1005: case 1007: case 1010: {
+            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : 2];
             char *end = nullptr; const long v = strtol(optarg, &end, 10);
-            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --snp-min-mapq %s: a MAPQ is a number from 0 to 255\n", optarg); return 1; }
-            g_snp.min_mapq = (uint32_t)v;
+            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --%s-min-mapq %s: a MAPQ is a number from 0 to 255\n", t.stem, optarg); return 1; }
+            t.run->min_mapq = (uint32_t)v;
             break;
         }
         case 1006: g_depth.on = true; g_depth.fn = optarg; break;
-        case 1007: {
-            char *end = nullptr; const long v = strtol(optarg, &end, 10);
-            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --depth-min-mapq %s: a MAPQ is a number from 0 to 255\n", optarg); return 1; }
-            g_depth.min_mapq = (uint32_t)v;
-            break;
-        }
         case 1008: {
             char *end = nullptr; errno = 0; const long long v = strtoll(optarg, &end, 10);
             if (end == optarg || *end || errno || v < 1 || v > 0xFFFFFFFFll) { fprintf(stderr, "[opt_parse]: --depth-window %s: a window is a number of positions from 1 to 4294967295\n", optarg); return 1; }
@@ -1407,12 +1385,6 @@ static int parse_options(int argc, char **argv, Opts &o)
             break;
         }
         case 1009: g_errprof.on = true; g_errprof.fn = optarg; break;
-        case 1010: {
-            char *end = nullptr; const long v = strtol(optarg, &end, 10);
-            if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --error-profile-min-mapq %s: a MAPQ is a number from 0 to 255\n", optarg); return 1; }
-            g_errprof.min_mapq = (uint32_t)v;
-            break;
-        }
         case 1011: g_errprof.full = true; break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
@@ -1430,30 +1402,17 @@ static int parse_options(int argc, char **argv, Opts &o)
     // out of the device's SAM text are deflated there too
     g_bam.device = g_bam.on && salt_gpu_ws_set_sam_bam != nullptr && !(getenv("SALT_BAM_HOST") && atoi(getenv("SALT_BAM_HOST")));
     if (g_bam.on && !g_bam.device) g_bgzf.device = false;
-    if (g_snp.on) {
-        g_snp.device = salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount;
-        // counted on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
-        if (!g_snp.device && g_polish) { fprintf(stderr, "[opt_parse]: --snp-counts with --polish needs a libsalt_gpu that counts on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
-        if (!g_snp.device) g_bgzf.device = g_bam.device = false;
-        if (!(g_snp.fp = fopen(g_snp.fn, "w"))) { fprintf(stderr, "[opt_parse]: --snp-counts: cannot open %s for writing: %s\n", g_snp.fn, strerror(errno)); return 1; }
+    for (const Tally &t : TALLIES) {
+        TallyRun &r = *t.run;
+        if (!r.on) continue;
+        r.device = t.symbols();
+        // made on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
+        if (!r.device && g_polish) { fprintf(stderr, "[opt_parse]: --%s with --polish needs a libsalt_gpu that %s on the device: this one does not, and no SAM lines exist under --polish\n", t.opt, t.does); return 1; }
+        if (!r.device) g_bgzf.device = g_bam.device = false;
+        if (!(r.fp = fopen(r.fn, t.mode))) { fprintf(stderr, "[opt_parse]: --%s: cannot open %s for writing: %s\n", t.opt, r.fn, strerror(errno)); return 1; }
     }
-    if (g_depth.on) {
-        g_depth.device = salt_gpu_index_depth_enable && salt_gpu_index_depth_fetch && salt_gpu_index_depth_add && salt_gpu_index_depth_text_begin &&
-                         salt_gpu_index_depth_text_next && salt_gpu_ws_depth_uncount;
-        // summed on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
-        if (!g_depth.device && g_polish) { fprintf(stderr, "[opt_parse]: --depth with --polish needs a libsalt_gpu that marks the coverage on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
-        if (!g_depth.device) g_bgzf.device = g_bam.device = false;
-        const size_t l = strlen(g_depth.fn);
-        g_depth.gz = l > 3 && strcmp(g_depth.fn + l - 3, ".gz") == 0;
-        if (!(g_depth.fp = fopen(g_depth.fn, "wb"))) { fprintf(stderr, "[opt_parse]: --depth: cannot open %s for writing: %s\n", g_depth.fn, strerror(errno)); return 1; }
-    }
-    if (g_errprof.on) {
-        g_errprof.device = salt_gpu_index_errprof_enable && salt_gpu_index_errprof_fetch && salt_gpu_ws_errprof_uncount && salt_gpu_ws_set_quals;
-        // summed on the host: from SAM lines, so the blocks reach the host as SAM lines and become records and BGZF blocks there
-        if (!g_errprof.device && g_polish) { fprintf(stderr, "[opt_parse]: --error-profile with --polish needs a libsalt_gpu that makes the profile on the device: this one does not, and no SAM lines exist under --polish\n"); return 1; }
-        if (!g_errprof.device) g_bgzf.device = g_bam.device = false;
-        if (!(g_errprof.fp = fopen(g_errprof.fn, "w"))) { fprintf(stderr, "[opt_parse]: --error-profile: cannot open %s for writing: %s\n", g_errprof.fn, strerror(errno)); return 1; }
-    }
+    const size_t l = g_depth.on ? strlen(g_depth.fn) : 0;
+    g_depth.gz = l > 3 && strcmp(g_depth.fn + l - 3, ".gz") == 0;
     return -1;
 }
 

@@ -98,3 +98,18 @@ def test_a_line_that_is_no_sam_record_is_an_error(bad, lam):
         salt_amd.snp_count_sam(ix, good + bad)
     with pytest.raises(salt_amd.SaltError, match="contiguous"):
         salt_amd.snp_count_sam(ix, good, counts=np.zeros((3, 4), dtype=np.uint32))
+
+
+# 2M at lambdaA:4 covers the site at genome position 3; the N behind it is an operation this program does not write
+@pytest.mark.parametrize("bad", [b"not a record\n", b"r1\t0\tlambdaA\t10\t30\n", b"r1\t0\tnowhere\t10\t30\t4M\t*\t0\t0\tACGT\tIIII\n",
+                                 b"r1\t0\tlambdaA\t10\t30\t5M\t*\t0\t0\tACGT\tIIII\n", b"r1\t0\tlambdaA\t10\t30\t4Q\t*\t0\t0\tACGT\tIIII\n",
+                                 b"r1\tx\tlambdaA\t10\t30\t4M\t*\t0\t0\tACGT\tIIII\n", b"r1\t0\tlambdaA\t4\t30\t2M2N\t*\t0\t0\tACGT\tIIII\n"])
+def test_a_line_that_is_no_sam_record_adds_nothing(bad, lam):
+    import salt_amd
+    ix, sites, _ = lam
+    assert sites[0] == 3
+    assert salt_amd.snp_count_sam(ix, b"r0\t0\tlambdaA\t4\t30\t2M\t*\t0\t0\tAC\tII\n")[0, 0] == 1      # the refused line's first run alone does count
+    counts = np.zeros((len(sites), 4), dtype=np.uint32)
+    with pytest.raises(salt_amd.SaltError, match="snp counts: "):
+        salt_amd.snp_count_sam(ix, bad, counts=counts)
+    assert not counts.any()
