@@ -406,7 +406,8 @@ int  salt_gpu_buffer_equal(int device, const void *a, const void *b, uint64_t by
  * (code_kmismatch, alnse.c:348-369; distances 0..3, range filter pos < ref_len) by rule_unsorted; 1: the same by
  * rule_sparse; 2: gapped rule (code_kdiff, alnse.c:371-393; distances 0..12, filter !(pos + L + 4 >= ref_len)); 3: as 1 by
  * rule_sparse on half-waves (32 lanes, what k_light2 runs), cases 2b and 2b + 1 side by side in the halves of wave b; 4: as 1 on
- * quarters of a wave (16 lanes, what k_light4 runs), cases 4b .. 4b + 3 side by side in the quarters of wave b.
+ * quarters of a wave (16 lanes, what k_light4 runs), cases 4b .. 4b + 3 side by side in the quarters of wave b; 5: as 2 through
+ * the front end for lists in global memory (what k_gapfin runs: several trips of 64 rows in flight, the first batch asked for ahead).
  * out[i][18] = found, best_pos, best_dist, n_hits, a0, bound_out, then 6 x (hit_pos, hit_dist) in position order. */
 int  salt_gpu_diag_rule(uint32_t n_cases, const uint32_t *pos, const uint8_t *val, const uint32_t *offs, const uint32_t *bound_in,
                         uint32_t L, uint32_t ref_len, int mode, uint32_t *out);
@@ -452,6 +453,10 @@ int  salt_gpu_ws_counters(salt_gpu_ws_t *ws, uint64_t out[SALT_CTR_N]);
  * ed_diff, ed_diff_withcigar (editdistance.c:88,174,234). */
 int  salt_gpu_diag_lv(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint32_t *pos,
                       const uint32_t *kdiff, const uint8_t *seqs, const uint32_t *offs, int32_t *out4, uint16_t *cigars);
+/* The same with lv_cigar's tables placed as k_cigar places them when lds_tab != 0: in the block's LDS for a distance of at most 12,
+ * in global memory above that.  lds_tab == 0 is salt_gpu_diag_lv. */
+int  salt_gpu_diag_lv_tab(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint32_t *pos,
+                          const uint32_t *kdiff, const uint8_t *seqs, const uint32_t *offs, int32_t *out4, uint16_t *cigars, int lds_tab);
 
 /* Unit entry of the Smith-Waterman mate-rescue kernel (ssw_init + ssw_align as snpaln_sw[_snpaware] call them,
  * alnpe.c:260-393; ssw.c): case i aligns codes[read_offs[i]..read_offs[i+1]) against reference symbols

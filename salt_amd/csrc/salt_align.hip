@@ -651,6 +651,10 @@ template <int NS> struct SaiListsT { uint32_t sp[2][NS], ep[2][NS], off[2][NS]; 
 struct SaiLists { uint32_t *sp[2], *ep[2], *off[2]; };                                // the same lists by reference (the sort replica below)
 template <int NS> __device__ __forceinline__ SaiLists sai_ref(SaiListsT<NS> &a) { return SaiLists{ { a.sp[0], a.sp[1] }, { a.ep[0], a.ep[1] }, { a.off[0], a.off[1] } }; }
 struct LvTables { short L[LVK][64]; char A[LVK][64]; };
+// Where lv_wave's furthest-reaching values and actions go, rows of 64 diagonals, one row a level: a block's LvTables in global memory
+// (any k the reference admits) or, for k <= LLV_K, LvTablesLds in the block's LDS, where lane 0's traceback reads them back without
+// a trip to L2 per load.  L == nullptr: the distance alone.
+struct LvTabRef { short *L; char *A; };
 // lane-parallel LV (one candidate per lane): nibble-packed text window per lane and the pattern, both zero-padded in LDS over every
 // word lv_lanes can ask for; the DP row lives in registers
 static constexpr int LLV_K = 12;                 // handles k <= 12 (reads up to 129 bp at k = L/10)
@@ -672,6 +676,12 @@ static_assert(((8 * (LLV_TW - 1) - LLV_WIN) >> 3) + 2 <= LLV_PW, "pattern words 
 // 22 words put 32 lanes on 16 banks).  P: the pattern all lanes share in k_gap and k_heavy (k_diag_lv gives every lane its own).
 struct LaneLv { uint32_t T[LLV_TS * LLV_N]; uint32_t P[LLV_PW]; };
 struct LvBytes { uint8_t T[MAXL + 4 + 64]; uint8_t P[MAXL + 64]; };
+struct LvTablesLds { short L[LLV_K + 1][64]; char A[LLV_K + 1][64]; };     // 2 496 B: levels 0 .. LLV_K
+__device__ __forceinline__ LvTabRef lv_tab(LvTables *t) { return t ? LvTabRef{ &t->L[0][0], &t->A[0][0] } : LvTabRef{ nullptr, nullptr }; }
+__device__ __forceinline__ LvTabRef lv_tab(LvTablesLds &t) { return LvTabRef{ &t.L[0][0], &t.A[0][0] }; }
+// the traceback's per-level actions and match runs: lane 0 keeps them over the byte strings, which are done with by then
+struct LvTrace { int matched[LVK + 1]; char act[LVK + 1]; };
+static_assert(sizeof(LvTrace) <= sizeof(LvBytes::T), "the traceback's levels fit the text bytes");
 // NS: seed slots per list the block can hold; LLV: with the lane-LV scratch (6 KB) for gapped passes finished inside the block.
 // k_heavy's usual shape is <32, false> = 7.5 KB: its LDS is what decides how much of a CU it leaves to the kernels of the other
 // batches in flight (18.6 KB per block with 512 slots and the lane-LV scratch: 303-345 Mreads/s on the 4-stream step; 7.5 KB: 383-388)
@@ -1210,11 +1220,13 @@ __device__ __forceinline__ void verify_quads_2(const uint32_t *__restrict__ ref,
 
 // ---- Landau-Vishkin on byte masks, one diagonal per lane ---------------------------------------
 // T: text masks (tlen bytes, zero padded), P: one-hot pattern (plen bytes, zero padded).
-// Returns e (<= k), or -1.  When tab != nullptr also fills the L / action tables and returns the
+// Returns e (<= k), or -1.  When tab.L != nullptr also fills the L / action tables and returns the
 // finishing diagonal in d_fin (order 0,-1,1,... LandauVishkin.c:248); otherwise the order is
-// irrelevant for the distance (LandauVishkin.c:67).
-__device__ __attribute__((noinline)) int lv_wave(const uint8_t *T, int tlen, const uint8_t *P, int plen, int k, LvTables *tab, int &d_fin)
+// irrelevant for the distance (LandauVishkin.c:67).  (Both come back by value: a reference into the caller's frame was scratch.)
+struct LvEnd { int e, d_fin; };
+__device__ __attribute__((noinline)) LvEnd lv_wave(const uint8_t *T, int tlen, const uint8_t *P, int plen, int k, const LvTabRef tab)
 {
+    int d_fin = 0;
     const int lane = (int)lane_id();
     const int d = lane - 31;
     const int ad = d < 0 ? -d : d;
@@ -1222,9 +1234,8 @@ __device__ __attribute__((noinline)) int lv_wave(const uint8_t *T, int tlen, con
     const int end0 = plen < tlen ? plen : tlen;
     if (d == 0) { int i = 0; while (i < end0 && (P[i] & T[i]) != 0) ++i; Lprev = i; }
     const int r0 = __shfl(Lprev, 31);
-    if (tab) tab->L[0][lane] = (short)Lprev;
-    d_fin = 0;
-    if (r0 == end0) return plen > end0 ? plen - end0 : 0;
+    if (tab.L) tab.L[lane] = (short)Lprev;
+    if (r0 == end0) return LvEnd{ plen > end0 ? plen - end0 : 0, 0 };
     if (k > LVK - 1) k = LVK - 1;
     for (int e = 1; e <= k; ++e) {
         int left = __shfl_up(Lprev, 1), right = __shfl_down(Lprev, 1);
@@ -1243,21 +1254,21 @@ __device__ __attribute__((noinline)) int lv_wave(const uint8_t *T, int tlen, con
             }
             cur = best;
         }
-        if (tab) { tab->L[e][lane] = (short)cur; tab->A[e][lane] = act; }
+        if (tab.L) { tab.L[e * 64 + lane] = (short)cur; tab.A[e * 64 + lane] = act; }
         uint64_t reach = __ballot(active && cur == plen);
         if (reach) {
-            if (tab) {
+            if (tab.L) {
                 // first finishing diagonal in the order 0,-1,1,-2,2,...
                 int rank = d == 0 ? 0 : (d < 0 ? 2 * ad - 1 : 2 * ad);
                 int my = (active && cur == plen) ? rank : 1000;
                 for (int o = 32; o > 0; o >>= 1) { int t = __shfl_xor(my, o); my = t < my ? t : my; }
                 d_fin = my == 0 ? 0 : ((my & 1) ? -((my + 1) >> 1) : (my >> 1));
             }
-            return e;
+            return LvEnd{ e, d_fin };
         }
         Lprev = cur;
     }
-    return -1;
+    return LvEnd{ -1, 0 };
 }
 
 // ---- Landau-Vishkin distance, one candidate per lane (computeEditDistance, LandauVishkin.c:19-122) ----
@@ -1342,11 +1353,57 @@ __device__ __attribute__((noinline)) uint32_t lv_lanes(LaneLv &s, const uint32_t
 // on the located rows as they come: per distance t the smallest position minpos[t] over P (one wave reduction each), then
 // "counts" is  pos < min(minpos[0..v-1]),  and the hits are extracted by repeated minimum.
 // pos / val: n entries in LDS or global memory; val > VMAX = no candidate.  GAPF: alnse_check_withgap's range filter.
+// B: trips of 64 rows asked for together.  1 = a trip is loaded where it is used (lists in LDS); above 1 the list lies in global
+// memory, where a trip is a round trip to L2 or HBM and a repeat read's ~900 rows were 15 of them in a row: list_trips keeps two
+// batches of B trips in flight, and the caller may have asked for the first batch already (`first`: rows_fetch at row 0).
 // ---------------------------------------------------------------------------------------------
-template <int VMAX, bool GAPF>
+template <int B> struct RowBatch { uint32_t p[B], v[B]; };
+static constexpr int GAPFIN_B = 8;               // k_gapfin: 512 rows a batch, a repeat read's strand (~900 rows, 1 000 at the cap) in two
+// rows b + 64 j + lane (j < B) of a list of n rows; the lanes behind the list's end load nothing and get "no candidate"
+template <int B>
+__device__ __forceinline__ void rows_fetch(RowBatch<B> &r, const uint32_t *pos, const uint8_t *val, const uint32_t n, const uint32_t b)
+{
+    const uint32_t lane = lane_id();
+#pragma unroll
+    for (int j = 0; j < B; ++j) {                                     // one lane offset and an immediate per load: nothing here waits
+        const uint32_t i = b + 64u * (uint32_t)j + lane;
+        r.p[j] = 0; r.v[j] = 0xFFFFFFFFu;
+        if (i < n) { r.p[j] = pos[i]; r.v[j] = val[i]; }
+    }
+}
+// trip(i, p, v) for every trip of the list, i = the lane's row (p = 0, v = NONE behind the end)
+// TWO: the batch behind the one in use is in flight as well (the first pass; the hit passes of a list with more than 64 members
+// inside the bound are rare and take a batch at a time, for the registers)
+template <int B, bool TWO, class F>
+__device__ __forceinline__ void list_trips(const uint32_t *pos, const uint8_t *val, const uint32_t n, const RowBatch<B> *first, F trip)
+{
+    const uint32_t lane = lane_id();
+    if constexpr (B == 1) {
+        for (uint32_t b = 0; b < n; b += 64) {
+            const uint32_t i = b + lane;
+            uint32_t p = 0, v = 0xFFFFFFFFu;
+            if (i < n) { p = pos[i]; v = val[i]; }
+            trip(i, p, v);
+        }
+    } else {
+        if (n == 0) return;
+        RowBatch<B> cur;
+        if (first) cur = *first; else rows_fetch<B>(cur, pos, val, n, 0u);
+        for (uint32_t b = 0; b < n; b += 64u * B) {
+            RowBatch<B> nxt;
+            const bool more = b + 64u * B < n;
+            if (TWO && more) rows_fetch<B>(nxt, pos, val, n, b + 64u * B);   // in flight while this batch is used
+#pragma unroll
+            for (int j = 0; j < B; ++j) if (b + 64u * (uint32_t)j < n) trip(b + 64u * (uint32_t)j + lane, cur.p[j], cur.v[j]);
+            if (more) { if (TWO) cur = nxt; else rows_fetch<B>(cur, pos, val, n, b + 64u * B); }
+        }
+    }
+}
+template <int VMAX, bool GAPF, int B = 1>
 __device__ __forceinline__ void rule_unsorted(const uint32_t *pos, const uint8_t *val, const uint32_t n, const uint32_t L, const uint32_t ref_len,
                                               uint32_t &bound, bool &any, uint32_t &best_pos, uint32_t &best_v,
-                                              uint32_t &n_hits, uint32_t &a0, uint32_t *hit_pos, uint8_t *hit_nd)
+                                              uint32_t &n_hits, uint32_t &a0, uint32_t *hit_pos, uint8_t *hit_nd,
+                                              const RowBatch<B> *first = nullptr)
 {
     const uint32_t lane = lane_id();
     const uint32_t NONE = 0xFFFFFFFFu;
@@ -1358,10 +1415,7 @@ __device__ __forceinline__ void rule_unsorted(const uint32_t *pos, const uint8_t
     // passes over whatever they are taken from: while P has at most 64 members, member k is copied to lane k (scalar steps per member,
     // none for a trip without one) and the hit passes run on that register copy instead of the list.
     uint32_t my_p = 0, my_v = NONE, n_p = 0;                      // n_p > 64: P outgrew the lanes, the passes walk the list
-    for (uint32_t b = 0; b < n; b += 64) {
-        const uint32_t i = b + lane;
-        uint32_t p = 0, v = NONE;
-        if (i < n) { p = pos[i]; v = val[i]; }
+    list_trips<B, true>(pos, val, n, first, [&](const uint32_t i, const uint32_t p, const uint32_t v) {
         const bool in = i < n && v <= bound && in_range(p);
         if (in) {
 #pragma unroll
@@ -1378,7 +1432,7 @@ __device__ __forceinline__ void rule_unsorted(const uint32_t *pos, const uint8_t
                     ++n_p; m &= m - 1;
                 }
         }
-    }
+    });
 #pragma unroll
     for (int t = 0; t <= VMAX; ++t)
         for (int o = 32; o > 0; o >>= 1) { const uint32_t x = (uint32_t)__shfl_xor((int)mp[t], o); mp[t] = x < mp[t] ? x : mp[t]; }
@@ -1404,19 +1458,15 @@ __device__ __forceinline__ void rule_unsorted(const uint32_t *pos, const uint8_t
         unsigned long long cur = ~0ull;
         if (in_lanes) { if (h == 0 || my_key > last) cur = my_key; }
         else
-        for (uint32_t b = 0; b < n; b += 64) {
-            const uint32_t i = b + lane;
-            if (i < n) {
-                const uint32_t p = pos[i], v = val[i];
-                if (v <= bound && in_range(p)) {
-                    uint32_t lim = NONE;
+        list_trips<B, false>(pos, val, n, (const RowBatch<B> *)nullptr, [&](const uint32_t i, const uint32_t p, const uint32_t v) {
+            if (i < n && v <= bound && in_range(p)) {
+                uint32_t lim = NONE;
 #pragma unroll
-                    for (int t = 1; t <= VMAX; ++t) if (v == (uint32_t)t) lim = before[t];
-                    const unsigned long long key = ((unsigned long long)p << 8) | v;
-                    if (p < lim && (h == 0 || key > last) && key < cur) cur = key;
-                }
+                for (int t = 1; t <= VMAX; ++t) if (v == (uint32_t)t) lim = before[t];
+                const unsigned long long key = ((unsigned long long)p << 8) | v;
+                if (p < lim && (h == 0 || key > last) && key < cur) cur = key;
             }
-        }
+        });
         for (int o = 32; o > 0; o >>= 1) {
             const unsigned long long x = ((unsigned long long)(uint32_t)__shfl_xor((int)(cur >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)cur, o);
             cur = x < cur ? x : cur;
@@ -1526,14 +1576,15 @@ __device__ void lv_unpack(const uint32_t *ref_generic, W &w, int strand, uint32_
 }
 
 // CIGAR of a gapped hit into w.cig / w.n_cig (computeEditDistanceWithCigar, useM=1) ------------------
+// lv_cigar_here is the body in place (k_cigar: a function that calls lv_wave from inside a call keeps a frame in scratch); lv_cigar,
+// below it, is the same as a call, for the kernels that hold it beside much else.
 template <class W>
-__device__ __attribute__((noinline)) void lv_cigar(const uint32_t *ref, W &w, LvTables *tabp, int strand, uint32_t L, uint32_t pos, int k)
+__device__ __forceinline__ void lv_cigar_here(const uint32_t *ref, W &w, const LvTabRef tab, int strand, uint32_t L, uint32_t pos, int k)
 {
-    LvTables &tab = *tabp;                  // per-block table in global memory (L2-resident, rare path)
     lv_unpack(ref, w, strand, L, pos);
-    int d_fin = 0;
     WSYNC();
-    int e = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, k, &tab, d_fin);
+    const LvEnd fin = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, k, tab);
+    const int e = fin.e, d_fin = fin.d_fin;
     __threadfence_block();
     WSYNC();
     if (lane_id() == 0) {
@@ -1541,17 +1592,18 @@ __device__ __attribute__((noinline)) void lv_cigar(const uint32_t *ref, W &w, Lv
         uint16_t *cg = w.cig;
         if (e == 0) { cg[n++] = (uint16_t)((L << 4) | 0u); }
         else if (e > 0) {
-            char act[LVK + 1]; int matched[LVK + 1];
+            LvTrace &tr = *reinterpret_cast<LvTrace *>(w.u.lvb.T);
+            char *act = tr.act; int *matched = tr.matched;
             int cd = d_fin;
             for (int ce = e; ce >= 1; --ce) {
-                char a = tab.A[ce][cd + 31];
+                char a = tab.A[ce * 64 + cd + 31];
                 act[ce] = a;
-                int cur = tab.L[ce][cd + 31];
-                if (a == 'I') { matched[ce] = cur - tab.L[ce - 1][cd + 1 + 31] - 1; cd += 1; }
-                else if (a == 'D') { matched[ce] = cur - tab.L[ce - 1][cd - 1 + 31]; cd -= 1; }
-                else { matched[ce] = cur - tab.L[ce - 1][cd + 31] - 1; }
+                int cur = tab.L[ce * 64 + cd + 31];
+                if (a == 'I') { matched[ce] = cur - tab.L[(ce - 1) * 64 + cd + 1 + 31] - 1; cd += 1; }
+                else if (a == 'D') { matched[ce] = cur - tab.L[(ce - 1) * 64 + cd - 1 + 31]; cd -= 1; }
+                else { matched[ce] = cur - tab.L[(ce - 1) * 64 + cd + 31] - 1; }
             }
-            int acc = tab.L[0][31];
+            int acc = tab.L[31];
             int ce = 1;
             while (ce <= e) {
                 char a = act[ce]; int cnt = 1;
@@ -1570,6 +1622,11 @@ __device__ __attribute__((noinline)) void lv_cigar(const uint32_t *ref, W &w, Lv
         w.n_cig = n;
     }
     WSYNC();
+}
+template <class W>
+__device__ __attribute__((noinline)) void lv_cigar(const uint32_t *ref, W &w, const LvTabRef tab, int strand, uint32_t L, uint32_t pos, int k)
+{
+    lv_cigar_here(ref, w, tab, strand, L, pos, k);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1820,8 +1877,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
                 if (lanes_ok) { const uint32_t ev = cand_e[i]; e = (ev != 255 && (int)ev <= maxd) ? (int)ev : -1; }
                 else if (!(pos > ix.ref_len || pos + L + 4 > ix.ref_len)) {   // ed_diff guard (editdistance.c:178)
                     lv_unpack(ix.ref, w, strand, L, pos);
-                    int dd;
-                    e = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, maxd, nullptr, dd);
+                    e = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, maxd, LvTabRef{ nullptr, nullptr }).e;
                     WSYNC();
                 }
                 ++c_lv;
@@ -1880,7 +1936,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
     // ---- CIGARs (query_gen_cigar query.c:282-296; XA cigars sam.c:216-225) ----
     if (q_pos != 0xFFFFFFFFu) {
         if (q_gap) {
-            lv_cigar(ix.ref, w, lvtab, (int)q_strand, L, q_pos, (int)q_ndiff);
+            lv_cigar(ix.ref, w, lv_tab(lvtab), (int)q_strand, L, q_pos, (int)q_ndiff);
             if (lane < (uint32_t)w.n_cig) out->cigar[lane] = w.cig[lane];
             if (lane == 0) out->n_cigar = (uint8_t)w.n_cig;
         } else if (lane == 0) { out->cigar[0] = (uint16_t)((L << 4) | 0u); out->n_cigar = 1; }
@@ -1891,7 +1947,7 @@ __device__ __forceinline__ void align_general(const IndexView ix, const AlignPar
             uint32_t h = sel_idx[s][j];
             if (w.hit_gap[s][h]) {
                 WSYNC();
-                lv_cigar(ix.ref, w, lvtab, s, L, w.hit_pos[s][h], (int)w.hit_nd[s][h]);
+                lv_cigar(ix.ref, w, lv_tab(lvtab), s, L, w.hit_pos[s][h], (int)w.hit_nd[s][h]);
                 if (lane < (uint32_t)w.n_cig) out->hit_cigar[hidx][lane] = w.cig[lane];
                 if (lane == 0) out->hit_n_cigar[hidx] = (uint8_t)w.n_cig;
             } else if (lane == 0) out->hit_n_cigar[hidx] = 0;
@@ -1934,6 +1990,31 @@ __device__ __forceinline__ uint32_t pop_ranged(QueueRange *ranges, const uint32_
             if (k < hi - lo) return lo + k;
         }
         seg = (seg + 1u) & (QUEUE_RANGES - 1u); ++tried;
+    }
+    return 0xFFFFFFFFu;
+}
+// The same for a whole wave: every lane calls it and gets the wave's item.  With pop_ranged a block whose range has run dry looks at
+// the other 63 heads one after the other, a round trip each, before it takes an item elsewhere or leaves -- for the kernels with a
+// few items a block (k_gapfin: about three) that walk is most of their time.  Here lane l looks at range l's head, all of them in
+// one trip, whenever an add has come back dry; `live` keeps the ranges that had items left at that look (all of them at launch) and
+// lane 0 adds to the first of them at or behind seg.  A head only grows, so `live` only shrinks and the loop ends.  k_gapfin takes
+// its items this way (87.6 / 92.6 -> 72.4 / 78.6 us alone, profiles/r19); k_gap, four times the blocks, lost 11 us with it and keeps
+// pop_ranged.
+__device__ __forceinline__ uint32_t pop_ranged_wave(QueueRange *ranges, const uint32_t which, const uint32_t n_items, uint32_t &seg, uint64_t &live)
+{
+    static_assert(QUEUE_RANGES == 64, "a range a lane");
+    const uint32_t lane = lane_id();
+    const uint32_t my_size = (uint32_t)((uint64_t)n_items * (lane + 1u) / QUEUE_RANGES) - (uint32_t)((uint64_t)n_items * lane / QUEUE_RANGES);
+    while (live) {
+        const uint64_t rot = seg ? (live >> seg) | (live << (64u - seg)) : live;
+        const uint32_t s = (seg + (uint32_t)__builtin_ctzll(rot)) & (QUEUE_RANGES - 1u);
+        const uint32_t lo = (uint32_t)((uint64_t)n_items * s / QUEUE_RANGES), hi = (uint32_t)((uint64_t)n_items * (s + 1u) / QUEUE_RANGES);
+        uint32_t k = 0;
+        if (lane == 0) k = atomicAdd(&ranges[s].heads[which], 1u);
+        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+        seg = s;
+        if (k < hi - lo) return lo + k;
+        live = __ballot(__hip_atomic_load(&ranges[lane].heads[which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < my_size);
     }
     return 0xFFFFFFFFu;
 }
@@ -2047,36 +2128,48 @@ k_gap(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, GapBufs g)
 // replayed by ballots over the stored distances, strand 0 then 1 with the bound carried over; then
 // query_set_hits / gen_mapq (query.c:270-333) and the result row; every LV traceback becomes a k_cigar item.
 struct FinLds { uint32_t hit_pos[2][NHIT]; uint8_t hit_nd[2][NHIT]; };
-__global__ void __launch_bounds__(64)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))      // 128 VGPRs: 16 one-wave blocks a CU, as the kernels beside it
 k_gapfin(IndexView ix, AlignParams ap, const uint32_t *__restrict__ pm, salt_result_t *__restrict__ results, GapBufs g,
          unsigned long long *__restrict__ ctr)
 {
     __shared__ FinLds w;
-    __shared__ uint32_t s_item;
     const uint32_t lane = lane_id();
-    const uint64_t lt = (1ull << lane) - 1ull;
     const uint32_t n_items = g.gctl->gap_slots < g.cap ? g.gctl->gap_slots : g.cap;
-    uint32_t seg = blockIdx.x & (QUEUE_RANGES - 1u), tried = 0;
+    uint32_t seg = blockIdx.x & (QUEUE_RANGES - 1u);
+    uint64_t live = ~0ull;
     for (;;) {
-        if (threadIdx.x == 0) s_item = pop_ranged(g.ranges, QueueRange::GAPFIN, n_items, seg, tried);
-        WSYNC();
-        const uint32_t slot = s_item;
-        WSYNC();
+        const uint32_t slot = pop_ranged_wave(g.ranges, QueueRange::GAPFIN, n_items, seg, live);
         if (slot == 0xFFFFFFFFu) break;
         const uint64_t rt0 = ctr ? __builtin_amdgcn_s_memrealtime() : 0;
-        const uint32_t r = g.gq[slot];
+        // An item is a chain of loads, not work: the slot's read and both strands' list heads are asked for together, then the read's
+        // length and the first GAPFIN_B trips of BOTH lists (strand 1's addresses do not depend on the bound strand 0 leaves, only its
+        // filter does), and the rule takes the rest of a list two batches at a time (list_trips).
+        // (Everything about the item is the wave's, not the lane's: said so, the lists' addresses are scalar and a batch's 2 B loads
+        // take one lane offset between them.)
+        auto uni = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+        const uint32_t r_v = g.gq[slot];
+        const uint2 n2 = *reinterpret_cast<const uint2 *>(g.gn + 2 * slot), off2 = *reinterpret_cast<const uint2 *>(g.goff + 2 * slot);
+        const uint32_t r = uni(r_v);
         if (r == 0xFFFFFFFFu) continue;                                   // the pool was full: k_heavy finished this read itself
-        const uint32_t L = pm[(uint64_t)r * ap.pg.pm_stride + 2 * ap.pg.nw8];
+        const uint32_t L_v = pm[(uint64_t)r * ap.pg.pm_stride + 2 * ap.pg.nw8];
+        const uint32_t n_s[2] = { uni(n2.x), uni(n2.y) };
+        const size_t row_s[2] = { uni(off2.x), uni(off2.y) };
+        RowBatch<GAPFIN_B> first[2];
+#pragma unroll
+        for (int strand = 0; strand < 2; ++strand)
+            if (n_s[strand]) rows_fetch<GAPFIN_B>(first[strand], g.gloci + row_s[strand], g.ge + row_s[strand], n_s[strand], 0u);
+        const uint32_t L = uni(L_v);
         salt_result_t *out = results + r;
         uint32_t q_pos = 0xFFFFFFFFu, q_strand = 3, q_ndiff = 255, q_gap = 255;
         uint32_t bound = ap.pe ? 3u : L / 10;                             // alnse.c:1090 (SE) / alnse.c:1016-1028 (PE keeps 3)
         uint32_t n_hits_s[2] = { 0, 0 }, a0[2] = { 0, 0 };
+#pragma unroll
         for (int strand = 0; strand < 2; ++strand) {
-            const uint32_t n = g.gn[2 * slot + strand];
-            const size_t row = g.goff[2 * slot + strand];
+            const uint32_t n = n_s[strand];
+            const size_t row = row_s[strand];
             bool any = false; uint32_t bp = 0, bv = 0;
-            rule_unsorted<LLV_K, true>(g.gloci + row, g.ge + row, n, L, ix.ref_len, bound, any, bp, bv, n_hits_s[strand], a0[strand],
-                                       w.hit_pos[strand], w.hit_nd[strand]);
+            rule_unsorted<LLV_K, true, GAPFIN_B>(g.gloci + row, g.ge + row, n, L, ix.ref_len, bound, any, bp, bv, n_hits_s[strand], a0[strand],
+                                                 w.hit_pos[strand], w.hit_nd[strand], &first[strand]);
             if (any) { q_pos = bp; q_ndiff = bv; q_gap = 1; q_strand = (uint32_t)strand; }
         }
         WSYNC();
@@ -2130,6 +2223,7 @@ k_cigar(IndexView ix, PackGeom pg, const uint32_t *__restrict__ pm, salt_result_
         LvTables *__restrict__ lvtab)
 {
     __shared__ WaveLdsCigar w;
+    __shared__ LvTablesLds tl;                                          // the tables of a traceback at k <= LLV_K; a larger k takes the block's global table
     __shared__ uint32_t s_item;
     const uint32_t lane = lane_id();
     const uint32_t n_items = *count < cap_items ? *count : cap_items;
@@ -2155,7 +2249,7 @@ k_cigar(IndexView ix, PackGeom pg, const uint32_t *__restrict__ pm, salt_result_
         }
         for (uint32_t t = lane; t < (L + 7) >> 3; t += 64) w.pm[strand][t] = rec[strand * ap.pg.nw8 + t];
         WSYNC();
-        lv_cigar(ix.ref, w, lvtab + blockIdx.x, (int)strand, L, pos, (int)k);
+        lv_cigar_here(ix.ref, w, k <= (uint32_t)LLV_K ? lv_tab(tl) : lv_tab(lvtab + blockIdx.x), (int)strand, L, pos, (int)k);
         uint16_t *dst = which == 0 ? out->cigar : out->hit_cigar[which - 1];
         if (lane < (uint32_t)w.n_cig) dst[lane] = w.cig[lane];
         if (lane == 0) { if (which == 0) out->n_cigar = (uint8_t)w.n_cig; else out->hit_n_cigar[which - 1] = (uint8_t)w.n_cig; }
@@ -2640,7 +2734,8 @@ size_t queue_words(uint32_t max_reads) { return (size_t)max_reads * 2 + (size_t)
 // best_v, n_hits, a0, bound_out, then NHIT x (hit_pos, hit_nd).  mode 0: rule_unsorted<3, false>, 1: rule_sparse<3, false>,
 // 2: rule_unsorted<LLV_K, true>, 3: rule_sparse<3, false, 32> as k_light2 runs it -- two cases per wave, 2b and 2b + 1 in the halves
 // of block b, each half with its own hit arrays, 4: rule_sparse<3, false, 16> as k_light4 runs it -- four cases per wave, 4b .. 4b + 3
-// in the quarters of block b, each quarter with its own hit arrays
+// in the quarters of block b, each quarter with its own hit arrays, 5: rule_unsorted<LLV_K, true, GAPFIN_B> as k_gapfin runs it on a
+// list in global memory, the first batch of rows asked for ahead of the call
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
 k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *__restrict__ val, const uint32_t *__restrict__ offs,
@@ -2662,6 +2757,11 @@ k_diag_rule(uint32_t n_cases, const uint32_t *__restrict__ pos, const uint8_t *_
     else if (mode == 1) rule_sparse<3, false>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else if (mode == 3) rule_sparse<3, false, 32>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     else if (mode == 4) rule_sparse<3, false, 16>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
+    else if (mode == 5) {
+        RowBatch<GAPFIN_B> first;
+        if (n) rows_fetch<GAPFIN_B>(first, pos + o, val + o, n, 0u);
+        rule_unsorted<LLV_K, true, GAPFIN_B>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd, &first);
+    }
     else rule_unsorted<LLV_K, true>(pos + o, val + o, n, L, ref_len, bound, any, bp, bv, nh, a0, hit_pos, hit_nd);
     WSYNC();
     uint32_t *w = out + (size_t)c * (6 + 2 * NHIT);
@@ -2691,9 +2791,10 @@ __global__ void __launch_bounds__(64)
 k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ kdiff,
           const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs, const uint32_t *__restrict__ lane_first,
           const uint32_t *__restrict__ lane_n, const uint32_t *__restrict__ lane_case, int32_t *__restrict__ out /* [n][4] */,
-          uint16_t *__restrict__ cig_out /* [n][64] */, LvTables *__restrict__ lvtab)
+          uint16_t *__restrict__ cig_out /* [n][64] */, LvTables *__restrict__ lvtab, int lds_tab)
 {
     __shared__ WaveLds w;
+    __shared__ LvTablesLds tl;                                             // lds_tab: lv_cigar's tables as k_cigar places them
     __shared__ uint32_t lane_pm[LLV_N][LLV_PW];
     const uint32_t c = blockIdx.x, lane = lane_id();
     if (c >= n_cases) return;
@@ -2715,8 +2816,7 @@ k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, cons
     const int k = (int)kdiff[c];
     if (in_range) {
         lv_unpack(ix.ref, w, 0, L, p);
-        int dd;
-        e_wave = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, k, nullptr, dd);
+        e_wave = lv_wave(w.u.lvb.T, (int)L + 4, w.u.lvb.P, (int)L, k, LvTabRef{ nullptr, nullptr }).e;
         WSYNC();
     }
     const bool fit = lv_fit_dev(L, (uint32_t)k);
@@ -2732,7 +2832,7 @@ k_diag_lv(IndexView ix, uint32_t n_cases, const uint32_t *__restrict__ pos, cons
         WSYNC();
     }
     if (in_range && e_wave >= 0 && e_wave < LVK) {
-        lv_cigar(ix.ref, w, lvtab + blockIdx.x, 0, L, p, e_wave);
+        lv_cigar(ix.ref, w, lds_tab && e_wave <= LLV_K ? lv_tab(tl) : lv_tab(lvtab + blockIdx.x), 0, L, p, e_wave);
         n_cig = w.n_cig;
         if (lane < (uint32_t)w.n_cig) cig_out[(size_t)c * SALT_MAX_CIGAR_OPS + lane] = w.cig[lane];
     }
@@ -2746,10 +2846,10 @@ size_t lv_table_bytes() { return sizeof(LvTables); }
 
 void launch_diag_lv(const IndexView &ix, uint32_t n, const uint32_t *pos, const uint32_t *kdiff, const uint8_t *seqs,
                     const uint32_t *offs, const uint32_t *lane_first, const uint32_t *lane_n, const uint32_t *lane_case,
-                    int32_t *out, uint16_t *cig, void *lvtab, hipStream_t st)
+                    int32_t *out, uint16_t *cig, void *lvtab, int lds_tab, hipStream_t st)
 {
     if (n) hipLaunchKernelGGL(k_diag_lv, dim3(n), dim3(64), 0, st, ix, n, pos, kdiff, seqs, offs, lane_first, lane_n, lane_case, out, cig,
-                              static_cast<LvTables *>(lvtab));
+                              static_cast<LvTables *>(lvtab), lds_tab);
 }
 
 // k_diag_verify: unit access to the candidate verifiers (tests only).  One wave per case: the read seqs[offs[c]..offs[c+1]) against
@@ -2838,9 +2938,9 @@ k_polish(const uint8_t *__restrict__ pac, const uint8_t *__restrict__ codes, con
             s.T[i] = tv;
         }
         WSYNC();
-        int d_fin = 0;
         LvTables *tab = want_cigar ? tabs + blockIdx.x : nullptr;
-        const int e = lv_wave(s.T, (int)tl, s.P, (int)L, (int)x.k, tab, d_fin);
+        const LvEnd fin = lv_wave(s.T, (int)tl, s.P, (int)L, (int)x.k, lv_tab(tab));
+        const int e = fin.e, d_fin = fin.d_fin;
         if (lane == 0) dist[it] = e;
         if (want_cigar) {
             __threadfence_block();
@@ -2923,7 +3023,7 @@ uint32_t heavy_blocks_per_cu()
 
 void launch_heavy(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint4 *sai_c,
                   const uint4 *sai_r, salt_result_t *results, const uint32_t *queue, unsigned long long *ctr,
-                  uint32_t n_blocks, uint32_t gap_blocks, void *lvtab, const GapBufs &g_in, uint32_t *ovq, QueueRange *ranges, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st)
+                  uint32_t n_blocks, uint32_t gap_blocks, uint32_t cigar_blocks, void *lvtab, const GapBufs &g_in, uint32_t *ovq, QueueRange *ranges, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st)
 {
     if (!ap.n_reads) { if (ev3) for (int i = 0; i < 3; ++i) hipEventRecord(ev3[i], st); return; }
     uint32_t blocks = n_blocks < ap.n_reads ? n_blocks : ap.n_reads;
@@ -2949,13 +3049,19 @@ void launch_heavy(const IndexView &ix, const AlignParams &ap, const uint32_t *pm
     else     hipLaunchKernelGGL(k_heavy_big, dim3(big_blocks), dim3(64), 0, st, ix, ap, pm, sai_c, sai_r, results, queue, ctr, tab, g, pe_scr, small ? 1 : 0);
     if (ev3) hipEventRecord(ev3[0], st);
     if (!g.cap) { if (ev3) { hipEventRecord(ev3[1], st); hipEventRecord(ev3[2], st); } return; }
-    // the deferred gapped passes: distances by (read, strand, 32 candidates), one finishing wave per read, one traceback per wave
-    // grids: k_gap has many ~70 us items and wants every wave; the other two have few, short items and start faster on fewer blocks
+    // the deferred gapped passes: distances by (read, strand, 64 candidates), one finishing wave per read, one traceback per wave.
+    // Grids (the workspace sets them): k_gap has many ~70 us items and wants every wave.  k_gapfin: a quarter of k_heavy's grid, about
+    // three reads a block on the flagship step; two and four times the waves did not move it (its time is its longest block, not its
+    // throughput).  k_cigar: cigar_blocks <= n_blocks (lvtab has n_blocks tables), by default all of them, 9.6 KB of LDS a block with
+    // the traceback tables, 16 blocks a CU: a block's first item is its own index and costs no atomic (sw_pull), so with more blocks
+    // than items nobody touches the queue head and nobody runs a second traceback (profiles/r19: 26 us alone against 84 on half the
+    // blocks, where every block went through the head after its first item).
+    if (cigar_blocks == 0 || cigar_blocks > n_blocks) cigar_blocks = n_blocks;
     hipLaunchKernelGGL(k_gap, dim3(gap_blocks), dim3(64), 0, st, ix, ap, pm, g);
     if (ev3) hipEventRecord(ev3[1], st);
     hipLaunchKernelGGL(k_gapfin, dim3((n_blocks + 3) / 4), dim3(64), 0, st, ix, ap, pm, results, g, ctr);
     if (ev3) hipEventRecord(ev3[2], st);
-    hipLaunchKernelGGL(k_cigar, dim3((n_blocks + 1) / 2), dim3(64), 0, st, ix, ap.pg, pm, results, g.cq, &g.gctl->cigar_items, &g.gctl->cigar_head, g.cap * (1u + SALT_MAX_HITS), tab);
+    hipLaunchKernelGGL(k_cigar, dim3(cigar_blocks), dim3(64), 0, st, ix, ap.pg, pm, results, g.cq, &g.gctl->cigar_items, &g.gctl->cigar_head, g.cap * (1u + SALT_MAX_HITS), tab);
 }
 
 GapBufs gap_bufs_layout(uint8_t *base, uint32_t cap, SeCtl *gctl, size_t *bytes)

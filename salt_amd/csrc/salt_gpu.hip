@@ -119,7 +119,7 @@ struct salt_gpu_ws {
     DevBuf<uint8_t> d_text; uint64_t text_bytes = 0;
     std::vector<unsigned long long> h_zoff; std::vector<uint32_t> h_zstat;
     uint32_t text_calls = 0;                                                 // SALT_TEXT_TRACE: stage clocks of the first text call
-    uint32_t heavy_blocks = 2048, gap_blocks = 2048;
+    uint32_t heavy_blocks = 2048, gap_blocks = 2048, cigar_blocks = 2048;
     QueueRange *d_ranges = nullptr;                                           // k_heavy's queue ranges: k_light's push counters, the heads
     // d_qctl, d_ranges and d_wq_cnt are blocks of ONE allocation, every block 256-byte aligned: one memset per call zeroes them all
     DevBuf<uint8_t> d_zero;
@@ -419,6 +419,11 @@ extern "C" int salt_gpu_ws_create(salt_gpu_index_t *ix, uint32_t max_reads, uint
         uint32_t gap_per_cu = 16;
         if (const char *e2 = getenv("SALT_GPU_GAP_PER_CU")) { int v = atoi(e2); if (v > 0 && v <= 16) gap_per_cu = (uint32_t)v; }
         ws->gap_blocks = (uint32_t)prop.multiProcessorCount * gap_per_cu;
+        // k_cigar behind k_gapfin: k_heavy's grid (it takes a block's traceback table from the same d_lvtab).  A block's first item is its own
+        // index and costs no atomic, so with more blocks than items (2 805 per 10^6 GRCh38-scale reads) nobody touches the queue head and
+        // nobody runs a second traceback: 26 us alone on 3 072 or 4 096 blocks against 84 on the 2 048 it had (profiles/r19)
+        ws->cigar_blocks = ws->heavy_blocks;
+        if (const char *e2 = getenv("SALT_GPU_CIGAR_BLOCKS")) { int v = atoi(e2); if (v > 0 && (uint32_t)v < ws->heavy_blocks) ws->cigar_blocks = (uint32_t)v; }      // measurements and tests: fewer blocks than items
         // k_seed_walk: 2 waves per SIMD in blocks of four waves.  Its lanes are all busy, so the grid is set by the four-stream step and not by
         // the kernel alone: 2 per CU 464 - 467 Mreads/s, 4 per CU 445 - 459, 8 per CU 450 - 458 (profiles/r07/ab_grid_and_order.log).  Measured again
         // with the walk that starts from its record (one turn less): 2 per CU 470 - 479, 3 per CU 469 - 479, 4 per CU 468 - 471; no range lies
@@ -609,7 +614,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                      static_cast<salt_result_t *>(d_results), ws->d_queue, ws->d_qctl, ws->d_queue + 2 * (size_t)ws->max_reads, ws->d_ranges, ctr, st);
     if (timed) HIPCHK(hipEventRecord(ev[3], st));
     launch_heavy(ws->ix->view, ap, ws->d_pm, ws->d_sai_c, ws->d_sai_r,
-                 static_cast<salt_result_t *>(d_results), ws->d_queue, ctr, ws->heavy_blocks, ws->gap_blocks, ws->d_lvtab,
+                 static_cast<salt_result_t *>(d_results), ws->d_queue, ctr, ws->heavy_blocks, ws->gap_blocks, ws->cigar_blocks, ws->d_lvtab,
                  gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr.p : nullptr, timed ? ev + 4 : nullptr, st);
     if (timed) { HIPCHK(hipEventRecord(ev[7], st)); ws->ev_pe[ws->n_timed] = 0; ++ws->n_timed; }
     HIPCHK(hipGetLastError());
@@ -1518,6 +1523,12 @@ extern "C" int salt_gpu_diag_lv(const uint32_t *ref_words, uint32_t ref_len, uin
                                 const uint32_t *kdiff, const uint8_t *seqs, const uint32_t *offs, int32_t *out4,
                                 uint16_t *cigars)
 {
+    return salt_gpu_diag_lv_tab(ref_words, ref_len, n_cases, pos, kdiff, seqs, offs, out4, cigars, 0);
+}
+extern "C" int salt_gpu_diag_lv_tab(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint32_t *pos,
+                                    const uint32_t *kdiff, const uint8_t *seqs, const uint32_t *offs, int32_t *out4,
+                                    uint16_t *cigars, int lds_tab)
+{
     if (!ref_words || !pos || !kdiff || !seqs || !offs || !out4 || !cigars) return fail(SALT_E_INVAL, "null argument");
     int n_dev = 0;
     HIPCHK(hipGetDeviceCount(&n_dev));
@@ -1561,7 +1572,7 @@ extern "C" int salt_gpu_diag_lv(const uint32_t *ref_words, uint32_t ref_len, uin
     HIPCHK(hipMalloc((void **)&d_lf, lane_first.size() * 4)); HIPCHK(hipMemcpy(d_lf, lane_first.data(), lane_first.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMalloc((void **)&d_ln, lane_n.size() * 4)); HIPCHK(hipMemcpy(d_ln, lane_n.data(), lane_n.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMalloc((void **)&d_lc, lane_case.size() * 4)); HIPCHK(hipMemcpy(d_lc, lane_case.data(), lane_case.size() * 4, hipMemcpyHostToDevice));
-    launch_diag_lv(v, n_cases, d_pos, d_k, d_seqs, d_offs, d_lf, d_ln, d_lc, d_out, d_cig, d_tab, nullptr);
+    launch_diag_lv(v, n_cases, d_pos, d_k, d_seqs, d_offs, d_lf, d_ln, d_lc, d_out, d_cig, d_tab, lds_tab, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out4, d_out, (uint64_t)n_cases * 16, hipMemcpyDeviceToHost));

@@ -119,7 +119,7 @@ struct GapBufs {
 GapBufs gap_bufs_layout(uint8_t *base, uint32_t cap, SeCtl *gctl, size_t *bytes);   // base = nullptr: size only
 void launch_heavy(const IndexView &ix, const AlignParams &ap, const uint32_t *pm, const uint4 *sai_c,
                   const uint4 *sai_r, salt_result_t *results, const uint32_t *queue, unsigned long long *ctr,
-                  uint32_t n_blocks, uint32_t gap_blocks, void *lvtab, const GapBufs &g, uint32_t *ovq, QueueRange *ranges, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st);
+                  uint32_t n_blocks, uint32_t gap_blocks, uint32_t cigar_blocks, void *lvtab, const GapBufs &g, uint32_t *ovq, QueueRange *ranges, uint8_t *pe_scr, hipEvent_t *ev3, hipStream_t st);
 size_t lv_table_bytes();                // per-block LV traceback table (global memory)
 
 // ---- paired end (salt_pe.hip) ----
@@ -176,7 +176,7 @@ void launch_diag_verify(const uint32_t *ref, uint32_t ref_len, uint32_t n_cases,
 // lane_first / lane_n / lane_case: which cases the block of case c hands to the one-candidate-per-lane kernel (k_diag_lv)
 void launch_diag_lv(const IndexView &ix, uint32_t n, const uint32_t *pos, const uint32_t *kdiff, const uint8_t *seqs,
                     const uint32_t *offs, const uint32_t *lane_first, const uint32_t *lane_n, const uint32_t *lane_case,
-                    int32_t *out, uint16_t *cig, void *lvtab, hipStream_t st);
+                    int32_t *out, uint16_t *cig, void *lvtab, int lds_tab, hipStream_t st);
 bool lv_lanes_fit(uint32_t L, uint32_t k);          // within the lane kernel's limits (LLV_K, LLV_TW)
 
 // ---- FASTQ text in, SAM text out (salt_text.hip) ----
