@@ -14,6 +14,7 @@
 #include <type_traits>
 #include "salt_device.h"
 #include "salt_kernels.h"
+#include "salt_sai_sort.h"
 
 namespace salt {
 
@@ -703,68 +704,62 @@ typedef WaveLdsT<SLOTS, true> WaveLds;                      // any read the ABI 
 typedef WaveLdsT<32, false> WaveLdsSmall;                   // <= 32 seed slots per strand; a gapped read without a k_gap slot goes to the overflow queue
 typedef WaveLdsT<1, false> WaveLdsCigar;                    // k_cigar: the read, the byte strings of one traceback, the CIGAR
 
-// ---- klib introsort replica on the (sp,ep,off) triple arrays (ksort.h:159-228) ------------------
-struct Sai { uint32_t sp, ep, off; };
-__device__ __forceinline__ Sai sai_get(const SaiLists &s, int w, int i) { return Sai{ s.sp[w][i], s.ep[w][i], s.off[w][i] }; }
-__device__ __forceinline__ void sai_set(SaiLists &s, int w, int i, Sai v) { s.sp[w][i] = v.sp; s.ep[w][i] = v.ep; s.off[w][i] = v.off; }
-__device__ __forceinline__ bool sai_ltv(Sai a, Sai b) { return a.ep - a.sp < b.ep - b.sp; }       // alnse.c:35
-__device__ __forceinline__ bool sai_lt(const SaiLists &s, int w, int i, int j) { return sai_ltv(sai_get(s, w, i), sai_get(s, w, j)); }
-__device__ __forceinline__ void sai_swap(SaiLists &s, int w, int i, int j) { Sai a = sai_get(s, w, i), b = sai_get(s, w, j); sai_set(s, w, i, b); sai_set(s, w, j, a); }
-
-__device__ void sai_insertsort(SaiLists &s, int w, int lo, int hi)
-{
-    for (int i = lo + 1; i < hi; ++i)
-        for (int j = i; j > lo && sai_lt(s, w, j, j - 1); --j) sai_swap(s, w, j, j - 1);
-}
-
-__device__ void sai_combsort(SaiLists &s, int w, int base, int n)
-{
-    const double shrink = 1.2473309501039786540366528676643;
-    int gap = n; bool do_swap;
-    do {
-        if (gap > 2) { gap = (int)(gap / shrink); if (gap == 9 || gap == 10) gap = 11; }
-        do_swap = false;
-        for (int i = 0; i < n - gap; ++i)
-            if (sai_lt(s, w, base + i + gap, base + i)) { sai_swap(s, w, base + i, base + i + gap); do_swap = true; }
-    } while (do_swap || gap > 2);
-    if (gap != 1) sai_insertsort(s, w, base, base + n);
-}
-
-__device__ __attribute__((noinline)) void sai_introsort(SaiLists &s, int w, int n)
-{
-    if (n < 1) return;
-    if (n == 2) { if (sai_lt(s, w, 1, 0)) sai_swap(s, w, 0, 1); return; }
-    int d; for (d = 2; (1 << d) < n; ++d) { }
-    d <<= 1;
-    int st_l[24], st_r[24], st_d[24], top = 0;
-    int lo = 0, hi = n - 1;
-    for (;;) {
-        if (lo < hi) {
-            if (--d == 0) { sai_combsort(s, w, lo, hi - lo + 1); hi = lo; continue; }
-            int i = lo, j = hi, k = i + ((j - i) >> 1) + 1;
-            if (sai_lt(s, w, k, i)) { if (sai_lt(s, w, k, j)) k = j; }
-            else k = sai_lt(s, w, j, i) ? i : j;
-            Sai rp = sai_get(s, w, k);
-            if (k != hi) sai_swap(s, w, k, hi);
-            for (;;) {
-                do ++i; while (sai_ltv(sai_get(s, w, i), rp));
-                do --j; while (i <= j && sai_ltv(rp, sai_get(s, w, j)));
-                if (j <= i) break;
-                sai_swap(s, w, i, j);
-            }
-            sai_swap(s, w, i, hi);
-            if (i - lo > hi - i) {
-                if (i - lo > 16 && top < 24) { st_l[top] = lo; st_r[top] = i - 1; st_d[top] = d; ++top; }
-                lo = hi - i > 16 ? i + 1 : hi;
-            } else {
-                if (hi - i > 16 && top < 24) { st_l[top] = i + 1; st_r[top] = hi; st_d[top] = d; ++top; }
-                hi = i - lo > 16 ? i - 1 : lo;
-            }
-        } else {
-            if (top == 0) { sai_insertsort(s, w, 0, n); return; }
-            --top; lo = st_l[top]; hi = st_r[top]; d = st_d[top];
-        }
+// ---- klib introsort replica (salt_sai_sort.h) on a read's seed lists ----------------------------------
+// The triples where they lie, list w: one lane runs the sort, every compare four dependent LDS loads and every swap twelve LDS
+// accesses.  For lists of more than 64 seeds (the big shapes).
+struct SaiLdsSort {
+    SaiLists &s; const int w;
+    uint32_t st[SAI_STACK];                                  // a postponed range a word: lo, hi < 2^12 (SLOTS seeds), the depth above them
+    __device__ __forceinline__ SaiLdsSort(SaiLists &s_, int w_) : s(s_), w(w_) {}
+    __device__ __forceinline__ uint32_t key(int i) const { return s.ep[w][i] - s.sp[w][i]; }       // alnse.c:35
+    __device__ __forceinline__ void swap(int i, int j)
+    {
+        const uint32_t a0 = s.sp[w][i], a1 = s.ep[w][i], a2 = s.off[w][i], b0 = s.sp[w][j], b1 = s.ep[w][j], b2 = s.off[w][j];
+        s.sp[w][i] = b0; s.ep[w][i] = b1; s.off[w][i] = b2; s.sp[w][j] = a0; s.ep[w][j] = a1; s.off[w][j] = a2;
     }
+    __device__ __forceinline__ void push(int top, int lo, int hi, int d) { st[top] = (uint32_t)lo | ((uint32_t)hi << 12) | ((uint32_t)d << 24); }
+    __device__ __forceinline__ void pop(int top, int &lo, int &hi, int &d) const { const uint32_t v = st[top]; lo = (int)(v & 4095u); hi = (int)((v >> 12) & 4095u); d = (int)(v >> 24); }
+};
+static_assert(SLOTS <= 4096, "a seed index in 12 bits");
+__device__ __attribute__((noinline)) void sai_introsort_lds(SaiLists &s, int w, int n) { SaiLdsSort a(s, w); sai_introsort(a, n); }
+
+// A list of up to 64 seeds, element e in lane e: its key (ep - sp) and where it came from.  Every index the sort asks for is the
+// same in all lanes, so a key is a v_readlane, a swap four of them and two selects, the stack a register as well (entry t in lane
+// t), and a step costs a few cycles where the LDS form waits for its loads; all 64 lanes run it, control flow is wave-uniform.
+// What comes out is the permutation: ix of lane e = the element that belongs at place e.
+struct SaiLaneSort {
+    uint32_t k, ix, stk;
+    __device__ __forceinline__ uint32_t key(int i) const { return (uint32_t)__builtin_amdgcn_readlane((int)k, i); }
+    __device__ __forceinline__ void swap(int i, int j)
+    {
+        const uint32_t ki = (uint32_t)__builtin_amdgcn_readlane((int)k, i), kj = (uint32_t)__builtin_amdgcn_readlane((int)k, j);
+        const uint32_t xi = (uint32_t)__builtin_amdgcn_readlane((int)ix, i), xj = (uint32_t)__builtin_amdgcn_readlane((int)ix, j);
+        const int lane = (int)lane_id();
+        if (lane == i) { k = kj; ix = xj; }
+        if (lane == j) { k = ki; ix = xi; }                    // (i == j: back to what it was)
+    }
+    __device__ __forceinline__ void push(int top, int lo, int hi, int d) { if ((int)lane_id() == top) stk = (uint32_t)lo | ((uint32_t)hi << 8) | ((uint32_t)d << 16); }
+    __device__ __forceinline__ void pop(int top, int &lo, int &hi, int &d) const
+    {
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)stk, top);
+        lo = (int)(v & 255u); hi = (int)((v >> 8) & 255u); d = (int)(v >> 16);
+    }
+};
+static_assert(SAI_STACK <= 64, "a stack entry a lane");
+// All 64 lanes call it (n <= 64, the same in all): sorts the list's keys in lanes, then moves the triples in one step.
+typedef uint32_t __attribute__((address_space(3))) *lds_u32w;
+__device__ __attribute__((noinline)) void sai_introsort_lanes(lds_u32w sp, lds_u32w ep, lds_u32w off, int n_)
+{
+    const int n = __builtin_amdgcn_readfirstlane(n_);         // an argument arrives in a VGPR: tell the compiler that every index and branch below is uniform
+    if (n < 2) return;
+    const int lane = (int)lane_id();
+    SaiLaneSort a;
+    a.k = lane < n ? ep[lane] - sp[lane] : 0u; a.ix = (uint32_t)lane; a.stk = 0;
+    sai_introsort(a, n);
+    uint32_t v0 = 0, v1 = 0, v2 = 0;
+    if (lane < n) { v0 = sp[a.ix]; v1 = ep[a.ix]; v2 = off[a.ix]; }
+    WSYNC();
+    if (lane < n) { sp[lane] = v0; ep[lane] = v1; off[lane] = v2; }
 }
 
 // ---- wave-wide bitonic sort of loci[0..n) in LDS (ks_introsort(uint32_t): any total sort) --------
@@ -891,8 +886,14 @@ __device__ __attribute__((noinline)) CandStats build_candidates(W &w)      // A 
     WSYNC();
     // The reference orders both lists by interval size (alnse.c:307-308, klib introsort).  The order only decides WHICH
     // rows are located before a cap stops the loops; when every row is located the loci are the same set, and they
-    // are sorted right after -- so the (serial) replica of the sort runs only when the cap can bite.
-    if (rows > cap_total && lane < 2) { SaiLists sl = sai_ref(w.u.sai); sai_introsort(sl, (int)lane, (int)n_list[lane]); }
+    // are sorted right after -- so the replica of the sort runs only when the cap can bite.
+    if (rows > cap_total) {
+        if (W::N_SLOTS <= 64 || (n_list[0] <= 64u && n_list[1] <= 64u)) {     // in lanes: the C list, then the R list (the usual shape has no other form)
+#pragma unroll
+            for (int which = 0; which < 2; ++which)
+                sai_introsort_lanes((lds_u32w)w.u.sai.sp[which], (lds_u32w)w.u.sai.ep[which], (lds_u32w)w.u.sai.off[which], (int)n_list[which]);
+        } else if (lane < 2) { SaiLists sl = sai_ref(w.u.sai); sai_introsort_lds(sl, (int)lane, (int)n_list[lane]); }
+    }
     // a PE mate may enumerate 0x40000 loci, which need the global scratch; the usual few hundred stay in LDS like an SE read's (the
     // verify and rule passes then pay one memory round trip per trip instead of two or three)
     const bool pe_in_lds = !glob || rows <= (uint32_t)MAXLOC;
