@@ -194,6 +194,7 @@ int  salt_gpu_ws_pe_counts(salt_gpu_ws_t *ws, uint32_t out[8]);
  *   salt_gpu_index_snp_enable  the first enable builds the site table and zeroes the counts (SALT_E_NOMEM names the size when there is no
  *                              room); on = 0 stops counting and keeps both; min_mapq 0 .. 255.  Call with no align call in flight.
  *   salt_gpu_index_snp_sites   *n_sites, and when pos is given (cap >= *n_sites entries) the sites' genome positions, ascending
+ *                              (also once salt_gpu_index_gt_enable has built the table)
  *   salt_gpu_index_snp_counts  synchronises the device; counts may be NULL (reset only); cap_words >= 4 * n_sites.  No align call in flight.
  *   salt_gpu_ws_snp_uncount    takes back what the workspace's LAST successful align call added (the call's buffers must be untouched
  *                              since): for a driver that discards a block it has aligned.  Nothing to take back: SALT_OK.
@@ -293,6 +294,65 @@ int  salt_gpu_index_errprof_enable(salt_gpu_index_t *ix, int on, uint32_t min_ma
 int  salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t rec[16], int reset);
 int  salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws);
 int  salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device);
+
+/* ---- genotypes at the index's SNP sites (`salt --genotype`) ---------------------------------------------------------------
+ * Sites, their numbering, which records contribute and the CIGAR walk are those of the SNP counts above: a record contributes iff it is
+ * mapped (pos != 0xFFFFFFFF), not skipped, and mapq >= min_mapq; only the primary alignment counts, never an alternative (XA) hit; an
+ * unmapped mate printed at its mate's position does not count.
+ * Events: every M column where g is a site and SEQ[s] is a base b in A C G T is one event (site, b, q).  The quality byte is that of the
+ * same sequenced base: it has the index of the code byte, rev ? L - 1 - s : s, in the FASTQ's order; q = byte - 33 when the byte is in
+ * 33 .. 126.  In every other case q = SALT_GT_Q_NONE = 20: no qualities on the call, a quality range that leaves the call's quality
+ * bytes, a byte outside 33 .. 126, SAM QUAL `*` in the host twin.
+ * Penalties: SALT_GT_TABLE[94][3] (salt_gt_table.h) holds uint32 { M, X, H } per q in units of 1 / 4096 Phred; the header states the formula.
+ * Sums: salt_gt_site_t, 128 bytes a site: per base A C G T { n, sm, sx, sh }, uint64.  An event adds 1, M[q], X[q], H[q] to its base's four
+ * words.  Integer sums: they do not depend on batch order, stream, workspace or GPU, nothing wraps, and the tables of several GPUs add
+ * word by word.
+ * Call, per site, from the sums, the site's mixRef mask and the 2-bit genome base r alone; flat priors, no floating point:
+ *   alleles      allele 0 = r; alleles 1 .. = the mask's other letters in A C G T order (the candidate set is mask + {r})
+ *   genotypes    the unordered pairs (i <= j) of allele indices in VCF order k = j (j + 1) / 2 + i: 3, 6 or 10 of them
+ *   raw          hom aa: sm[a] + sum of sx[c], c != a; het ab: sh[a] + sh[b] + sum of sx[c], c not in {a, b}; c runs over all four bases, so a
+ *                base outside the candidate set is an error under every genotype
+ *   PL_k         (raw_k - min_raw + 2048) >> 12, in 64 bits, uncapped
+ *   GT           the first genotype in VCF order with raw_k == min_raw;  GQ = min(99, the smallest PL among the other genotypes)
+ *   AD[i]        n[allele i];  DP = the sum of n over all four bases;  QUAL = the PL of genotype 0/0
+ * Record: "contig\tpos\t.\tREF\tALT[,ALT..]\tQUAL\t.\tDP=dp\tGT:AD:DP:GQ:PL\ta/b:ad,..:dp:gq:pl,..\n", pos 1-based and contig-relative, the
+ * contig the one that contains the site's global position (salt_gpu_index_set_contigs' table).  A site with DP == 0 prints QUAL `.` and the
+ * sample field "./.:0,..:0:.:." (one 0 per allele).  Every site is printed, in genome order.  The header is salt_gt_header's (salt_host.h).
+ * While the tally is on, every entry point that leaves result rows adds its batch behind the kernels that finish the rows, on the same
+ * stream (k_gt_add: four 64-bit atomics into one 32-byte sector per event), with the qualities of the error profile's sources: the text
+ * entry points' raw block, salt_gpu_ws_set_quals' bytes, or none.  The sums belong to the device index and are shared by its workspaces and
+ * forks; they lie outside the image (128 bytes a site: 1.9 GB at 14.8 M sites; there is no narrower mode).  The site table is the SNP
+ * counts' own, built by whichever of the two is enabled first.  With the tally off no kernel is launched; before the first enable nothing
+ * is allocated, and every other call below fails with SALT_E_INVAL "never enabled".
+ *   salt_gpu_index_gt_enable      the first enable builds the site table if need be and zeroes the sums (SALT_E_NOMEM names the size); on = 0
+ *                                 stops and keeps them; min_mapq 0 .. 255 (above: SALT_E_INVAL).  No align call in flight, like the rest.
+ *   salt_gpu_index_gt_reset       sums = 0
+ *   salt_gpu_index_gt_fetch       out[0 .. n) = sums[first_site .. first_site + n); synchronises the device
+ *   salt_gpu_index_gt_add         sums[first_site .. first_site + n) += in[0 .. n), by a kernel: how the tables of several GPUs are summed,
+ *                                 chunk by chunk, and how any sums can be put in front of the call kernels.  A range that leaves
+ *                                 [0, n_sites) is SALT_E_INVAL with the range in the message, for both.
+ *   salt_gpu_index_gt_text_begin  starts the records of the sums as they stand: tile_sites = sites called at a time, 0 = the default (the
+ *                                 text does not depend on it); bgzf != 0: whole BGZF blocks instead of text, deflated on the device,
+ *                                 without the end-of-file block.  Needs the contig table.  No header.
+ *   salt_gpu_index_gt_text_next   the next piece, in genome order: *data points into a buffer the index owns, valid until the next call on
+ *                                 the index; *n_bytes == 0: complete.  The sums are never written by these two: the text can be made
+ *                                 twice with the same bytes, and counting can go on afterwards.
+ *   salt_gpu_ws_gt_uncount        takes back what the workspace's LAST successful align call added (the same kernel with the negated
+ *                                 addends and that call's quality source).  Nothing to take back: SALT_OK. */
+#define SALT_GT_Q_NONE 20
+typedef struct { uint64_t n, sm, sx, sh; } salt_gt_base_t;
+typedef struct { salt_gt_base_t b[4]; } salt_gt_site_t;                     /* A C G T; 128 bytes */
+typedef struct {
+    uint32_t tile_sites;        /* 0: default */
+    int32_t  bgzf;              /* the pieces are BGZF blocks */
+} salt_gt_text_opt_t;
+int  salt_gpu_index_gt_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq);
+int  salt_gpu_index_gt_reset(salt_gpu_index_t *ix);
+int  salt_gpu_index_gt_fetch(salt_gpu_index_t *ix, uint64_t first_site, uint64_t n, salt_gt_site_t *out);
+int  salt_gpu_index_gt_add(salt_gpu_index_t *ix, uint64_t first_site, uint64_t n, const salt_gt_site_t *in);
+int  salt_gpu_index_gt_text_begin(salt_gpu_index_t *ix, const salt_gt_text_opt_t *opt);
+int  salt_gpu_index_gt_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes);
+int  salt_gpu_ws_gt_uncount(salt_gpu_ws_t *ws);
 
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,

@@ -124,6 +124,27 @@ int64_t salt_depth_text(const salt_index_t *ix, const uint32_t *diff, uint64_t n
 int64_t salt_errprof_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint64_t *cells, uint64_t n_cells, uint64_t rec[16]);
 int64_t salt_errprof_text(const uint64_t *cells, const uint64_t rec[16], uint32_t min_mapq, int full, char *out, uint64_t cap);
 
+/* Genotypes at the SNP sites (`salt --genotype`): the host twins of the device's k_gt_add and of its call and text kernels, and the one
+ * header of the file, written from the definition in salt_gpu.h; they share the penalty table (salt_gt_table.h) with the kernels and
+ * nothing else.  sites is salt_gt_site_t[n_sites], n_sites = salt_snp_sites' count (anything else is an error).
+ *   salt_gt_add_sam  sites += the events of the record lines of this program's own SAM text: a record counts iff it is mapped (FLAG 0x4
+ *                    clear) and MAPQ >= min_mapq; global position = contig offset + POS - 1; an M column at a site whose SEQ letter is A, C, G
+ *                    or T adds 1, M[q], X[q], H[q] to that letter's words, q = QUAL[s] as printed minus 33 when the byte is in 33 .. 126,
+ *                    else SALT_GT_Q_NONE; QUAL `*` gives SALT_GT_Q_NONE everywhere.  Header lines ('@') and empty lines are skipped; any
+ *                    other line that is no SAM record of this program's is an error; a line is checked whole before anything of it is added.
+ *                    Returns the records that counted.
+ *   salt_gt_text     the records of sites [first, first + n) of the index from sites[0 .. n): the call of salt_gpu.h and its VCF line, no
+ *                    header.  Returns the bytes the text takes; the first min(cap, that) of them are in out (out may be NULL with cap 0:
+ *                    the size only).  The model of the device's text, and what `salt` prints on the host path.
+ *   salt_gt_header   the header of the file, one function for both paths: ##fileformat=VCFv4.2, ##source, one ##contig=<ID=,length=> per
+ *                    sequence of <P>.C.ann, the INFO line, the five FORMAT lines, the #CHROM line ending in `sample` (NULL or empty:
+ *                    "sample").  Sizes as salt_gt_text.
+ * All return -1 with salt_host_last_error() set on failure. */
+int64_t salt_gt_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, salt_gt_site_t *sites, uint64_t n_sites);
+int64_t salt_gt_text(const salt_index_t *ix, const salt_gt_site_t *sites, uint64_t first, uint64_t n, char *out, uint64_t cap);
+int64_t salt_gt_header(const salt_index_t *ix, const char *sample, char *out, uint64_t cap);
+const uint32_t *salt_gt_table(void);      /* SALT_GT_TABLE as this library holds it: 94 x 3 words, for bindings */
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

@@ -550,6 +550,79 @@ def errprof_text(E, R, min_mapq=0, full=False):
     return out.raw[:n]
 
 
+GT_Q_NONE = 20                            # the quality of an event without a quality byte (SALT_GT_Q_NONE)
+
+
+def _gt_host():
+    h = host_lib()
+    h.salt_snp_sites.restype = ctypes.c_int64
+    h.salt_snp_sites.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_gt_add_sam.restype = ctypes.c_int64
+    h.salt_gt_add_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_gt_text.restype = ctypes.c_int64
+    h.salt_gt_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_gt_header.restype = ctypes.c_int64
+    h.salt_gt_header.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_gt_table.restype = ctypes.c_void_p
+    h.salt_gt_table.argtypes = []
+    return h
+
+
+def gt_table():
+    """The penalty table of the genotype calls as the libraries hold it: (94, 3) uint32, per quality 0 .. 93 the penalties M, X, H in
+    1 / 4096 Phred (SALT_GT_TABLE of include/salt_gt_table.h)."""
+    h = _gt_host()
+    return np.ctypeslib.as_array(ctypes.cast(h.salt_gt_table(), ctypes.POINTER(ctypes.c_uint32)), shape=(94, 3)).copy()
+
+
+def gt_add_sam(index, sam, min_mapq=0, sums=None):
+    """The genotype sums of this program's own SAM text (salt_gt_add_sam, the host twin of the device's k_gt_add): (n_sites, 4, 4) uint64,
+    per site and base A C G T the words n, sm, sx, sh.  sums: the array of an earlier call to add into.  Returns (sums, records that counted)."""
+    h = _gt_host()
+    sam = bytes(sam)
+    n_sites = h.salt_snp_sites(index._h, None, 0)
+    if sums is None:
+        sums = np.zeros((n_sites, 4, 4), dtype=np.uint64)
+    if sums.dtype != np.uint64 or sums.shape != (n_sites, 4, 4) or not sums.flags.c_contiguous:
+        raise SaltError("gt_add_sam: sums must be a contiguous (%d, 4, 4) uint64 array" % n_sites)
+    n = h.salt_gt_add_sam(index._h, sam, len(sam), int(min_mapq), sums.ctypes.data, n_sites)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    return sums, int(n)
+
+
+def gt_text(index, sums, first=0):
+    """The VCF records of sites [first, first + len(sums)) for the sums given (salt_gt_text, the host twin of the device's call and text
+    kernels; no header).  bytes."""
+    h = _gt_host()
+    sums = np.ascontiguousarray(sums, dtype=np.uint64)
+    if sums.ndim != 3 or sums.shape[1:] != (4, 4):
+        raise SaltError("gt_text: sums of shape (n, 4, 4)")
+    n = h.salt_gt_text(index._h, sums.ctypes.data, int(first), sums.shape[0], None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_gt_text(index._h, sums.ctypes.data, int(first), sums.shape[0], out, n) != n:
+        raise SaltError("gt_text: the size of the text changed between two calls")
+    return out.raw[:n]
+
+
+def gt_header(index, sample=None):
+    """The header of `salt --genotype`'s file (salt_gt_header).  bytes."""
+    h = _gt_host()
+    name = None if sample is None else os.fsencode(sample)
+    n = h.salt_gt_header(index._h, name, None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    h.salt_gt_header(index._h, name, out, n)
+    return out.raw[:n]
+
+
+class _GtTextOpt(ctypes.Structure):
+    _fields_ = [("tile_sites", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
+
+
 class _DepthTextOpt(ctypes.Structure):
     _fields_ = [("window", ctypes.c_uint32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
@@ -846,6 +919,62 @@ class GpuAligner:
         while True:
             p, n = ctypes.c_void_p(), ctypes.c_uint64()
             _gpu_check(lib.salt_gpu_index_depth_text_next(self._ix, ctypes.byref(p), ctypes.byref(n)))
+            if n.value == 0:
+                break
+            out.append(ctypes.string_at(p.value, n.value))
+        return out if pieces else b"".join(out)
+
+    def gt_enable(self, on=True, min_mapq=0):
+        """Add, from now on, the base and quality events of every align call on this aligner's device index (its forks included) to the
+        index's genotype sums; records below min_mapq do not count.  The first enable builds the site table if snp_enable has not, and
+        zeroes the sums (128 bytes a site); on=False stops and keeps them."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_gt_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_gt_enable(self._ix, 1 if on else 0, int(min_mapq)))
+
+    def gt_reset(self):
+        lib = gpu_lib()
+        lib.salt_gpu_index_gt_reset.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_index_gt_reset(self._ix))
+
+    def gt_fetch(self, first=0, n=None):
+        """The sums of sites [first, first + n) (n None: all behind first): (n, 4, 4) uint64, per site and base A C G T the words n, sm, sx,
+        sh.  Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_gt_fetch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        if n is None:
+            n = max(len(self.snp_sites()) - int(first), 0)
+        out = np.zeros((max(int(n), 0), 4, 4), dtype=np.uint64)
+        _gpu_check(lib.salt_gpu_index_gt_fetch(self._ix, int(first), int(n), out.ctypes.data))
+        return out
+
+    def gt_add(self, first, sums):
+        """sums[first .. first + len(sums)) += sums, on the device: how the tables of several GPUs are summed."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_gt_add.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        sums = np.ascontiguousarray(sums, dtype=np.uint64)
+        if sums.ndim != 3 or sums.shape[1:] != (4, 4):
+            raise SaltError("gt_add: sums of shape (n, 4, 4)")
+        _gpu_check(lib.salt_gpu_index_gt_add(self._ix, int(first), sums.shape[0], sums.ctypes.data))
+
+    def gt_uncount(self):
+        """Takes back what this aligner's last align call added to the genotype sums."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_gt_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_ws_gt_uncount(self._ws))
+
+    def gt_text(self, tile_sites=0, bgzf=False, pieces=False):
+        """The VCF records of the sums as they stand, called and printed on the device (no header); with bgzf whole BGZF blocks (no
+        end-of-file block).  pieces=True: the list of pieces as they left the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_gt_text_begin.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GtTextOpt)]
+        lib.salt_gpu_index_gt_text_next.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        opt = _GtTextOpt(int(tile_sites), 1 if bgzf else 0)
+        _gpu_check(lib.salt_gpu_index_gt_text_begin(self._ix, ctypes.byref(opt)))
+        out = []
+        while True:
+            p, n = ctypes.c_void_p(), ctypes.c_uint64()
+            _gpu_check(lib.salt_gpu_index_gt_text_next(self._ix, ctypes.byref(p), ctypes.byref(n)))
             if n.value == 0:
                 break
             out.append(ctypes.string_at(p.value, n.value))

@@ -72,12 +72,14 @@ struct salt_gpu_index {
     // The row tallies (in front of 4.6): each table is allocated by its first enable (not part of the image) and shared by every workspace of
     // the index while its gate is on.  snp: the site table (one record per 64 genome positions) and counts[snp_sites][4]; depth: the
     // difference array of ref_len + 1 words (the text state and its buffers come with the first salt_gpu_index_depth_text_begin);
-    // errprof: E[2][512][95][4][4] and R[2][8] behind it, uint64.
-    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof;
+    // errprof: E[2][512][95][4][4] and R[2][8] behind it, uint64; gt: salt_gt_site_t[snp_sites] as uint64 words, over the snp tally's site table
+    // (built by whichever of the two is enabled first; the text state and its buffers come with the first salt_gpu_index_gt_text_begin).
+    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt;
     DevBuf<SnpWin> d_snp_tab; DevBuf<uint32_t> d_snp_counts; uint64_t snp_win = 0; uint32_t snp_sites = 0;
     DevBuf<uint32_t> d_depth; DepthText *depth_text = nullptr;
     std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
     DevBuf<unsigned long long> d_errprof;
+    DevBuf<unsigned long long> d_gt; GtText *gt_text = nullptr;
 };
 
 // Every allocation below is a DevBuf / PinBuf: a new buffer is one field here and one reserve() or alloc() where it is sized.  Buffers that
@@ -132,9 +134,9 @@ struct salt_gpu_ws {
     // what the last align call added to each tally (n_rec 0: nothing) and on which stream, for the salt_gpu_ws_*_uncount calls; the error
     // profile's job carries its quality source
     template <class Job> struct LastJob { Job job{}; hipStream_t st = nullptr; };
-    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last;
-    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; }
-    // the error profile's quality bytes: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
+    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last;
+    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; }
+    // the quality bytes of the error profile and the genotype sums: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
     // q_cur is the source of the call that is being queued (the text entry points set it to their raw block); d_quals holds a host call's bytes
     const uint8_t *q_next = nullptr; bool q_next_dev = false;
     struct { const uint8_t *quals = nullptr; const FqRec *rec = nullptr; uint64_t bytes = 0; } q_cur;
@@ -312,6 +314,7 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     if (ix->d_c_off) { hipSetDevice(ix->device); hipFree(ix->d_c_off); hipFree(ix->d_c_name_off); hipFree(ix->d_c_names); }
     hipSetDevice(ix->device);                                  // the tallies' DevBufs go with the index
     depth_text_free(ix->depth_text);
+    gt_text_free(ix->gt_text);
     delete ix;
 }
 
@@ -481,7 +484,8 @@ template <class Job> static int tally_launch(salt_gpu_ws::LastJob<Job> &last, hi
 }
 // The launches behind the kernels that finish a batch's result rows, on the batch's stream, one per tally that is on: the rows' bases at the
 // SNP sites into the index's counts (k_snp_count), their M runs into its difference array (k_depth_mark), their base events into its error
-// profile (k_errprof), the last with the qualities of the call's source (ws->q_cur: the text block, salt_gpu_ws_set_quals' bytes, or
+// profile (k_errprof), their bases and qualities at the SNP sites into its genotype sums (k_gt_add), the last two with the qualities of the
+// call's source (ws->q_cur: the text block, salt_gpu_ws_set_quals' bytes, or
 // none).  Every entry point that leaves result rows passes here: single end at the end of align_resident_impl, paired end at the end of
 // pe_resident_impl (the rows are final only behind k_pe_final).
 static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
@@ -507,14 +511,21 @@ static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, con
         c.ref = ix->view.ref; c.ref_len = ix->view.ref_len; c.cells = ix->d_errprof; c.min_mapq = ix->errprof.min_mapq; c.pe = pe; c.delta = 1ull;
         if (const int rc = tally_launch(ws->ep_last, launch_errprof, c, st)) return rc;
     }
+    if (ix->gt.on) {
+        GtAdd c{};
+        c.res = res; c.seqs = seqs; c.offs = offs; c.n_rec = n_rec;
+        c.quals = ws->q_cur.quals; c.rec = ws->q_cur.rec; c.q_bytes = ws->q_cur.bytes;
+        c.tab = ix->d_snp_tab; c.n_win = ix->snp_win; c.sums = ix->d_gt; c.n_sites = ix->snp_sites; c.min_mapq = ix->gt.min_mapq; c.pe = pe; c.delta = 1ull;
+        if (const int rc = tally_launch(ws->gt_last, launch_gt_add, c, st)) return rc;
+    }
     return SALT_OK;
 }
 // salt_gpu_ws_set_quals' bytes on their way into a call.  A host-buffer call copies host bytes up beside its bases (quals_upload; with the
-// profile off nothing is copied and they are dropped); every host-buffer or resident call then consumes the pointer (quals_take).
+// profile and the genotype sums off nothing is copied and they are dropped); every host-buffer or resident call then consumes the pointer (quals_take).
 static int quals_upload(salt_gpu_ws_t *ws, uint64_t bases, hipStream_t st)
 {
     if (!ws->q_next || ws->q_next_dev) return SALT_OK;
-    if (!ws->ix->errprof.on) { ws->q_next = nullptr; return SALT_OK; }
+    if (!ws->ix->errprof.on && !ws->ix->gt.on) { ws->q_next = nullptr; return SALT_OK; }
     if (int rc = ws->d_quals.reserve(bases + 64, st)) { ws->q_next = nullptr; return rc; }
     const hipError_t e = hipMemcpyAsync(ws->d_quals, ws->q_next, bases, hipMemcpyHostToDevice, st);
     ws->q_next = ws->d_quals; ws->q_next_dev = true;
@@ -1835,36 +1846,45 @@ static int tally_uncount(salt_gpu_ws_t *ws, salt_gpu_ws::LastJob<Job> salt_gpu_w
 }
 
 // ---- allele counts at the SNP sites ----
-// The first enable builds the site table from view.ref (k_snp_bits, a scan of the windows' popcounts, k_snp_rank) and the zeroed counts.
+// The site table from view.ref (k_snp_bits, a scan of the windows' popcounts, k_snp_rank), for the tally named by `prefix`: the SNP counts
+// and the genotype sums share it, and whichever is enabled first builds it.  Already built: SALT_OK.
+static int snp_table_build(salt_gpu_index_t *ix, const char *prefix)
+{
+    if (ix->d_snp_tab) return SALT_OK;
+    const std::string pre = std::string(prefix) + ": ";
+    const uint32_t ref_len = ix->view.ref_len;
+    if (ref_len == 0) return fail(SALT_E_INVAL, pre + "the index has an empty genome");
+    const uint64_t n_win = ((uint64_t)ref_len + 63) / 64;
+    DevBuf<uint32_t> cnt; DevBuf<uint8_t> tmp; DevBuf<SnpWin> tab;
+    const size_t tmp_bytes = snp_scan_bytes(n_win);
+    if (tab.alloc(n_win) != hipSuccess || cnt.alloc(n_win + 1) != hipSuccess || tmp.alloc(tmp_bytes ? tmp_bytes : 1) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SALT_E_NOMEM, pre + "no room for the site table: " + std::to_string(n_win * sizeof(SnpWin)) + " bytes (16 per 64 genome positions) and " +
+                                  std::to_string((n_win + 1) * 4 + tmp_bytes) + " bytes of scratch while it is built");
+    }
+    HIPCHK(launch_snp_table(ix->view.ref, ref_len, n_win, tab, cnt, tmp, tmp_bytes, nullptr));
+    uint32_t n_sites = 0;
+    HIPCHK(hipMemcpy(&n_sites, cnt + n_win, 4, hipMemcpyDeviceToHost));
+    ix->d_snp_tab.take(tab);                                                   // the index owns it from here
+    ix->snp_win = n_win; ix->snp_sites = n_sites;
+    return SALT_OK;
+}
+
+// The first enable builds the site table if the genotype sums have not, and the zeroed counts.
 extern "C" int salt_gpu_index_snp_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
 {
     return tally_enable(ix, &salt_gpu_index::snp, "snp counts", on, min_mapq, [&]() -> int {
-        if (ix->d_snp_tab) return SALT_OK;
-        const uint32_t ref_len = ix->view.ref_len;
-        if (ref_len == 0) return fail(SALT_E_INVAL, "snp counts: the index has an empty genome");
-        const uint64_t n_win = ((uint64_t)ref_len + 63) / 64;
-        DevBuf<uint32_t> cnt, counts; DevBuf<uint8_t> tmp; DevBuf<SnpWin> tab;
-        const size_t tmp_bytes = snp_scan_bytes(n_win);
-        if (tab.alloc(n_win) != hipSuccess || cnt.alloc(n_win + 1) != hipSuccess || tmp.alloc(tmp_bytes ? tmp_bytes : 1) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SALT_E_NOMEM, "snp counts: no room for the site table: " + std::to_string(n_win * sizeof(SnpWin)) + " bytes (16 per 64 genome positions) and " +
-                                      std::to_string((n_win + 1) * 4 + tmp_bytes) + " bytes of scratch while it is built");
-        }
-        HIPCHK(launch_snp_table(ix->view.ref, ref_len, n_win, tab, cnt, tmp, tmp_bytes, nullptr));
-        uint32_t n_sites = 0;
-        HIPCHK(hipMemcpy(&n_sites, cnt + n_win, 4, hipMemcpyDeviceToHost));
-        const uint64_t rows = (uint64_t)n_sites + 1;                                // (one spare row: an index without sites still has a table)
-        if (const int rc = alloc_zeroed(counts, rows * 4, "snp counts", "the counts: " + std::to_string(rows * 16) + " bytes (16 per site, " + std::to_string(n_sites) + " sites)")) return rc;
-        ix->d_snp_tab.take(tab); ix->d_snp_counts.take(counts);                    // the index owns them from here
-        ix->snp_win = n_win; ix->snp_sites = n_sites;
-        return SALT_OK;
+        if (ix->d_snp_counts) return SALT_OK;
+        if (const int rc = snp_table_build(ix, "snp counts")) return rc;
+        const uint64_t rows = (uint64_t)ix->snp_sites + 1;                          // (one spare row: an index without sites still has a table)
+        return alloc_zeroed(ix->d_snp_counts, rows * 4, "snp counts", "the counts: " + std::to_string(rows * 16) + " bytes (16 per site, " + std::to_string(ix->snp_sites) + " sites)");
     });
 }
 
 extern "C" int salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites, uint32_t *pos, uint64_t cap)
 {
     if (!ix || !n_sites) return fail(SALT_E_INVAL, "null argument");
-    if (!ix->d_snp_tab) return fail(SALT_E_INVAL, "snp counts: counting was never enabled on this index (salt_gpu_index_snp_enable)");
+    if (!ix->d_snp_tab) return fail(SALT_E_INVAL, "snp counts: counting was never enabled on this index (salt_gpu_index_snp_enable)");      // (the genotype sums' enable builds the table too)
     *n_sites = ix->snp_sites;
     if (!pos || ix->snp_sites == 0) return SALT_OK;
     if (cap < ix->snp_sites) return fail(SALT_E_INVAL, "snp counts: room for " + std::to_string(cap) + " positions, the index has " + std::to_string(ix->snp_sites) + " sites");
@@ -1879,7 +1899,7 @@ extern "C" int salt_gpu_index_snp_sites(salt_gpu_index_t *ix, uint32_t *n_sites,
 extern "C" int salt_gpu_index_snp_counts(salt_gpu_index_t *ix, uint32_t *counts, uint64_t cap_words, int reset)
 {
     if (!ix) return fail(SALT_E_INVAL, "null argument");
-    if (!ix->d_snp_tab) return fail(SALT_E_INVAL, "snp counts: counting was never enabled on this index (salt_gpu_index_snp_enable)");
+    if (!ix->d_snp_counts) return fail(SALT_E_INVAL, "snp counts: counting was never enabled on this index (salt_gpu_index_snp_enable)");
     const uint64_t words = (uint64_t)ix->snp_sites * 4;
     if (counts && cap_words < words) return fail(SALT_E_INVAL, "snp counts: room for " + std::to_string(cap_words) + " words, the table has " + std::to_string(words) + " (4 per site)");
     HIPCHK(hipSetDevice(ix->device));
@@ -2012,6 +2032,97 @@ extern "C" int salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cell
 extern "C" int salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws)
 {
     return tally_uncount(ws, &salt_gpu_ws::ep_last, launch_errprof, ~0ull, &salt_gpu_index::d_errprof, ERRPROF_NEVER);
+}
+
+// ---- genotypes at the SNP sites ----
+static const char *const GT_NEVER = "genotype: the genotype sums were never enabled on this index (salt_gpu_index_gt_enable)";
+static const uint64_t GT_WORDS = sizeof(salt_gt_site_t) / 8;               // 16 words a site
+
+// The first enable builds the site table if the SNP counts have not, and the zeroed sums.
+extern "C" int salt_gpu_index_gt_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
+{
+    return tally_enable(ix, &salt_gpu_index::gt, "genotype", on, min_mapq, [&]() -> int {
+        if (ix->d_gt) return SALT_OK;
+        if (const int rc = snp_table_build(ix, "genotype")) return rc;
+        const uint64_t rows = (uint64_t)ix->snp_sites + 1;                          // (one spare row: an index without sites still has a table)
+        return alloc_zeroed(ix->d_gt, rows * GT_WORDS, "genotype", "the sums: " + std::to_string(rows * sizeof(salt_gt_site_t)) + " bytes (128 per site, " + std::to_string(ix->snp_sites) + " sites)");
+    });
+}
+
+extern "C" int salt_gpu_index_gt_reset(salt_gpu_index_t *ix)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_gt) return fail(SALT_E_INVAL, GT_NEVER);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemset(ix->d_gt, 0, ((uint64_t)ix->snp_sites + 1) * sizeof(salt_gt_site_t)));
+    return SALT_OK;
+}
+
+// first + n sites inside the table, or the message that names the range
+static int gt_range(const salt_gpu_index *ix, const char *what, uint64_t first, uint64_t n)
+{
+    const uint64_t sites = ix->snp_sites;
+    if (first > sites || n > sites - first)
+        return fail(SALT_E_INVAL, std::string("genotype ") + what + ": sites [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") leave the table's [0, " +
+                                  std::to_string(sites) + ")");
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_gt_fetch(salt_gpu_index_t *ix, uint64_t first_site, uint64_t n, salt_gt_site_t *out)
+{
+    if (!ix || (!out && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_gt) return fail(SALT_E_INVAL, GT_NEVER);
+    if (const int rc = gt_range(ix, "fetch", first_site, n)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (n) HIPCHK(hipMemcpy(out, ix->d_gt + first_site * GT_WORDS, n * sizeof(salt_gt_site_t), hipMemcpyDeviceToHost));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_gt_add(salt_gpu_index_t *ix, uint64_t first_site, uint64_t n, const salt_gt_site_t *in)
+{
+    if (!ix || (!in && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_gt) return fail(SALT_E_INVAL, GT_NEVER);
+    if (const int rc = gt_range(ix, "add", first_site, n)) return rc;
+    if (n == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf<unsigned long long> d_in;
+    if (d_in.alloc(n * GT_WORDS) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, "genotype add: no room for " + std::to_string(n * sizeof(salt_gt_site_t)) + " bytes of sums to add"); }
+    HIPCHK(hipMemcpy(d_in, in, n * sizeof(salt_gt_site_t), hipMemcpyHostToDevice));
+    HIPCHK(launch_gt_sum(ix->d_gt + first_site * GT_WORDS, d_in, n * GT_WORDS, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_gt_text_begin(salt_gpu_index_t *ix, const salt_gt_text_opt_t *opt)
+{
+    if (!ix || !opt) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_gt) return fail(SALT_E_INVAL, GT_NEVER);
+    if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "genotype text needs the contig table: call salt_gpu_index_set_contigs first");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!ix->gt_text) ix->gt_text = gt_text_new();
+    std::string err;
+    const int rc = gt_text_begin(ix->gt_text, ix->d_gt, ix->d_snp_tab, ix->snp_win, ix->snp_sites, ix->view.ref, ix->view.text, ix->view.ref_len, ix->view.c_seq_len,
+                                 ix->d_c_off, ix->d_c_name_off, ix->d_c_names, ix->n_contigs, ix->c_name_max, opt->tile_sites, opt->bgzf, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_index_gt_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes)
+{
+    if (!ix || !data || !n_bytes) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_gt) return fail(SALT_E_INVAL, GT_NEVER);
+    if (!ix->gt_text) return fail(SALT_E_INVAL, "genotype text: no text was begun (salt_gpu_index_gt_text_begin)");
+    HIPCHK(hipSetDevice(ix->device));
+    std::string err;
+    const int rc = gt_text_next(ix->gt_text, data, n_bytes, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_gt_uncount(salt_gpu_ws_t *ws)
+{
+    return tally_uncount(ws, &salt_gpu_ws::gt_last, launch_gt_add, ~0ull, &salt_gpu_index::d_gt, GT_NEVER);
 }
 
 extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device)

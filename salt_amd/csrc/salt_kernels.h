@@ -297,6 +297,27 @@ struct ErrProf {                                                               /
 };
 hipError_t launch_errprof(const ErrProf &c, hipStream_t st);
 
+// ---- genotypes at the SNP sites (salt_gt.hip) ----
+struct GtAdd {                                                                 // what k_gt_add reads (by value)
+    const salt_result_t *res; const uint8_t *seqs; const uint32_t *offs; uint32_t n_rec;      // the batch: rows, codes as sequenced, offsets
+    const uint8_t *quals; const FqRec *rec; uint64_t q_bytes;                  // the quality bytes, as ErrProf has them; a read without them counts at SALT_GT_Q_NONE
+    const SnpWin *tab; uint64_t n_win;                                         // the index's site table (the SNP counts' own)
+    unsigned long long *sums; uint64_t n_sites;                                // salt_gt_site_t[n_sites] as words: [site][A C G T][n sm sx sh]
+    uint32_t min_mapq; int32_t pe;                                             // pe: rows of a paired-end batch (reverse iff strand == 1, soft clips)
+    unsigned long long delta;                                                  // 1; 2^64 - 1 negates the addends: a batch's adds are taken back
+};
+hipError_t launch_gt_add(const GtAdd &c, hipStream_t st);
+hipError_t launch_gt_sum(unsigned long long *sums, const unsigned long long *in, uint64_t n_words, hipStream_t st);      // sums[i] += in[i]
+// The records of the sums, piece by piece (salt_gpu_index_gt_text_begin / _next): the device and page-locked buffers and where the text
+// stands.  Both return SALT_OK or an error code with the message in err.
+struct GtText;
+GtText *gt_text_new();
+void gt_text_free(GtText *t);
+int gt_text_begin(GtText *t, const unsigned long long *d_sums, const SnpWin *d_tab, uint64_t n_win, uint32_t n_sites, const uint32_t *d_ref, const uint32_t *d_text,
+                  uint32_t ref_len, uint32_t text_len, const int64_t *d_c_off, const uint32_t *d_c_name_off, const char *d_c_names, int32_t n_contigs, uint32_t max_name,
+                  uint32_t tile_sites, int bgzf, std::string &err);
+int gt_text_next(GtText *t, const char **data, uint64_t *n_bytes, std::string &err);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

@@ -953,3 +953,124 @@ extern "C" int64_t salt_errprof_text(const uint64_t *cells, const uint64_t rec[1
     }
     return (int64_t)o.n;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Genotypes at the SNP sites: the host twin of k_gt_add and of the device's call and text kernels (salt_gt.hip; include/salt_gpu.h has the
+// definition), written from that definition over this program's own SAM record lines.  It shares the penalty table's header with the
+// kernels and nothing else.
+// ---------------------------------------------------------------------------------------------
+#include "../../include/salt_gt_table.h"
+
+namespace {
+
+// one record line [l, e): its events into sites; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with g_err set.  The line is
+// checked whole (head, QUAL's length, CIGAR) before anything is added.
+int gt_add_line(const salt_index *ix, const RefIds &ids, const std::vector<uint32_t> &pos, const char *l, const char *e, uint32_t min_mapq, salt_gt_site_t *sites)
+{
+    SamLine L; MRuns m; uint64_t g0;
+    const int h = twin_head(ix, ids, L, "genotype: ", l, e, min_mapq, &g0);
+    if (h != 1) return h;
+    const char *seq = L.f[9], *qual = L.f[10]; const size_t l_seq = L.len(9), l_qual = L.len(10);
+    const bool no_qual = l_qual == 1 && qual[0] == '*' && l_seq != 1;
+    if (!no_qual && l_qual != l_seq) return L.bad("QUAL is neither * nor as long as SEQ"), -1;
+    if (!twin_cigar(L, g0, m)) return -1;
+    for (int r = 0; r < m.n; ++r)
+        for (uint64_t k = 0; k < m.len[r]; ++k) {
+            const uint64_t g = m.g[r] + k; const size_t s = m.s[r] + k;
+            const auto it = std::lower_bound(pos.begin(), pos.end(), g);
+            if (g > 0xFFFFFFFFull || it == pos.end() || *it != g) continue;
+            const int b = base_code(seq[s]);
+            if (b < 0) continue;
+            const uint8_t qb = no_qual ? 0 : (uint8_t)qual[s];
+            const uint32_t q = qb >= 33 && qb <= 126 ? (uint32_t)qb - 33u : (uint32_t)SALT_GT_Q_NONE;
+            salt_gt_base_t &w = sites[(size_t)(it - pos.begin())].b[b];
+            w.n += 1; w.sm += SALT_GT_TABLE[q][0]; w.sx += SALT_GT_TABLE[q][1]; w.sh += SALT_GT_TABLE[q][2];
+        }
+    return 1;
+}
+
+} // namespace
+
+extern "C" int64_t salt_gt_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, salt_gt_site_t *sites, uint64_t n_sites)
+{
+    if (!ix || (!sam && n) || !sites) { g_err = "genotype: null argument"; return -1; }
+    const std::vector<uint32_t> &pos = snp_positions(ix);
+    if (n_sites != pos.size()) { g_err = "genotype: sums for " + std::to_string(n_sites) + " sites, the index has " + std::to_string(pos.size()); return -1; }
+    const RefIds ids(ix);
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return gt_add_line(ix, ids, pos, l, e, min_mapq, sites); });
+}
+
+extern "C" int64_t salt_gt_text(const salt_index_t *ix, const salt_gt_site_t *sites, uint64_t first, uint64_t n, char *out, uint64_t cap)
+{
+    if (!ix || (!sites && n) || (!out && cap)) { g_err = "genotype: null argument"; return -1; }
+    const std::vector<uint32_t> &pos = snp_positions(ix);
+    if (first > pos.size() || n > pos.size() - first) {
+        g_err = "genotype: sites [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") leave the index's [0, " + std::to_string(pos.size()) + ")";
+        return -1;
+    }
+    DepthOut o{ out, cap };
+    static const char NT[] = "ACGT";
+    for (uint64_t i = 0; i < n; ++i) {
+        const salt_gt_site_t &S = sites[i];                            // (sites[0] is site `first`)
+        const uint32_t g = pos[(size_t)(first + i)];
+        const uint32_t mask = mask_at(ix, g), r = (int64_t)g < ix->l_pac ? pac_at(ix, g) : 0u;
+        int al[4], n_al = 0;
+        al[n_al++] = (int)r;
+        for (int b = 0; b < 4; ++b) if (((mask >> b) & 1u) && (uint32_t)b != r) al[n_al++] = b;
+        uint64_t all_x = 0, dp = 0;
+        for (int b = 0; b < 4; ++b) { all_x += S.b[b].sx; dp += S.b[b].n; }
+        uint64_t raw[10]; int n_gt = 0, ga[10], gb[10];
+        for (int b = 0; b < n_al; ++b)
+            for (int a = 0; a <= b; ++a, ++n_gt) {                     // VCF order: b (b + 1) / 2 + a
+                const salt_gt_base_t &A = S.b[al[a]], &B = S.b[al[b]];
+                raw[n_gt] = a == b ? A.sm + (all_x - A.sx) : A.sh + B.sh + (all_x - A.sx - B.sx);
+                ga[n_gt] = a; gb[n_gt] = b;
+            }
+        int best = 0;
+        for (int k = 1; k < n_gt; ++k) if (raw[k] < raw[best]) best = k;      // the first of the smallest
+        size_t c = 0;                                                  // the last contig that begins at or in front of g
+        for (size_t k = 1; k < ix->anns.size(); ++k) if ((uint64_t)ix->anns[k].offset <= g) c = k;
+        o.puts(ix->anns[c].name); o.put('\t'); o.putu((uint64_t)g - (uint64_t)ix->anns[c].offset + 1); o.puts("\t.\t");
+        o.put(NT[r]); o.put('\t');
+        for (int k = 1; k < n_al; ++k) { if (k > 1) o.put(','); o.put(NT[al[k]]); }
+        o.put('\t');
+        if (dp == 0) {
+            o.puts(".\t.\tDP=0\tGT:AD:DP:GQ:PL\t./.:");
+            for (int k = 0; k < n_al; ++k) { if (k) o.put(','); o.put('0'); }
+            o.puts(":0:.:.\n");
+            continue;
+        }
+        auto pl = [&](int k) { return (raw[k] - raw[best] + 2048u) >> 12; };
+        uint64_t gq = ~0ull;
+        for (int k = 0; k < n_gt; ++k) if (k != best) gq = std::min<uint64_t>(gq, pl(k));
+        gq = std::min<uint64_t>(gq, 99);
+        o.putu(pl(0)); o.puts("\t.\tDP="); o.putu(dp); o.puts("\tGT:AD:DP:GQ:PL\t");
+        o.putu((uint64_t)ga[best]); o.put('/'); o.putu((uint64_t)gb[best]); o.put(':');
+        for (int k = 0; k < n_al; ++k) { if (k) o.put(','); o.putu(S.b[al[k]].n); }
+        o.put(':'); o.putu(dp); o.put(':'); o.putu(gq); o.put(':');
+        for (int k = 0; k < n_gt; ++k) { if (k) o.put(','); o.putu(pl(k)); }
+        o.put('\n');
+    }
+    return (int64_t)o.n;
+}
+
+extern "C" int64_t salt_gt_header(const salt_index_t *ix, const char *sample, char *out, uint64_t cap)
+{
+    if (!ix || (!out && cap)) { g_err = "genotype: null argument"; return -1; }
+    const std::string name = sample && *sample ? sample : "sample";
+    for (char ch : name) if (ch == '\t' || ch == '\n' || ch == '\r') { g_err = "genotype: the sample name holds a tab or a line end"; return -1; }
+    DepthOut o{ out, cap };
+    o.puts("##fileformat=VCFv4.2\n##source=salt --genotype\n");
+    for (const Ann &a : ix->anns) { o.puts("##contig=<ID="); o.puts(a.name); o.puts(",length="); o.putu((uint64_t)a.len); o.puts(">\n"); }
+    o.puts("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Bases of counted reads at the site (A, C, G, T)\">\n"
+           "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+           "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Bases that show each allele\">\n"
+           "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Bases of counted reads at the site (A, C, G, T)\">\n"
+           "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the smallest PL of another genotype, at most 99\">\n"
+           "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, flat priors, uncapped\">\n"
+           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t");
+    o.puts(name); o.put('\n');
+    return (int64_t)o.n;
+}
+
+extern "C" const uint32_t *salt_gt_table(void) { return &SALT_GT_TABLE[0][0]; }

@@ -84,6 +84,14 @@ extern "C" int salt_gpu_index_errprof_enable(salt_gpu_index_t *ix, int on, uint3
 extern "C" int salt_gpu_index_errprof_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t rec[16], int reset) __attribute__((weak));
 extern "C" int salt_gpu_ws_errprof_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device) __attribute__((weak));
+// Likewise the genotypes at the SNP sites (--genotype): without the device's sums and call kernels the sums come from the SAM lines
+// (salt_gt_add_sam) and the records from the host twin's printer (salt_gt_text); the header is salt_gt_header's either way.
+extern "C" int salt_gpu_index_gt_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq) __attribute__((weak));
+extern "C" int salt_gpu_index_gt_fetch(salt_gpu_index_t *ix, uint64_t first_site, uint64_t n, salt_gt_site_t *out) __attribute__((weak));
+extern "C" int salt_gpu_index_gt_add(salt_gpu_index_t *ix, uint64_t first_site, uint64_t n, const salt_gt_site_t *in) __attribute__((weak));
+extern "C" int salt_gpu_index_gt_text_begin(salt_gpu_index_t *ix, const salt_gt_text_opt_t *opt) __attribute__((weak));
+extern "C" int salt_gpu_index_gt_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
+extern "C" int salt_gpu_ws_gt_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
 namespace {
 
@@ -463,7 +471,7 @@ struct BamRun {
     const salt_index_t *ix = nullptr;
 } g_bam;
 
-// The three row tallies (--snp-counts, --depth, --error-profile) run alike.  On the device the table belongs to each GPU's index and every
+// The four row tallies (--snp-counts, --depth, --error-profile, --genotype) run alike.  On the device the table belongs to each GPU's index and every
 // align call adds into it (salt_gpu_index_*_enable); a block the text path has aligned and then drops at a hand-over is taken back
 // (salt_gpu_ws_*_uncount): the host pipeline aligns those reads again.  Without the device's symbols the SAM lines of every block and
 // batch that is written go through the tally's host twin, one caller at a time.
@@ -482,15 +490,18 @@ struct DepthRun : TallyRun { bool gz = false; uint32_t window = 0; std::vector<u
 // prints the file on both paths.
 const size_t ERRPROF_CELLS = 2u * 512u * 95u * 16u;
 struct ErrprofRun : TallyRun { bool full = false; std::vector<uint64_t> cells; uint64_t rec[16] = { 0 }; } g_errprof;
+// --genotype FILE: a VCF record per SNP site of the index.  Like the profile, the host pipeline hands its batches' qualities over; after the
+// last block the other GPUs' sums are added into the first GPU's, whose kernels make the calls and print the records piece by piece.
+struct GtRun : TallyRun { bool gz = false; const char *sample = nullptr; std::vector<salt_gt_site_t> host_sums; } g_gt;
 
-// What differs between them where they run alike, in the order snp, depth, error profile.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
+// What differs between them where they run alike, in the order snp, depth, error profile, genotype.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
 // how the file is opened; does: what a libsalt_gpu without the symbols does not do (the --polish refusal); symbols: this libsalt_gpu has
 // the device side; host_add: the twin over SAM lines (< 0: refused); uncount: the last align call's adds leave the device's table.
 struct Tally {
     TallyRun *run; const char *opt, *stem, *mode, *does;
     bool (*symbols)(); int64_t (*host_add)(const char *sam, size_t n); int (*uncount)(salt_gpu_ws_t *ws);
 };
-const Tally TALLIES[3] = {
+const Tally TALLIES[4] = {
     { &g_snp, "snp-counts", "snp", "w", "counts",
       [] { return salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount; },
       [](const char *sam, size_t n) { return salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites); }, salt_gpu_ws_snp_uncount },
@@ -500,6 +511,9 @@ const Tally TALLIES[3] = {
     { &g_errprof, "error-profile", "error-profile", "w", "makes the profile",
       [] { return salt_gpu_index_errprof_enable && salt_gpu_index_errprof_fetch && salt_gpu_ws_errprof_uncount && salt_gpu_ws_set_quals; },
       [](const char *sam, size_t n) { return salt_errprof_add_sam(g_errprof.ix, sam, n, g_errprof.min_mapq, g_errprof.cells.data(), g_errprof.cells.size(), g_errprof.rec); }, salt_gpu_ws_errprof_uncount },
+    { &g_gt, "genotype", "genotype", "wb", "sums and calls the genotypes",
+      [] { return salt_gpu_index_gt_enable && salt_gpu_index_gt_fetch && salt_gpu_index_gt_add && salt_gpu_index_gt_text_begin && salt_gpu_index_gt_text_next && salt_gpu_ws_gt_uncount && salt_gpu_ws_set_quals; },
+      [](const char *sam, size_t n) { return salt_gt_add_sam(g_gt.ix, sam, n, g_gt.min_mapq, g_gt.host_sums.data(), g_gt.host_sums.size()); }, salt_gpu_ws_gt_uncount },
 };
 
 // the SAM lines of a block or batch that is about to be written, through every host twin that is on; false with the reason on stderr
@@ -633,6 +647,11 @@ int usage()
             "                                        substitution, the index's SNP sites left out (counted on the GPU; tab-separated) [off]\n"
             "               --error-profile-min-mapq <int>  --error-profile: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
             "               --error-profile-full     --error-profile: also every non-zero cell (mate, cycle, quality, ref, read)\n"
+            "               --genotype      <file>   write a VCF 4.2 record per SNP site of the index: the genotype, allele depths and\n"
+            "                                        likelihoods from the reads' bases and base qualities (summed, called and printed on\n"
+            "                                        the GPU); a name ending in .gz is written as BGZF [off]\n"
+            "               --genotype-min-mapq <int>  --genotype: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
+            "               --genotype-sample <name>   --genotype: the sample column's name [sample]\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -1347,7 +1366,8 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "read_length", 1, 0, 'l' }, { "overlap", 1, 0, 'r' }, { "xa_cigar", 0, 0, 'c' }, { "md", 0, 0, 'd' }, { "ref", 0, 0, 'v' },
         { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 },
         { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { "depth", 1, 0, 1006 }, { "depth-min-mapq", 1, 0, 1007 }, { "depth-window", 1, 0, 1008 },
-        { "error-profile", 1, 0, 1009 }, { "error-profile-min-mapq", 1, 0, 1010 }, { "error-profile-full", 0, 0, 1011 }, { 0, 0, 0, 0 } };
+        { "error-profile", 1, 0, 1009 }, { "error-profile-min-mapq", 1, 0, 1010 }, { "error-profile-full", 0, 0, 1011 },
+        { "genotype", 1, 0, 1012 }, { "genotype-min-mapq", 1, 0, 1013 }, { "genotype-sample", 1, 0, 1014 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1370,8 +1390,8 @@ static int parse_options(int argc, char **argv, Opts &o)
             else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
             break;
         case 1004: g_snp.on = true; g_snp.fn = optarg; break;
-        case 1005: case 1007: case 1010: {
-            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : 2];
+        case 1005: case 1007: case 1010: case 1013: {
+            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : 3];
             char *end = nullptr; const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --%s-min-mapq %s: a MAPQ is a number from 0 to 255\n", t.stem, optarg); return 1; }
             t.run->min_mapq = (uint32_t)v;
@@ -1386,6 +1406,11 @@ static int parse_options(int argc, char **argv, Opts &o)
         }
         case 1009: g_errprof.on = true; g_errprof.fn = optarg; break;
         case 1011: g_errprof.full = true; break;
+        case 1012: g_gt.on = true; g_gt.fn = optarg; break;
+        case 1014:
+            if (!*optarg || strpbrk(optarg, "\t\n\r")) { fprintf(stderr, "[opt_parse]: --genotype-sample: a sample name is not empty and holds no tab or line end\n"); return 1; }
+            g_gt.sample = optarg;
+            break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1413,6 +1438,8 @@ static int parse_options(int argc, char **argv, Opts &o)
     }
     const size_t l = g_depth.on ? strlen(g_depth.fn) : 0;
     g_depth.gz = l > 3 && strcmp(g_depth.fn + l - 3, ".gz") == 0;
+    const size_t lg = g_gt.on ? strlen(g_gt.fn) : 0;
+    g_gt.gz = lg > 3 && strcmp(g_gt.fn + lg - 3, ".gz") == 0;
     return -1;
 }
 
@@ -1567,8 +1594,8 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (b->n() == 0) { std::unique_lock<std::mutex> lk(mu); done.push_back(std::move(b)); cv.notify_all(); continue; }
                 b->res.resize((size_t)b->n() * (pe ? 2 : 1));
                 double tg0 = now();
-                std::vector<uint8_t> iqual;                      // --error-profile on the device: the batch's qualities, parallel to the bases
-                if (g_errprof.on && g_errprof.device) {
+                std::vector<uint8_t> iqual;                      // --error-profile or --genotype on the device: the batch's qualities, parallel to the bases
+                if ((g_errprof.on && g_errprof.device) || (g_gt.on && g_gt.device)) {
                     batch_quals(*b, pe ? b->mate.get() : nullptr, iqual);
                     if (salt_gpu_ws_set_quals(ws[(size_t)g], iqual.data(), 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 }
@@ -1578,7 +1605,7 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
-                if (g_snp.host() || g_depth.host() || g_errprof.host()) {
+                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host()) {
                     bool good = true;
                     for (const std::string &piece : b->sam) good = good && host_twins_add(piece.data(), piece.size());
                     if (!good) { set_failed(); break; }
@@ -1795,6 +1822,79 @@ static bool depth_finish(const salt_index_t *ix, const std::vector<salt_gpu_inde
     return true;
 }
 
+// --genotype, before the first block: the sums on on every GPU's index, or the host's table
+static bool gt_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_gt.on) return true;
+    g_gt.ix = ix;
+    const int64_t n = salt_snp_sites(ix, nullptr, 0);
+    if (n < 0) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+    if (!g_gt.device) { g_gt.host_sums.assign((size_t)n, salt_gt_site_t{}); return true; }
+    for (salt_gpu_index_t *g : gix)
+        if (salt_gpu_index_gt_enable(g, 1, g_gt.min_mapq)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    return true;
+}
+
+// --genotype, after the last block of a run that succeeded: the header (salt_gt_header; through the host's BGZF encoder for a .gz file), then
+// the records: the sums of the other GPUs are added into the first one's, in chunks through a page-locked buffer, and its kernels make the
+// calls and print the records piece by piece; on the host the twin's printer does.  A .gz file ends with the BGZF end-of-file block.
+static bool gt_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &C)
+{
+    if (!g_gt.on) return true;
+    FILE *f = g_gt.fp;
+    uint64_t text_bytes = 0, file_bytes = 0;
+    const uint64_t n_sites = (uint64_t)salt_snp_sites(ix, nullptr, 0);
+    const int64_t hn = salt_gt_header(ix, g_gt.sample, nullptr, 0);
+    std::string head(hn > 0 ? (size_t)hn : 0, '\0'), z;
+    if (hn < 0 || salt_gt_header(ix, g_gt.sample, &head[0], (uint64_t)hn) != hn) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+    if (g_gt.gz && !bgzf_deflate_host(head.data(), head.size(), z)) { fprintf(stderr, "[salt] --genotype: no BGZF blocks for the header\n"); return false; }
+    bool ok = fwrite((g_gt.gz ? z : head).data(), 1, (g_gt.gz ? z : head).size(), f) == (g_gt.gz ? z : head).size();
+    text_bytes += head.size(); file_bytes += (g_gt.gz ? z : head).size();
+    if (g_gt.device) {
+        const uint64_t chunk = std::min<uint64_t>(n_sites, 1u << 17);             // 16 MiB of sums at a time
+        auto gpu_fail = [&]() { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; };
+        if (gix.size() > 1 && n_sites) {
+            salt_gt_site_t *buf = nullptr;
+            if (salt_gpu_host_alloc(chunk * sizeof(salt_gt_site_t), (void **)&buf)) return gpu_fail();
+            for (size_t k = 1; k < gix.size() && ok; ++k)
+                for (uint64_t at = 0; at < n_sites && ok; at += chunk) {
+                    const uint64_t n = std::min(chunk, n_sites - at);
+                    ok = salt_gpu_index_gt_fetch(gix[k], at, n, buf) == 0 && salt_gpu_index_gt_add(gix[0], at, n, buf) == 0;
+                }
+            if (!ok) gpu_fail();
+            salt_gpu_host_free(buf);
+            if (!ok) return false;
+        }
+        salt_gt_text_opt_t to; to.tile_sites = 0; to.bgzf = g_gt.gz ? 1 : 0;
+        if (salt_gpu_index_gt_enable(gix[0], 0, g_gt.min_mapq) || salt_gpu_index_set_contigs(gix[0], C.n(), C.off.data(), C.nm.data()) ||
+            salt_gpu_index_gt_text_begin(gix[0], &to)) return gpu_fail();
+        for (;;) {
+            const char *data = nullptr; uint64_t n = 0;
+            if (salt_gpu_index_gt_text_next(gix[0], &data, &n)) return gpu_fail();
+            if (n == 0) break;
+            ok = ok && fwrite(data, 1, (size_t)n, f) == n;
+            file_bytes += n; text_bytes += g_gt.gz ? bgzf_text_bytes(data, n) : n;
+        }
+    } else {
+        const int64_t need = salt_gt_text(ix, g_gt.host_sums.data(), 0, n_sites, nullptr, 0);
+        std::string text(need > 0 ? (size_t)need : 0, '\0');
+        if (need < 0 || salt_gt_text(ix, g_gt.host_sums.data(), 0, n_sites, &text[0], (uint64_t)need) != need) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+        z.clear();
+        if (g_gt.gz && !text.empty() && !bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] --genotype: no BGZF blocks for the records\n"); return false; }
+        const std::string &out = g_gt.gz ? z : text;
+        ok = ok && fwrite(out.data(), 1, out.size(), f) == out.size();
+        text_bytes += text.size(); file_bytes += out.size();
+    }
+    if (g_gt.gz) { ok = ok && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, f) == sizeof BGZF_EOF; file_bytes += sizeof BGZF_EOF; }
+    ok = !ferror(f) && fclose(f) == 0 && ok;
+    g_gt.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --genotype: write error on %s\n", g_gt.fn); return false; }
+    fprintf(stderr, "[salt] genotypes: %llu sites, %s, MAPQ >= %u, %llu bytes of text -> %s (%llu bytes)\n", (unsigned long long)n_sites,
+            g_gt.device ? "summed, called and printed on the device" : "summed on the host from the SAM lines", g_gt.min_mapq, (unsigned long long)text_bytes, g_gt.fn,
+            (unsigned long long)file_bytes);
+    return true;
+}
+
 } // namespace
 
 // options; choice of path (TextPlan); index load and attach; header; text path; host pipeline
@@ -1843,16 +1943,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
-    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
+    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix)) ? 1 : rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs)) ? 1 : rc); }
         header_out = true;
     }
     const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
-    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix)) ? 1 : rc);
+    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs)) ? 1 : rc);
 }
