@@ -354,6 +354,79 @@ int  salt_gpu_index_gt_text_begin(salt_gpu_index_t *ix, const salt_gt_text_opt_t
 int  salt_gpu_index_gt_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes);
 int  salt_gpu_ws_gt_uncount(salt_gpu_ws_t *ws);
 
+/* ---- SNP candidates off the index's sites (`salt --discover`) -----------------------------------------------------------
+ * Which records contribute and the CIGAR walk are those of the SNP counts above (4.6): a record contributes iff it is mapped
+ * (pos != 0xFFFFFFFF), not skipped, and mapq >= min_mapq; only the primary alignment counts, never an alternative (XA) hit; the record is
+ * walked as the SAM / BAM writers lay it out (leading soft clip, M / I / D).
+ * Events: an M column (genome position g, base s of SEQ as printed, L bases) is an event iff g < ref_len and s < L, SEQ[s] is a base b in
+ * A C G T (0 .. 3), and the mixRef mask m = (ref[g >> 3] >> 4 * (g & 7)) & 15 has m != 0 and bit b CLEAR: the read shows a base the index
+ * does not have there.  That holds at a plain position (one bit set) and at a known site (two or three bits: a third allele) alike; a
+ * genome N (m == 0) and a mask of 15 give no event.
+ * Quality: the FASTQ byte of the same sequenced base (index rev ? L - 1 - s : s in the FASTQ's order) minus 33, from the sources of the
+ * genotype sums (the text entry points' raw block, salt_gpu_ws_set_quals' bytes, or none).  The event counts iff that quality is
+ * >= min_baseq, or there is no usable quality: no qualities on the call, a quality range that leaves the call's quality bytes, a byte
+ * outside 33 .. 126, SAM QUAL `*` in the host twin.
+ * alt: uint64[ref_len], three fields of 21 bits a position.  Field k = popcount(~m & 15 & ((1 << b) - 1)) is the rank of b among the bases
+ * outside the mask, in A C G T order; an event that counts adds 1 << 21 k.  Taking a batch back adds the two's complement, so the sums are
+ * modular: they do not depend on batch order, stream, workspace or GPU, and the tables of several GPUs add word by word.  A field wraps
+ * INTO ITS NEIGHBOUR beyond 2 097 151 observations of one base at one position.
+ * diff: this tally's OWN uint32[ref_len + 1] difference array by the rule of the coverage above (4.7): every M run [g, end) cut at ref_len
+ * adds 1 at g and takes 1 at end; depth[g] is the prefix sum, mod 2^32.  It is marked under THIS tally's MAPQ floor and counts every M
+ * column, whatever its base (a read's N too) and whatever its quality: the denominator is the coverage by counted records, not the
+ * bases that passed the quality filter.  It is not `--depth`'s array, whose floor is its own.
+ * Call, per position, in integers: with n_b the field of a base b outside the mask, b is CALLED at g iff n_b >= min_alt and
+ * 100 * n_b >= min_pct * depth[g].  A position is a candidate iff its mask is not 0 and a base is called there.
+ * Defaults (definitions): min_mapq 20 (the only tally whose default floor is not 0: mismapped paralogs are what makes false SNPs),
+ * min_baseq 20, min_alt 3, min_pct 20.  Ranges: min_mapq 0 .. 255, min_baseq 0 .. 93, min_alt 1 .. 2 097 151, min_pct 0 .. 100.
+ * File: one line per candidate, in genome order, no header line (salt-idx's SNP-file reader has no comment syntax):
+ *   "contig\tpos\talleles\tref\tdepth\tcA,cC,cG,cT\n"
+ * pos 1-based and contig-relative, the contig the one that contains g (salt_gpu_index_set_contigs' table); alleles the letters of the mask
+ * and of the called bases in A C G T order joined by '/' ("C/G"); ref the 2-bit genome's letter; depth = depth[g]; c* the count of a base
+ * outside the mask and `.` for a base in it.  Columns 1 .. 4 are salt-idx's SNP-file format; it ignores the rest.  With all_sites the
+ * index's sites (two or more bits in the mask) without a called base are printed too, their mask as alleles: the file is then a whole SNP
+ * file for the rebuilt index.
+ * While the tally is on, every entry point that leaves result rows adds its batch behind the kernels that finish the rows, on the same
+ * stream (k_disc_add: two 32-bit atomics per M run, the columns compared with the mixRef eight at a time, one 64-bit atomic per event that
+ * counts).  Both arrays belong to the device index and are shared by its workspaces and forks; they lie outside the image: 12 bytes a
+ * genome position (there is no narrower mode).  With the tally off no kernel is launched; before the first enable nothing is allocated,
+ * and every other call below fails with SALT_E_INVAL "never enabled".
+ *   salt_gpu_index_disc_enable      the first enable allocates and zeroes both arrays (SALT_E_NOMEM names the size); on = 0 stops and keeps
+ *                                   them; min_mapq 0 .. 255, min_baseq 0 .. 93 (above: SALT_E_INVAL).  No align call in flight.
+ *   salt_gpu_index_disc_reset       both arrays = 0
+ *   salt_gpu_index_disc_fetch       which = SALT_DISC_ALT: out is uint64[n], words [first, first + n) of alt, inside [0, ref_len);
+ *                                   which = SALT_DISC_DIFF: out is uint32[n], words of diff, inside [0, ref_len].  Synchronises the device.
+ *   salt_gpu_index_disc_add         array[first .. first + n) += in[0 .. n), by a kernel (64-bit words for alt, 32-bit for diff): how the
+ *                                   arrays of several GPUs are summed, chunk by chunk, and how any arrays can be put in front of the text
+ *                                   kernels.  A range that leaves the array is SALT_E_INVAL with the range in the message, for both.
+ *   salt_gpu_index_disc_text_begin  starts the lines of the arrays as they stand: tile_positions = genome positions scanned at a time, 0 =
+ *                                   the default (the text does not depend on it); bgzf != 0: whole BGZF blocks instead of text, deflated
+ *                                   on the device, without the end-of-file block.  Needs the contig table.
+ *   salt_gpu_index_disc_text_next   the next piece, in genome order: *data points into a buffer the index owns, valid until the next call on
+ *                                   the index; *n_bytes == 0: complete.  A tile without a line yields no piece.  The arrays are never
+ *                                   written by these two: the text can be made twice with the same bytes, and counting can go on.
+ *   salt_gpu_index_disc_text_seen   once the text is complete: seen[c] = 1 iff contig c has a line, else 0 (cap >= the contigs' number)
+ *   salt_gpu_ws_disc_uncount        takes back what the workspace's LAST successful align call added (the same kernel with the negated
+ *                                   addends and that call's quality source).  Nothing to take back: SALT_OK. */
+#define SALT_DISC_ALT  0
+#define SALT_DISC_DIFF 1
+#define SALT_DISC_FIELD_BITS 21
+#define SALT_DISC_FIELD_MAX  2097151u
+typedef struct {
+    uint32_t min_alt;           /* 1 .. 2 097 151 */
+    uint32_t min_pct;           /* 0 .. 100 */
+    int32_t  all_sites;         /* also the index's sites without a called base */
+    uint32_t tile_positions;    /* 0: default */
+    int32_t  bgzf;              /* the pieces are BGZF blocks */
+} salt_disc_text_opt_t;
+int  salt_gpu_index_disc_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq, uint32_t min_baseq);
+int  salt_gpu_index_disc_reset(salt_gpu_index_t *ix);
+int  salt_gpu_index_disc_fetch(salt_gpu_index_t *ix, int which, uint64_t first, uint64_t n, void *out);
+int  salt_gpu_index_disc_add(salt_gpu_index_t *ix, int which, uint64_t first, uint64_t n, const void *in);
+int  salt_gpu_index_disc_text_begin(salt_gpu_index_t *ix, const salt_disc_text_opt_t *opt);
+int  salt_gpu_index_disc_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes);
+int  salt_gpu_index_disc_text_seen(salt_gpu_index_t *ix, uint8_t *seen, uint64_t cap);
+int  salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws);
+
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,
  * strict 4-line FASTQ records: the block is parsed, aligned and formatted on the device; the host only hands over the text and

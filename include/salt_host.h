@@ -145,6 +145,25 @@ int64_t salt_gt_text(const salt_index_t *ix, const salt_gt_site_t *sites, uint64
 int64_t salt_gt_header(const salt_index_t *ix, const char *sample, char *out, uint64_t cap);
 const uint32_t *salt_gt_table(void);      /* SALT_GT_TABLE as this library holds it: 94 x 3 words, for bindings */
 
+/* SNP candidates off the index's sites (`salt --discover`): the host twins of the device's k_disc_add and of its flag and line kernels,
+ * written from the definition in salt_gpu.h; they share nothing with the kernels.  alt is uint64[n_pos] and diff uint32[n_pos + 1],
+ * n_pos = the index's ref_len (anything else is an error).
+ *   salt_disc_add_sam  both arrays += the record lines of this program's own SAM text: a record counts iff it is mapped (FLAG 0x4 clear)
+ *                      and MAPQ >= min_mapq; global position = contig offset + POS - 1; every M run, cut at ref_len, marks diff; an M
+ *                      column whose SEQ letter is A, C, G or T and not in the position's mixRef mask (mask != 0) is an event, and adds
+ *                      1 << 21 k (k: the letter's rank among the bases outside the mask) to alt iff QUAL[s] as printed minus 33 is
+ *                      >= min_baseq or the byte is outside 33 .. 126; QUAL `*` passes everywhere.  Header lines ('@') and empty lines
+ *                      are skipped; any other line that is no SAM record of this program's is an error; a line is checked whole before
+ *                      anything of it is added.  Returns the records that counted.
+ *   salt_disc_text     the candidate lines of the arrays: the call rule of salt_gpu.h and its line, no header; all_sites: also the
+ *                      index's sites without a called base.  Returns the bytes the text takes; the first min(cap, that) of them are in
+ *                      out (out may be NULL with cap 0: the size only).  seen, when given, has a byte per sequence of the index:
+ *                      1 iff the sequence has a line.  The model of the device's text, and what `salt` prints on the host path.
+ * Both return -1 with salt_host_last_error() set on failure. */
+int64_t salt_disc_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t min_baseq, uint64_t *alt, uint32_t *diff, uint64_t n_pos);
+int64_t salt_disc_text(const salt_index_t *ix, const uint64_t *alt, const uint32_t *diff, uint64_t n_pos, uint32_t min_alt, uint32_t min_pct, int all_sites,
+                       char *out, uint64_t cap, uint8_t *seen);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

@@ -619,6 +619,64 @@ def gt_header(index, sample=None):
     return out.raw[:n]
 
 
+DISC_ALT, DISC_DIFF = 0, 1              # the two arrays of the SNP candidates (SALT_DISC_ALT, SALT_DISC_DIFF)
+DISC_FIELD_BITS = 21                    # alt: three fields of 21 bits a position
+DISC_DEFAULTS = dict(min_mapq=20, min_baseq=20, min_alt=3, min_pct=20)
+
+
+def _disc_host():
+    h = host_lib()
+    h.salt_disc_add_sam.restype = ctypes.c_int64
+    h.salt_disc_add_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_disc_text.restype = ctypes.c_int64
+    h.salt_disc_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    return h
+
+
+def disc_add_sam(index, sam, min_mapq=20, min_baseq=20, alt=None, diff=None):
+    """The candidate arrays of this program's own SAM text (salt_disc_add_sam, the host twin of the device's k_disc_add): alt, uint64[ref_len]
+    of three 21-bit fields a position, and diff, the tally's own uint32[ref_len + 1] difference array.  alt, diff: the arrays of an earlier
+    call to add into.  Returns (alt, diff, records that counted)."""
+    h = _disc_host()
+    sam = bytes(sam)
+    n_pos = int(index.ref_len)
+    if alt is None:
+        alt = np.zeros(n_pos, dtype=np.uint64)
+    if diff is None:
+        diff = np.zeros(n_pos + 1, dtype=np.uint32)
+    if alt.dtype != np.uint64 or alt.shape != (n_pos,) or not alt.flags.c_contiguous or diff.dtype != np.uint32 or diff.shape != (n_pos + 1,) or not diff.flags.c_contiguous:
+        raise SaltError("disc_add_sam: alt must be a contiguous (%d,) uint64 array and diff a contiguous (%d,) uint32 array" % (n_pos, n_pos + 1))
+    n = h.salt_disc_add_sam(index._h, sam, len(sam), int(min_mapq), int(min_baseq), alt.ctypes.data, diff.ctypes.data, n_pos)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    return alt, diff, int(n)
+
+
+def disc_text(index, alt, diff, min_alt=3, min_pct=20, all_sites=False, seen=False):
+    """The candidate lines of the two arrays (salt_disc_text, the host twin of the device's flag and line kernels).  bytes; with seen=True
+    (bytes, a uint8 per sequence of the index: it has a line)."""
+    h = _disc_host()
+    alt = np.ascontiguousarray(alt, dtype=np.uint64)
+    diff = np.ascontiguousarray(diff, dtype=np.uint32)
+    if alt.ndim != 1 or diff.shape != (alt.shape[0] + 1,):
+        raise SaltError("disc_text: alt of shape (n,) and diff of shape (n + 1,)")
+    n_seqs = host_lib().salt_index_n_seqs(index._h)
+    marks = np.zeros(max(n_seqs, 1), dtype=np.uint8)
+    args = (index._h, alt.ctypes.data, diff.ctypes.data, alt.shape[0], int(min_alt), int(min_pct), 1 if all_sites else 0)
+    n = h.salt_disc_text(*args, None, 0, None)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_disc_text(*args, out, n, marks.ctypes.data) != n:
+        raise SaltError("disc_text: the size of the text changed between two calls")
+    return (out.raw[:n], marks[:n_seqs]) if seen else out.raw[:n]
+
+
+class _DiscTextOpt(ctypes.Structure):
+    _fields_ = [("min_alt", ctypes.c_uint32), ("min_pct", ctypes.c_uint32), ("all_sites", ctypes.c_int32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
+
+
 class _GtTextOpt(ctypes.Structure):
     _fields_ = [("tile_sites", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
@@ -979,6 +1037,66 @@ class GpuAligner:
                 break
             out.append(ctypes.string_at(p.value, n.value))
         return out if pieces else b"".join(out)
+
+    def disc_enable(self, on=True, min_mapq=20, min_baseq=20):
+        """Add, from now on, every align call on this aligner's device index (its forks included) to the index's SNP candidate arrays: a
+        base the mixRef does not have at its position, with a quality of at least min_baseq or none; records below min_mapq do not count.
+        The first enable allocates and zeroes both arrays (12 bytes a genome position); on=False stops and keeps them."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_disc_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_disc_enable(self._ix, 1 if on else 0, int(min_mapq), int(min_baseq)))
+
+    def disc_reset(self):
+        lib = gpu_lib()
+        lib.salt_gpu_index_disc_reset.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_index_disc_reset(self._ix))
+
+    def disc_fetch(self, which, first, n):
+        """Words [first, first + n) of alt (which = DISC_ALT: uint64, ref_len words) or of diff (DISC_DIFF: uint32, ref_len + 1 words).
+        Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_disc_fetch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        out = np.zeros(max(int(n), 0), dtype=np.uint32 if which == DISC_DIFF else np.uint64)
+        _gpu_check(lib.salt_gpu_index_disc_fetch(self._ix, int(which), int(first), int(n), out.ctypes.data))
+        return out
+
+    def disc_add(self, which, first, words):
+        """array[first .. first + len(words)) += words, on the device: how the arrays of several GPUs are summed."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_disc_add.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        words = np.ascontiguousarray(words, dtype=np.uint32 if which == DISC_DIFF else np.uint64)
+        if words.ndim != 1:
+            raise SaltError("disc_add: words of shape (n,)")
+        _gpu_check(lib.salt_gpu_index_disc_add(self._ix, int(which), int(first), words.shape[0], words.ctypes.data))
+
+    def disc_uncount(self):
+        """Takes back what this aligner's last align call added to the SNP candidate arrays."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_disc_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_ws_disc_uncount(self._ws))
+
+    def disc_text(self, min_alt=3, min_pct=20, all_sites=False, tile_positions=0, bgzf=False, pieces=False, seen=0):
+        """The candidate lines of the arrays as they stand, flagged, compacted and printed on the device; with bgzf whole BGZF blocks (no
+        end-of-file block).  pieces=True: the list of pieces as they left the device.  seen=N, the contigs' number: (that, a uint8 per contig: it has a line)."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_disc_text_begin.argtypes = [ctypes.c_void_p, ctypes.POINTER(_DiscTextOpt)]
+        lib.salt_gpu_index_disc_text_next.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        lib.salt_gpu_index_disc_text_seen.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        opt = _DiscTextOpt(int(min_alt), int(min_pct), 1 if all_sites else 0, int(tile_positions), 1 if bgzf else 0)
+        _gpu_check(lib.salt_gpu_index_disc_text_begin(self._ix, ctypes.byref(opt)))
+        out = []
+        while True:
+            p, n = ctypes.c_void_p(), ctypes.c_uint64()
+            _gpu_check(lib.salt_gpu_index_disc_text_next(self._ix, ctypes.byref(p), ctypes.byref(n)))
+            if n.value == 0:
+                break
+            out.append(ctypes.string_at(p.value, n.value))
+        text = out if pieces else b"".join(out)
+        if not seen:
+            return text
+        marks = np.zeros(int(seen), dtype=np.uint8)
+        _gpu_check(lib.salt_gpu_index_disc_text_seen(self._ix, marks.ctypes.data, marks.shape[0]))
+        return text, marks
 
     def errprof_enable(self, on=True, min_mapq=0):
         """Add, from now on, the base events of every align call on this aligner's device index (its forks included) to the index's error

@@ -32,10 +32,7 @@ __global__ void __launch_bounds__(256) k_depth_mark(DepthMark c)
         const salt_result_t *q = c.res + i;
         const TallyRow r = tally_row(q, 0, c.min_mapq);                            // (a leading soft clip moves in the read only)
         if (r.fate != TALLY_COUNTED) continue;
-        tally_m_runs(q, r, [&](uint64_t g, uint32_t, uint32_t len) {
-            const uint64_t end = g + len < c.ref_len ? g + len : (uint64_t)c.ref_len;      // cut at the genome's end
-            if (g < end) { atomicAdd(c.diff + g, c.delta); atomicAdd(c.diff + end, 0u - c.delta); }
-        });
+        tally_m_runs(q, r, [&](uint64_t g, uint32_t, uint32_t len) { tally_diff_mark(c.diff, c.ref_len, g, len, c.delta); });      // cut at the genome's end
     }
 }
 

@@ -74,12 +74,14 @@ struct salt_gpu_index {
     // difference array of ref_len + 1 words (the text state and its buffers come with the first salt_gpu_index_depth_text_begin);
     // errprof: E[2][512][95][4][4] and R[2][8] behind it, uint64; gt: salt_gt_site_t[snp_sites] as uint64 words, over the snp tally's site table
     // (built by whichever of the two is enabled first; the text state and its buffers come with the first salt_gpu_index_gt_text_begin).
-    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt;
+    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt, disc;
     DevBuf<SnpWin> d_snp_tab; DevBuf<uint32_t> d_snp_counts; uint64_t snp_win = 0; uint32_t snp_sites = 0;
     DevBuf<uint32_t> d_depth; DepthText *depth_text = nullptr;
     std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
     DevBuf<unsigned long long> d_errprof;
     DevBuf<unsigned long long> d_gt; GtText *gt_text = nullptr;
+    // disc: alt, uint64[ref_len] of three 21-bit fields, and the tally's own difference array of ref_len + 1 words (4.10)
+    DevBuf<unsigned long long> d_disc_alt; DevBuf<uint32_t> d_disc_diff; uint32_t disc_min_baseq = 0; DiscText *disc_text = nullptr;
 };
 
 // Every allocation below is a DevBuf / PinBuf: a new buffer is one field here and one reserve() or alloc() where it is sized.  Buffers that
@@ -134,8 +136,8 @@ struct salt_gpu_ws {
     // what the last align call added to each tally (n_rec 0: nothing) and on which stream, for the salt_gpu_ws_*_uncount calls; the error
     // profile's job carries its quality source
     template <class Job> struct LastJob { Job job{}; hipStream_t st = nullptr; };
-    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last;
-    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; }
+    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last; LastJob<DiscAdd> disc_last;
+    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; disc_last.job.n_rec = 0; }
     // the quality bytes of the error profile and the genotype sums: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
     // q_cur is the source of the call that is being queued (the text entry points set it to their raw block); d_quals holds a host call's bytes
     const uint8_t *q_next = nullptr; bool q_next_dev = false;
@@ -315,6 +317,7 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     hipSetDevice(ix->device);                                  // the tallies' DevBufs go with the index
     depth_text_free(ix->depth_text);
     gt_text_free(ix->gt_text);
+    disc_text_free(ix->disc_text);
     delete ix;
 }
 
@@ -484,7 +487,8 @@ template <class Job> static int tally_launch(salt_gpu_ws::LastJob<Job> &last, hi
 }
 // The launches behind the kernels that finish a batch's result rows, on the batch's stream, one per tally that is on: the rows' bases at the
 // SNP sites into the index's counts (k_snp_count), their M runs into its difference array (k_depth_mark), their base events into its error
-// profile (k_errprof), their bases and qualities at the SNP sites into its genotype sums (k_gt_add), the last two with the qualities of the
+// profile (k_errprof), their bases and qualities at the SNP sites into its genotype sums (k_gt_add), the bases the mixRef does not have into
+// its candidate arrays (k_disc_add), the last three with the qualities of the
 // call's source (ws->q_cur: the text block, salt_gpu_ws_set_quals' bytes, or
 // none).  Every entry point that leaves result rows passes here: single end at the end of align_resident_impl, paired end at the end of
 // pe_resident_impl (the rows are final only behind k_pe_final).
@@ -518,14 +522,22 @@ static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, con
         c.tab = ix->d_snp_tab; c.n_win = ix->snp_win; c.sums = ix->d_gt; c.n_sites = ix->snp_sites; c.min_mapq = ix->gt.min_mapq; c.pe = pe; c.delta = 1ull;
         if (const int rc = tally_launch(ws->gt_last, launch_gt_add, c, st)) return rc;
     }
+    if (ix->disc.on) {
+        DiscAdd c{};
+        c.res = res; c.seqs = seqs; c.offs = offs; c.n_rec = n_rec;
+        c.quals = ws->q_cur.quals; c.rec = ws->q_cur.rec; c.q_bytes = ws->q_cur.bytes;
+        c.ref = ix->view.ref; c.ref_len = ix->view.ref_len; c.alt = ix->d_disc_alt; c.diff = ix->d_disc_diff;
+        c.min_mapq = ix->disc.min_mapq; c.min_baseq = ix->disc_min_baseq; c.pe = pe; c.delta = 1ull;
+        if (const int rc = tally_launch(ws->disc_last, launch_disc_add, c, st)) return rc;
+    }
     return SALT_OK;
 }
 // salt_gpu_ws_set_quals' bytes on their way into a call.  A host-buffer call copies host bytes up beside its bases (quals_upload; with the
-// profile and the genotype sums off nothing is copied and they are dropped); every host-buffer or resident call then consumes the pointer (quals_take).
+// profile, the genotype sums and the candidate arrays off nothing is copied and they are dropped); every host-buffer or resident call then consumes the pointer (quals_take).
 static int quals_upload(salt_gpu_ws_t *ws, uint64_t bases, hipStream_t st)
 {
     if (!ws->q_next || ws->q_next_dev) return SALT_OK;
-    if (!ws->ix->errprof.on && !ws->ix->gt.on) { ws->q_next = nullptr; return SALT_OK; }
+    if (!ws->ix->errprof.on && !ws->ix->gt.on && !ws->ix->disc.on) { ws->q_next = nullptr; return SALT_OK; }
     if (int rc = ws->d_quals.reserve(bases + 64, st)) { ws->q_next = nullptr; return rc; }
     const hipError_t e = hipMemcpyAsync(ws->d_quals, ws->q_next, bases, hipMemcpyHostToDevice, st);
     ws->q_next = ws->d_quals; ws->q_next_dev = true;
@@ -2123,6 +2135,124 @@ extern "C" int salt_gpu_index_gt_text_next(salt_gpu_index_t *ix, const char **da
 extern "C" int salt_gpu_ws_gt_uncount(salt_gpu_ws_t *ws)
 {
     return tally_uncount(ws, &salt_gpu_ws::gt_last, launch_gt_add, ~0ull, &salt_gpu_index::d_gt, GT_NEVER);
+}
+
+// ---- SNP candidates off the index's sites ----
+static const char *const DISC_NEVER = "discover: the candidate arrays were never enabled on this index (salt_gpu_index_disc_enable)";
+
+// The first enable allocates and zeroes both arrays: 8 + 4 bytes a genome position.
+extern "C" int salt_gpu_index_disc_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq, uint32_t min_baseq)
+{
+    if (min_baseq > 93) return fail(SALT_E_INVAL, "discover: min_baseq " + std::to_string(min_baseq) + " is above 93, the largest base quality");
+    const int rc = tally_enable(ix, &salt_gpu_index::disc, "discover", on, min_mapq, [&]() -> int {
+        if (ix->d_disc_alt) return SALT_OK;
+        const uint64_t n = ix->view.ref_len;
+        if (n == 0) return fail(SALT_E_INVAL, "discover: the index has an empty genome");
+        const std::string size = std::to_string(n * 8 + (n + 1) * 4) + " bytes (8 + 4 per genome position)";
+        DevBuf<unsigned long long> alt; DevBuf<uint32_t> diff;
+        if (const int rc = alloc_zeroed(alt, n, "discover", "the candidate arrays: " + size)) return rc;
+        if (const int rc = alloc_zeroed(diff, n + 1, "discover", "the candidate arrays: " + size)) return rc;
+        ix->d_disc_alt.take(alt); ix->d_disc_diff.take(diff);                      // the index owns them from here
+        return SALT_OK;
+    });
+    if (rc == SALT_OK) ix->disc_min_baseq = min_baseq;
+    return rc;
+}
+
+extern "C" int salt_gpu_index_disc_reset(salt_gpu_index_t *ix)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_disc_alt) return fail(SALT_E_INVAL, DISC_NEVER);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemset(ix->d_disc_alt, 0, (uint64_t)ix->view.ref_len * 8));
+    HIPCHK(hipMemset(ix->d_disc_diff, 0, ((uint64_t)ix->view.ref_len + 1) * 4));
+    return SALT_OK;
+}
+
+// first + n words inside the array `which` names, or the message that names the range
+static int disc_range(const salt_gpu_index *ix, const char *what, int which, uint64_t first, uint64_t n)
+{
+    if (which != SALT_DISC_ALT && which != SALT_DISC_DIFF) return fail(SALT_E_INVAL, std::string("discover ") + what + ": array " + std::to_string(which) + " is neither SALT_DISC_ALT (0) nor SALT_DISC_DIFF (1)");
+    const uint64_t words = (uint64_t)ix->view.ref_len + (which == SALT_DISC_DIFF ? 1 : 0);
+    if (first > words || n > words - first)
+        return fail(SALT_E_INVAL, std::string("discover ") + what + ": words [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") leave " +
+                                  (which == SALT_DISC_DIFF ? "diff's" : "alt's") + " [0, " + std::to_string(words) + ")");
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_disc_fetch(salt_gpu_index_t *ix, int which, uint64_t first, uint64_t n, void *out)
+{
+    if (!ix || (!out && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_disc_alt) return fail(SALT_E_INVAL, DISC_NEVER);
+    if (const int rc = disc_range(ix, "fetch", which, first, n)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (n && which == SALT_DISC_ALT) HIPCHK(hipMemcpy(out, ix->d_disc_alt + first, n * 8, hipMemcpyDeviceToHost));
+    if (n && which == SALT_DISC_DIFF) HIPCHK(hipMemcpy(out, ix->d_disc_diff + first, n * 4, hipMemcpyDeviceToHost));
+    return SALT_OK;
+}
+
+// The adds are the 64-bit and 32-bit word sums of the genotype sums and of the coverage: one kernel a width.
+extern "C" int salt_gpu_index_disc_add(salt_gpu_index_t *ix, int which, uint64_t first, uint64_t n, const void *in)
+{
+    if (!ix || (!in && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_disc_alt) return fail(SALT_E_INVAL, DISC_NEVER);
+    if (const int rc = disc_range(ix, "add", which, first, n)) return rc;
+    if (n == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    const uint64_t bytes = n * (which == SALT_DISC_ALT ? 8 : 4);
+    DevBuf<uint8_t> d_in;
+    if (d_in.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, "discover add: no room for " + std::to_string(bytes) + " bytes of words to add"); }
+    HIPCHK(hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice));
+    if (which == SALT_DISC_ALT) HIPCHK(launch_gt_sum(ix->d_disc_alt + first, reinterpret_cast<const unsigned long long *>(d_in.p), n, nullptr));
+    else HIPCHK(launch_depth_add(ix->d_disc_diff + first, reinterpret_cast<const uint32_t *>(d_in.p), n, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_disc_text_begin(salt_gpu_index_t *ix, const salt_disc_text_opt_t *opt)
+{
+    if (!ix || !opt) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_disc_alt) return fail(SALT_E_INVAL, DISC_NEVER);
+    if (opt->min_alt < 1 || opt->min_alt > SALT_DISC_FIELD_MAX) return fail(SALT_E_INVAL, "discover text: min_alt " + std::to_string(opt->min_alt) + " is outside 1 .. 2097151");
+    if (opt->min_pct > 100) return fail(SALT_E_INVAL, "discover text: min_pct " + std::to_string(opt->min_pct) + " is above 100");
+    if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "discover text needs the contig table: call salt_gpu_index_set_contigs first");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!ix->disc_text) ix->disc_text = disc_text_new();
+    std::string err;
+    const int rc = disc_text_begin(ix->disc_text, ix->d_disc_alt, ix->d_disc_diff, ix->view.ref, ix->view.text, ix->view.ref_len, ix->view.c_seq_len,
+                                   ix->d_c_off, ix->d_c_name_off, ix->d_c_names, ix->n_contigs, ix->c_name_max, opt->min_alt, opt->min_pct, opt->all_sites,
+                                   opt->tile_positions, opt->bgzf, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_index_disc_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes)
+{
+    if (!ix || !data || !n_bytes) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_disc_alt) return fail(SALT_E_INVAL, DISC_NEVER);
+    if (!ix->disc_text) return fail(SALT_E_INVAL, "discover text: no text was begun (salt_gpu_index_disc_text_begin)");
+    HIPCHK(hipSetDevice(ix->device));
+    std::string err;
+    const int rc = disc_text_next(ix->disc_text, data, n_bytes, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_index_disc_text_seen(salt_gpu_index_t *ix, uint8_t *seen, uint64_t cap)
+{
+    if (!ix || !seen) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_disc_alt) return fail(SALT_E_INVAL, DISC_NEVER);
+    if (!ix->disc_text) return fail(SALT_E_INVAL, "discover text: no text was begun (salt_gpu_index_disc_text_begin)");
+    HIPCHK(hipSetDevice(ix->device));
+    std::string err;
+    const int rc = disc_text_seen(ix->disc_text, seen, cap, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws)
+{
+    return tally_uncount(ws, &salt_gpu_ws::disc_last, launch_disc_add, ~0ull, &salt_gpu_index::d_disc_alt, DISC_NEVER);
 }
 
 extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device)

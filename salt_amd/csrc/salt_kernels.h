@@ -318,6 +318,27 @@ int gt_text_begin(GtText *t, const unsigned long long *d_sums, const SnpWin *d_t
                   uint32_t tile_sites, int bgzf, std::string &err);
 int gt_text_next(GtText *t, const char **data, uint64_t *n_bytes, std::string &err);
 
+// ---- SNP candidates off the index's sites (salt_discover.hip) ----
+struct DiscAdd {                                                               // what k_disc_add reads (by value)
+    const salt_result_t *res; const uint8_t *seqs; const uint32_t *offs; uint32_t n_rec;      // the batch: rows, codes as sequenced, offsets
+    const uint8_t *quals; const FqRec *rec; uint64_t q_bytes;                  // the quality bytes, as GtAdd has them; a read without them passes the filter
+    const uint32_t *ref; uint32_t ref_len;                                     // the 4-bit mixRef, (ref_len + 7) / 8 words
+    unsigned long long *alt; uint32_t *diff;                                   // uint64[ref_len] of three 21-bit fields; this tally's own difference array, ref_len + 1 words
+    uint32_t min_mapq, min_baseq; int32_t pe;                                  // pe: rows of a paired-end batch (reverse iff strand == 1, soft clips)
+    unsigned long long delta;                                                  // 1; 2^64 - 1 negates the addends of both arrays: a batch's adds are taken back
+};
+hipError_t launch_disc_add(const DiscAdd &c, hipStream_t st);
+// The candidate lines of the two arrays, piece by piece (salt_gpu_index_disc_text_begin / _next): the device and page-locked buffers and
+// where the text stands.  Both return SALT_OK or an error code with the message in err.
+struct DiscText;
+DiscText *disc_text_new();
+void disc_text_free(DiscText *t);
+int disc_text_begin(DiscText *t, const unsigned long long *d_alt, const uint32_t *d_diff, const uint32_t *d_ref, const uint32_t *d_text, uint32_t ref_len, uint32_t text_len,
+                    const int64_t *d_c_off, const uint32_t *d_c_name_off, const char *d_c_names, int32_t n_contigs, uint32_t max_name,
+                    uint32_t min_alt, uint32_t min_pct, int all_sites, uint32_t tile_positions, int bgzf, std::string &err);
+int disc_text_next(DiscText *t, const char **data, uint64_t *n_bytes, std::string &err);
+int disc_text_seen(DiscText *t, uint8_t *seen, uint64_t cap, std::string &err);      // seen[c] = contig c has a line; the text must be complete
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

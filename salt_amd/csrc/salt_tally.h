@@ -55,4 +55,13 @@ template <class F> __device__ __forceinline__ void tally_m_runs(const salt_resul
     }
 }
 
+// An M run [g, g + len) into a difference array of ref_len + 1 words (DESIGN.md 4.7's rule; k_depth_mark and k_disc_add): delta at g, taken
+// again at the run's end, the run cut at the genome's end.  Returns that end (<= g: nothing of the run lies in the genome, nothing marked).
+__device__ __forceinline__ uint64_t tally_diff_mark(uint32_t *diff, uint32_t ref_len, uint64_t g, uint32_t len, uint32_t delta)
+{
+    const uint64_t end = g + len < ref_len ? g + len : (uint64_t)ref_len;
+    if (g < end) { atomicAdd(diff + g, delta); atomicAdd(diff + end, 0u - delta); }
+    return end;
+}
+
 } // namespace salt

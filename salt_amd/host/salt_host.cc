@@ -1074,3 +1074,95 @@ extern "C" int64_t salt_gt_header(const salt_index_t *ix, const char *sample, ch
 }
 
 extern "C" const uint32_t *salt_gt_table(void) { return &SALT_GT_TABLE[0][0]; }
+
+// ---------------------------------------------------------------------------------------------
+// SNP candidates off the index's sites: the host twin of k_disc_add and of the device's flag and line kernels (salt_discover.hip;
+// include/salt_gpu.h has the definition), written from that definition over this program's own SAM record lines.  It shares nothing with
+// anything under csrc/.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// one record line [l, e): its M runs into diff, its events into alt; 1 it contributed, 0 it did not (unmapped, below min_mapq), -1 with
+// g_err set.  The line is checked whole (head, QUAL's length, CIGAR) before anything is added.
+int disc_add_line(const salt_index *ix, const RefIds &ids, const char *l, const char *e, uint32_t min_mapq, uint32_t min_baseq, uint64_t *alt, uint32_t *diff)
+{
+    SamLine L; MRuns m; uint64_t g0;
+    const int h = twin_head(ix, ids, L, "discover: ", l, e, min_mapq, &g0);
+    if (h != 1) return h;
+    const char *seq = L.f[9], *qual = L.f[10]; const size_t l_seq = L.len(9), l_qual = L.len(10);
+    const bool no_qual = l_qual == 1 && qual[0] == '*' && l_seq != 1;
+    if (!no_qual && l_qual != l_seq) return L.bad("QUAL is neither * nor as long as SEQ"), -1;
+    if (!twin_cigar(L, g0, m)) return -1;
+    const uint64_t ref_len = ix->view.ref_len;
+    for (int r = 0; r < m.n; ++r) {
+        const uint64_t a = m.g[r], b = std::min<uint64_t>(a + m.len[r], ref_len);      // cut at the genome's end: not wrapped, not refused
+        if (a >= b) continue;
+        diff[a] += 1u; diff[b] -= 1u;
+        for (uint64_t g = a; g < b; ++g) {
+            const size_t s = m.s[r] + (size_t)(g - a);
+            const int base = base_code(seq[s]);
+            if (base < 0) continue;                                            // a read's N
+            const uint32_t mk = mask_at(ix, (uint32_t)g);
+            if (mk == 0 || ((mk >> base) & 1u)) continue;                      // N of the genome; a base the index has there
+            const uint8_t qb = no_qual ? 0 : (uint8_t)qual[s];
+            if (qb >= 33 && qb <= 126 && (uint32_t)qb - 33u < min_baseq) continue;      // a usable quality below the floor
+            int k = 0;
+            for (int c = 0; c < base; ++c) if (!((mk >> c) & 1u)) ++k;         // the rank of the base among those outside the mask
+            alt[g] += 1ull << (SALT_DISC_FIELD_BITS * k);
+        }
+    }
+    return 1;
+}
+
+bool disc_sizes(const salt_index *ix, uint64_t n_pos)
+{
+    if (n_pos == ix->view.ref_len) return true;
+    g_err = "discover: arrays for " + std::to_string(n_pos) + " positions, the index has " + std::to_string((uint64_t)ix->view.ref_len) + " (alt: ref_len words, diff: ref_len + 1)";
+    return false;
+}
+
+} // namespace
+
+extern "C" int64_t salt_disc_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint32_t min_baseq, uint64_t *alt, uint32_t *diff, uint64_t n_pos)
+{
+    if (!ix || (!sam && n) || !alt || !diff) { g_err = "discover: null argument"; return -1; }
+    if (!disc_sizes(ix, n_pos)) return -1;
+    const RefIds ids(ix);
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return disc_add_line(ix, ids, l, e, min_mapq, min_baseq, alt, diff); });
+}
+
+extern "C" int64_t salt_disc_text(const salt_index_t *ix, const uint64_t *alt, const uint32_t *diff, uint64_t n_pos, uint32_t min_alt, uint32_t min_pct, int all_sites,
+                                  char *out, uint64_t cap, uint8_t *seen)
+{
+    if (!ix || !alt || !diff || (!out && cap)) { g_err = "discover: null argument"; return -1; }
+    if (!disc_sizes(ix, n_pos)) return -1;
+    if (min_alt < 1 || min_alt > SALT_DISC_FIELD_MAX || min_pct > 100) { g_err = "discover: min_alt is 1 .. 2097151 and min_pct 0 .. 100"; return -1; }
+    DepthOut o{ out, cap };
+    static const char NT[] = "ACGT";
+    if (seen) memset(seen, 0, ix->anns.size());
+    uint32_t depth = 0;                                                // the prefix sum of diff, mod 2^32
+    size_t c = 0;                                                      // the last contig that begins at or in front of g
+    for (uint64_t g = 0; g < n_pos; ++g) {
+        depth += diff[g];
+        const uint64_t w = alt[g];
+        if (w == 0 && !all_sites) continue;
+        const uint32_t mk = mask_at(ix, (uint32_t)g);
+        if (mk == 0) continue;
+        uint32_t called = 0; uint64_t cnt[4] = { 0, 0, 0, 0 };
+        for (int b = 0, k = 0; b < 4; ++b) {
+            if ((mk >> b) & 1u) continue;
+            cnt[b] = (w >> (SALT_DISC_FIELD_BITS * k++)) & SALT_DISC_FIELD_MAX;
+            if (cnt[b] >= min_alt && 100 * cnt[b] >= (uint64_t)min_pct * depth) called |= 1u << b;
+        }
+        if (!called && !(all_sites && (mk & (mk - 1u)))) continue;
+        while (c + 1 < ix->anns.size() && (uint64_t)ix->anns[c + 1].offset <= g) ++c;
+        if (seen) seen[c] = 1;
+        o.puts(ix->anns[c].name); o.put('\t'); o.putu(g - (uint64_t)ix->anns[c].offset + 1); o.put('\t');
+        bool first = true;
+        for (int b = 0; b < 4; ++b) if (((mk | called) >> b) & 1u) { if (!first) o.put('/'); o.put(NT[b]); first = false; }
+        o.put('\t'); o.put(NT[(int64_t)g < ix->l_pac ? pac_at(ix, (uint32_t)g) : 0u]); o.put('\t'); o.putu(depth); o.put('\t');
+        for (int b = 0; b < 4; ++b) { if (b) o.put(','); if ((mk >> b) & 1u) o.put('.'); else o.putu(cnt[b]); }
+        o.put('\n');
+    }
+    return (int64_t)o.n;
+}

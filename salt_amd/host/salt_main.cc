@@ -92,6 +92,15 @@ extern "C" int salt_gpu_index_gt_add(salt_gpu_index_t *ix, uint64_t first_site, 
 extern "C" int salt_gpu_index_gt_text_begin(salt_gpu_index_t *ix, const salt_gt_text_opt_t *opt) __attribute__((weak));
 extern "C" int salt_gpu_index_gt_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
 extern "C" int salt_gpu_ws_gt_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
+// Likewise the SNP candidates off the sites (--discover): without the device's arrays and text kernels the arrays come from the SAM lines
+// (salt_disc_add_sam) and the lines from the host twin's printer (salt_disc_text).
+extern "C" int salt_gpu_index_disc_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq, uint32_t min_baseq) __attribute__((weak));
+extern "C" int salt_gpu_index_disc_fetch(salt_gpu_index_t *ix, int which, uint64_t first, uint64_t n, void *out) __attribute__((weak));
+extern "C" int salt_gpu_index_disc_add(salt_gpu_index_t *ix, int which, uint64_t first, uint64_t n, const void *in) __attribute__((weak));
+extern "C" int salt_gpu_index_disc_text_begin(salt_gpu_index_t *ix, const salt_disc_text_opt_t *opt) __attribute__((weak));
+extern "C" int salt_gpu_index_disc_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
+extern "C" int salt_gpu_index_disc_text_seen(salt_gpu_index_t *ix, uint8_t *seen, uint64_t cap) __attribute__((weak));
+extern "C" int salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
 namespace {
 
@@ -471,7 +480,7 @@ struct BamRun {
     const salt_index_t *ix = nullptr;
 } g_bam;
 
-// The four row tallies (--snp-counts, --depth, --error-profile, --genotype) run alike.  On the device the table belongs to each GPU's index and every
+// The five row tallies (--snp-counts, --depth, --error-profile, --genotype, --discover) run alike.  On the device the table belongs to each GPU's index and every
 // align call adds into it (salt_gpu_index_*_enable); a block the text path has aligned and then drops at a hand-over is taken back
 // (salt_gpu_ws_*_uncount): the host pipeline aligns those reads again.  Without the device's symbols the SAM lines of every block and
 // batch that is written go through the tally's host twin, one caller at a time.
@@ -493,15 +502,22 @@ struct ErrprofRun : TallyRun { bool full = false; std::vector<uint64_t> cells; u
 // --genotype FILE: a VCF record per SNP site of the index.  Like the profile, the host pipeline hands its batches' qualities over; after the
 // last block the other GPUs' sums are added into the first GPU's, whose kernels make the calls and print the records piece by piece.
 struct GtRun : TallyRun { bool gz = false; const char *sample = nullptr; std::vector<salt_gt_site_t> host_sums; } g_gt;
+// --discover FILE: SNP candidates off the index's sites, in salt-idx's SNP-file format.  Like the genotypes, the host pipeline hands its
+// batches' qualities over; after the last block the other GPUs' two arrays are added into the first GPU's, whose kernels flag, compact and
+// print the candidates piece by piece.  The only tally whose default MAPQ floor is not 0.
+struct DiscRun : TallyRun {
+    bool gz = false, all = false; uint32_t min_baseq = 20, min_alt = 3, min_pct = 20; std::vector<uint64_t> host_alt; std::vector<uint32_t> host_diff;
+    DiscRun() { min_mapq = 20; }
+} g_disc;
 
-// What differs between them where they run alike, in the order snp, depth, error profile, genotype.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
+// What differs between them where they run alike, in the order snp, depth, error profile, genotype, discover.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
 // how the file is opened; does: what a libsalt_gpu without the symbols does not do (the --polish refusal); symbols: this libsalt_gpu has
 // the device side; host_add: the twin over SAM lines (< 0: refused); uncount: the last align call's adds leave the device's table.
 struct Tally {
     TallyRun *run; const char *opt, *stem, *mode, *does;
     bool (*symbols)(); int64_t (*host_add)(const char *sam, size_t n); int (*uncount)(salt_gpu_ws_t *ws);
 };
-const Tally TALLIES[4] = {
+const Tally TALLIES[5] = {
     { &g_snp, "snp-counts", "snp", "w", "counts",
       [] { return salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount; },
       [](const char *sam, size_t n) { return salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites); }, salt_gpu_ws_snp_uncount },
@@ -514,6 +530,10 @@ const Tally TALLIES[4] = {
     { &g_gt, "genotype", "genotype", "wb", "sums and calls the genotypes",
       [] { return salt_gpu_index_gt_enable && salt_gpu_index_gt_fetch && salt_gpu_index_gt_add && salt_gpu_index_gt_text_begin && salt_gpu_index_gt_text_next && salt_gpu_ws_gt_uncount && salt_gpu_ws_set_quals; },
       [](const char *sam, size_t n) { return salt_gt_add_sam(g_gt.ix, sam, n, g_gt.min_mapq, g_gt.host_sums.data(), g_gt.host_sums.size()); }, salt_gpu_ws_gt_uncount },
+    { &g_disc, "discover", "discover", "wb", "counts and prints the candidates",
+      [] { return salt_gpu_index_disc_enable && salt_gpu_index_disc_fetch && salt_gpu_index_disc_add && salt_gpu_index_disc_text_begin && salt_gpu_index_disc_text_next && salt_gpu_index_disc_text_seen &&
+                  salt_gpu_ws_disc_uncount && salt_gpu_ws_set_quals; },
+      [](const char *sam, size_t n) { return salt_disc_add_sam(g_disc.ix, sam, n, g_disc.min_mapq, g_disc.min_baseq, g_disc.host_alt.data(), g_disc.host_diff.data(), g_disc.host_alt.size()); }, salt_gpu_ws_disc_uncount },
 };
 
 // the SAM lines of a block or batch that is about to be written, through every host twin that is on; false with the reason on stderr
@@ -652,6 +672,15 @@ int usage()
             "                                        the GPU); a name ending in .gz is written as BGZF [off]\n"
             "               --genotype-min-mapq <int>  --genotype: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
             "               --genotype-sample <name>   --genotype: the sample column's name [sample]\n"
+            "               --discover      <file>   write the SNP candidates OFF the index's sites: positions where the reads show a base\n"
+            "                                        the index does not have there, in salt-idx's SNP-file format (contig, pos, alleles, ref;\n"
+            "                                        then depth and counts), counted and printed on the GPU; .gz is written as BGZF [off]\n"
+            "               --discover-min-mapq <int>  --discover: records with a smaller MAPQ do not count, 0 .. 255 [20: the only tally\n"
+            "                                        whose default is not 0, because mismapped paralogs are what makes false SNPs]\n"
+            "               --discover-min-baseq <int> --discover: bases with a smaller quality do not count, 0 .. 93 [20]\n"
+            "               --discover-min-alt <int>   --discover: a base is called from this many observations, 1 .. 2097151 [3]\n"
+            "               --discover-min-pct <int>   --discover: ... that are at least this share of the depth, 0 .. 100 [20]\n"
+            "               --discover-all           --discover: also the index's sites without a called base: a whole SNP file\n"
             "           (-n -e -l -M -O -E -X are accepted and ignored like in the reference)\n\n");
     return 1;
 }
@@ -1367,7 +1396,9 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "mismatch", 1, 0, 'M' }, { "gapop", 1, 0, 'O' }, { "gapex", 1, 0, 'E' }, { "extend", 1, 0, 'X' }, { "gpus", 1, 0, 1000 }, { "bgzf", 0, 0, 1001 }, { "bam", 0, 0, 1002 }, { "polish", 2, 0, 1003 },
         { "snp-counts", 1, 0, 1004 }, { "snp-min-mapq", 1, 0, 1005 }, { "depth", 1, 0, 1006 }, { "depth-min-mapq", 1, 0, 1007 }, { "depth-window", 1, 0, 1008 },
         { "error-profile", 1, 0, 1009 }, { "error-profile-min-mapq", 1, 0, 1010 }, { "error-profile-full", 0, 0, 1011 },
-        { "genotype", 1, 0, 1012 }, { "genotype-min-mapq", 1, 0, 1013 }, { "genotype-sample", 1, 0, 1014 }, { 0, 0, 0, 0 } };
+        { "genotype", 1, 0, 1012 }, { "genotype-min-mapq", 1, 0, 1013 }, { "genotype-sample", 1, 0, 1014 },
+        { "discover", 1, 0, 1015 }, { "discover-min-mapq", 1, 0, 1016 }, { "discover-min-baseq", 1, 0, 1017 }, { "discover-min-alt", 1, 0, 1018 }, { "discover-min-pct", 1, 0, 1019 },
+        { "discover-all", 0, 0, 1020 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1390,8 +1421,8 @@ static int parse_options(int argc, char **argv, Opts &o)
             else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
             break;
         case 1004: g_snp.on = true; g_snp.fn = optarg; break;
-        case 1005: case 1007: case 1010: case 1013: {
-            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : 3];
+        case 1005: case 1007: case 1010: case 1013: case 1016: {
+            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : c == 1013 ? 3 : 4];
             char *end = nullptr; const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --%s-min-mapq %s: a MAPQ is a number from 0 to 255\n", t.stem, optarg); return 1; }
             t.run->min_mapq = (uint32_t)v;
@@ -1411,6 +1442,16 @@ static int parse_options(int argc, char **argv, Opts &o)
             if (!*optarg || strpbrk(optarg, "\t\n\r")) { fprintf(stderr, "[opt_parse]: --genotype-sample: a sample name is not empty and holds no tab or line end\n"); return 1; }
             g_gt.sample = optarg;
             break;
+        case 1015: g_disc.on = true; g_disc.fn = optarg; break;
+        case 1017: case 1018: case 1019: {
+            const char *name = c == 1017 ? "baseq" : c == 1018 ? "alt" : "pct";
+            const long lo = c == 1018 ? 1 : 0, hi = c == 1017 ? 93 : c == 1018 ? 2097151 : 100;
+            char *end = nullptr; errno = 0; const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || errno || v < lo || v > hi) { fprintf(stderr, "[opt_parse]: --discover-min-%s %s: a number from %ld to %ld\n", name, optarg, lo, hi); return 1; }
+            (c == 1017 ? g_disc.min_baseq : c == 1018 ? g_disc.min_alt : g_disc.min_pct) = (uint32_t)v;
+            break;
+        }
+        case 1020: g_disc.all = true; break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1440,6 +1481,8 @@ static int parse_options(int argc, char **argv, Opts &o)
     g_depth.gz = l > 3 && strcmp(g_depth.fn + l - 3, ".gz") == 0;
     const size_t lg = g_gt.on ? strlen(g_gt.fn) : 0;
     g_gt.gz = lg > 3 && strcmp(g_gt.fn + lg - 3, ".gz") == 0;
+    const size_t ld = g_disc.on ? strlen(g_disc.fn) : 0;
+    g_disc.gz = ld > 3 && strcmp(g_disc.fn + ld - 3, ".gz") == 0;
     return -1;
 }
 
@@ -1594,8 +1637,8 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (b->n() == 0) { std::unique_lock<std::mutex> lk(mu); done.push_back(std::move(b)); cv.notify_all(); continue; }
                 b->res.resize((size_t)b->n() * (pe ? 2 : 1));
                 double tg0 = now();
-                std::vector<uint8_t> iqual;                      // --error-profile or --genotype on the device: the batch's qualities, parallel to the bases
-                if ((g_errprof.on && g_errprof.device) || (g_gt.on && g_gt.device)) {
+                std::vector<uint8_t> iqual;                      // --error-profile, --genotype or --discover on the device: the batch's qualities, parallel to the bases
+                if ((g_errprof.on && g_errprof.device) || (g_gt.on && g_gt.device) || (g_disc.on && g_disc.device)) {
                     batch_quals(*b, pe ? b->mate.get() : nullptr, iqual);
                     if (salt_gpu_ws_set_quals(ws[(size_t)g], iqual.data(), 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 }
@@ -1605,7 +1648,7 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
-                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host()) {
+                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host() || g_disc.host()) {
                     bool good = true;
                     for (const std::string &piece : b->sam) good = good && host_twins_add(piece.data(), piece.size());
                     if (!good) { set_failed(); break; }
@@ -1895,6 +1938,88 @@ static bool gt_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_t
     return true;
 }
 
+// --discover, before the first block: the arrays on on every GPU's index, or the host's arrays
+static bool disc_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_disc.on) return true;
+    g_disc.ix = ix;
+    const size_t ref_len = salt_index_host_view(ix)->ref_len;
+    if (!g_disc.device) { g_disc.host_alt.assign(ref_len, 0ull); g_disc.host_diff.assign(ref_len + 1, 0u); return true; }
+    for (salt_gpu_index_t *g : gix)
+        if (salt_gpu_index_disc_enable(g, 1, g_disc.min_mapq, g_disc.min_baseq)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    return true;
+}
+
+// --discover, after the last block of a run that succeeded: both arrays of the other GPUs are added into the first one's, in chunks through
+// a page-locked buffer, and its kernels flag, compact and print the candidates piece by piece; on the host the twin's printer does.  A .gz
+// file ends with the BGZF end-of-file block.  salt-idx lays the i-th group of lines over the i-th contig whatever its name: a contig without
+// a line shifts those behind it, which is said on stderr.
+static bool disc_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &C)
+{
+    if (!g_disc.on) return true;
+    FILE *f = g_disc.fp;
+    uint64_t text_bytes = 0, file_bytes = 0;
+    bool ok = true;
+    const uint64_t ref_len = salt_index_host_view(ix)->ref_len;
+    std::vector<uint8_t> seen((size_t)C.n() + 1, 0);
+    if (g_disc.device) {
+        const uint64_t chunk = std::min<uint64_t>(ref_len + 1, 4u << 20);              // 32 MiB of alt at a time
+        auto gpu_fail = [&]() { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; };
+        if (gix.size() > 1) {
+            void *buf = nullptr;
+            if (salt_gpu_host_alloc(chunk * 8, &buf)) return gpu_fail();
+            for (size_t k = 1; k < gix.size() && ok; ++k)
+                for (int which = SALT_DISC_ALT; which <= SALT_DISC_DIFF && ok; ++which) {
+                    const uint64_t words = ref_len + (which == SALT_DISC_DIFF ? 1 : 0);
+                    for (uint64_t at = 0; at < words && ok; at += chunk) {
+                        const uint64_t n = std::min(chunk, words - at);
+                        ok = salt_gpu_index_disc_fetch(gix[k], which, at, n, buf) == 0 && salt_gpu_index_disc_add(gix[0], which, at, n, buf) == 0;
+                    }
+                }
+            if (!ok) gpu_fail();
+            salt_gpu_host_free(buf);
+            if (!ok) return false;
+        }
+        salt_disc_text_opt_t to; to.min_alt = g_disc.min_alt; to.min_pct = g_disc.min_pct; to.all_sites = g_disc.all ? 1 : 0; to.tile_positions = 0; to.bgzf = g_disc.gz ? 1 : 0;
+        if (salt_gpu_index_disc_enable(gix[0], 0, g_disc.min_mapq, g_disc.min_baseq) || salt_gpu_index_set_contigs(gix[0], C.n(), C.off.data(), C.nm.data()) ||
+            salt_gpu_index_disc_text_begin(gix[0], &to)) return gpu_fail();
+        for (;;) {
+            const char *data = nullptr; uint64_t n = 0;
+            if (salt_gpu_index_disc_text_next(gix[0], &data, &n)) return gpu_fail();
+            if (n == 0) break;
+            ok = ok && fwrite(data, 1, (size_t)n, f) == n;
+            file_bytes += n; text_bytes += g_disc.gz ? bgzf_text_bytes(data, n) : n;
+        }
+        if (salt_gpu_index_disc_text_seen(gix[0], seen.data(), seen.size())) return gpu_fail();
+    } else {
+        const int64_t need = salt_disc_text(ix, g_disc.host_alt.data(), g_disc.host_diff.data(), ref_len, g_disc.min_alt, g_disc.min_pct, g_disc.all, nullptr, 0, nullptr);
+        std::string text(need > 0 ? (size_t)need : 0, '\0'), z;
+        if (need < 0 || salt_disc_text(ix, g_disc.host_alt.data(), g_disc.host_diff.data(), ref_len, g_disc.min_alt, g_disc.min_pct, g_disc.all, &text[0], (uint64_t)need, seen.data()) != need) {
+            fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false;
+        }
+        if (g_disc.gz && !text.empty() && !bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] --discover: no BGZF blocks for the text\n"); return false; }
+        const std::string &out = g_disc.gz ? z : text;
+        ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+        text_bytes = text.size(); file_bytes = out.size();
+    }
+    if (g_disc.gz) { ok = ok && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, f) == sizeof BGZF_EOF; file_bytes += sizeof BGZF_EOF; }
+    ok = !ferror(f) && fclose(f) == 0 && ok;
+    g_disc.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --discover: write error on %s\n", g_disc.fn); return false; }
+    fprintf(stderr, "[salt] discover: %s, MAPQ >= %u, base quality >= %u, min_alt %u, min_pct %u%s, %llu bytes of text -> %s (%llu bytes)\n",
+            g_disc.device ? "counted and printed on the device" : "counted on the host from the SAM lines", g_disc.min_mapq, g_disc.min_baseq, g_disc.min_alt, g_disc.min_pct,
+            g_disc.all ? ", all sites" : "", (unsigned long long)text_bytes, g_disc.fn, (unsigned long long)file_bytes);
+    int n_without = 0, first_without = -1;
+    for (int c = 0; c < C.n(); ++c) if (!seen[(size_t)c]) { if (first_without < 0) first_without = c; ++n_without; }
+    if (n_without) {
+        int64_t off = 0; int32_t len = 0; const char *name = "?";
+        salt_index_seq(ix, first_without, &off, &len, &name);
+        fprintf(stderr, "[salt] discover: %d of %d contigs have no line in %s, the first is %s: salt-idx lays the i-th group of lines over the i-th contig whatever its name, "
+                        "so the groups behind it would shift\n", n_without, C.n(), g_disc.fn, name);
+    }
+    return true;
+}
+
 } // namespace
 
 // options; choice of path (TextPlan); index load and attach; header; text path; host pipeline
@@ -1943,16 +2068,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
-    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
+    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix) || !disc_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs)) ? 1 : rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs)) ? 1 : rc); }
         header_out = true;
     }
     const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
-    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs)) ? 1 : rc);
+    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs)) ? 1 : rc);
 }
