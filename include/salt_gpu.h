@@ -568,6 +568,25 @@ int  salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t 
  *   [10], [11] 0 */
 int  salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t n, const uint32_t *queries, uint32_t *out);
 
+/* Unit entry of the text stage (tests): the FASTQ scan, k_pack's records and k_sam_len / k_sam_write or k_bam_len / k_bam_write, on result rows
+ * of the caller's choosing.  It runs the stages of salt_gpu_align_se_text (pe == NULL: one block, fastq2 ignored) or salt_gpu_align_pe_text
+ * (pe given: two blocks, row 2p + m belongs to mate m of pair p) through the same two functions -- the parse stage and the output stage --
+ * with the align kernels between them replaced by k_pack and a copy of rows[0 .. n_rows) into the workspace's result rows.  Output as the
+ * production entries give it: *out points into the workspace's page-locked buffer, salt_gpu_ws_set_sam_bam and salt_gpu_ws_set_sam_bgzf
+ * are honoured, *n_records = the number of parsed records (both mates counted).  With salt_gpu_ws_set_polish on: SALT_E_INVAL.
+ * The rows are checked on the host before a kernel reads one, with the read lengths the parse kernels found; SALT_E_INVAL and a message
+ * "text rows: ..." (the row is named) for:
+ *   n_rows different from the number of parsed records; a read longer than SALT_MAX_READ_LEN;
+ *   any row:       n_hits[0] + n_hits[1] > SALT_MAX_HITS, a hit_n_cigar of a listed hit > SALT_MAX_CIGAR_OPS, a listed hit's pos >= ref_len
+ *                  (paired end prints XA for an unmapped mate too);
+ *   a mapped row (pos != 0xFFFFFFFF; single end: and not skipped -- the paired-end kernels do not read `skipped`):
+ *                  n_cigar > SALT_MAX_CIGAR_OPS, pos >= ref_len, pos + (sum of M and D) > ref_len, seq_start + (sum of M and I) > the read's
+ *                  length, seq_end >= the read's length.
+ * The tallies (SNP counts, depth, error profile, genotype, discover) do not see these rows. */
+int  salt_gpu_diag_text_rows(salt_gpu_ws_t *ws, const salt_text_opt_t *topt, const salt_pe_opt_t *pe, const char *fastq1, uint64_t n1_bytes,
+                             const char *fastq2, uint64_t n2_bytes, const salt_result_t *rows, uint32_t n_rows,
+                             const char **out, uint64_t *out_bytes, uint32_t *n_records);
+
 /* Work-queue counters of the LAST batch (diagnostics): [0] reads k_light handed to k_heavy, [2] reads whose gapped pass
  * was deferred, [5] k_gap items (32 candidates each), [6] k_cigar items, [7] k_cigar's queue head; [1] / [3] the longest R / C list among
  * the 64 segments of the seed walk queues; [4] reads the quarter-wave light kernel (k_light4: four reads a wave, for reads of at most 120

@@ -891,6 +891,30 @@ class GpuAligner:
                                               ctypes.byref(out), ctypes.byref(n), ctypes.byref(pairs)))
         return ctypes.string_at(out.value, n.value) if n.value else b"", pairs.value
 
+    def _text_rows(self, opt, paired, fastq1, fastq2, rows):
+        lib = gpu_lib()
+        lib.salt_gpu_diag_text_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(_TextOpt), ctypes.POINTER(_PeOpt), ctypes.c_char_p, ctypes.c_uint64,
+                                                ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        rows = np.ascontiguousarray(rows, dtype=RESULT_DTYPE)
+        fastq1, fastq2 = bytes(fastq1), bytes(fastq2)
+        pe, to = opt._pe(), _TextOpt(opt.print_xa_cigar, opt.print_nm_md, opt.rg_id.encode() if opt.rg_id else None)
+        out, n, recs = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint32()
+        _gpu_check(lib.salt_gpu_diag_text_rows(self._ws, ctypes.byref(to), ctypes.byref(pe) if paired else None, fastq1, len(fastq1), fastq2, len(fastq2),
+                                               rows.ctypes.data if len(rows) else None, len(rows), ctypes.byref(out), ctypes.byref(n), ctypes.byref(recs)))
+        return ctypes.string_at(out.value, n.value) if n.value else b"", recs.value
+
+    def text_from_rows(self, opt, fastq, rows):
+        """The text stage alone (salt_gpu_diag_text_rows): one FASTQ block and one RESULT_DTYPE row per record of it -> (what align_se_text
+        would return had the aligner produced these rows; records).  The library refuses rows that lie outside the genome or the reads."""
+        return self._text_rows(opt, False, fastq, b"", rows)
+
+    def text_from_rows_pe(self, opt, index, fastq1, fastq2, rows):
+        """The same for two blocks of mates: rows[2p], rows[2p + 1] are the mates of pair p -> (what align_pe_text would return; records,
+        both mates counted)."""
+        self.set_pac(index)
+        return self._text_rows(opt, True, fastq1, fastq2, rows)
+
     def align_pe_resident(self, opt, index, n_pairs, max_read_len, d_seqs, d_offs, d_results, stream=0):
         lib = gpu_lib()
         self.set_pac(index)
@@ -1244,8 +1268,9 @@ for _i, _c in enumerate("ACGT"):
 
 
 def read_fastq(path):
-    """4-line FASTQ (optionally .gz) -> names, seqs (codes), offs, quals.  Names end at the first
-    blank and lose a trailing /1 or /2 like trim_readno (query.c:139-143)."""
+    """4-line FASTQ (optionally .gz) -> names, seqs (codes), offs, quals.  A name ends at the first white-space
+    byte of C's isspace() behind the '@', as kseq and the device parser end it (so it is empty when the header
+    begins with one), and loses a trailing /digit when longer than 2 like trim_readno (query.c:139-143)."""
     import gzip
     op = gzip.open if path.endswith(".gz") else open
     names, quals, chunks, offs = [], [], [], [0]
@@ -1259,7 +1284,11 @@ def read_fastq(path):
             s = f.readline().rstrip(b"\r\n")
             f.readline()
             q = f.readline().rstrip(b"\r\n")
-            nm = h[1:].split()[0] if len(h) > 1 else b""
+            nm = h[1:]
+            for k, c in enumerate(nm):                    # up to the first white space of isspace(): the name may be empty
+                if c in b" \t\n\v\f\r":
+                    nm = nm[:k]
+                    break
             if len(nm) > 2 and nm[-2:-1] == b"/" and nm[-1:].isdigit():
                 nm = nm[:-2]
             names.append(nm)

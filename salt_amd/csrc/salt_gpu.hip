@@ -1182,18 +1182,12 @@ static int text_emit(salt_gpu_ws_t *ws, const salt_text_opt_t *to, const salt_pe
     return SALT_OK;
 }
 
-static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, const uint8_t *d_src, uint64_t n_bytes, int add_newline,
-                        const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
+// The parse stage of a single-end text call: the block to the device (from the host, or n_src bytes of d_src with a newline behind them when
+// n_bytes says so), its lines, records, offsets and codes.  *n_rec = 0: a block without a record, and nothing further was queued.
+static int text_parse_se(salt_gpu_ws_t *ws, const char *fastq, const uint8_t *d_src, uint64_t n_src, uint64_t n_bytes, hipStream_t st, TextTrace &tr,
+                         uint32_t *n_rec_out, uint32_t *max_len)
 {
-    const uint64_t n_src = n_bytes;
-    if (d_src && add_newline) ++n_bytes;
-    ws->forget_last();
-    salt_gpu_index *ix = ws->ix;
-    if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
-    HIPCHK(hipSetDevice(ix->device));
-    hipStream_t st = ws->stream;
-    TextTrace tr; tr.on = ws->text_calls++ == 0 && getenv("SALT_TEXT_TRACE");
-    tr.mark();
+    *n_rec_out = 0;
     // ---- the raw block and its lines ----
     int rc = reserve_parse(ws, n_bytes, st);
     if (rc) return rc;
@@ -1202,7 +1196,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
     if (d_src) {
         static const char nl = '\n';
         HIPCHK(hipMemcpyAsync(ws->d_raw, d_src, n_src, hipMemcpyDeviceToDevice, st));
-        if (add_newline) HIPCHK(hipMemcpyAsync(ws->d_raw + n_src, &nl, 1, hipMemcpyHostToDevice, st));
+        if (n_bytes > n_src) HIPCHK(hipMemcpyAsync(ws->d_raw + n_src, &nl, 1, hipMemcpyHostToDevice, st));
     } else
         HIPCHK(hipMemcpyAsync(ws->d_raw, fastq, n_bytes, hipMemcpyHostToDevice, st));
     // newline count first: the line table is sized by it
@@ -1220,11 +1214,30 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
     // ---- records, offsets, codes ----
     if ((rc = reserve_records(ws))) return rc;
     HIPCHK(launch_fq_parse(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, ws->d_scan, ws->d_scan.cap, st));
-    uint32_t max_len = 0;
-    if ((rc = text_codes(ws, n_rec, "block", st, &max_len))) return rc;
+    if ((rc = text_codes(ws, n_rec, "block", st, max_len))) return rc;
+    ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = n_bytes;      // the error profile reads the qualities where they lie
+    *n_rec_out = n_rec;
+    return SALT_OK;
+}
+
+static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_text_opt_t *to, const char *fastq, const uint8_t *d_src, uint64_t n_bytes, int add_newline,
+                        const char **sam, uint64_t *sam_bytes, uint32_t *n_reads)
+{
+    const uint64_t n_src = n_bytes;
+    if (d_src && add_newline) ++n_bytes;
+    ws->forget_last();
+    salt_gpu_index *ix = ws->ix;
+    if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = ws->stream;
+    TextTrace tr; tr.on = ws->text_calls++ == 0 && getenv("SALT_TEXT_TRACE");
+    tr.mark();
+    uint32_t n_rec = 0, max_len = 0;
+    int rc = text_parse_se(ws, fastq, d_src, n_src, n_bytes, st, tr, &n_rec, &max_len);
+    if (rc) return rc;
+    if (n_rec == 0) return SALT_OK;
     // ---- align ----
     tr.mark();
-    ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = n_bytes;      // the error profile reads the qualities where they lie
     if ((rc = align_resident_impl(ws, o, n_rec, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st, 0))) return rc;
     tr.mark();
     // ---- SAM text ----
@@ -1239,23 +1252,11 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
     return SALT_OK;
 }
 
-// Paired end: two blocks holding the same number of whole 4-line records (mates in file order); the SAM block holds both records of
-// every pair, each followed by the reference's empty line (alnpe.c:640-648).
-extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, const salt_text_opt_t *to,
-                                      const char *fastq1, uint64_t n1, const char *fastq2, uint64_t n2,
-                                      const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
+// The parse stage of a paired-end text call: both blocks to the device, their lines, the mates' records interleaved (record 2p + m = mate m
+// of pair p), offsets and codes.  *n_pairs = 0: blocks without a record, and nothing further was queued.
+static int text_parse_pe(salt_gpu_ws_t *ws, const char *fastq1, uint64_t n1, const char *fastq2, uint64_t n2, hipStream_t st, uint32_t *n_pairs, uint32_t *max_len)
 {
-    if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
-    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->forget_last();
-    if (n1 == 0 && n2 == 0) return SALT_OK;
-    if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
-    if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
-    if (fastq1[n1 - 1] != '\n' || fastq2[n2 - 1] != '\n') return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
-    salt_gpu_index *ix = ws->ix;
-    if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
-    if (!ix->d_pac) return fail(SALT_E_INVAL, "paired end needs the 2-bit genome: call salt_gpu_index_set_pac first");
-    HIPCHK(hipSetDevice(ix->device));
-    hipStream_t st = ws->stream;
+    *n_pairs = 0;
     const uint64_t b2 = (n1 + 3) & ~3ull;                      // block 2 behind block 1, on a word boundary
     int rc = reserve_parse(ws, b2 + n2, st);
     if (rc) return rc;
@@ -1284,13 +1285,110 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     HIPCHK(launch_fq_parse_mate(ws->d_raw, 0u, lines1, n, 0u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, (uint32_t)b2, lines2, n, 1u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
     HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->d_scan.cap, st));
-    uint32_t max_len = 0;
-    if ((rc = text_codes(ws, n_rec, "blocks", st, &max_len))) return rc;
+    if ((rc = text_codes(ws, n_rec, "blocks", st, max_len))) return rc;
     ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = b2 + n2;      // both blocks; a mate's qual_off counts from d_raw
+    *n_pairs = n;
+    return SALT_OK;
+}
+
+// Paired end: two blocks holding the same number of whole 4-line records (mates in file order); the SAM block holds both records of
+// every pair, each followed by the reference's empty line (alnpe.c:640-648).
+extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, const salt_text_opt_t *to,
+                                      const char *fastq1, uint64_t n1, const char *fastq2, uint64_t n2,
+                                      const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
+{
+    if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
+    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->forget_last();
+    if (n1 == 0 && n2 == 0) return SALT_OK;
+    if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
+    if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
+    if (fastq1[n1 - 1] != '\n' || fastq2[n2 - 1] != '\n') return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
+    salt_gpu_index *ix = ws->ix;
+    if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
+    if (!ix->d_pac) return fail(SALT_E_INVAL, "paired end needs the 2-bit genome: call salt_gpu_index_set_pac first");
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = ws->stream;
+    uint32_t n = 0, max_len = 0;
+    int rc = text_parse_pe(ws, fastq1, n1, fastq2, n2, st, &n, &max_len);
+    if (rc) return rc;
+    if (n == 0) return SALT_OK;
+    const uint32_t n_rec = 2 * n;
     if ((rc = pe_resident_impl(ws, o, pe, n, max_len, ws->d_seqs, ws->d_offs, ws->d_results, st))) return rc;
     TextTrace tr;                                               // off: the stage clocks are single end's
     if ((rc = text_emit(ws, to, pe, n_rec, max_len, st, tr, sam, sam_bytes))) return rc;
     *n_pairs = n;
+    return SALT_OK;
+}
+
+// One row of salt_gpu_diag_text_rows against what the record kernels index with it: empty = the row is in range.  L: the read's length.
+// pe: the paired-end kernels never read `skipped` (mapped is pos alone there), so only a single-end row is excused by it.
+static std::string text_row_fault(const salt_result_t &q, uint32_t L, uint32_t ref_len, bool pe)
+{
+    const uint32_t n_hits = (uint32_t)q.n_hits[0] + q.n_hits[1];
+    if (n_hits > SALT_MAX_HITS) return "n_hits[0] + n_hits[1] = " + std::to_string(n_hits) + " is more than SALT_MAX_HITS";
+    for (uint32_t s = 0, h = 0; s < 2; ++s)
+        for (uint32_t k = 0; k < q.n_hits[s]; ++k, ++h) {
+            if (q.hit_n_cigar[h] > SALT_MAX_CIGAR_OPS) return "hit_n_cigar[" + std::to_string(h) + "] is more than SALT_MAX_CIGAR_OPS";
+            if (q.hits[s][k].pos >= ref_len) return "the pos of hit " + std::to_string(h) + " lies beyond the genome";
+        }
+    if ((!pe && q.skipped) || q.pos == 0xFFFFFFFFu) return "";
+    if (q.n_cigar > SALT_MAX_CIGAR_OPS) return "n_cigar is more than SALT_MAX_CIGAR_OPS";
+    if (q.pos >= ref_len) return "pos lies beyond the genome";
+    uint64_t on_ref = 0, on_read = 0;
+    for (uint32_t c = 0; c < q.n_cigar; ++c) {
+        const uint32_t n = q.cigar[c] >> 4, op = q.cigar[c] & 15u;
+        if (op == 0) { on_ref += n; on_read += n; } else if (op == 1) on_read += n; else if (op == 2) on_ref += n;
+    }
+    if ((uint64_t)q.pos + on_ref > ref_len) return "pos + the CIGAR's M and D operations end beyond the genome";
+    if ((uint64_t)q.seq_start + on_read > L) return "seq_start + the CIGAR's M and I operations end beyond the read";
+    if (q.seq_end >= L) return "seq_end lies beyond the read";
+    return "";
+}
+
+// The text stage on rows of the caller's (include/salt_gpu.h): the parse stage and text_emit of the production entry points, and between them
+// k_pack and a copy where those align.  Every row is checked on the host against the lengths the parse kernels found: no kernel sees a row
+// that would take it outside the genome, the read or the row itself.
+extern "C" int salt_gpu_diag_text_rows(salt_gpu_ws_t *ws, const salt_text_opt_t *to, const salt_pe_opt_t *pe, const char *fastq1, uint64_t n1,
+                                       const char *fastq2, uint64_t n2, const salt_result_t *rows, uint32_t n_rows,
+                                       const char **out, uint64_t *out_bytes, uint32_t *n_records)
+{
+    if (!ws || !to || !fastq1 || (pe && !fastq2) || (n_rows && !rows) || !out || !out_bytes || !n_records) return fail(SALT_E_INVAL, "null argument");
+    *out = nullptr; *out_bytes = 0; *n_records = 0; ws->forget_last();
+    if (ws->polish) return fail(SALT_E_INVAL, "text rows: the polish stage is not driven from rows (salt_gpu_ws_set_polish is on)");
+    if (n1 == 0 || (pe && n2 == 0)) return fail(SALT_E_INVAL, "text rows: an empty FASTQ block");
+    if (n1 + (pe ? n2 : 0) >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
+    if (fastq1[n1 - 1] != '\n' || (pe && fastq2[n2 - 1] != '\n')) return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
+    salt_gpu_index *ix = ws->ix;
+    if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = ws->stream;
+    TextTrace tr;                                               // off
+    uint32_t n_rec = 0, max_len = 0;
+    int rc;
+    if (pe) { uint32_t n = 0; rc = text_parse_pe(ws, fastq1, n1, fastq2, n2, st, &n, &max_len); n_rec = 2 * n; }
+    else rc = text_parse_se(ws, fastq1, nullptr, n1, n1, st, tr, &n_rec, &max_len);
+    if (rc) return rc;
+    if (n_rows != n_rec) return fail(SALT_E_INVAL, "text rows: " + std::to_string(n_rows) + " rows for " + std::to_string(n_rec) + " parsed records");
+    if (n_rec == 0) return SALT_OK;
+    if (max_len > SALT_MAX_READ_LEN) return fail(SALT_E_INVAL, "read longer than SALT_MAX_READ_LEN (512)");
+    // ---- the rows, checked against the parsed lengths before anything reads them ----
+    std::vector<uint32_t> offs((size_t)n_rec + 1);
+    HIPCHK(hipMemcpyAsync(offs.data(), ws->d_offs, ((uint64_t)n_rec + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n_rec; ++i) {
+        const std::string what = text_row_fault(rows[i], offs[i + 1] - offs[i], ix->view.ref_len, pe != nullptr);
+        if (!what.empty()) return fail(SALT_E_INVAL, "text rows: row " + std::to_string(i) + ": " + what);
+    }
+    // ---- where the align kernels stand: k_pack's records (the MD / NM / XV words of k_sam_len), then the rows ----
+    const PackGeom pg = PackGeom::make(max_len);
+    if ((rc = reserve_pack(ws, n_rec, pg, st))) return rc;
+    launch_pack(pg, n_rec, ws->d_seqs, ws->d_offs, ws->d_pm, ws->d_tb, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ws->d_results, rows, (uint64_t)n_rec * sizeof(salt_result_t), hipMemcpyHostToDevice, st));
+    if (pe && ws->d_pctl) HIPCHK(hipMemsetAsync(ws->d_pctl, 0, sizeof(PeCtl), st));      // no rescue ran: text_emit reads its overflow count
+    HIPCHK(hipStreamSynchronize(st));                           // the rows are the caller's memory
+    if ((rc = text_emit(ws, to, pe, n_rec, max_len, st, tr, out, out_bytes))) return rc;
+    *n_records = n_rec;
     return SALT_OK;
 }
 
