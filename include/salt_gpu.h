@@ -427,6 +427,64 @@ int  salt_gpu_index_disc_text_next(salt_gpu_index_t *ix, const char **data, uint
 int  salt_gpu_index_disc_text_seen(salt_gpu_index_t *ix, uint8_t *seen, uint64_t cap);
 int  salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws);
 
+/* ---- the run's summary: mapping counts, histograms and per-contig counts (`salt --stats`) --------------------------------
+ * The five tallies above are about the genome; this one is about the run: what `samtools flagstat`, `stats` and `idxstats` would be asked
+ * for after a second pass over the output.
+ * A record's fate is the error profile's R: skipped, unmapped (pos == 0xFFFFFFFF) and below min_mapq are exclusive and tested in that
+ * order; the rest is COUNTED, and MAPPED means below or counted.  Only the primary alignment is read, never an alternative (XA) hit.
+ * mate = 0 single end and read 2i of a pair, 1 for read 2i + 1.  L is the read's length from the offsets.  "Printed" is what the SAM / BAM
+ * writers print: reverse iff strand != 0 single end, strand == 1 paired end; a paired-end row's soft clips seq_start and L - 1 - seq_end
+ * (single end prints none); an XA entry for every listed hit whose pos differs from the row's; for a pair, flag 0x2, RNEXT, PNEXT and
+ * TLEN by the rule of alnpe_sam (sam.c:350-358) with the -a / -b window of the call's salt_pe_opt_t: both mates mapped on one contig, the
+ * template inside the window and not 0.  The contig of a position is the one salt_gpu_index_set_contigs' table gives (the SAM writer's
+ * search); POS is 1-based and contig-relative.
+ * Tables, all uint64, owned by the device index and shared by its workspaces and forks, outside the image.  SALT_STATS_CELLS cells at the
+ * offsets below, then, apart, CT:
+ *   SN[2][16]   per mate: 0 records seen, 1 skipped, 2 unmapped, 3 below the floor, 4 counted, 5 counted and printed reverse, 6 counted
+ *               with any I, D or printed soft clip, 7 counted with at least one printed XA entry, 8 counted with flag 0x2, 9 counted with
+ *               the mate unmapped, 10 counted with the mate mapped on another contig, 11 bases of records not skipped (sum of L), 12 M
+ *               columns of counted records with g < ref_len (the walk and the cut of the coverage above), 13 / 14 / 15 I, D and printed S
+ *               bases of counted records
+ *   MQ[2][256]  mapped records by MAPQ
+ *   RL[2][513]  records not skipped, by L
+ *   GC[2][102]  records not skipped, by GC percent: gc = bases with code 1 or 2, n = bases with code 0 .. 3, bin (200 gc + n) / (2 n) in
+ *               integers (the percentage, halves rounded up); bin 101: n == 0
+ *   XA[2][8]    counted records by their number of printed XA entries (0 .. 5; more would count in 7)
+ *   IS[4097]    one entry per pair, from the mate-0 record when it is counted and its printed TLEN is not 0: index min(|TLEN|, 4096)
+ *   OR[4]       mate-0 counted records whose mate is mapped on the same contig: 0 inward (the strands differ and POS of the forward mate
+ *               <= POS of the reverse mate), 1 outward (the strands differ otherwise), 2 the same strand; 3 stays 0
+ *   ID[2][65]   the I ops (row 0) and D ops (row 1) of counted records by min(length, 64)
+ *   CT[n][8]    per contig of the table, by the contig of the record's pos: 0 / 1 mapped records of mate 0 / 1, 2 / 3 counted records of
+ *               mate 0 / 1, 4 counted and printed reverse, 5 the record's SN 12 columns, 6 and 7 stay 0
+ * The sums do not depend on batch order, stream, workspace or GPU, and the cells are 64-bit: the tables of several GPUs add cell by cell.
+ * (k_stats_add sums per workgroup in 32-bit LDS cells that it sends on once: such a cell grows by less than 2^18 a record and a
+ * workgroup owns 2 048 records.)  While the tally is on, every entry point that leaves result rows adds its batch behind the kernels that
+ * finish the rows, on the same stream, under salt_gpu_ws_set_polish too.  With it off no kernel is launched; before the first enable
+ * nothing is allocated.
+ *   salt_gpu_index_stats_enable   the first enable allocates and zeroes the tables (SALT_E_NOMEM names the size) and needs the contig table
+ *                                 (salt_gpu_index_set_contigs; without it SALT_E_INVAL names it); on = 0 stops and keeps them; min_mapq
+ *                                 0 .. 255 (above: SALT_E_INVAL).  Call with no align call in flight, like fetch.  A contig table of another
+ *                                 size set afterwards makes the align calls fail with SALT_E_INVAL while the tally is on.
+ *   salt_gpu_index_stats_fetch    synchronises the device; cells (SALT_STATS_CELLS of them) and ct (8 per contig) may each be NULL; a cap
+ *                                 that is too small is SALT_E_INVAL with the numbers in the message; reset != 0 zeroes all tables
+ *                                 afterwards.  Never enabled: SALT_E_INVAL.
+ *   salt_gpu_ws_stats_uncount     takes back what the workspace's LAST successful align call added (the same kernel with delta 2^64 - 1;
+ *                                 the call's buffers must be untouched since).  Nothing to take back: SALT_OK. */
+#define SALT_STATS_SN       0u                    /* [2][16] */
+#define SALT_STATS_MQ       32u                   /* [2][256] */
+#define SALT_STATS_RL       544u                  /* [2][513] */
+#define SALT_STATS_GC       1570u                 /* [2][102] */
+#define SALT_STATS_XA       1774u                 /* [2][8] */
+#define SALT_STATS_IS       1790u                 /* [4097] */
+#define SALT_STATS_OR       5887u                 /* [4] */
+#define SALT_STATS_ID       5891u                 /* [2][65] */
+#define SALT_STATS_CELLS    6021u
+#define SALT_STATS_IS_MAX   4096u                 /* the last bin of IS: templates of this length and longer */
+#define SALT_STATS_CT_LDS   64u                   /* contigs whose CT rows a workgroup of k_stats_add sums in LDS; the others' go to global memory directly */
+int  salt_gpu_index_stats_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq);
+int  salt_gpu_index_stats_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t *ct, uint64_t cap_ct, int reset);
+int  salt_gpu_ws_stats_uncount(salt_gpu_ws_t *ws);
+
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,
  * strict 4-line FASTQ records: the block is parsed, aligned and formatted on the device; the host only hands over the text and

@@ -164,6 +164,34 @@ int64_t salt_disc_add_sam(const salt_index_t *ix, const char *sam, size_t n, uin
 int64_t salt_disc_text(const salt_index_t *ix, const uint64_t *alt, const uint32_t *diff, uint64_t n_pos, uint32_t min_alt, uint32_t min_pct, int all_sites,
                        char *out, uint64_t cap, uint8_t *seen);
 
+/* The run's summary (`salt --stats`): the host twin of the device's k_stats_add and the one printer of the file, written from the
+ * definition in salt_gpu.h without any code of the kernel's.  cells is uint64[n_cells], n_cells = SALT_STATS_CELLS = 6 021, the fixed tables
+ * at salt_gpu.h's offsets; ct is uint64[n_ct], n_ct = 8 x the index's sequences (anything else is an error for both).
+ *   salt_stats_add_sam  the tables += the record lines of this program's own SAM text: mate from FLAG 0x80, reverse from 0x10, unmapped from
+ *                       0x4, the pair's fields from 0x1, 0x2, 0x8 and 0x20, RNAME, POS, MAPQ, CIGAR (M I D S), RNEXT, PNEXT, TLEN, SEQ
+ *                       (length and letters) and the entries of the XA tag.  Header lines ('@') and empty lines are skipped; any other
+ *                       line that is no SAM record of this program's of at most 512 bases is an error, and a line is checked whole before
+ *                       anything of it is added.  A skipped read prints as an empty line, so SN's "skipped" stays 0 here and "seen" does
+ *                       not count such reads: the device's seen - skipped is this function's seen.  Returns the records that counted.
+ *   salt_stats_text     the bytes of the file: tab-separated, '\n' line ends, one tag per line, integers only.
+ *                         #salt-stats v1 min_mapq=<n> <a remark on ISQ>
+ *                         SN mate key value     the 16 cells of SN under fixed keys (seen skipped unmapped low_mapq counted reverse gapped
+ *                                               with_xa proper mate_unmapped mate_other_contig bases m_bases i_bases d_bases s_bases)
+ *                         MQ mate mapq n, RL mate len n, GC mate pct n (pct "none": no A, C, G or T), XA mate k n: the non-zero cells
+ *                         IS tlen n             the non-zero cells, the last bin as ">=4096"
+ *                         ISQ pairs q25 q50 q75 mean   q: the smallest length at which the cumulative count reaches that share of the pairs
+ *                                               (">=4096" in the last bin); mean: (100 sum + n / 2) / n as h / 100 '.' h % 100 over the bins
+ *                                               below 4096; "." where there is nothing to divide by
+ *                         OR inward outward tandem
+ *                         ID len ins del        the lengths with an I or D op, the last as ">=64"
+ *                         CT name length mapped0 mapped1 counted0 counted1 reverse mbases   every sequence, in index order
+ *                       Mate 1's lines are printed only when mate 1 has seen records.  Returns the bytes the text takes; the first
+ *                       min(cap, that) of them are in out (out may be NULL with cap 0: the size only).  Both paths of `salt` print
+ *                       through this function.
+ * Both return -1 with salt_host_last_error() set on failure. */
+int64_t salt_stats_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint64_t *cells, uint64_t n_cells, uint64_t *ct, uint64_t n_ct);
+int64_t salt_stats_text(const salt_index_t *ix, const uint64_t *cells, uint64_t n_cells, const uint64_t *ct, uint64_t n_ct, uint32_t min_mapq, char *out, uint64_t cap);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

@@ -550,6 +550,61 @@ def errprof_text(E, R, min_mapq=0, full=False):
     return out.raw[:n]
 
 
+# the run's summary (salt_gpu.h, SALT_STATS_*): name -> (offset in the fixed cells, shape)
+STATS_TABLES = {"SN": (0, (2, 16)), "MQ": (32, (2, 256)), "RL": (544, (2, 513)), "GC": (1570, (2, 102)), "XA": (1774, (2, 8)), "IS": (1790, (4097,)),
+                "OR": (5887, (4,)), "ID": (5891, (2, 65))}
+STATS_CELLS = 6021
+STATS_CT_LDS = 64                         # contigs whose CT rows k_stats_add sums in LDS (SALT_STATS_CT_LDS)
+STATS_CHUNK = 2048                        # records a workgroup of k_stats_add owns (SALT_STATS_CHUNK)
+
+
+def stats_split(cells):
+    """The fixed cells of the summary as a dict of views, name -> array of the table's shape."""
+    cells = np.asarray(cells)
+    if cells.shape != (STATS_CELLS,):
+        raise SaltError("stats_split: %d cells, the summary has %d" % (cells.size, STATS_CELLS))
+    return {k: cells[o:o + int(np.prod(shape))].reshape(shape) for k, (o, shape) in STATS_TABLES.items()}
+
+
+def _stats_arrays(index, tables, what):
+    n = len(index.contigs())
+    cells, ct = tables if tables is not None else (np.zeros(STATS_CELLS, dtype=np.uint64), np.zeros((n, 8), dtype=np.uint64))
+    for a, shape in ((cells, (STATS_CELLS,)), (ct, (n, 8))):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or a.shape != shape or not a.flags.c_contiguous:
+            raise SaltError("%s: tables must be contiguous uint64 arrays of shapes (%d,) and (%d, 8)" % (what, STATS_CELLS, n))
+    return cells, ct
+
+
+def stats_add_sam(index, sam, min_mapq=0, tables=None):
+    """The summary of this program's own SAM text (salt_stats_add_sam, the host twin of the device's k_stats_add).  tables: the (cells, ct)
+    of an earlier call to add into.  Returns (cells uint64 (6021,), ct uint64 (contigs, 8), records that counted); stats_split names the
+    tables inside cells."""
+    h = host_lib()
+    h.salt_stats_add_sam.restype = ctypes.c_int64
+    h.salt_stats_add_sam.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
+    sam = bytes(sam)
+    cells, ct = _stats_arrays(index, tables, "stats_add_sam")
+    n = h.salt_stats_add_sam(index._h, sam, len(sam), int(min_mapq), cells.ctypes.data, cells.size, ct.ctypes.data, ct.size)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    return cells, ct, int(n)
+
+
+def stats_text(index, cells, ct, min_mapq=0):
+    """The bytes of `salt --stats`'s file for the tables (salt_stats_text)."""
+    h = host_lib()
+    h.salt_stats_text.restype = ctypes.c_int64
+    h.salt_stats_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    cells, ct = _stats_arrays(index, (np.ascontiguousarray(cells, dtype=np.uint64), np.ascontiguousarray(ct, dtype=np.uint64)), "stats_text")
+    n = h.salt_stats_text(index._h, cells.ctypes.data, cells.size, ct.ctypes.data, ct.size, int(min_mapq), None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_stats_text(index._h, cells.ctypes.data, cells.size, ct.ctypes.data, ct.size, int(min_mapq), out, n) != n:
+        raise SaltError("stats_text: the size of the text changed between two calls")
+    return out.raw[:n]
+
+
 GT_Q_NONE = 20                            # the quality of an event without a quality byte (SALT_GT_Q_NONE)
 
 
@@ -847,6 +902,13 @@ class GpuAligner:
         lib = gpu_lib()
         lib.salt_gpu_index_set_contigs.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
         _gpu_check(lib.salt_gpu_index_set_contigs(self._ix, len(cs), offs, names))
+        self._ix_state()["n_contigs"] = len(cs)
+
+    def _ix_state(self):
+        """what Python remembers of the device index, shared with the forks"""
+        if not hasattr(self, "_ix_shared"):
+            self._ix_shared = {}
+        return self._ix_shared
 
     def set_sam_bgzf(self, on=True):
         """The text entry points return BGZF blocks (deflated on the device) instead of the bytes themselves."""
@@ -1146,6 +1208,30 @@ class GpuAligner:
         lib.salt_gpu_ws_errprof_uncount.argtypes = [ctypes.c_void_p]
         _gpu_check(lib.salt_gpu_ws_errprof_uncount(self._ws))
 
+    def stats_enable(self, on=True, min_mapq=0):
+        """Add, from now on, every align call on this aligner's device index (its forks included) to the index's summary tables (mapping
+        counts, histograms, per-contig counts; salt_gpu.h); records below min_mapq are mapped but not counted.  The first enable
+        allocates and zeroes the tables and needs set_contigs; on=False stops and keeps them."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_stats_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_stats_enable(self._ix, 1 if on else 0, int(min_mapq)))
+
+    def stats_tables(self, reset=False):
+        """(cells uint64 (6021,), ct uint64 (contigs, 8)): the adds of all align calls since the first enable or the last reset;
+        stats_split names the tables inside cells.  Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_stats_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]
+        cells = np.zeros(STATS_CELLS, dtype=np.uint64)
+        ct = np.zeros((self._ix_state().get("n_contigs", 0), 8), dtype=np.uint64)
+        _gpu_check(lib.salt_gpu_index_stats_fetch(self._ix, cells.ctypes.data, cells.size, ct.ctypes.data if ct.size else None, ct.size, 1 if reset else 0))
+        return cells, ct
+
+    def stats_uncount(self):
+        """Takes back what this aligner's last align call added to the summary tables."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_stats_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_ws_stats_uncount(self._ws))
+
     def set_quals(self, quals, on_device=False):
         """Quality bytes (Phred + 33, FASTQ order) parallel to the bases of the NEXT alnse_core1 / alnpe_core1 (a uint8 array or bytes) or,
         with on_device, of the next align_resident / align_pe_resident (a device pointer).  That call consumes them; None: none."""
@@ -1178,6 +1264,7 @@ class GpuAligner:
         Close the forks before the aligner they came from."""
         other = GpuAligner.__new__(GpuAligner)
         other._ix, other._owns_ix = self._ix, False
+        other._ix_shared = self._ix_state()
         other._ws = ctypes.c_void_p()
         other.max_reads = max_reads or self.max_reads
         other.max_bases = max_bases or self.max_bases

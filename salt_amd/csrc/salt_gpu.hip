@@ -74,7 +74,7 @@ struct salt_gpu_index {
     // difference array of ref_len + 1 words (the text state and its buffers come with the first salt_gpu_index_depth_text_begin);
     // errprof: E[2][512][95][4][4] and R[2][8] behind it, uint64; gt: salt_gt_site_t[snp_sites] as uint64 words, over the snp tally's site table
     // (built by whichever of the two is enabled first; the text state and its buffers come with the first salt_gpu_index_gt_text_begin).
-    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt, disc;
+    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt, disc, stats;
     DevBuf<SnpWin> d_snp_tab; DevBuf<uint32_t> d_snp_counts; uint64_t snp_win = 0; uint32_t snp_sites = 0;
     DevBuf<uint32_t> d_depth; DepthText *depth_text = nullptr;
     std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
@@ -82,6 +82,8 @@ struct salt_gpu_index {
     DevBuf<unsigned long long> d_gt; GtText *gt_text = nullptr;
     // disc: alt, uint64[ref_len] of three 21-bit fields, and the tally's own difference array of ref_len + 1 words (4.10)
     DevBuf<unsigned long long> d_disc_alt; DevBuf<uint32_t> d_disc_diff; uint32_t disc_min_baseq = 0; DiscText *disc_text = nullptr;
+    // stats: SALT_STATS_CELLS cells, then CT[stats_contigs][8], uint64; stats_contigs is n_contigs as the first enable found it (4.11)
+    DevBuf<unsigned long long> d_stats; int32_t stats_contigs = 0;
 };
 
 // Every allocation below is a DevBuf / PinBuf: a new buffer is one field here and one reserve() or alloc() where it is sized.  Buffers that
@@ -136,8 +138,8 @@ struct salt_gpu_ws {
     // what the last align call added to each tally (n_rec 0: nothing) and on which stream, for the salt_gpu_ws_*_uncount calls; the error
     // profile's job carries its quality source
     template <class Job> struct LastJob { Job job{}; hipStream_t st = nullptr; };
-    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last; LastJob<DiscAdd> disc_last;
-    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; disc_last.job.n_rec = 0; }
+    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last; LastJob<DiscAdd> disc_last; LastJob<StatsAdd> stats_last;
+    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; disc_last.job.n_rec = 0; stats_last.job.n_rec = 0; }
     // the quality bytes of the error profile and the genotype sums: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
     // q_cur is the source of the call that is being queued (the text entry points set it to their raw block); d_quals holds a host call's bytes
     const uint8_t *q_next = nullptr; bool q_next_dev = false;
@@ -490,10 +492,12 @@ template <class Job> static int tally_launch(salt_gpu_ws::LastJob<Job> &last, hi
 // profile (k_errprof), their bases and qualities at the SNP sites into its genotype sums (k_gt_add), the bases the mixRef does not have into
 // its candidate arrays (k_disc_add), the last three with the qualities of the
 // call's source (ws->q_cur: the text block, salt_gpu_ws_set_quals' bytes, or
-// none).  Every entry point that leaves result rows passes here: single end at the end of align_resident_impl, paired end at the end of
+// none), and what the run's summary counts of them into its tables (k_stats_add; pe_opt: the call's -a / -b window, null single end).
+// Every entry point that leaves result rows passes here: single end at the end of align_resident_impl, paired end at the end of
 // pe_resident_impl (the rows are final only behind k_pe_final).
-static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, int pe, hipStream_t st)
+static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, const salt_pe_opt_t *pe_opt, hipStream_t st)
 {
+    const int pe = pe_opt ? 1 : 0;
     const salt_gpu_index *ix = ws->ix;
     const salt_result_t *res = static_cast<const salt_result_t *>(d_results);
     const uint8_t *seqs = static_cast<const uint8_t *>(d_seqs); const uint32_t *offs = static_cast<const uint32_t *>(d_offs);
@@ -529,6 +533,16 @@ static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, con
         c.ref = ix->view.ref; c.ref_len = ix->view.ref_len; c.alt = ix->d_disc_alt; c.diff = ix->d_disc_diff;
         c.min_mapq = ix->disc.min_mapq; c.min_baseq = ix->disc_min_baseq; c.pe = pe; c.delta = 1ull;
         if (const int rc = tally_launch(ws->disc_last, launch_disc_add, c, st)) return rc;
+    }
+    if (ix->stats.on) {
+        if (!ix->d_c_off || ix->n_contigs != ix->stats_contigs)
+            return fail(SALT_E_INVAL, "stats: the contig table was set again with " + std::to_string(ix->n_contigs) + " contigs, the tables were made for " + std::to_string(ix->stats_contigs));
+        StatsAdd c{};
+        c.res = res; c.seqs = seqs; c.offs = offs; c.n_rec = n_rec;
+        c.c_off = ix->d_c_off; c.n_contigs = ix->n_contigs; c.ref_len = ix->view.ref_len;
+        c.cells = ix->d_stats; c.ct = ix->d_stats + SALT_STATS_CELLS;
+        c.min_mapq = ix->stats.min_mapq; c.min_tlen = pe ? pe_opt->min_tlen : 0u; c.max_tlen = pe ? pe_opt->max_tlen : 0u; c.pe = pe; c.delta = 1ull;
+        if (const int rc = tally_launch(ws->stats_last, launch_stats_add, c, st)) return rc;
     }
     return SALT_OK;
 }
@@ -641,7 +655,7 @@ static int align_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, uint3
                  gap_bufs_layout(ws->d_gap, ws->gcap, ws->d_qctl, nullptr), ws->d_queue + ws->max_reads, ws->d_ranges, glob_loci ? ws->d_pe_scr.p : nullptr, timed ? ev + 4 : nullptr, st);
     if (timed) { HIPCHK(hipEventRecord(ev[7], st)); ws->ev_pe[ws->n_timed] = 0; ++ws->n_timed; }
     HIPCHK(hipGetLastError());
-    if (!pe) return rows_hooks(ws, n_reads, d_seqs, d_offs, d_results, 0, st);
+    if (!pe) return rows_hooks(ws, n_reads, d_seqs, d_offs, d_results, nullptr, st);
     return SALT_OK;
 }
 
@@ -2353,6 +2367,51 @@ extern "C" int salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws)
     return tally_uncount(ws, &salt_gpu_ws::disc_last, launch_disc_add, ~0ull, &salt_gpu_index::d_disc_alt, DISC_NEVER);
 }
 
+// ---- the run's summary ----
+static const char *const STATS_NEVER = "stats: the tables were never enabled on this index (salt_gpu_index_stats_enable)";
+
+extern "C" int salt_gpu_index_stats_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq)
+{
+    return tally_enable(ix, &salt_gpu_index::stats, "stats", on, min_mapq, [&]() -> int {
+        if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "stats needs the contig table for its per-contig counts: call salt_gpu_index_set_contigs first");
+        if (ix->d_stats) {
+            if (ix->n_contigs == ix->stats_contigs) return SALT_OK;
+            return fail(SALT_E_INVAL, "stats: the contig table was set again with " + std::to_string(ix->n_contigs) + " contigs, the tables were made for " + std::to_string(ix->stats_contigs));
+        }
+        const uint64_t n = (uint64_t)SALT_STATS_CELLS + (uint64_t)ix->n_contigs * 8;
+        if (const int rc = alloc_zeroed(ix->d_stats, n, "stats", "the tables: " + std::to_string(n * 8) + " bytes (8 per cell: " + std::to_string((uint64_t)SALT_STATS_CELLS) +
+                                        " fixed cells and 8 for each of " + std::to_string(ix->n_contigs) + " contigs)")) return rc;
+        ix->stats_contigs = ix->n_contigs;
+        return SALT_OK;
+    });
+}
+
+extern "C" int salt_gpu_index_stats_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t *ct, uint64_t cap_ct, int reset)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_stats) return fail(SALT_E_INVAL, STATS_NEVER);
+    const uint64_t n_ct = (uint64_t)ix->stats_contigs * 8;
+    if (cells && cap_cells < SALT_STATS_CELLS)
+        return fail(SALT_E_INVAL, "stats: room for " + std::to_string(cap_cells) + " cells, the fixed tables have " + std::to_string((uint64_t)SALT_STATS_CELLS));
+    if (ct && cap_ct < n_ct)
+        return fail(SALT_E_INVAL, "stats: room for " + std::to_string(cap_ct) + " cells of CT, the table has " + std::to_string(n_ct) + " (8 for each of " + std::to_string(ix->stats_contigs) + " contigs)");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (cells) HIPCHK(hipMemcpy(cells, ix->d_stats, (uint64_t)SALT_STATS_CELLS * 8, hipMemcpyDeviceToHost));
+    if (ct) HIPCHK(hipMemcpy(ct, ix->d_stats + SALT_STATS_CELLS, n_ct * 8, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ix->d_stats, 0, ((uint64_t)SALT_STATS_CELLS + n_ct) * 8));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_stats_uncount(salt_gpu_ws_t *ws)
+{
+    if (ws && ws->stats_last.job.n_rec) {                      // the contig table may have been set again since (with as many contigs): the job reads the one that stands
+        if (!ws->ix->d_c_off || ws->ix->n_contigs != ws->stats_last.job.n_contigs) return fail(SALT_E_INVAL, "stats: the contig table changed since the call that is to be taken back");
+        ws->stats_last.job.c_off = ws->ix->d_c_off;
+    }
+    return tally_uncount(ws, &salt_gpu_ws::stats_last, launch_stats_add, ~0ull, &salt_gpu_index::d_stats, STATS_NEVER);
+}
+
 extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device)
 {
     if (!ws) return fail(SALT_E_INVAL, "null argument");
@@ -2457,7 +2516,7 @@ static int pe_resident_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const sa
     }
 #endif
     HIPCHK(hipGetLastError());
-    return rows_hooks(ws, 2 * n_pairs, d_seqs, d_offs, d_results, 1, st);
+    return rows_hooks(ws, 2 * n_pairs, d_seqs, d_offs, d_results, pe, st);
 }
 
 extern "C" int salt_gpu_align_pe_resident(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_pe_opt_t *pe, uint32_t n_pairs,

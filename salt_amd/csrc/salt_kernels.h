@@ -339,6 +339,17 @@ int disc_text_begin(DiscText *t, const unsigned long long *d_alt, const uint32_t
 int disc_text_next(DiscText *t, const char **data, uint64_t *n_bytes, std::string &err);
 int disc_text_seen(DiscText *t, uint8_t *seen, uint64_t cap, std::string &err);      // seen[c] = contig c has a line; the text must be complete
 
+// ---- the run's summary (salt_stats.hip) ----
+static constexpr uint32_t SALT_STATS_CHUNK = 2048;                             // records a workgroup of k_stats_add owns
+struct StatsAdd {                                                              // what k_stats_add reads (by value)
+    const salt_result_t *res; const uint8_t *seqs; const uint32_t *offs; uint32_t n_rec;      // the batch: rows, codes as sequenced, offsets
+    const int64_t *c_off; int32_t n_contigs; uint32_t ref_len;                 // set_contigs' offsets (n_contigs >= 1)
+    unsigned long long *cells, *ct;                                            // SALT_STATS_CELLS cells; CT[n_contigs][8]
+    uint32_t min_mapq, min_tlen, max_tlen; int32_t pe;                         // pe: rows of a paired-end batch (mate = i & 1, the mate's row is i ^ 1), with the call's -a / -b window
+    unsigned long long delta;                                                  // 1; 2^64 - 1 takes a batch's adds back
+};
+hipError_t launch_stats_add(const StatsAdd &c, hipStream_t st);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

@@ -1166,3 +1166,167 @@ extern "C" int64_t salt_disc_text(const salt_index_t *ix, const uint64_t *alt, c
     }
     return (int64_t)o.n;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The run's summary: the host twin of k_stats_add (salt_stats.hip; include/salt_gpu.h has the definition), written from that definition
+// over this program's own SAM record lines and without any code of the kernel's, and the printer of the file.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+const uint64_t ST_SN = 0, ST_MQ = 32, ST_RL = 544, ST_GC = 1570, ST_XA = 1774, ST_IS = 1790, ST_OR = 5887, ST_ID = 5891, ST_CELLS = 6021, ST_IS_MAX = 4096;
+
+bool stats_sizes(const salt_index *ix, uint64_t n_cells, uint64_t n_ct)
+{
+    if (n_cells == ST_CELLS && n_ct == 8 * (uint64_t)ix->anns.size()) return true;
+    g_err = "stats: tables of " + std::to_string(n_cells) + " and " + std::to_string(n_ct) + " cells, the summary has " + std::to_string(ST_CELLS) + " fixed cells and 8 for each of the index's " +
+            std::to_string(ix->anns.size()) + " sequences";
+    return false;
+}
+
+// one record line [l, e) into the tables; 1 it counted, 0 it did not (unmapped, below min_mapq), -1 with g_err set.  The line is checked
+// whole (head, SEQ, CIGAR, RNEXT, PNEXT, TLEN) before anything is added.
+int stats_add_line(const salt_index *ix, const RefIds &ids, const char *l, const char *e, uint32_t min_mapq, uint64_t *cells, uint64_t *ct)
+{
+    SamLine L; MRuns m; uint64_t g0 = 0;
+    const int h = twin_head(ix, ids, L, "stats: ", l, e, 0, &g0);                  // (the floor is looked at below: a record below it is still mapped)
+    if (h < 0) return h;
+    const char *seq = L.f[9]; const size_t l_seq = L.len(9);
+    if (l_seq == 0 || l_seq > 512) return L.bad("SEQ is empty or longer than 512 bases"), -1;
+    int64_t pnext = 0, tlen = 0;
+    if (!field_int(L.f[7], L.fe(7), &pnext) || !field_int(L.f[8], L.fe(8), &tlen) || pnext < 0 || pnext > 0x7FFFFFFF || tlen < INT32_MIN || tlen > INT32_MAX)
+        return L.bad("a numeric field is no number of its range"), -1;
+    const uint64_t mate = (L.flag & 0x80) ? 1 : 0;
+    const bool paired = (L.flag & 1) != 0, mate_mapped = paired && !(L.flag & 8);
+    int32_t rid = -1, rid_ot = -1;
+    uint64_t n_i = 0, n_d = 0, n_s = 0, m_cols = 0, ops_i[64], ops_d[64]; int k_i = 0, k_d = 0;
+    if (h == 1) {
+        rid = ids.find(L.f[2], L.fe(2));
+        if (!twin_cigar(L, g0, m)) return -1;
+        if (mate_mapped) {
+            if (L.is(6, '=')) rid_ot = rid;
+            else if ((rid_ot = ids.find(L.f[6], L.fe(6))) < 0) return L.bad("RNEXT is no sequence of the index"), -1;
+        }
+        uint64_t n = 0;                                                            // (twin_cigar has checked the text: digits, then one of M I S D)
+        for (const char *p = L.f[5]; p < L.fe(5); ++p) {
+            if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); continue; }
+            if (*p == 'I') { n_i += n; if (k_i < 64) ops_i[k_i++] = n; }
+            else if (*p == 'D') { n_d += n; if (k_d < 64) ops_d[k_d++] = n; }
+            else if (*p == 'S') n_s += n;
+            n = 0;
+        }
+        for (int k = 0; k < m.n; ++k) {
+            const uint64_t a = m.g[k], b = std::min<uint64_t>(a + m.len[k], ix->view.ref_len);
+            if (a < b) m_cols += b - a;
+        }
+    }
+    uint64_t *sn = cells + ST_SN + mate * 16;
+    ++sn[0];
+    uint64_t gc = 0, acgt = 0;
+    for (size_t s = 0; s < l_seq; ++s) { const int b = base_code(seq[s]); if (b >= 0) ++acgt; if (b == 1 || b == 2) ++gc; }
+    ++cells[ST_RL + mate * 513 + l_seq];
+    ++cells[ST_GC + mate * 102 + (acgt ? (200 * gc + acgt) / (2 * acgt) : 101)];
+    sn[11] += l_seq;
+    if (h == 0) { ++sn[2]; return 0; }
+    uint64_t *c = ct + (uint64_t)rid * 8;
+    ++cells[ST_MQ + mate * 256 + (uint64_t)L.mapq];
+    ++c[mate];
+    if ((uint64_t)L.mapq < min_mapq) { ++sn[3]; return 0; }
+    const bool rev = (L.flag & 0x10) != 0;
+    ++sn[4]; ++c[2 + mate];
+    if (rev) { ++sn[5]; ++c[4]; }
+    if (m.gapped) ++sn[6];
+    sn[12] += m_cols; c[5] += m_cols; sn[13] += n_i; sn[14] += n_d; sn[15] += n_s;
+    for (int k = 0; k < k_i; ++k) ++cells[ST_ID + std::min<uint64_t>(ops_i[k], 64)];
+    for (int k = 0; k < k_d; ++k) ++cells[ST_ID + 65 + std::min<uint64_t>(ops_d[k], 64)];
+    uint64_t n_xa = 0;
+    for (const char *t = L.nf > 11 ? L.f[11] : e; t < e; ) {
+        const char *te = (const char *)memchr(t, '\t', (size_t)(e - t));
+        if (!te) te = e;
+        if (te - t >= 5 && memcmp(t, "XA:Z:", 5) == 0) for (const char *p = t + 5; p < te; ++p) n_xa += *p == ';';
+        t = te + 1;
+    }
+    if (n_xa) ++sn[7];
+    ++cells[ST_XA + mate * 8 + std::min<uint64_t>(n_xa, 7)];
+    if (L.flag & 2) ++sn[8];
+    if (!paired) return 1;
+    if (!mate_mapped) { ++sn[9]; return 1; }
+    if (rid_ot != rid) { ++sn[10]; return 1; }
+    if (mate == 0) {
+        if (tlen != 0) ++cells[ST_IS + std::min<uint64_t>((uint64_t)(tlen < 0 ? -tlen : tlen), ST_IS_MAX)];
+        const bool rev_ot = (L.flag & 0x20) != 0;
+        uint64_t o = 2;
+        if (rev != rev_ot) o = (rev ? pnext : L.pos1) <= (rev ? L.pos1 : pnext) ? 0 : 1;
+        ++cells[ST_OR + o];
+    }
+    return 1;
+}
+
+} // namespace
+
+extern "C" int64_t salt_stats_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint64_t *cells, uint64_t n_cells, uint64_t *ct, uint64_t n_ct)
+{
+    if (!ix || (!sam && n) || !cells || !ct) { g_err = "stats: null argument"; return -1; }
+    if (!stats_sizes(ix, n_cells, n_ct)) return -1;
+    const RefIds ids(ix);
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return stats_add_line(ix, ids, l, e, min_mapq, cells, ct); });
+}
+
+extern "C" int64_t salt_stats_text(const salt_index_t *ix, const uint64_t *cells, uint64_t n_cells, const uint64_t *ct, uint64_t n_ct, uint32_t min_mapq, char *out, uint64_t cap)
+{
+    if (!ix || !cells || !ct || (!out && cap)) { g_err = "stats: null argument"; return -1; }
+    if (!stats_sizes(ix, n_cells, n_ct)) return -1;
+    DepthOut o{ out, cap };
+    static const char *const SN_KEY[16] = { "seen", "skipped", "unmapped", "low_mapq", "counted", "reverse", "gapped", "with_xa", "proper", "mate_unmapped", "mate_other_contig",
+                                            "bases", "m_bases", "i_bases", "d_bases", "s_bases" };
+    auto num = [&](uint64_t v) { o.put('\t'); o.putu(v); };
+    const uint64_t n_mates = cells[ST_SN + 16] ? 2 : 1;                       // single end prints mate 0 only
+    o.puts("#salt-stats\tv1\tmin_mapq="); o.putu(min_mapq); o.puts("\tISQ mean: hundredths, the >=4096 bin left out\n");
+    for (uint64_t m = 0; m < n_mates; ++m)
+        for (uint64_t k = 0; k < 16; ++k) { o.puts("SN"); num(m); o.put('\t'); o.puts(SN_KEY[k]); num(cells[ST_SN + m * 16 + k]); o.put('\n'); }
+    auto hist = [&](const char *tag, uint64_t at, uint64_t width, uint64_t none) {
+        for (uint64_t m = 0; m < n_mates; ++m)
+            for (uint64_t k = 0; k < width; ++k) {
+                const uint64_t v = cells[at + m * width + k];
+                if (!v) continue;
+                o.puts(tag); num(m); o.put('\t');
+                if (k == none) o.puts("none"); else o.putu(k);
+                num(v); o.put('\n');
+            }
+    };
+    hist("MQ", ST_MQ, 256, ~0ull); hist("RL", ST_RL, 513, ~0ull); hist("GC", ST_GC, 102, 101); hist("XA", ST_XA, 8, ~0ull);
+    const uint64_t *is = cells + ST_IS;
+    auto tl = [&](uint64_t t) { o.put('\t'); if (t == ST_IS_MAX) o.puts(">=4096"); else o.putu(t); };
+    uint64_t pairs = 0, in_n = 0, in_sum = 0;
+    for (uint64_t t = 0; t <= ST_IS_MAX; ++t) {
+        pairs += is[t];
+        if (t < ST_IS_MAX) { in_n += is[t]; in_sum += t * is[t]; }
+        if (is[t]) { o.puts("IS"); tl(t); num(is[t]); o.put('\n'); }
+    }
+    o.puts("ISQ"); num(pairs);
+    for (uint64_t k = 1; k <= 3; ++k) {                                        // the smallest length at which the cumulative count reaches k quarters of the pairs
+        if (!pairs) { o.puts("\t."); continue; }
+        uint64_t cum = 0, t = 0;
+        for (; t <= ST_IS_MAX; ++t) { cum += is[t]; if (4 * cum >= k * pairs) break; }
+        tl(t);
+    }
+    if (!in_n) o.puts("\t.");
+    else {
+        // h = (100 sum + n / 2) / n without leaving 64 bits: sum = q n + r gives 100 q + (100 r + n / 2) / n
+        const uint64_t hh = 100u * (in_sum / in_n) + (100u * (in_sum % in_n) + in_n / 2) / in_n;
+        num(hh / 100u); o.put('.'); o.put((char)('0' + (int)(hh % 100u) / 10)); o.put((char)('0' + (int)(hh % 100u) % 10));
+    }
+    o.put('\n');
+    o.puts("OR"); num(cells[ST_OR]); num(cells[ST_OR + 1]); num(cells[ST_OR + 2]); o.put('\n');
+    for (uint64_t k = 0; k <= 64; ++k) {
+        const uint64_t a = cells[ST_ID + k], b = cells[ST_ID + 65 + k];
+        if (!a && !b) continue;
+        o.puts("ID\t"); if (k == 64) o.puts(">=64"); else o.putu(k);
+        num(a); num(b); o.put('\n');
+    }
+    for (size_t c = 0; c < ix->anns.size(); ++c) {
+        o.puts("CT\t"); o.puts(ix->anns[c].name); num((uint64_t)ix->anns[c].len);
+        for (int k = 0; k < 6; ++k) num(ct[c * 8 + (size_t)k]);
+        o.put('\n');
+    }
+    return (int64_t)o.n;
+}

@@ -101,6 +101,11 @@ extern "C" int salt_gpu_index_disc_text_begin(salt_gpu_index_t *ix, const salt_d
 extern "C" int salt_gpu_index_disc_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
 extern "C" int salt_gpu_index_disc_text_seen(salt_gpu_index_t *ix, uint8_t *seen, uint64_t cap) __attribute__((weak));
 extern "C" int salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
+// Likewise the run's summary (--stats): without the device's tables and kernel it is summed from the SAM lines by the host twin
+// (salt_stats_add_sam); the file is printed by salt_stats_text either way.
+extern "C" int salt_gpu_index_stats_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq) __attribute__((weak));
+extern "C" int salt_gpu_index_stats_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t *ct, uint64_t cap_ct, int reset) __attribute__((weak));
+extern "C" int salt_gpu_ws_stats_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
 namespace {
 
@@ -480,7 +485,7 @@ struct BamRun {
     const salt_index_t *ix = nullptr;
 } g_bam;
 
-// The five row tallies (--snp-counts, --depth, --error-profile, --genotype, --discover) run alike.  On the device the table belongs to each GPU's index and every
+// The six row tallies (--snp-counts, --depth, --error-profile, --genotype, --discover, --stats) run alike.  On the device the table belongs to each GPU's index and every
 // align call adds into it (salt_gpu_index_*_enable); a block the text path has aligned and then drops at a hand-over is taken back
 // (salt_gpu_ws_*_uncount): the host pipeline aligns those reads again.  Without the device's symbols the SAM lines of every block and
 // batch that is written go through the tally's host twin, one caller at a time.
@@ -498,6 +503,7 @@ struct DepthRun : TallyRun { bool gz = false; uint32_t window = 0; std::vector<u
 // qualities over with salt_gpu_ws_set_quals; after the last block the GPUs' tables are fetched and summed on the host.  salt_errprof_text
 // prints the file on both paths.
 const size_t ERRPROF_CELLS = 2u * 512u * 95u * 16u;
+const size_t STATS_CELLS = 6021;                 // SALT_STATS_CELLS of salt_gpu.h
 struct ErrprofRun : TallyRun { bool full = false; std::vector<uint64_t> cells; uint64_t rec[16] = { 0 }; } g_errprof;
 // --genotype FILE: a VCF record per SNP site of the index.  Like the profile, the host pipeline hands its batches' qualities over; after the
 // last block the other GPUs' sums are added into the first GPU's, whose kernels make the calls and print the records piece by piece.
@@ -509,15 +515,18 @@ struct DiscRun : TallyRun {
     bool gz = false, all = false; uint32_t min_baseq = 20, min_alt = 3, min_pct = 20; std::vector<uint64_t> host_alt; std::vector<uint32_t> host_diff;
     DiscRun() { min_mapq = 20; }
 } g_disc;
+// --stats FILE: the run's summary -- mapping counts, histograms of MAPQ, read length, GC, insert size and indel length, counts per contig.
+// After the last block the GPUs' tables are fetched and summed on the host; salt_stats_text prints the file on both paths.
+struct StatsRun : TallyRun { std::vector<uint64_t> cells, ct; } g_stats;
 
-// What differs between them where they run alike, in the order snp, depth, error profile, genotype, discover.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
+// What differs between them where they run alike, in the order snp, depth, error profile, genotype, discover, stats.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
 // how the file is opened; does: what a libsalt_gpu without the symbols does not do (the --polish refusal); symbols: this libsalt_gpu has
 // the device side; host_add: the twin over SAM lines (< 0: refused); uncount: the last align call's adds leave the device's table.
 struct Tally {
     TallyRun *run; const char *opt, *stem, *mode, *does;
     bool (*symbols)(); int64_t (*host_add)(const char *sam, size_t n); int (*uncount)(salt_gpu_ws_t *ws);
 };
-const Tally TALLIES[5] = {
+const Tally TALLIES[6] = {
     { &g_snp, "snp-counts", "snp", "w", "counts",
       [] { return salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount; },
       [](const char *sam, size_t n) { return salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites); }, salt_gpu_ws_snp_uncount },
@@ -534,6 +543,9 @@ const Tally TALLIES[5] = {
       [] { return salt_gpu_index_disc_enable && salt_gpu_index_disc_fetch && salt_gpu_index_disc_add && salt_gpu_index_disc_text_begin && salt_gpu_index_disc_text_next && salt_gpu_index_disc_text_seen &&
                   salt_gpu_ws_disc_uncount && salt_gpu_ws_set_quals; },
       [](const char *sam, size_t n) { return salt_disc_add_sam(g_disc.ix, sam, n, g_disc.min_mapq, g_disc.min_baseq, g_disc.host_alt.data(), g_disc.host_diff.data(), g_disc.host_alt.size()); }, salt_gpu_ws_disc_uncount },
+    { &g_stats, "stats", "stats", "w", "makes the summary",
+      [] { return salt_gpu_index_stats_enable && salt_gpu_index_stats_fetch && salt_gpu_ws_stats_uncount; },
+      [](const char *sam, size_t n) { return salt_stats_add_sam(g_stats.ix, sam, n, g_stats.min_mapq, g_stats.cells.data(), g_stats.cells.size(), g_stats.ct.data(), g_stats.ct.size()); }, salt_gpu_ws_stats_uncount },
 };
 
 // the SAM lines of a block or batch that is about to be written, through every host twin that is on; false with the reason on stderr
@@ -667,6 +679,9 @@ int usage()
             "                                        substitution, the index's SNP sites left out (counted on the GPU; tab-separated) [off]\n"
             "               --error-profile-min-mapq <int>  --error-profile: records with a smaller MAPQ do not count, 0 .. 255 [0]\n"
             "               --error-profile-full     --error-profile: also every non-zero cell (mate, cycle, quality, ref, read)\n"
+            "               --stats <file>           write the run's summary: mapped, properly paired and per-contig counts, histograms of MAPQ,\n"
+            "                                        read length, GC, insert size and indel length, summed on the GPU behind every block\n"
+            "               --stats-min-mapq <int>   --stats: records with a smaller MAPQ are mapped but not counted, 0 .. 255 [0]\n"
             "               --genotype      <file>   write a VCF 4.2 record per SNP site of the index: the genotype, allele depths and\n"
             "                                        likelihoods from the reads' bases and base qualities (summed, called and printed on\n"
             "                                        the GPU); a name ending in .gz is written as BGZF [off]\n"
@@ -1398,7 +1413,7 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "error-profile", 1, 0, 1009 }, { "error-profile-min-mapq", 1, 0, 1010 }, { "error-profile-full", 0, 0, 1011 },
         { "genotype", 1, 0, 1012 }, { "genotype-min-mapq", 1, 0, 1013 }, { "genotype-sample", 1, 0, 1014 },
         { "discover", 1, 0, 1015 }, { "discover-min-mapq", 1, 0, 1016 }, { "discover-min-baseq", 1, 0, 1017 }, { "discover-min-alt", 1, 0, 1018 }, { "discover-min-pct", 1, 0, 1019 },
-        { "discover-all", 0, 0, 1020 }, { 0, 0, 0, 0 } };
+        { "discover-all", 0, 0, 1020 }, { "stats", 1, 0, 1021 }, { "stats-min-mapq", 1, 0, 1022 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1421,8 +1436,8 @@ static int parse_options(int argc, char **argv, Opts &o)
             else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
             break;
         case 1004: g_snp.on = true; g_snp.fn = optarg; break;
-        case 1005: case 1007: case 1010: case 1013: case 1016: {
-            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : c == 1013 ? 3 : 4];
+        case 1005: case 1007: case 1010: case 1013: case 1016: case 1022: {
+            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : c == 1013 ? 3 : c == 1016 ? 4 : 5];
             char *end = nullptr; const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --%s-min-mapq %s: a MAPQ is a number from 0 to 255\n", t.stem, optarg); return 1; }
             t.run->min_mapq = (uint32_t)v;
@@ -1452,6 +1467,7 @@ static int parse_options(int argc, char **argv, Opts &o)
             break;
         }
         case 1020: g_disc.all = true; break;
+        case 1021: g_stats.on = true; g_stats.fn = optarg; break;
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1648,7 +1664,7 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
-                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host() || g_disc.host()) {
+                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host() || g_disc.host() || g_stats.host()) {
                     bool good = true;
                     for (const std::string &piece : b->sam) good = good && host_twins_add(piece.data(), piece.size());
                     if (!good) { set_failed(); break; }
@@ -1793,6 +1809,47 @@ static bool errprof_finish(const std::vector<salt_gpu_index_t *> &gix)
     for (uint64_t v : g_errprof.cells) bases += v;
     fprintf(stderr, "[salt] error profile: %llu records, %llu bases, %s, MAPQ >= %u -> %s (%llu bytes)\n", (unsigned long long)(g_errprof.rec[4] + g_errprof.rec[12]),
             (unsigned long long)bases, g_errprof.device ? "counted on the device" : "counted on the host from the SAM lines", g_errprof.min_mapq, g_errprof.fn,
+            (unsigned long long)text.size());
+    return true;
+}
+
+// --stats, before the first block: the contig table (the tally's per-contig counts need it on the host pipeline too) and the tally on on
+// every GPU's index, or the host's tables
+static bool stats_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &C)
+{
+    if (!g_stats.on) return true;
+    g_stats.ix = ix;
+    g_stats.cells.assign(STATS_CELLS, 0);
+    g_stats.ct.assign((size_t)salt_index_n_seqs(ix) * 8, 0);
+    if (!g_stats.device) return true;
+    for (salt_gpu_index_t *g : gix)
+        if (salt_gpu_index_set_contigs(g, C.n(), C.off.data(), C.nm.data()) || salt_gpu_index_stats_enable(g, 1, g_stats.min_mapq)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    return true;
+}
+
+// --stats, after the last block of a run that succeeded: every GPU's tables are fetched and summed on the host, and the file is printed
+static bool stats_finish(const std::vector<salt_gpu_index_t *> &gix)
+{
+    if (!g_stats.on) return true;
+    if (g_stats.device) {
+        std::vector<uint64_t> one(g_stats.cells.size()), one_ct(g_stats.ct.size());
+        for (salt_gpu_index_t *g : gix) {
+            if (salt_gpu_index_stats_fetch(g, one.data(), one.size(), one_ct.data(), one_ct.size(), 0)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+            for (size_t i = 0; i < one.size(); ++i) g_stats.cells[i] += one[i];
+            for (size_t i = 0; i < one_ct.size(); ++i) g_stats.ct[i] += one_ct[i];
+        }
+    }
+    auto text_of = [&](char *out, uint64_t cap) { return salt_stats_text(g_stats.ix, g_stats.cells.data(), g_stats.cells.size(), g_stats.ct.data(), g_stats.ct.size(), g_stats.min_mapq, out, cap); };
+    const int64_t need = text_of(nullptr, 0);
+    std::string text(need > 0 ? (size_t)need : 0, '\0');
+    if (need < 0 || text_of(&text[0], (uint64_t)need) != need) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+    FILE *f = g_stats.fp;
+    bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    ok = !ferror(f) && fclose(f) == 0 && ok;
+    g_stats.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --stats: write error on %s\n", g_stats.fn); return false; }
+    fprintf(stderr, "[salt] stats: %llu records seen, %llu counted, %s, MAPQ >= %u -> %s (%llu bytes)\n", (unsigned long long)(g_stats.cells[0] + g_stats.cells[16]),
+            (unsigned long long)(g_stats.cells[4] + g_stats.cells[20]), g_stats.device ? "counted on the device" : "counted on the host from the SAM lines", g_stats.min_mapq, g_stats.fn,
             (unsigned long long)text.size());
     return true;
 }
@@ -2068,16 +2125,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
-    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix) || !disc_begin(ix, gix)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
+    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix) || !disc_begin(ix, gix) || !stats_begin(ix, gix, contigs)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs)) ? 1 : rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs) && stats_finish(gix)) ? 1 : rc); }
         header_out = true;
     }
     const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
-    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs)) ? 1 : rc);
+    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs) && stats_finish(gix)) ? 1 : rc);
 }
