@@ -485,6 +485,95 @@ int  salt_gpu_index_stats_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq
 int  salt_gpu_index_stats_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t *ct, uint64_t cap_ct, int reset);
 int  salt_gpu_ws_stats_uncount(salt_gpu_ws_t *ws);
 
+/* ---- indel candidates (`salt --indels`) -----------------------------------------------------------------------------------
+ * The seventh row tally, and the first whose table is not indexed by position: a hash table of allele keys.  This is the definition; it
+ * is implemented three times (the kernels of salt_indel.hip, the host twin salt_indel_add_sam / salt_indel_text, tests/indel_check.py).
+ * Contributing records are those of the SNP counts (4.6): mapped (pos != 0xFFFFFFFF), not skipped, mapq >= min_mapq (default 20, as for
+ * the SNP candidates); only the primary alignment, never an alternative (XA) hit.  The row's ops are walked as tally_m_runs walks them: g
+ * starts at pos and s at the leading soft clip (0 single end); M advances both, I advances s, D advances g, an op of 3 advances neither.
+ * L is the read's length from the offsets.  n_ops is the row's op count (the soft clips the writers print are not ops).
+ * Genome letters: letter(x) = the 2-bit genome's base at x (text, which the SAM writers read; a genome N reads as its pac letter) for
+ * x < the 2-bit genome's length, else A.  Contigs: those of salt_gpu_index_set_contigs' table; contig c is [off[c], end[c]) with end[c] =
+ * off[c + 1], and ref_len for the last one; the contig of a position is the last one that begins at or in front of it.
+ * Events: an I or D op k of length n, met at (g, s), is an EVENT iff all of
+ *   (length)  I: 1 <= n <= 12; D: 1 <= n <= 63;
+ *   (anchor)  0 < k < n_ops - 1, and ops k - 1 and k + 1 are both M with a length of at least 1;
+ *   (contig)  with c the contig of the anchor g - 1: g < end[c]; for D also g + n <= end[c] and g + n <= ref_len;
+ *   (bases)   for I: s + n <= L and the n bases of SEQ as printed at [s, s + n) are all A, C, G or T (for a row printed reverse they are
+ *             the sequenced bases L - 1 - x, complemented).
+ * An I or D op that is no event goes to exactly one counter: `long` when (length) fails, else `unanchored`.
+ * Left shift (normalisation), against the 2-bit genome alone.  D: while g - 1 > off[c] and letter(g - 1) == letter(g + n - 1): g -= 1.
+ * I with bases b[0 .. n): while g - 1 > off[c] and letter(g - 1) == b[n - 1]: b is rotated right by one, letter(g - 1) entering at the
+ * front, and g -= 1.  At most SALT_INDEL_MAX_SHIFT steps are taken: the bound on work is part of the definition.  The anchor never
+ * leaves the contig: the leftmost allele has its anchor on the contig's first position.
+ * Key, 64 bits, never 0: bit 63 = 1; bits 62 .. 31 = g (the first position behind the anchor); bit 30 = 1 for D; bits 29 .. 24 = n; bits
+ * 23 .. 0 = the inserted bases, 2 bits each, b[0] highest, left-justified in the 24 bits (0 for D).  Keys sorted as integers are in genome
+ * order.  A word is a WELL-FORMED key iff bit 63 is set, 1 <= g <= ref_len, n is in its type's range, and for I the bits below the 2 n
+ * used ones are 0, for D all 24; only well-formed keys are ever printed (others can only come from salt_gpu_index_indel_add).
+ * Value, one 64-bit word: observations from rows printed forward in the low 32 bits, from rows printed reverse in the high 32.  An event
+ * adds 1 or 1 << 32; taking a batch back adds the two's complement.
+ * Table: 2^log2_slots slots of 16 bytes (key, value), 2^6 .. 2^28 slots, fixed at the first enable; default 2^24 (256 MB).  The home slot
+ * of a key is (key * 0x9E3779B97F4A7C15) >> (64 - log2_slots); probing is linear over at most SALT_INDEL_PROBE slots (and at most all of
+ * them) and wraps at the table's end.  On each slot atomicCAS(&slot.key, 0, key): 0 or key returned means the slot is this allele's, and
+ * one 64-bit atomicAdd on its value follows; anything else moves on.  A probe run that ends without a slot adds the event to `dropped`
+ * instead.  Nothing waits for another thread.  Taking back (a negative addend) claims nothing: it looks the key up along the same run, and
+ * a key that is not found (an empty slot, or the run's end) takes its event back from `dropped`.  A slot is never emptied, so a key that
+ * was dropped once is dropped always, and tabled + dropped is the number of events added, whatever the order.
+ * stat, uint64[4]: SALT_INDEL_TABLED, _DROPPED (events), _LONG, _UNANCHORED (ops).
+ * diff: this tally's OWN uint32[ref_len + 1] difference array under its own floor, marked per M run exactly as the SNP candidates' (4.10).
+ * Call, in integers, for a well-formed key with value (fwd, rev) and depth = depth[g - 1] (the anchor's): the allele is called iff
+ * fwd + rev >= min_alt and 100 * (fwd + rev) >= min_pct * depth.  Defaults 3 and 20; ranges min_alt 1 .. 2^32 - 1, min_pct 0 .. 100.
+ * File: one VCF 4.2 record per called allele, in key order: "CHROM\tPOS\t.\tREF\tALT\t.\t.\tINFO\n"; CHROM the contig of the anchor, POS
+ * the anchor, 1-based and contig-relative; for D REF = letter(g - 1) letter(g) .. letter(g + n - 1) and ALT = letter(g - 1); for I REF =
+ * letter(g - 1) and ALT = letter(g - 1) b[0] .. b[n - 1]; INFO = "TYPE=INS|DEL;LEN=n;DP=depth;AO=fwd+rev;AOF=fwd;AOR=rev".
+ * While the tally is on, every entry point that leaves result rows adds its batch behind the kernels that finish the rows, on the same
+ * stream (k_indel_add: a thread per record, no queue, no spin).  Table, counters and diff belong to the device index, outside the image.
+ * With the tally off no kernel is launched; before the first enable nothing is allocated and every other call below is SALT_E_INVAL.
+ *   salt_gpu_index_indel_enable      the first enable allocates and zeroes table, counters and diff (SALT_E_NOMEM names the size) and
+ *                                    needs the contig table (salt_gpu_index_set_contigs); log2_slots 6 .. 28, 0 = the default, and later
+ *                                    enables must name the same size or 0; on = 0 stops and keeps everything.  No align call in flight.
+ *   salt_gpu_index_indel_reset       table, counters and diff = 0
+ *   salt_gpu_index_indel_stats       the four counters; synchronises the device
+ *   salt_gpu_index_indel_fetch       the slots with a non-zero value as (key, value) pairs, uint64[2 n], in key order; *n is their number
+ *                                    whatever cap (in pairs) is, and min(cap, *n) pairs are written
+ *   salt_gpu_index_indel_add         inserts n hand-given (key, value) pairs by a kernel with the insert routine above, the value as the
+ *                                    addend and its two halves' sum as the events: how the tables of several GPUs are summed
+ *   salt_gpu_index_indel_fetch_diff / _add_diff   words [first, first + n) of diff, inside [0, ref_len], as the SNP candidates'
+ *   salt_gpu_index_indel_text_begin  starts the records of table and diff as they stand; tile_positions = genome positions of diff scanned
+ *                                    at a time, 0 = the default (the text does not depend on it); bgzf != 0: whole BGZF blocks, without
+ *                                    the end-of-file block
+ *   salt_gpu_index_indel_text_next   the next piece, cut at a line end: *data points into a buffer the index owns, valid until the next
+ *                                    call on the index; *n_bytes == 0: complete.  Table and diff are only read: the text can be made
+ *                                    twice, and counting can go on.
+ *   salt_gpu_ws_indel_uncount        takes back what the workspace's LAST successful align call added.  Nothing to take back: SALT_OK. */
+#define SALT_INDEL_MAX_INS    12u
+#define SALT_INDEL_MAX_DEL    63u
+#define SALT_INDEL_MAX_SHIFT  4096u
+#define SALT_INDEL_PROBE      128u
+#define SALT_INDEL_LOG2_MIN   6u
+#define SALT_INDEL_LOG2_MAX   28u
+#define SALT_INDEL_LOG2_DEFAULT 24u
+#define SALT_INDEL_TABLED     0
+#define SALT_INDEL_DROPPED    1
+#define SALT_INDEL_LONG       2
+#define SALT_INDEL_UNANCHORED 3
+typedef struct {
+    uint32_t min_alt;           /* 1 .. 2^32 - 1 */
+    uint32_t min_pct;           /* 0 .. 100 */
+    uint32_t tile_positions;    /* 0: default */
+    int32_t  bgzf;              /* the pieces are BGZF blocks */
+} salt_indel_text_opt_t;
+int  salt_gpu_index_indel_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq, uint32_t log2_slots);
+int  salt_gpu_index_indel_reset(salt_gpu_index_t *ix);
+int  salt_gpu_index_indel_stats(salt_gpu_index_t *ix, uint64_t out[4]);
+int  salt_gpu_index_indel_fetch(salt_gpu_index_t *ix, uint64_t cap, uint64_t *entries, uint64_t *n);
+int  salt_gpu_index_indel_add(salt_gpu_index_t *ix, const uint64_t *entries, uint64_t n);
+int  salt_gpu_index_indel_fetch_diff(salt_gpu_index_t *ix, uint64_t first, uint64_t n, uint32_t *out);
+int  salt_gpu_index_indel_add_diff(salt_gpu_index_t *ix, uint64_t first, uint64_t n, const uint32_t *in);
+int  salt_gpu_index_indel_text_begin(salt_gpu_index_t *ix, const salt_indel_text_opt_t *opt);
+int  salt_gpu_index_indel_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes);
+int  salt_gpu_ws_indel_uncount(salt_gpu_ws_t *ws);
+
 /* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------
  * query_read_seq (query.c:146-239) + alnse_core1 + aln_samse / sam_add_xa / sam_add_md_nm (sam.c:87-328) for one block of whole,
  * strict 4-line FASTQ records: the block is parsed, aligned and formatted on the device; the host only hands over the text and

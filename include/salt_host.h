@@ -192,6 +192,39 @@ int64_t salt_disc_text(const salt_index_t *ix, const uint64_t *alt, const uint32
 int64_t salt_stats_add_sam(const salt_index_t *ix, const char *sam, size_t n, uint32_t min_mapq, uint64_t *cells, uint64_t n_cells, uint64_t *ct, uint64_t n_ct);
 int64_t salt_stats_text(const salt_index_t *ix, const uint64_t *cells, uint64_t n_cells, const uint64_t *ct, uint64_t n_ct, uint32_t min_mapq, char *out, uint64_t cap);
 
+/* Indel candidates (`salt --indels`): the host twins of the device's k_indel_add and of its text kernels, written from the definition in
+ * salt_gpu.h; they share nothing with the kernels.  A salt_indel_t holds what the device's table and counters hold: a sorted map from
+ * allele key to value (forward observations low, reverse high) and the four counters tabled, dropped (always 0 here: a map has room),
+ * long, unanchored.  diff is the tally's own uint32[n_pos + 1] difference array, n_pos = the index's ref_len (anything else is an error).
+ *   salt_indel_add_sam  map, counters and diff += the record lines of this program's own SAM text: a record counts iff it is mapped
+ *                       (FLAG 0x4 clear) and MAPQ >= min_mapq; global position = contig offset + POS - 1; reverse from FLAG 0x10; the ops
+ *                       are those of the CIGAR without its S ops, whose lengths only advance in SEQ; every M run, cut at ref_len, marks
+ *                       diff; every I and D op is an event, long or unanchored by the definition, and an event is left-shifted against the
+ *                       index's 2-bit genome and added under its key.  Header lines ('@') and empty lines are skipped; any other line
+ *                       that is no SAM record of this program's is an error; a line is checked whole before anything of it is added.
+ *                       Returns the records that counted.
+ *   salt_indel_entries  the map's (key, value) pairs with a non-zero value, in key order, uint64[2 n]: returns n; the first min(cap, n)
+ *                       pairs are in out (out may be NULL with cap 0)
+ *   salt_indel_stats    the four counters
+ *   salt_indel_text     the VCF records of n (key, value) pairs in key order (a map's, or the device's salt_gpu_index_indel_fetch) and a
+ *                       difference array: the call rule of salt_gpu.h and its line, no header; pairs out of order are an error, keys that
+ *                       are not well-formed and values of 0 get no line.  Returns the bytes the text takes; the first min(cap, that) of
+ *                       them are in out (out may be NULL with cap 0: the size only).  The model of the device's text, and what `salt`
+ *                       prints on the host path.
+ *   salt_indel_header   the header of the file, one function for both paths: ##fileformat=VCFv4.2, ##source, one ##contig=<ID=,length=>
+ *                       per sequence of the index, the INFO definitions, ##salt_indels_parameters=<min_mapq=,min_alt=,min_pct=>,
+ *                       ##salt_indels_dropped=N, the #CHROM line.
+ * The int64_t functions return -1 with salt_host_last_error() set on failure. */
+typedef struct salt_indel salt_indel_t;
+salt_indel_t *salt_indel_new(void);
+void    salt_indel_free(salt_indel_t *t);
+int64_t salt_indel_add_sam(const salt_index_t *ix, salt_indel_t *t, const char *sam, size_t n, uint32_t min_mapq, uint32_t *diff, uint64_t n_pos);
+int64_t salt_indel_entries(const salt_indel_t *t, uint64_t *out, uint64_t cap);
+void    salt_indel_stats(const salt_indel_t *t, uint64_t out[4]);
+int64_t salt_indel_text(const salt_index_t *ix, const uint64_t *entries, uint64_t n, const uint32_t *diff, uint64_t n_pos, uint32_t min_alt, uint32_t min_pct,
+                        char *out, uint64_t cap);
+int64_t salt_indel_header(const salt_index_t *ix, uint32_t min_mapq, uint32_t min_alt, uint32_t min_pct, uint64_t dropped, char *out, uint64_t cap);
+
 /* Index builder (row N1): writes <prefix>.{R.seedLen,C.pac,C.ann,C.amb,C.lkt,C.bwt,C.sa,lp,
  * R.backward.bwt,R.backward.occ,R.backward.sa,ref} in salt-idx's formats from a FASTA (plain or .gz)
  * and salt's 4-column SNP file (chr, 1-based pos, alleles "A/G", ref; no header; grouped by

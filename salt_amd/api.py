@@ -728,6 +728,91 @@ def disc_text(index, alt, diff, min_alt=3, min_pct=20, all_sites=False, seen=Fal
     return (out.raw[:n], marks[:n_seqs]) if seen else out.raw[:n]
 
 
+INDEL_DEFAULTS = dict(min_mapq=20, min_alt=3, min_pct=20, log2_slots=24)
+INDEL_STATS = ("tabled", "dropped", "long", "unanchored")      # the four counters (SALT_INDEL_TABLED ..)
+INDEL_PROBE, INDEL_MAX_INS, INDEL_MAX_DEL, INDEL_MAX_SHIFT = 128, 12, 63, 4096
+
+
+def _indel_host():
+    h = host_lib()
+    h.salt_indel_new.restype = ctypes.c_void_p
+    h.salt_indel_free.argtypes = [ctypes.c_void_p]
+    h.salt_indel_free.restype = None
+    h.salt_indel_add_sam.restype = ctypes.c_int64
+    h.salt_indel_add_sam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_indel_entries.restype = ctypes.c_int64
+    h.salt_indel_entries.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_indel_stats.restype = None
+    h.salt_indel_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    h.salt_indel_text.restype = ctypes.c_int64
+    h.salt_indel_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
+    h.salt_indel_header.restype = ctypes.c_int64
+    h.salt_indel_header.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
+    return h
+
+
+def indel_add_sam(index, sam, min_mapq=20):
+    """The indel table of this program's own SAM text (salt_indel_add_sam, the host twin of the device's k_indel_add).  sam: bytes, or a
+    list of texts that are added one after the other into one table.  Returns (entries, diff, stats, records that counted): entries a
+    uint64 (n, 2) array of (key, value) pairs in key order, diff the tally's own uint32[ref_len + 1] difference array, stats the four
+    counters INDEL_STATS."""
+    h = _indel_host()
+    n_pos = int(index.ref_len)
+    diff = np.zeros(n_pos + 1, dtype=np.uint32)
+    t = h.salt_indel_new()
+    try:
+        n_rec = 0
+        for text in ([sam] if isinstance(sam, (bytes, bytearray, memoryview)) else sam):
+            text = bytes(text)
+            n = h.salt_indel_add_sam(index._h, t, text, len(text), int(min_mapq), diff.ctypes.data, n_pos)
+            if n < 0:
+                raise SaltError(h.salt_host_last_error().decode())
+            n_rec += int(n)
+        n = h.salt_indel_entries(t, None, 0)
+        entries = np.zeros((max(n, 0), 2), dtype=np.uint64)
+        if n < 0 or h.salt_indel_entries(t, entries.ctypes.data, n) != n:
+            raise SaltError("indel_add_sam: the entries changed between two calls")
+        stats = np.zeros(4, dtype=np.uint64)
+        h.salt_indel_stats(t, stats.ctypes.data)
+    finally:
+        h.salt_indel_free(t)
+    return entries, diff, stats, n_rec
+
+
+def indel_text(index, entries, diff, min_alt=3, min_pct=20):
+    """The VCF records of (key, value) pairs in key order and a difference array (salt_indel_text, the host twin of the device's text kernels)."""
+    h = _indel_host()
+    entries = np.ascontiguousarray(entries, dtype=np.uint64).reshape(-1, 2)
+    diff = np.ascontiguousarray(diff, dtype=np.uint32)
+    if diff.ndim != 1 or diff.shape[0] < 1:
+        raise SaltError("indel_text: diff of shape (ref_len + 1,)")
+    args = (index._h, entries.ctypes.data, entries.shape[0], diff.ctypes.data, diff.shape[0] - 1, int(min_alt), int(min_pct))
+    n = h.salt_indel_text(*args, None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_indel_text(*args, out, n) != n:
+        raise SaltError("indel_text: the size of the text changed between two calls")
+    return out.raw[:n]
+
+
+def indel_header(index, min_mapq=20, min_alt=3, min_pct=20, dropped=0):
+    """The header of the `--indels` file (salt_indel_header)."""
+    h = _indel_host()
+    args = (index._h, int(min_mapq), int(min_alt), int(min_pct), int(dropped))
+    n = h.salt_indel_header(*args, None, 0)
+    if n < 0:
+        raise SaltError(h.salt_host_last_error().decode())
+    out = ctypes.create_string_buffer(max(n, 1))
+    if h.salt_indel_header(*args, out, n) != n:
+        raise SaltError("indel_header: the size of the text changed between two calls")
+    return out.raw[:n]
+
+
+class _IndelTextOpt(ctypes.Structure):
+    _fields_ = [("min_alt", ctypes.c_uint32), ("min_pct", ctypes.c_uint32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
+
+
 class _DiscTextOpt(ctypes.Structure):
     _fields_ = [("min_alt", ctypes.c_uint32), ("min_pct", ctypes.c_uint32), ("all_sites", ctypes.c_int32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
@@ -1231,6 +1316,88 @@ class GpuAligner:
         lib = gpu_lib()
         lib.salt_gpu_ws_stats_uncount.argtypes = [ctypes.c_void_p]
         _gpu_check(lib.salt_gpu_ws_stats_uncount(self._ws))
+
+    def indel_enable(self, on=True, min_mapq=20, log2_slots=0):
+        """Add, from now on, the insertions and deletions of every align call on this aligner's device index (its forks included) to the
+        index's table of allele keys, left-normalised; records below min_mapq do not count.  The first enable allocates and zeroes the
+        table (2^log2_slots slots of 16 bytes; 0: the default, 2^24), the counters and the difference array and needs set_contigs;
+        on=False stops and keeps them."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        _gpu_check(lib.salt_gpu_index_indel_enable(self._ix, 1 if on else 0, int(min_mapq), int(log2_slots)))
+
+    def indel_reset(self):
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_reset.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_index_indel_reset(self._ix))
+
+    def indel_stats(self):
+        """The four counters INDEL_STATS, uint64 (4,).  Synchronises the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        out = np.zeros(4, dtype=np.uint64)
+        _gpu_check(lib.salt_gpu_index_indel_stats(self._ix, out.ctypes.data))
+        return out
+
+    def indel_fetch(self):
+        """The slots with a non-zero value as a uint64 (n, 2) array of (key, value) pairs in key order."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_fetch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        n = ctypes.c_uint64()
+        _gpu_check(lib.salt_gpu_index_indel_fetch(self._ix, 0, None, ctypes.byref(n)))
+        out = np.zeros((n.value, 2), dtype=np.uint64)
+        if n.value:
+            m = ctypes.c_uint64()
+            _gpu_check(lib.salt_gpu_index_indel_fetch(self._ix, n.value, out.ctypes.data, ctypes.byref(m)))
+            if m.value != n.value:
+                raise SaltError("indel_fetch: the table changed between two calls")
+        return out
+
+    def indel_add(self, entries):
+        """Inserts (key, value) pairs with the kernels' insert routine: how the tables of several GPUs are summed."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        entries = np.ascontiguousarray(entries, dtype=np.uint64).reshape(-1, 2)
+        _gpu_check(lib.salt_gpu_index_indel_add(self._ix, entries.ctypes.data, entries.shape[0]))
+
+    def indel_fetch_diff(self, first, n):
+        """Words [first, first + n) of the tally's own difference array (uint32, ref_len + 1 words)."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_fetch_diff.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        out = np.zeros(max(int(n), 0), dtype=np.uint32)
+        _gpu_check(lib.salt_gpu_index_indel_fetch_diff(self._ix, int(first), int(n), out.ctypes.data))
+        return out
+
+    def indel_add_diff(self, first, words):
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_add_diff.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        if words.ndim != 1:
+            raise SaltError("indel_add_diff: words of shape (n,)")
+        _gpu_check(lib.salt_gpu_index_indel_add_diff(self._ix, int(first), words.shape[0], words.ctypes.data))
+
+    def indel_uncount(self):
+        """Takes back what this aligner's last align call added to the indel table, its counters and its difference array."""
+        lib = gpu_lib()
+        lib.salt_gpu_ws_indel_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(lib.salt_gpu_ws_indel_uncount(self._ws))
+
+    def indel_text(self, min_alt=3, min_pct=20, tile_positions=0, bgzf=False, pieces=False):
+        """The VCF records of the table and the difference array as they stand, sorted, called and printed on the device (no header); with
+        bgzf whole BGZF blocks (no end-of-file block).  pieces=True: the list of pieces as they left the device."""
+        lib = gpu_lib()
+        lib.salt_gpu_index_indel_text_begin.argtypes = [ctypes.c_void_p, ctypes.POINTER(_IndelTextOpt)]
+        lib.salt_gpu_index_indel_text_next.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        opt = _IndelTextOpt(int(min_alt), int(min_pct), int(tile_positions), 1 if bgzf else 0)
+        _gpu_check(lib.salt_gpu_index_indel_text_begin(self._ix, ctypes.byref(opt)))
+        out = []
+        while True:
+            p, n = ctypes.c_void_p(), ctypes.c_uint64()
+            _gpu_check(lib.salt_gpu_index_indel_text_next(self._ix, ctypes.byref(p), ctypes.byref(n)))
+            if n.value == 0:
+                break
+            out.append(ctypes.string_at(p.value, n.value))
+        return out if pieces else b"".join(out)
 
     def set_quals(self, quals, on_device=False):
         """Quality bytes (Phred + 33, FASTQ order) parallel to the bases of the NEXT alnse_core1 / alnpe_core1 (a uint8 array or bytes) or,

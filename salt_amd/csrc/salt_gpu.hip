@@ -74,7 +74,7 @@ struct salt_gpu_index {
     // difference array of ref_len + 1 words (the text state and its buffers come with the first salt_gpu_index_depth_text_begin);
     // errprof: E[2][512][95][4][4] and R[2][8] behind it, uint64; gt: salt_gt_site_t[snp_sites] as uint64 words, over the snp tally's site table
     // (built by whichever of the two is enabled first; the text state and its buffers come with the first salt_gpu_index_gt_text_begin).
-    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt, disc, stats;
+    struct Tally { uint32_t min_mapq = 0; bool on = false; } snp, depth, errprof, gt, disc, stats, indel;
     DevBuf<SnpWin> d_snp_tab; DevBuf<uint32_t> d_snp_counts; uint64_t snp_win = 0; uint32_t snp_sites = 0;
     DevBuf<uint32_t> d_depth; DepthText *depth_text = nullptr;
     std::vector<int64_t> h_c_off; uint32_t c_name_max = 0;      // set_contigs' offsets and longest name, for the depth text
@@ -84,6 +84,8 @@ struct salt_gpu_index {
     DevBuf<unsigned long long> d_disc_alt; DevBuf<uint32_t> d_disc_diff; uint32_t disc_min_baseq = 0; DiscText *disc_text = nullptr;
     // stats: SALT_STATS_CELLS cells, then CT[stats_contigs][8], uint64; stats_contigs is n_contigs as the first enable found it (4.11)
     DevBuf<unsigned long long> d_stats; int32_t stats_contigs = 0;
+    // indel: 2^indel_log2 slots of (key, value), the four counters, and the tally's own difference array of ref_len + 1 words (4.12)
+    DevBuf<IndelSlot> d_indel; DevBuf<unsigned long long> d_indel_stat; DevBuf<uint32_t> d_indel_diff; uint32_t indel_log2 = 0; IndelText *indel_text = nullptr;
 };
 
 // Every allocation below is a DevBuf / PinBuf: a new buffer is one field here and one reserve() or alloc() where it is sized.  Buffers that
@@ -138,8 +140,8 @@ struct salt_gpu_ws {
     // what the last align call added to each tally (n_rec 0: nothing) and on which stream, for the salt_gpu_ws_*_uncount calls; the error
     // profile's job carries its quality source
     template <class Job> struct LastJob { Job job{}; hipStream_t st = nullptr; };
-    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last; LastJob<DiscAdd> disc_last; LastJob<StatsAdd> stats_last;
-    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; disc_last.job.n_rec = 0; stats_last.job.n_rec = 0; }
+    LastJob<SnpCount> snp_last; LastJob<DepthMark> depth_last; LastJob<ErrProf> ep_last; LastJob<GtAdd> gt_last; LastJob<DiscAdd> disc_last; LastJob<StatsAdd> stats_last; LastJob<IndelAdd> indel_last;
+    void forget_last() { snp_last.job.n_rec = 0; depth_last.job.n_rec = 0; ep_last.job.n_rec = 0; gt_last.job.n_rec = 0; disc_last.job.n_rec = 0; stats_last.job.n_rec = 0; indel_last.job.n_rec = 0; }
     // the quality bytes of the error profile and the genotype sums: q_next is salt_gpu_ws_set_quals' pointer, waiting for the next host-buffer or resident call;
     // q_cur is the source of the call that is being queued (the text entry points set it to their raw block); d_quals holds a host call's bytes
     const uint8_t *q_next = nullptr; bool q_next_dev = false;
@@ -320,6 +322,7 @@ extern "C" void salt_gpu_index_detach(salt_gpu_index_t *ix)
     depth_text_free(ix->depth_text);
     gt_text_free(ix->gt_text);
     disc_text_free(ix->disc_text);
+    indel_text_free(ix->indel_text);
     delete ix;
 }
 
@@ -492,7 +495,8 @@ template <class Job> static int tally_launch(salt_gpu_ws::LastJob<Job> &last, hi
 // profile (k_errprof), their bases and qualities at the SNP sites into its genotype sums (k_gt_add), the bases the mixRef does not have into
 // its candidate arrays (k_disc_add), the last three with the qualities of the
 // call's source (ws->q_cur: the text block, salt_gpu_ws_set_quals' bytes, or
-// none), and what the run's summary counts of them into its tables (k_stats_add; pe_opt: the call's -a / -b window, null single end).
+// none), what the run's summary counts of them into its tables (k_stats_add; pe_opt: the call's -a / -b window, null single end), and their
+// insertions and deletions, left-shifted, into its table of allele keys (k_indel_add).
 // Every entry point that leaves result rows passes here: single end at the end of align_resident_impl, paired end at the end of
 // pe_resident_impl (the rows are final only behind k_pe_final).
 static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, const void *d_offs, const void *d_results, const salt_pe_opt_t *pe_opt, hipStream_t st)
@@ -543,6 +547,15 @@ static int rows_hooks(salt_gpu_ws_t *ws, uint32_t n_rec, const void *d_seqs, con
         c.cells = ix->d_stats; c.ct = ix->d_stats + SALT_STATS_CELLS;
         c.min_mapq = ix->stats.min_mapq; c.min_tlen = pe ? pe_opt->min_tlen : 0u; c.max_tlen = pe ? pe_opt->max_tlen : 0u; c.pe = pe; c.delta = 1ull;
         if (const int rc = tally_launch(ws->stats_last, launch_stats_add, c, st)) return rc;
+    }
+    if (ix->indel.on) {
+        if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "indels: the contig table is gone (salt_gpu_index_set_contigs)");
+        IndelAdd c{};
+        c.res = res; c.seqs = seqs; c.offs = offs; c.n_rec = n_rec;
+        c.text = ix->view.text; c.text_len = ix->view.c_seq_len; c.ref_len = ix->view.ref_len; c.c_off = ix->d_c_off; c.n_contigs = ix->n_contigs;
+        c.diff = ix->d_indel_diff; c.tab = ix->d_indel; c.log2_slots = ix->indel_log2; c.stat = ix->d_indel_stat;
+        c.min_mapq = ix->indel.min_mapq; c.pe = pe; c.delta = 1ull;
+        if (const int rc = tally_launch(ws->indel_last, launch_indel_add, c, st)) return rc;
     }
     return SALT_OK;
 }
@@ -2410,6 +2423,159 @@ extern "C" int salt_gpu_ws_stats_uncount(salt_gpu_ws_t *ws)
         ws->stats_last.job.c_off = ws->ix->d_c_off;
     }
     return tally_uncount(ws, &salt_gpu_ws::stats_last, launch_stats_add, ~0ull, &salt_gpu_index::d_stats, STATS_NEVER);
+}
+
+// ---- indel candidates ----
+static const char *const INDEL_NEVER = "indels: the table was never enabled on this index (salt_gpu_index_indel_enable)";
+
+// The first enable allocates and zeroes the table (16 bytes a slot), the counters and the difference array (4 bytes a genome position).
+extern "C" int salt_gpu_index_indel_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq, uint32_t log2_slots)
+{
+    if (log2_slots && (log2_slots < SALT_INDEL_LOG2_MIN || log2_slots > SALT_INDEL_LOG2_MAX))
+        return fail(SALT_E_INVAL, "indels: log2_slots " + std::to_string(log2_slots) + " is outside 6 .. 28 (0: the default, 24)");
+    return tally_enable(ix, &salt_gpu_index::indel, "indels", on, min_mapq, [&]() -> int {
+        if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "indels need the contig table (an allele stays inside its contig): call salt_gpu_index_set_contigs first");
+        if (ix->d_indel) {
+            if (log2_slots == 0 || log2_slots == ix->indel_log2) return SALT_OK;
+            return fail(SALT_E_INVAL, "indels: the table has 2^" + std::to_string(ix->indel_log2) + " slots since the first enable, not 2^" + std::to_string(log2_slots));
+        }
+        const uint32_t lg = log2_slots ? log2_slots : SALT_INDEL_LOG2_DEFAULT;
+        const uint64_t slots = 1ull << lg, n = ix->view.ref_len;
+        if (n == 0) return fail(SALT_E_INVAL, "indels: the index has an empty genome");
+        const std::string size = std::to_string(slots * 16 + 32 + (n + 1) * 4) + " bytes (16 for each of 2^" + std::to_string(lg) + " slots, 4 per genome position)";
+        DevBuf<IndelSlot> tab; DevBuf<unsigned long long> stat; DevBuf<uint32_t> diff;
+        if (const int rc = alloc_zeroed(tab, slots, "indels", "the table and the difference array: " + size)) return rc;
+        if (const int rc = alloc_zeroed(stat, 4, "indels", "the table and the difference array: " + size)) return rc;
+        if (const int rc = alloc_zeroed(diff, n + 1, "indels", "the table and the difference array: " + size)) return rc;
+        ix->d_indel.take(tab); ix->d_indel_stat.take(stat); ix->d_indel_diff.take(diff); ix->indel_log2 = lg;      // the index owns them from here
+        return SALT_OK;
+    });
+}
+
+extern "C" int salt_gpu_index_indel_reset(salt_gpu_index_t *ix)
+{
+    if (!ix) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemset(ix->d_indel, 0, (16ull << ix->indel_log2)));
+    HIPCHK(hipMemset(ix->d_indel_stat, 0, 32));
+    HIPCHK(hipMemset(ix->d_indel_diff, 0, ((uint64_t)ix->view.ref_len + 1) * 4));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_stats(salt_gpu_index_t *ix, uint64_t out[4])
+{
+    if (!ix || !out) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, ix->d_indel_stat, 32, hipMemcpyDeviceToHost));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_fetch(salt_gpu_index_t *ix, uint64_t cap, uint64_t *entries, uint64_t *n)
+{
+    if (!ix || !n || (!entries && cap)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!ix->indel_text) ix->indel_text = indel_text_new();
+    std::string err; uint64_t live = 0; const unsigned long long *keys = nullptr, *vals = nullptr;
+    if (const int rc = indel_sorted(ix->indel_text, ix->d_indel, ix->indel_log2, &live, &keys, &vals, err)) return fail(rc, err);
+    *n = live;
+    const uint64_t take = std::min(cap, live);
+    if (take == 0) return SALT_OK;
+    std::vector<uint64_t> k((size_t)take), v((size_t)take);
+    HIPCHK(hipMemcpy(k.data(), keys, take * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v.data(), vals, take * 8, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < take; ++i) { entries[2 * i] = k[(size_t)i]; entries[2 * i + 1] = v[(size_t)i]; }
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_add(salt_gpu_index_t *ix, const uint64_t *entries, uint64_t n)
+{
+    if (!ix || (!entries && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    if (n == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf<unsigned long long> d_in;
+    if (d_in.alloc(n * 2) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, "indels add: no room for " + std::to_string(n * 16) + " bytes of pairs to add"); }
+    HIPCHK(hipMemcpy(d_in, entries, n * 16, hipMemcpyHostToDevice));
+    HIPCHK(launch_indel_put(d_in, n, ix->d_indel, ix->indel_log2, ix->d_indel_stat, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return SALT_OK;
+}
+
+// first + n words inside diff's [0, ref_len], or the message that names the range
+static int indel_diff_range(const salt_gpu_index *ix, const char *what, uint64_t first, uint64_t n)
+{
+    const uint64_t words = (uint64_t)ix->view.ref_len + 1;
+    if (first > words || n > words - first)
+        return fail(SALT_E_INVAL, std::string("indels ") + what + ": words [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") leave diff's [0, " + std::to_string(words) + ")");
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_fetch_diff(salt_gpu_index_t *ix, uint64_t first, uint64_t n, uint32_t *out)
+{
+    if (!ix || (!out && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    if (const int rc = indel_diff_range(ix, "fetch", first, n)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (n) HIPCHK(hipMemcpy(out, ix->d_indel_diff + first, n * 4, hipMemcpyDeviceToHost));
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_add_diff(salt_gpu_index_t *ix, uint64_t first, uint64_t n, const uint32_t *in)
+{
+    if (!ix || (!in && n)) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    if (const int rc = indel_diff_range(ix, "add", first, n)) return rc;
+    if (n == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf<uint32_t> d_in;
+    if (d_in.alloc(n) != hipSuccess) { (void)hipGetLastError(); return fail(SALT_E_NOMEM, "indels add: no room for " + std::to_string(n * 4) + " bytes of words to add"); }
+    HIPCHK(hipMemcpy(d_in, in, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_depth_add(ix->d_indel_diff + first, d_in, n, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_text_begin(salt_gpu_index_t *ix, const salt_indel_text_opt_t *opt)
+{
+    if (!ix || !opt) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    if (opt->min_alt < 1) return fail(SALT_E_INVAL, "indel text: min_alt 0 is outside 1 .. 4294967295");
+    if (opt->min_pct > 100) return fail(SALT_E_INVAL, "indel text: min_pct " + std::to_string(opt->min_pct) + " is above 100");
+    if (!ix->d_c_off || ix->n_contigs < 1) return fail(SALT_E_INVAL, "indel text needs the contig table: call salt_gpu_index_set_contigs first");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!ix->indel_text) ix->indel_text = indel_text_new();
+    std::string err;
+    const int rc = indel_text_begin(ix->indel_text, ix->d_indel, ix->indel_log2, ix->d_indel_diff, ix->view.text, ix->view.ref_len, ix->view.c_seq_len,
+                                    ix->d_c_off, ix->d_c_name_off, ix->d_c_names, ix->n_contigs, ix->c_name_max, opt->min_alt, opt->min_pct, opt->tile_positions, opt->bgzf, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_index_indel_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes)
+{
+    if (!ix || !data || !n_bytes) return fail(SALT_E_INVAL, "null argument");
+    if (!ix->d_indel) return fail(SALT_E_INVAL, INDEL_NEVER);
+    if (!ix->indel_text) return fail(SALT_E_INVAL, "indel text: no text was begun (salt_gpu_index_indel_text_begin)");
+    HIPCHK(hipSetDevice(ix->device));
+    std::string err;
+    const int rc = indel_text_next(ix->indel_text, data, n_bytes, err);
+    return rc ? fail(rc, err) : SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_indel_uncount(salt_gpu_ws_t *ws)
+{
+    if (ws && ws->indel_last.job.n_rec) {                      // the contig table may have been set again since: the job reads the one that stands
+        if (!ws->ix->d_c_off || ws->ix->n_contigs < 1) return fail(SALT_E_INVAL, "indels: the contig table is gone since the call that is to be taken back");
+        ws->indel_last.job.c_off = ws->ix->d_c_off; ws->indel_last.job.n_contigs = ws->ix->n_contigs;
+    }
+    return tally_uncount(ws, &salt_gpu_ws::indel_last, launch_indel_add, ~0ull, &salt_gpu_index::d_indel, INDEL_NEVER);
 }
 
 extern "C" int salt_gpu_ws_set_quals(salt_gpu_ws_t *ws, const uint8_t *quals, int on_device)

@@ -350,6 +350,30 @@ struct StatsAdd {                                                              /
 };
 hipError_t launch_stats_add(const StatsAdd &c, hipStream_t st);
 
+// ---- indel candidates (salt_indel.hip) ----
+struct IndelSlot { unsigned long long key, val; };                             // key 0: empty; val: forward observations low, reverse high
+struct IndelAdd {                                                              // what k_indel_add reads (by value)
+    const salt_result_t *res; const uint8_t *seqs; const uint32_t *offs; uint32_t n_rec;      // the batch: rows, codes as sequenced, offsets
+    const uint32_t *text; uint32_t text_len, ref_len;                          // the 2-bit genome, 16 bases a word, and the positions it holds
+    const int64_t *c_off; int32_t n_contigs;                                   // set_contigs' offsets (n_contigs >= 1)
+    uint32_t *diff; IndelSlot *tab; uint32_t log2_slots; unsigned long long *stat;      // this tally's difference array, ref_len + 1 words; 2^log2_slots slots; stat[4]
+    uint32_t min_mapq; int32_t pe;                                             // pe: rows of a paired-end batch (reverse iff strand == 1, soft clips)
+    unsigned long long delta;                                                  // 1; 2^64 - 1 takes a batch's adds back
+};
+hipError_t launch_indel_add(const IndelAdd &c, hipStream_t st);
+// n hand-given (key, value) pairs through the insert routine of k_indel_add
+hipError_t launch_indel_put(const unsigned long long *pairs, uint64_t n, IndelSlot *tab, uint32_t log2_slots, unsigned long long *stat, hipStream_t st);
+// The slots with a non-zero value, sorted by key, into buffers the text state owns (salt_gpu_index_indel_fetch reads them from there), and
+// the records of the called ones piece by piece.  All return SALT_OK or an error code with the message in err.
+struct IndelText;
+IndelText *indel_text_new();
+void indel_text_free(IndelText *t);
+int indel_sorted(IndelText *t, const IndelSlot *d_tab, uint32_t log2_slots, uint64_t *n, const unsigned long long **d_keys, const unsigned long long **d_vals, std::string &err);
+int indel_text_begin(IndelText *t, const IndelSlot *d_tab, uint32_t log2_slots, const uint32_t *d_diff, const uint32_t *d_text, uint32_t ref_len, uint32_t text_len,
+                     const int64_t *d_c_off, const uint32_t *d_c_name_off, const char *d_c_names, int32_t n_contigs, uint32_t max_name,
+                     uint32_t min_alt, uint32_t min_pct, uint32_t tile_positions, int bgzf, std::string &err);
+int indel_text_next(IndelText *t, const char **data, uint64_t *n_bytes, std::string &err);
+
 // attach-time re-packing + expansion kernels (salt_index.hip)
 void launch_pack_c_occ(const uint32_t *bwt, uint64_t bwt_words, uint32_t seq_len, uint64_t n_blocks, COcc *out, uint32_t *err, hipStream_t st);
 void launch_pack_r_occ(const uint32_t *code, uint64_t code_words, const uint32_t *minor, uint64_t minor_words, const uint32_t *major, uint64_t major_words,

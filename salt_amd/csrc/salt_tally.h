@@ -55,6 +55,25 @@ template <class F> __device__ __forceinline__ void tally_m_runs(const salt_resul
     }
 }
 
+// The same walk for a tally that also reads the gaps (k_indel_add): fm(g, s, len) for every M run as above, and fgap(what, len, g, s, prev,
+// next) for every I (what 1) and D (what 2) op met at genome position g and base s of SEQ as printed, with the CIGAR words of the ops in
+// front of it and behind it; TALLY_NO_OP where the row has none (its `& 3` is 3: no M).
+static constexpr uint32_t TALLY_NO_OP = 0xFFFFFFFFu;
+template <class FM, class FG> __device__ __forceinline__ void tally_ops(const salt_result_t *q, const TallyRow &r, FM fm, FG fgap)
+{
+    uint64_t g = r.pos;
+    uint32_t s = r.s_lead, prev = TALLY_NO_OP, op = r.n_ops ? q->cigar[0] : TALLY_NO_OP;
+    for (uint32_t k = 0; k < r.n_ops; ++k) {
+        const uint32_t next = k + 1 < r.n_ops ? q->cigar[k + 1] : TALLY_NO_OP, len = op >> 4, what = op & 3u;
+        if (what == 0u) { fm(g, s, len); g += len; s += len; }
+        else if (what != 3u) {
+            fgap(what, len, g, s, prev, next);
+            if (what == 1u) s += len; else g += len;
+        }
+        prev = op; op = next;
+    }
+}
+
 // An M run [g, g + len) into a difference array of ref_len + 1 words (DESIGN.md 4.7's rule; k_depth_mark and k_disc_add): delta at g, taken
 // again at the run's end, the run cut at the genome's end.  Returns that end (<= g: nothing of the run lies in the genome, nothing marked).
 __device__ __forceinline__ uint64_t tally_diff_mark(uint32_t *diff, uint32_t ref_len, uint64_t g, uint32_t len, uint32_t delta)

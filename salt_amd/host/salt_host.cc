@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cmath>
 #include <fstream>
+#include <map>
 #include <mutex>
 #include <sstream>
 #include <algorithm>
@@ -1328,5 +1329,170 @@ extern "C" int64_t salt_stats_text(const salt_index_t *ix, const uint64_t *cells
         for (int k = 0; k < 6; ++k) num(ct[c * 8 + (size_t)k]);
         o.put('\n');
     }
+    return (int64_t)o.n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Indel candidates: the host twin of k_indel_add and of the device's text kernels (salt_indel.hip; include/salt_gpu.h has the
+// definition), written from that definition over this program's own SAM record lines.  It shares nothing with anything under csrc/.
+// ---------------------------------------------------------------------------------------------
+struct salt_indel { std::map<uint64_t, uint64_t> tab; uint64_t stat[4] = { 0, 0, 0, 0 }; };
+
+namespace {
+
+// letter(x) of the definition: the 2-bit genome's base, A beyond it
+inline uint32_t indel_letter(const salt_index *ix, uint64_t x) { return (int64_t)x < ix->l_pac ? pac_at(ix, (uint32_t)x) : 0u; }
+
+struct IndelOp { char what; uint64_t n, g; size_t s; };
+
+// one record line [l, e): its M runs into diff, its I and D ops into the map and the counters; 1 it contributed, 0 it did not (unmapped,
+// below min_mapq), -1 with g_err set.  The line is checked whole (head, CIGAR) before anything is added.
+int indel_add_line(const salt_index *ix, const RefIds &ids, salt_indel &t, const char *l, const char *e, uint32_t min_mapq, uint32_t *diff)
+{
+    SamLine L; MRuns m; uint64_t g0;
+    const int h = twin_head(ix, ids, L, "indels: ", l, e, min_mapq, &g0);
+    if (h != 1) return h;
+    if (!twin_cigar(L, g0, m)) return -1;
+    const char *seq = L.f[9]; const size_t l_seq = L.len(9);
+    const bool rev = (L.flag & 16) != 0;
+    const uint64_t ref_len = ix->view.ref_len;
+    // the ops without the soft clips (twin_cigar has checked the text: digits, then one of M I S D)
+    std::vector<IndelOp> ops;
+    {
+        uint64_t g = g0, n = 0; size_t s = 0;
+        for (const char *p = L.f[5]; p < L.fe(5); ++p) {
+            if (*p >= '0' && *p <= '9') { n = 10 * n + (uint64_t)(*p - '0'); continue; }
+            if (*p != 'S') ops.push_back(IndelOp{ *p, n, g, s });
+            if (*p == 'M') { g += n; s += (size_t)n; } else if (*p == 'D') g += n; else s += (size_t)n;
+            n = 0;
+        }
+    }
+    for (int r = 0; r < m.n; ++r) {
+        const uint64_t a = m.g[r], b = std::min<uint64_t>(a + m.len[r], ref_len);      // cut at the genome's end: not wrapped, not refused
+        if (a < b) { diff[a] += 1u; diff[b] -= 1u; }
+    }
+    for (size_t k = 0; k < ops.size(); ++k) {
+        const IndelOp &op = ops[k];
+        if (op.what == 'M') continue;
+        const bool del = op.what == 'D';
+        const uint64_t n = op.n;
+        if (n < 1 || n > (del ? SALT_INDEL_MAX_DEL : SALT_INDEL_MAX_INS)) { ++t.stat[SALT_INDEL_LONG]; continue; }
+        uint64_t g = op.g;
+        bool ok = k > 0 && k + 1 < ops.size() && ops[k - 1].what == 'M' && ops[k - 1].n >= 1 && ops[k + 1].what == 'M' && ops[k + 1].n >= 1 && g >= 1;
+        uint64_t first = 0;
+        if (ok) {
+            size_t c = 0;                                                          // the last contig that begins at or in front of the anchor
+            while (c + 1 < ix->anns.size() && (uint64_t)ix->anns[c + 1].offset <= g - 1) ++c;
+            first = (uint64_t)ix->anns[c].offset;
+            const uint64_t end = std::min<uint64_t>(c + 1 < ix->anns.size() ? (uint64_t)ix->anns[c + 1].offset : ref_len, ref_len);
+            ok = g < end && (!del || g + n <= end);
+        }
+        uint8_t b[SALT_INDEL_MAX_INS] = { 0 };
+        if (ok && !del) {
+            ok = op.s + n <= l_seq;
+            for (uint64_t j = 0; ok && j < n; ++j) { const int code = base_code(seq[op.s + j]); if (code < 0) ok = false; else b[j] = (uint8_t)code; }
+        }
+        if (!ok) { ++t.stat[SALT_INDEL_UNANCHORED]; continue; }
+        for (uint32_t step = 0; step < SALT_INDEL_MAX_SHIFT && g - 1 > first; ++step) {
+            const uint32_t a = indel_letter(ix, g - 1);
+            if (del) { if (a != indel_letter(ix, g + n - 1)) break; }
+            else {
+                if (a != b[n - 1]) break;
+                for (uint64_t j = n - 1; j > 0; --j) b[j] = b[j - 1];
+                b[0] = (uint8_t)a;
+            }
+            --g;
+        }
+        uint64_t key = 1ull << 63 | g << 31 | (del ? 1ull << 30 : 0ull) | n << 24;
+        if (!del) for (uint64_t j = 0; j < n; ++j) key |= (uint64_t)b[j] << (22 - 2 * j);
+        t.tab[key] += rev ? 1ull << 32 : 1ull;
+        ++t.stat[SALT_INDEL_TABLED];
+    }
+    return 1;
+}
+
+bool indel_sizes(const salt_index *ix, uint64_t n_pos)
+{
+    if (n_pos == ix->view.ref_len) return true;
+    g_err = "indels: a difference array for " + std::to_string(n_pos) + " positions, the index has " + std::to_string((uint64_t)ix->view.ref_len) + " (diff: ref_len + 1 words)";
+    return false;
+}
+
+} // namespace
+
+extern "C" salt_indel_t *salt_indel_new(void) { return new salt_indel; }
+extern "C" void salt_indel_free(salt_indel_t *t) { delete t; }
+
+extern "C" int64_t salt_indel_add_sam(const salt_index_t *ix, salt_indel_t *t, const char *sam, size_t n, uint32_t min_mapq, uint32_t *diff, uint64_t n_pos)
+{
+    if (!ix || !t || (!sam && n) || !diff) { g_err = "indels: null argument"; return -1; }
+    if (!indel_sizes(ix, n_pos)) return -1;
+    const RefIds ids(ix);
+    return for_record_lines(sam, n, true, [&](const char *l, const char *e) { return indel_add_line(ix, ids, *t, l, e, min_mapq, diff); });
+}
+
+extern "C" int64_t salt_indel_entries(const salt_indel_t *t, uint64_t *out, uint64_t cap)
+{
+    if (!t || (!out && cap)) { g_err = "indels: null argument"; return -1; }
+    uint64_t n = 0;
+    for (const auto &kv : t->tab) {
+        if (kv.second == 0) continue;
+        if (n < cap) { out[2 * n] = kv.first; out[2 * n + 1] = kv.second; }
+        ++n;
+    }
+    return (int64_t)n;
+}
+
+extern "C" void salt_indel_stats(const salt_indel_t *t, uint64_t out[4]) { for (int i = 0; i < 4; ++i) out[i] = t ? t->stat[i] : 0; }
+
+extern "C" int64_t salt_indel_text(const salt_index_t *ix, const uint64_t *entries, uint64_t n, const uint32_t *diff, uint64_t n_pos, uint32_t min_alt, uint32_t min_pct,
+                                   char *out, uint64_t cap)
+{
+    if (!ix || (!entries && n) || !diff || (!out && cap)) { g_err = "indels: null argument"; return -1; }
+    if (!indel_sizes(ix, n_pos)) return -1;
+    if (min_alt < 1 || min_pct > 100) { g_err = "indels: min_alt is 1 .. 4294967295 and min_pct 0 .. 100"; return -1; }
+    for (uint64_t i = 1; i < n; ++i) if (entries[2 * i] <= entries[2 * (i - 1)]) { g_err = "indels: the pairs are not in key order"; return -1; }
+    DepthOut o{ out, cap };
+    static const char NT[] = "ACGT";
+    uint32_t depth = 0; uint64_t at = 0;                               // depth = the prefix sum of diff[0 .. at), mod 2^32
+    size_t c = 0;                                                      // the last contig that begins at or in front of the anchor
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t key = entries[2 * i], v = entries[2 * i + 1];
+        const uint64_t g = (key >> 31) & 0xFFFFFFFFull, len = (key >> 24) & 63u, bases = key & 0xFFFFFFu;
+        const bool del = (key >> 30) & 1u;
+        if (!(key >> 63) || g < 1 || g > n_pos || len < 1 || v == 0) continue;
+        if (del ? bases != 0 : len > SALT_INDEL_MAX_INS || (bases & ((1u << (24 - 2 * len)) - 1u)) != 0) continue;
+        const uint64_t a = g - 1;
+        while (at <= a) depth += diff[at++];                           // (keys in order: the anchors do not go back)
+        const uint64_t fwd = v & 0xFFFFFFFFull, rev = v >> 32, ao = fwd + rev;
+        if (ao < min_alt || 100 * ao < (uint64_t)min_pct * depth) continue;
+        while (c + 1 < ix->anns.size() && (uint64_t)ix->anns[c + 1].offset <= a) ++c;
+        o.puts(ix->anns[c].name); o.put('\t'); o.putu(a - (uint64_t)ix->anns[c].offset + 1); o.puts("\t.\t");
+        const char anchor = NT[indel_letter(ix, a)];
+        o.put(anchor);
+        if (del) for (uint64_t k = 0; k < len; ++k) o.put(NT[indel_letter(ix, g + k)]);
+        o.put('\t'); o.put(anchor);
+        if (!del) for (uint64_t k = 0; k < len; ++k) o.put(NT[(bases >> (22 - 2 * k)) & 3u]);
+        o.puts("\t.\t.\tTYPE="); o.puts(del ? "DEL" : "INS"); o.puts(";LEN="); o.putu(len); o.puts(";DP="); o.putu(depth);
+        o.puts(";AO="); o.putu(ao); o.puts(";AOF="); o.putu(fwd); o.puts(";AOR="); o.putu(rev); o.put('\n');
+    }
+    return (int64_t)o.n;
+}
+
+extern "C" int64_t salt_indel_header(const salt_index_t *ix, uint32_t min_mapq, uint32_t min_alt, uint32_t min_pct, uint64_t dropped, char *out, uint64_t cap)
+{
+    if (!ix || (!out && cap)) { g_err = "indels: null argument"; return -1; }
+    DepthOut o{ out, cap };
+    o.puts("##fileformat=VCFv4.2\n##source=salt --indels\n");
+    for (const Ann &a : ix->anns) { o.puts("##contig=<ID="); o.puts(a.name); o.puts(",length="); o.putu((uint64_t)a.len); o.puts(">\n"); }
+    o.puts("##INFO=<ID=TYPE,Number=1,Type=String,Description=\"INS or DEL\">\n"
+           "##INFO=<ID=LEN,Number=1,Type=Integer,Description=\"Inserted or deleted bases\">\n"
+           "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Counted reads whose M runs cover the anchor base\">\n"
+           "##INFO=<ID=AO,Number=1,Type=Integer,Description=\"Counted reads that show the allele, left-normalised\">\n"
+           "##INFO=<ID=AOF,Number=1,Type=Integer,Description=\"... on the forward strand\">\n"
+           "##INFO=<ID=AOR,Number=1,Type=Integer,Description=\"... on the reverse strand\">\n"
+           "##salt_indels_parameters=<min_mapq="); o.putu(min_mapq); o.puts(",min_alt="); o.putu(min_alt); o.puts(",min_pct="); o.putu(min_pct);
+    o.puts(">\n##salt_indels_dropped="); o.putu(dropped);
+    o.puts("\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     return (int64_t)o.n;
 }

@@ -106,6 +106,17 @@ extern "C" int salt_gpu_ws_disc_uncount(salt_gpu_ws_t *ws) __attribute__((weak))
 extern "C" int salt_gpu_index_stats_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq) __attribute__((weak));
 extern "C" int salt_gpu_index_stats_fetch(salt_gpu_index_t *ix, uint64_t *cells, uint64_t cap_cells, uint64_t *ct, uint64_t cap_ct, int reset) __attribute__((weak));
 extern "C" int salt_gpu_ws_stats_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
+// Likewise the indel candidates (--indels): without the device's table and text kernels the map comes from the SAM lines
+// (salt_indel_add_sam) and the records from the host twin's printer (salt_indel_text).
+extern "C" int salt_gpu_index_indel_enable(salt_gpu_index_t *ix, int on, uint32_t min_mapq, uint32_t log2_slots) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_stats(salt_gpu_index_t *ix, uint64_t out[4]) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_fetch(salt_gpu_index_t *ix, uint64_t cap, uint64_t *entries, uint64_t *n) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_add(salt_gpu_index_t *ix, const uint64_t *entries, uint64_t n) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_fetch_diff(salt_gpu_index_t *ix, uint64_t first, uint64_t n, uint32_t *out) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_add_diff(salt_gpu_index_t *ix, uint64_t first, uint64_t n, const uint32_t *in) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_text_begin(salt_gpu_index_t *ix, const salt_indel_text_opt_t *opt) __attribute__((weak));
+extern "C" int salt_gpu_index_indel_text_next(salt_gpu_index_t *ix, const char **data, uint64_t *n_bytes) __attribute__((weak));
+extern "C" int salt_gpu_ws_indel_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 
 namespace {
 
@@ -485,7 +496,7 @@ struct BamRun {
     const salt_index_t *ix = nullptr;
 } g_bam;
 
-// The six row tallies (--snp-counts, --depth, --error-profile, --genotype, --discover, --stats) run alike.  On the device the table belongs to each GPU's index and every
+// The seven row tallies (--snp-counts, --depth, --error-profile, --genotype, --discover, --stats, --indels) run alike.  On the device the table belongs to each GPU's index and every
 // align call adds into it (salt_gpu_index_*_enable); a block the text path has aligned and then drops at a hand-over is taken back
 // (salt_gpu_ws_*_uncount): the host pipeline aligns those reads again.  Without the device's symbols the SAM lines of every block and
 // batch that is written go through the tally's host twin, one caller at a time.
@@ -518,15 +529,22 @@ struct DiscRun : TallyRun {
 // --stats FILE: the run's summary -- mapping counts, histograms of MAPQ, read length, GC, insert size and indel length, counts per contig.
 // After the last block the GPUs' tables are fetched and summed on the host; salt_stats_text prints the file on both paths.
 struct StatsRun : TallyRun { std::vector<uint64_t> cells, ct; } g_stats;
+// --indels FILE: indel candidates as VCF.  Every GPU's index keeps a hash table of left-normalised allele keys and the tally's own
+// difference array; after the last block the other GPUs' live slots and arrays are added into the first GPU's, whose kernels sort the
+// alleles, apply the call rule and print the records piece by piece.  Like --discover its default MAPQ floor is 20.
+struct IndelRun : TallyRun {
+    bool gz = false; uint32_t min_alt = 3, min_pct = 20, log2_slots = 24; salt_indel_t *host_tab = nullptr; std::vector<uint32_t> host_diff;
+    IndelRun() { min_mapq = 20; }
+} g_indel;
 
-// What differs between them where they run alike, in the order snp, depth, error profile, genotype, discover, stats.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
+// What differs between them where they run alike, in the order snp, depth, error profile, genotype, discover, stats, indels.  opt: --OPT FILE; stem: --STEM-min-mapq; mode:
 // how the file is opened; does: what a libsalt_gpu without the symbols does not do (the --polish refusal); symbols: this libsalt_gpu has
 // the device side; host_add: the twin over SAM lines (< 0: refused); uncount: the last align call's adds leave the device's table.
 struct Tally {
     TallyRun *run; const char *opt, *stem, *mode, *does;
     bool (*symbols)(); int64_t (*host_add)(const char *sam, size_t n); int (*uncount)(salt_gpu_ws_t *ws);
 };
-const Tally TALLIES[6] = {
+const Tally TALLIES[7] = {
     { &g_snp, "snp-counts", "snp", "w", "counts",
       [] { return salt_gpu_index_snp_enable && salt_gpu_index_snp_sites && salt_gpu_index_snp_counts && salt_gpu_ws_snp_uncount; },
       [](const char *sam, size_t n) { return salt_snp_count_sam(g_snp.ix, sam, n, g_snp.min_mapq, g_snp.host_counts.data(), g_snp.n_sites); }, salt_gpu_ws_snp_uncount },
@@ -546,6 +564,10 @@ const Tally TALLIES[6] = {
     { &g_stats, "stats", "stats", "w", "makes the summary",
       [] { return salt_gpu_index_stats_enable && salt_gpu_index_stats_fetch && salt_gpu_ws_stats_uncount; },
       [](const char *sam, size_t n) { return salt_stats_add_sam(g_stats.ix, sam, n, g_stats.min_mapq, g_stats.cells.data(), g_stats.cells.size(), g_stats.ct.data(), g_stats.ct.size()); }, salt_gpu_ws_stats_uncount },
+    { &g_indel, "indels", "indels", "wb", "tables and prints the indels",
+      [] { return salt_gpu_index_indel_enable && salt_gpu_index_indel_stats && salt_gpu_index_indel_fetch && salt_gpu_index_indel_add && salt_gpu_index_indel_fetch_diff &&
+                  salt_gpu_index_indel_add_diff && salt_gpu_index_indel_text_begin && salt_gpu_index_indel_text_next && salt_gpu_ws_indel_uncount; },
+      [](const char *sam, size_t n) { return salt_indel_add_sam(g_indel.ix, g_indel.host_tab, sam, n, g_indel.min_mapq, g_indel.host_diff.data(), g_indel.host_diff.size() - 1); }, salt_gpu_ws_indel_uncount },
 };
 
 // the SAM lines of a block or batch that is about to be written, through every host twin that is on; false with the reason on stderr
@@ -682,6 +704,14 @@ int usage()
             "               --stats <file>           write the run's summary: mapped, properly paired and per-contig counts, histograms of MAPQ,\n"
             "                                        read length, GC, insert size and indel length, summed on the GPU behind every block\n"
             "               --stats-min-mapq <int>   --stats: records with a smaller MAPQ are mapped but not counted, 0 .. 255 [0]\n"
+            "               --indels        <file>   write the insertions and deletions the reads show as VCF 4.2 records, left-normalised\n"
+            "                                        against the genome: anchor position, REF, ALT, depth and the observations per strand\n"
+            "                                        (tabled, sorted, called and printed on the GPU); .gz is written as BGZF [off]\n"
+            "               --indels-min-mapq <int>  --indels: records with a smaller MAPQ do not count, 0 .. 255 [20]\n"
+            "               --indels-min-alt <int>   --indels: an allele is called from this many observations, 1 .. 4294967295 [3]\n"
+            "               --indels-min-pct <int>   --indels: ... that are at least this share of the depth at the anchor, 0 .. 100 [20]\n"
+            "               --indels-slots <int>     --indels: slots of the GPU's allele table, a power of two from 64 to 268435456, 16 bytes\n"
+            "                                        each; alleles that find no slot are dropped and counted [16777216]\n"
             "               --genotype      <file>   write a VCF 4.2 record per SNP site of the index: the genotype, allele depths and\n"
             "                                        likelihoods from the reads' bases and base qualities (summed, called and printed on\n"
             "                                        the GPU); a name ending in .gz is written as BGZF [off]\n"
@@ -1413,7 +1443,8 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "error-profile", 1, 0, 1009 }, { "error-profile-min-mapq", 1, 0, 1010 }, { "error-profile-full", 0, 0, 1011 },
         { "genotype", 1, 0, 1012 }, { "genotype-min-mapq", 1, 0, 1013 }, { "genotype-sample", 1, 0, 1014 },
         { "discover", 1, 0, 1015 }, { "discover-min-mapq", 1, 0, 1016 }, { "discover-min-baseq", 1, 0, 1017 }, { "discover-min-alt", 1, 0, 1018 }, { "discover-min-pct", 1, 0, 1019 },
-        { "discover-all", 0, 0, 1020 }, { "stats", 1, 0, 1021 }, { "stats-min-mapq", 1, 0, 1022 }, { 0, 0, 0, 0 } };
+        { "discover-all", 0, 0, 1020 }, { "stats", 1, 0, 1021 }, { "stats-min-mapq", 1, 0, 1022 },
+        { "indels", 1, 0, 1023 }, { "indels-min-mapq", 1, 0, 1024 }, { "indels-min-alt", 1, 0, 1025 }, { "indels-min-pct", 1, 0, 1026 }, { "indels-slots", 1, 0, 1027 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1436,8 +1467,8 @@ static int parse_options(int argc, char **argv, Opts &o)
             else { fprintf(stderr, "[opt_parse]: --polish=%s: the re-scoring is lv (Landau-Vishkin, the default) or sw (Smith-Waterman)\n", optarg); return 1; }
             break;
         case 1004: g_snp.on = true; g_snp.fn = optarg; break;
-        case 1005: case 1007: case 1010: case 1013: case 1016: case 1022: {
-            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : c == 1013 ? 3 : c == 1016 ? 4 : 5];
+        case 1005: case 1007: case 1010: case 1013: case 1016: case 1022: case 1024: {
+            const Tally &t = TALLIES[c == 1005 ? 0 : c == 1007 ? 1 : c == 1010 ? 2 : c == 1013 ? 3 : c == 1016 ? 4 : c == 1022 ? 5 : 6];
             char *end = nullptr; const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > 255) { fprintf(stderr, "[opt_parse]: --%s-min-mapq %s: a MAPQ is a number from 0 to 255\n", t.stem, optarg); return 1; }
             t.run->min_mapq = (uint32_t)v;
@@ -1468,6 +1499,22 @@ static int parse_options(int argc, char **argv, Opts &o)
         }
         case 1020: g_disc.all = true; break;
         case 1021: g_stats.on = true; g_stats.fn = optarg; break;
+        case 1023: g_indel.on = true; g_indel.fn = optarg; break;
+        case 1025: case 1026: {
+            const long long lo = c == 1025 ? 1 : 0, hi = c == 1025 ? 0xFFFFFFFFll : 100;
+            char *end = nullptr; errno = 0; const long long v = strtoll(optarg, &end, 10);
+            if (end == optarg || *end || errno || v < lo || v > hi) { fprintf(stderr, "[opt_parse]: --indels-min-%s %s: a number from %lld to %lld\n", c == 1025 ? "alt" : "pct", optarg, lo, hi); return 1; }
+            (c == 1025 ? g_indel.min_alt : g_indel.min_pct) = (uint32_t)v;
+            break;
+        }
+        case 1027: {
+            char *end = nullptr; errno = 0; const long long v = strtoll(optarg, &end, 10);
+            uint32_t lg = 0;
+            while (lg < 63 && (1ll << lg) < v) ++lg;
+            if (end == optarg || *end || errno || v < 64 || v > (1ll << 28) || (1ll << lg) != v) { fprintf(stderr, "[opt_parse]: --indels-slots %s: a power of two from 64 to 268435456\n", optarg); return 1; }
+            g_indel.log2_slots = lg;
+            break;
+        }
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1499,6 +1546,8 @@ static int parse_options(int argc, char **argv, Opts &o)
     g_gt.gz = lg > 3 && strcmp(g_gt.fn + lg - 3, ".gz") == 0;
     const size_t ld = g_disc.on ? strlen(g_disc.fn) : 0;
     g_disc.gz = ld > 3 && strcmp(g_disc.fn + ld - 3, ".gz") == 0;
+    const size_t li = g_indel.on ? strlen(g_indel.fn) : 0;
+    g_indel.gz = li > 3 && strcmp(g_indel.fn + li - 3, ".gz") == 0;
     return -1;
 }
 
@@ -1664,7 +1713,7 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 if (grc) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); set_failed(); break; }
                 double tf0 = now();
                 if (pe) format_batch_pe(ix, &o.so, &o.po, *b, pool); else format_batch(ix, &o.so, *b, pool);
-                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host() || g_disc.host() || g_stats.host()) {
+                if (g_snp.host() || g_depth.host() || g_errprof.host() || g_gt.host() || g_disc.host() || g_stats.host() || g_indel.host()) {
                     bool good = true;
                     for (const std::string &piece : b->sam) good = good && host_twins_add(piece.data(), piece.size());
                     if (!good) { set_failed(); break; }
@@ -2077,6 +2126,101 @@ static bool disc_finish(const salt_index_t *ix, const std::vector<salt_gpu_index
     return true;
 }
 
+// --indels, before the first block: the contig table (an allele stays inside its contig) and the tally on on every GPU's index, or the host's map
+static bool indel_begin(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &C)
+{
+    if (!g_indel.on) return true;
+    g_indel.ix = ix;
+    if (!g_indel.device) { g_indel.host_tab = salt_indel_new(); g_indel.host_diff.assign((size_t)salt_index_host_view(ix)->ref_len + 1, 0u); return true; }
+    for (salt_gpu_index_t *g : gix)
+        if (salt_gpu_index_set_contigs(g, C.n(), C.off.data(), C.nm.data()) || salt_gpu_index_indel_enable(g, 1, g_indel.min_mapq, g_indel.log2_slots)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; }
+    return true;
+}
+
+// --indels, after the last block of a run that succeeded: the other GPUs' live slots (through the insert kernel) and difference arrays are
+// added into the first one's, whose kernels sort the alleles, apply the call rule and print the records piece by piece; on the host the
+// twin's printer does.  The header carries the dropped events; a .gz file ends with the BGZF end-of-file block.
+static bool indel_finish(const salt_index_t *ix, const std::vector<salt_gpu_index_t *> &gix, const Contigs &C)
+{
+    if (!g_indel.on) return true;
+    FILE *f = g_indel.fp;
+    uint64_t text_bytes = 0, file_bytes = 0, stat[4] = { 0, 0, 0, 0 };
+    bool ok = true;
+    const uint64_t ref_len = salt_index_host_view(ix)->ref_len;
+    auto gpu_fail = [&]() { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return false; };
+    auto emit = [&](const std::string &text) {                         // text that was made on the host: the header, the host path's records
+        std::string z;
+        if (g_indel.gz && !text.empty() && !bgzf_deflate_host(text.data(), text.size(), z)) { fprintf(stderr, "[salt] --indels: no BGZF blocks for the text\n"); return false; }
+        const std::string &out = g_indel.gz ? z : text;
+        ok = ok && fwrite(out.data(), 1, out.size(), f) == out.size();
+        text_bytes += text.size(); file_bytes += out.size();
+        return true;
+    };
+    auto header = [&]() {
+        const int64_t need = salt_indel_header(ix, g_indel.min_mapq, g_indel.min_alt, g_indel.min_pct, stat[1], nullptr, 0);
+        std::string h(need > 0 ? (size_t)need : 0, '\0');
+        if (need < 0 || salt_indel_header(ix, g_indel.min_mapq, g_indel.min_alt, g_indel.min_pct, stat[1], &h[0], (uint64_t)need) != need) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+        return emit(h);
+    };
+    if (g_indel.device) {
+        // GPU 0's counters after the merge hold its own events and the others' tabled ones (tabled or dropped again on GPU 0); the others'
+        // dropped, long and unanchored are added on the host
+        uint64_t extra[4] = { 0, 0, 0, 0 };
+        if (gix.size() > 1) {
+            const uint64_t chunk = std::min<uint64_t>(ref_len + 1, 8u << 20);
+            std::vector<uint32_t> words((size_t)chunk);
+            std::vector<uint64_t> pairs;
+            for (size_t k = 1; k < gix.size(); ++k) {
+                uint64_t one[4], n = 0;
+                if (salt_gpu_index_indel_stats(gix[k], one) || salt_gpu_index_indel_fetch(gix[k], 0, nullptr, &n)) return gpu_fail();
+                pairs.resize((size_t)n * 2);
+                if (n && (salt_gpu_index_indel_fetch(gix[k], n, pairs.data(), &n) || salt_gpu_index_indel_add(gix[0], pairs.data(), n))) return gpu_fail();
+                for (int i = 1; i < 4; ++i) extra[i] += one[i];
+                for (uint64_t at = 0; at < ref_len + 1; at += chunk) {
+                    const uint64_t m = std::min(chunk, ref_len + 1 - at);
+                    if (salt_gpu_index_indel_fetch_diff(gix[k], at, m, words.data()) || salt_gpu_index_indel_add_diff(gix[0], at, m, words.data())) return gpu_fail();
+                }
+            }
+        }
+        if (salt_gpu_index_indel_enable(gix[0], 0, g_indel.min_mapq, 0) || salt_gpu_index_indel_stats(gix[0], stat)) return gpu_fail();
+        for (int i = 1; i < 4; ++i) stat[i] += extra[i];
+        if (!header()) return false;
+        salt_indel_text_opt_t to; to.min_alt = g_indel.min_alt; to.min_pct = g_indel.min_pct; to.tile_positions = 0; to.bgzf = g_indel.gz ? 1 : 0;
+        if (salt_gpu_index_set_contigs(gix[0], C.n(), C.off.data(), C.nm.data()) || salt_gpu_index_indel_text_begin(gix[0], &to)) return gpu_fail();
+        for (;;) {
+            const char *data = nullptr; uint64_t n = 0;
+            if (salt_gpu_index_indel_text_next(gix[0], &data, &n)) return gpu_fail();
+            if (n == 0) break;
+            ok = ok && fwrite(data, 1, (size_t)n, f) == n;
+            file_bytes += n; text_bytes += g_indel.gz ? bgzf_text_bytes(data, n) : n;
+        }
+    } else {
+        salt_indel_stats(g_indel.host_tab, stat);
+        if (!header()) return false;
+        const int64_t n = salt_indel_entries(g_indel.host_tab, nullptr, 0);
+        std::vector<uint64_t> pairs(n > 0 ? (size_t)n * 2 : 0);
+        if (n < 0 || salt_indel_entries(g_indel.host_tab, pairs.data(), (uint64_t)n) != n) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false; }
+        const int64_t need = salt_indel_text(ix, pairs.data(), (uint64_t)n, g_indel.host_diff.data(), ref_len, g_indel.min_alt, g_indel.min_pct, nullptr, 0);
+        std::string text(need > 0 ? (size_t)need : 0, '\0');
+        if (need < 0 || salt_indel_text(ix, pairs.data(), (uint64_t)n, g_indel.host_diff.data(), ref_len, g_indel.min_alt, g_indel.min_pct, &text[0], (uint64_t)need) != need) {
+            fprintf(stderr, "[salt] %s\n", salt_host_last_error()); return false;
+        }
+        if (!emit(text)) return false;
+        salt_indel_free(g_indel.host_tab); g_indel.host_tab = nullptr;
+    }
+    if (g_indel.gz) { ok = ok && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, f) == sizeof BGZF_EOF; file_bytes += sizeof BGZF_EOF; }
+    ok = !ferror(f) && fclose(f) == 0 && ok;
+    g_indel.fp = nullptr;
+    if (!ok) { fprintf(stderr, "[salt] --indels: write error on %s\n", g_indel.fn); return false; }
+    fprintf(stderr, "[salt] indels: %s, MAPQ >= %u, min_alt %u, min_pct %u, %llu slots, tabled %llu, dropped %llu, long %llu, unanchored %llu, %llu bytes of text -> %s (%llu bytes)\n",
+            g_indel.device ? "tabled and printed on the device" : "tabled on the host from the SAM lines", g_indel.min_mapq, g_indel.min_alt, g_indel.min_pct,
+            (unsigned long long)(g_indel.device ? 1ull << g_indel.log2_slots : 0ull), (unsigned long long)stat[0], (unsigned long long)stat[1], (unsigned long long)stat[2], (unsigned long long)stat[3],
+            (unsigned long long)text_bytes, g_indel.fn, (unsigned long long)file_bytes);
+    if (stat[1]) fprintf(stderr, "[salt] indels: WARNING: %llu events found no slot within %u of their home slot and are not in %s: the table of %llu slots is too full, raise --indels-slots\n",
+                         (unsigned long long)stat[1], 128u, g_indel.fn, (unsigned long long)(1ull << g_indel.log2_slots));
+    return true;
+}
+
 } // namespace
 
 // options; choice of path (TextPlan); index load and attach; header; text path; host pipeline
@@ -2125,16 +2269,16 @@ int main(int argc, char **argv)
     const Contigs contigs(ix);
     auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
-    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix) || !disc_begin(ix, gix) || !stats_begin(ix, gix, contigs)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
+    if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix) || !disc_begin(ix, gix) || !stats_begin(ix, gix, contigs) || !indel_begin(ix, gix, contigs)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
     if (text_path) {
         fprintf(stderr, "%lf sec escaped.\n", now() - t0);
         if (!print_header(ix, o)) return 1;
         const int rc = pe ? run_pe_text(o.fn_reads, o.fn_mates, gix, contigs, plan, o.ao, o.so, o.po, now(), resume)
                           : run_se_text(o.fn_reads, gix, contigs, plan, o.ao, o.so, now(), &resume[0]);
-        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs) && stats_finish(gix)) ? 1 : rc); }
+        if (rc != 2) { if (rc == 0) bgzf_finish(); return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs) && stats_finish(gix) && indel_finish(ix, gix, contigs)) ? 1 : rc); }
         header_out = true;
     }
     const int rc = run_host_pipeline(o, ix, gix, contigs, header_out, resume, t0);
-    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs) && stats_finish(gix)) ? 1 : rc);
+    return leave(rc == 0 && !(snp_finish(ix, gix) && depth_finish(ix, gix, contigs) && errprof_finish(gix) && gt_finish(ix, gix, contigs) && disc_finish(ix, gix, contigs) && stats_finish(gix) && indel_finish(ix, gix, contigs)) ? 1 : rc);
 }
