@@ -831,6 +831,36 @@ int  salt_gpu_idx_build_r(int device, const uint8_t *rtext, uint64_t n, const ui
                           uint32_t cum4, uint32_t *inv_sa0, uint32_t *code, uint64_t code_words, uint32_t *rsa);
 const char *salt_gpu_idx_last_error(void);
 
+/* ---- SNP sites from a VCF, parsed on the device (`salt-idx --gpu --vcf`; the rule is DESIGN.md 2.2) -------------------
+ * A handle holds the genome's bases, the contig names a CHROM may carry in a hash table, and one mask byte per genome position.
+ * Text goes in as whole lines, in any number of calls and cut anywhere between lines; the result does not depend on the cuts or on the
+ * order of the lines.  One thread parses one line as far as ALT (FILTER with pass_only) and ORs its allele mask into the position's byte;
+ * finish compacts the non-zero bytes into per-contig site lists, what salt_idx_build_mem takes as salt_idx_snps_t.
+ *   salt_gpu_vcf_open    seq[i]: the len[i] base LETTERS of contig i, as the FASTA holds them.  keys[k] (n_keys of them, NUL-terminated,
+ *                        distinct) is a name a CHROM may carry and key_contig[k] the contig it means: the FASTA names after the rename
+ *                        map.  Needs two bytes of device memory per genome position; SALT_E_NOMEM names the size.
+ *   salt_gpu_vcf_add     n bytes of whole lines from a host buffer; only the last line of the last call may lack its '\n'.  The text is
+ *                        cut at line ends into chunks of about opt.chunk_bytes (0: 16 MiB), and a longer line grows the chunk; the
+ *                        copy of one chunk runs beside the parse of the one before.  Returns when the text has been copied out of `text`.
+ *   salt_gpu_vcf_finish  waits for the parse, compacts, and gives the counters and (n_per_contig may be NULL) the sites of every contig.
+ *                        A malformed line (fewer than 5 fields, POS not 1-10 digits) makes it return SALT_E_DATA; the message names the
+ *                        smallest 1-based line number of such a line, counted over all calls of salt_gpu_vcf_add.
+ *   salt_gpu_vcf_fetch   contig i's sites, ascending: 0-based positions, allele masks (bit A=0 C=1 G=2 T=3), reference codes; each array
+ *                        holds n_per_contig[i] entries.  After finish only.
+ * The host twin, which gives the same lists and counters, is declared in salt_host.h. */
+typedef struct {
+    uint64_t lines, kept, sites, unknown_contig, out_of_range, not_snv, ref_mismatch, filtered;
+    uint64_t first_unknown_line;        /* 1-based line of the first CHROM that matched no contig; 0: none */
+} salt_vcf_counters_t;
+typedef struct { int32_t pass_only, reserved; uint64_t chunk_bytes; } salt_gpu_vcf_opt_t;
+typedef struct salt_gpu_vcf salt_gpu_vcf_t;
+int  salt_gpu_vcf_open(int device, int32_t n_contigs, const char *const *seq, const uint64_t *len, int32_t n_keys, const char *const *keys,
+                       const int32_t *key_contig, const salt_gpu_vcf_opt_t *opt, salt_gpu_vcf_t **out);
+int  salt_gpu_vcf_add(salt_gpu_vcf_t *h, const char *text, uint64_t n);
+int  salt_gpu_vcf_finish(salt_gpu_vcf_t *h, salt_vcf_counters_t *counters, uint32_t *n_per_contig);
+int  salt_gpu_vcf_fetch(salt_gpu_vcf_t *h, int32_t contig, uint32_t *pos, uint8_t *alleles, uint8_t *ref);
+void salt_gpu_vcf_close(salt_gpu_vcf_t *h);
+
 const char *salt_gpu_last_error(void);
 uint32_t    salt_gpu_result_size(void);         /* sizeof(salt_result_t), for bindings */
 

@@ -254,6 +254,49 @@ typedef struct { const char *name, *comment; const char *seq; uint64_t len; } sa
 typedef struct { const char *chr; const uint32_t *pos; const uint8_t *alleles; const uint8_t *ref; uint32_t n; } salt_idx_snps_t;
 int salt_idx_build_mem(const salt_idx_contig_t *contigs, int n_contigs, const salt_idx_snps_t *snps, int n_groups, const char *prefix,
                        int l_seed, const salt_idx_backend_t *backend, int flags);
+/* SNP sites straight from a VCF (`salt-idx --vcf`; the rule is DESIGN.md 2.2): per contig of the FASTA, in FASTA order, the ascending
+ * 0-based positions of the sites with their allele masks and reference codes -- one salt_idx_snps_t per contig, by NAME, an empty group
+ * for a contig without sites -- and the eight counters.  CHROM goes through the rename map (n_rename pairs: VCF name, FASTA name; a name
+ * the map does not hold stays as it is) and is then compared byte for byte with the FASTA names.
+ *   salt_vcf_snps       the whole text (plain, already inflated) in one call.  device == NULL: the host twin, plain C++ on one thread, which
+ *                       compiles the same per-line function as the device's kernel (salt_amd/csrc/salt_vcf_line.h); else the entry
+ *                       points of libsalt_gpu.so, where opt.chunk_bytes cuts the text into device chunks (0: the default).  NULL on
+ *                       failure with salt_idx_last_error() set; a malformed line names its 1-based line number there.
+ *   salt_vcf_counters / salt_vcf_group   the result; a group's arrays live as long as the handle, chr is the FASTA name
+ *   salt_idx_build_vcf  salt_idx_build_ex with a VCF (plain, BGZF or gzip) in place of the SNP file: reads the FASTA once, ingests the VCF
+ *                       in pieces cut at line ends, and goes on as salt_idx_build_mem does.  vcf_opts (may be NULL) also carries the
+ *                       rename map's file, the SNP file to write beside the index, and where the counters and the first unknown CHROM go.
+ * In the memory path a contig without sites keeps its place in the genome's coordinates: the local patterns of the contigs behind it
+ * carry their own offsets (the file path keeps the reference's by-order behaviour, which tests/golden/index_cases/gap_short pins). */
+typedef struct {
+    int device;
+    int  (*open)(int device, int32_t n_contigs, const char *const *seq, const uint64_t *len, int32_t n_keys, const char *const *keys,
+                 const int32_t *key_contig, const salt_gpu_vcf_opt_t *opt, salt_gpu_vcf_t **out);
+    int  (*add)(salt_gpu_vcf_t *h, const char *text, uint64_t n);
+    int  (*finish)(salt_gpu_vcf_t *h, salt_vcf_counters_t *counters, uint32_t *n_per_contig);
+    int  (*fetch)(salt_gpu_vcf_t *h, int32_t contig, uint32_t *pos, uint8_t *alleles, uint8_t *ref);
+    void (*close)(salt_gpu_vcf_t *h);
+    const char *(*last_error)(void);
+} salt_vcf_device_t;                /* salt_gpu_vcf_open, _add, _finish, _fetch, _close and salt_gpu_last_error of libsalt_gpu.so */
+typedef struct {
+    int32_t pass_only;                              /* --vcf-pass-only */
+    int32_t n_rename;
+    const char *const *rename_from, *const *rename_to;
+    uint64_t chunk_bytes;                           /* device ingest: bytes per chunk, 0 = the default */
+    const salt_vcf_device_t *device;                /* NULL: the host twin */
+    /* salt_idx_build_vcf only */
+    const char *rename_file;                        /* --vcf-contigs: two TAB-separated columns, read in front of the pairs above; NULL: none */
+    const char *snp_out;                            /* --snp-out: the sites as a four-column SNP file; NULL: none */
+    salt_vcf_counters_t *counters;                  /* out, may be NULL */
+    char *unknown_name; uint32_t unknown_name_cap;  /* out, may be NULL: the CHROM of line counters->first_unknown_line, cut to the room */
+} salt_vcf_opt_t;
+typedef struct salt_vcf salt_vcf_t;
+salt_vcf_t *salt_vcf_snps(const salt_idx_contig_t *contigs, int n_contigs, const char *vcf, uint64_t n, const salt_vcf_opt_t *opt);
+void salt_vcf_counters(const salt_vcf_t *v, salt_vcf_counters_t *out);
+int  salt_vcf_group(const salt_vcf_t *v, int contig, salt_idx_snps_t *out);
+void salt_vcf_free(salt_vcf_t *v);
+int  salt_idx_build_vcf(const char *fn_fa, const char *fn_vcf, const char *prefix, int l_seed, const salt_idx_backend_t *backend, int flags,
+                        const salt_vcf_opt_t *vcf_opts);
 /* the host suffix sorter alone: sa_out[0..n] for text[0..n) of `bits`-bit symbols (2 or 3), empty suffix first */
 int salt_idx_suffix_array_cpu(const uint8_t *text, uint64_t n, int bits, uint32_t *sa_out);
 const char *salt_idx_last_error(void);

@@ -4,7 +4,7 @@ Only what the path needs: csrc/ (HIP kernels + the C ABI of include/salt_gpu.h),
 files + SAM text, include/salt_host.h) and api.py (ctypes bindings that mirror the reference's
 batch-level interface)."""
 from .api import (AlnOpt, GpuAligner, Index, SaltError, RESULT_DTYPE, read_fastq, sam_text, sam_text_pe, interleave_pairs,  # noqa: F401
-                  gpu_lib, host_lib, idx_build, idx_build_mem, suffix_array, IDX_NO_LP, bgzf_deflate, bgzf_inflate, BGZF_CUT, BGZF_EOF, bam_header, bam_from_sam,
+                  gpu_lib, host_lib, idx_build, idx_build_mem, vcf_snps, VCF_COUNTERS, suffix_array, IDX_NO_LP, bgzf_deflate, bgzf_inflate, BGZF_CUT, BGZF_EOF, bam_header, bam_from_sam,
                   BAM_MAX_NAME, Polisher, POLISH_STATS, snp_sites, snp_count_sam, depth_add_sam, depth_text, errprof_add_sam, errprof_text, ERRPROF_SHAPE, stats_add_sam, stats_text, stats_split, STATS_TABLES, STATS_CELLS, STATS_CT_LDS, STATS_CHUNK,
                   gt_add_sam, gt_text, gt_header, gt_table, GT_Q_NONE,
                   disc_add_sam, disc_text, DISC_ALT, DISC_DIFF, DISC_FIELD_BITS, DISC_DEFAULTS,

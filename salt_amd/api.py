@@ -332,10 +332,119 @@ def _idx_backend(gpu_device):
                        ctypes.cast(g.salt_gpu_idx_last_error, _LAST_ERR))
 
 
-def idx_build(fasta, snps, prefix, l_seed, gpu_device=None, flags=0):
-    """salt-idx: FASTA + SNP file -> index files (index_main, Index_src/index1.c:46-185)."""
+_VCF_OPEN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_void_p, ctypes.c_void_p)
+_VCF_ADD = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
+_VCF_FINISH = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+_VCF_FETCH = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+_VCF_CLOSE = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
+VCF_COUNTERS = ("lines", "kept", "sites", "unknown_contig", "out_of_range", "not_snv", "ref_mismatch", "filtered")
+
+
+class _VcfDevice(ctypes.Structure):
+    _fields_ = [("device", ctypes.c_int), ("open", _VCF_OPEN), ("add", _VCF_ADD), ("finish", _VCF_FINISH), ("fetch", _VCF_FETCH), ("close", _VCF_CLOSE),
+                ("last_error", _LAST_ERR)]
+
+
+class _VcfCounters(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in VCF_COUNTERS + ("first_unknown_line",)]
+
+
+class _VcfOpt(ctypes.Structure):
+    _fields_ = [("pass_only", ctypes.c_int32), ("n_rename", ctypes.c_int32), ("rename_from", ctypes.POINTER(ctypes.c_char_p)),
+                ("rename_to", ctypes.POINTER(ctypes.c_char_p)), ("chunk_bytes", ctypes.c_uint64), ("device", ctypes.POINTER(_VcfDevice)),
+                ("rename_file", ctypes.c_char_p), ("snp_out", ctypes.c_char_p), ("counters", ctypes.POINTER(_VcfCounters)),
+                ("unknown_name", ctypes.c_void_p), ("unknown_name_cap", ctypes.c_uint32)]
+
+
+def _vcf_opt(gpu_device, pass_only, rename, chunk_bytes, keep):
+    """salt_vcf_opt_t; `keep` collects what the struct points to.  gpu_device None: the host twin, else the device ingest of libsalt_gpu.so."""
+    o = _VcfOpt()
+    o.pass_only = 1 if pass_only else 0
+    pairs = list(rename.items()) if isinstance(rename, dict) else list(rename or [])
+    o.n_rename = len(pairs)
+    if pairs:
+        fr = (ctypes.c_char_p * len(pairs))(*[os.fsencode(a) for a, _ in pairs])
+        to = (ctypes.c_char_p * len(pairs))(*[os.fsencode(b) for _, b in pairs])
+        keep += [fr, to]
+        o.rename_from, o.rename_to = fr, to
+    o.chunk_bytes = int(chunk_bytes or 0)
+    if gpu_device is not None:
+        g = gpu_lib()
+        d = _VcfDevice(int(gpu_device), ctypes.cast(g.salt_gpu_vcf_open, _VCF_OPEN), ctypes.cast(g.salt_gpu_vcf_add, _VCF_ADD),
+                       ctypes.cast(g.salt_gpu_vcf_finish, _VCF_FINISH), ctypes.cast(g.salt_gpu_vcf_fetch, _VCF_FETCH),
+                       ctypes.cast(g.salt_gpu_vcf_close, _VCF_CLOSE), ctypes.cast(g.salt_gpu_last_error, _LAST_ERR))
+        keep.append(d)
+        o.device = ctypes.pointer(d)
+    return o
+
+
+def vcf_snps(contigs, vcf_bytes, gpu_device=None, pass_only=False, rename=None, chunk_bytes=None):
+    """SNP sites from the text of a VCF under the rule of DESIGN.md 2.2 (salt_vcf_snps): contigs as idx_build_mem takes them, vcf_bytes the plain
+    text.  Returns (groups, counters): groups is what idx_build_mem takes -- one (name, positions, allele masks, reference codes) per contig
+    in FASTA order, matched by NAME, empty for a contig without sites -- and counters a dict of the eight counts plus first_unknown_line.
+    gpu_device None: the host twin; a device number: the device parser, cut into chunks of chunk_bytes (None: its default).  rename: VCF name
+    -> FASTA name (dict or pairs).  SaltError on a malformed line names its 1-based line number."""
+    lib = host_lib()
+    keep = []
+    cs = (_IdxContig * len(contigs))()
+    for i, (name, seq) in enumerate(contigs):
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        keep.append(seq)
+        cs[i] = _IdxContig(name.encode(), None, seq.ctypes.data, len(seq))
+    opt = _vcf_opt(gpu_device, pass_only, rename, chunk_bytes, keep)
+    text = np.frombuffer(vcf_bytes, dtype=np.uint8)            # bytes, a memoryview or a uint8 array: not copied
+    lib.salt_vcf_snps.restype = ctypes.c_void_p
+    lib.salt_vcf_snps.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    lib.salt_vcf_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.salt_vcf_group.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    lib.salt_vcf_free.argtypes = [ctypes.c_void_p]
+    lib.salt_idx_last_error.restype = ctypes.c_char_p
+    h = lib.salt_vcf_snps(cs, len(contigs), text.ctypes.data if len(text) else None, len(text), ctypes.byref(opt))
+    if not h:
+        raise SaltError("VCF: %s" % lib.salt_idx_last_error().decode())
+    try:
+        ct = _VcfCounters()
+        lib.salt_vcf_counters(h, ctypes.byref(ct))
+        groups = []
+        for i, (name, _) in enumerate(contigs):
+            g = _IdxSnps()
+            if lib.salt_vcf_group(h, i, ctypes.byref(g)) != 0:
+                raise SaltError("VCF: %s" % lib.salt_idx_last_error().decode())
+            n = g.n
+            pos = np.ctypeslib.as_array(ctypes.cast(g.pos, ctypes.POINTER(ctypes.c_uint32)), (n,)).copy() if n else np.zeros(0, np.uint32)
+            al = np.ctypeslib.as_array(ctypes.cast(g.alleles, ctypes.POINTER(ctypes.c_uint8)), (n,)).copy() if n else np.zeros(0, np.uint8)
+            rf = np.ctypeslib.as_array(ctypes.cast(g.ref, ctypes.POINTER(ctypes.c_uint8)), (n,)).copy() if n else np.zeros(0, np.uint8)
+            groups.append((name, pos, al, rf))
+        return groups, {n: int(getattr(ct, n)) for n, _ in _VcfCounters._fields_}
+    finally:
+        lib.salt_vcf_free(h)
+
+
+def idx_build(fasta, snps, prefix, l_seed, gpu_device=None, flags=0, vcf=False, vcf_opts=None):
+    """salt-idx: FASTA + SNP file -> index files (index_main, Index_src/index1.c:46-185).  vcf=True: `snps` is a VCF (plain, BGZF or gzip;
+    salt_idx_build_vcf) and vcf_opts a dict of pass_only, rename (dict or pairs), rename_file, snp_out, device (True: parse on gpu_device),
+    chunk_bytes; the eight counters and first_unknown_line are returned as a dict."""
     lib = host_lib()
     be = _idx_backend(gpu_device)
+    if vcf:
+        vo = dict(vcf_opts or {})
+        keep = []
+        opt = _vcf_opt(gpu_device if vo.pop("device", False) else None, vo.pop("pass_only", False), vo.pop("rename", None), vo.pop("chunk_bytes", None), keep)
+        ct = _VcfCounters()
+        opt.counters = ctypes.pointer(ct)
+        if vo.get("rename_file"):
+            opt.rename_file = os.fsencode(vo.pop("rename_file"))
+        if vo.get("snp_out"):
+            opt.snp_out = os.fsencode(vo.pop("snp_out"))
+        if any(v for v in vo.values()):
+            raise SaltError("unknown vcf_opts: %s" % ", ".join(sorted(vo)))
+        lib.salt_idx_build_vcf.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        lib.salt_idx_last_error.restype = ctypes.c_char_p
+        if lib.salt_idx_build_vcf(os.fsencode(fasta), os.fsencode(snps), os.fsencode(prefix), int(l_seed), ctypes.byref(be) if be else None, int(flags),
+                                  ctypes.byref(opt)) != 0:
+            raise SaltError("index build failed: %s" % lib.salt_idx_last_error().decode())
+        return {n: int(getattr(ct, n)) for n, _ in _VcfCounters._fields_}
     lib.salt_idx_build_ex.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     lib.salt_idx_last_error.restype = ctypes.c_char_p
     if lib.salt_idx_build_ex(os.fsencode(fasta), os.fsencode(snps), os.fsencode(prefix), int(l_seed), ctypes.byref(be) if be else None, int(flags)) != 0:

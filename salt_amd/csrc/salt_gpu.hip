@@ -22,6 +22,7 @@ using namespace salt;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
+namespace salt { int set_last_error(int code, const std::string &msg) { return fail(code, msg); } }      // for the entry points of salt_vcf.hip
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
     return fail(SALT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)

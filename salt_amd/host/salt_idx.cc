@@ -25,6 +25,7 @@
 //   .R.forward.bwt/.occ                Rbwt_bwt_bwtgen on .R.rpac         index1.c:162-167
 //   .R.forward.sa                      Rbwt_gen_sa(direction=+1)          rbwt.c:424-475
 #include "../../include/salt_host.h"
+#include "../csrc/salt_vcf_line.h"
 #include <zlib.h>
 #include <cstdio>
 #include <cstdlib>
@@ -331,7 +332,8 @@ struct LocalPatterns {
     std::vector<char> lp;                // the .lp text (when wanted)
 };
 
-bool local_patterns(const std::vector<ContigView> &fa, const std::vector<Group> &groups, int l_seed, bool want_lp, LocalPatterns &out)
+// by_name (the memory and VCF paths): a contig without windows keeps its place, so the contigs behind it carry their own offsets
+bool local_patterns(const std::vector<ContigView> &fa, const std::vector<Group> &groups, int l_seed, bool want_lp, bool by_name, LocalPatterns &out)
 {
     const int D = l_seed - 1;                                 // WIN_SNP_DISTANCE
     struct Job { size_t ci; uint32_t tot_l; uint64_t w0; uint32_t seq_from; bool sorted; };   // windows [w0, w0 + n) of contig ci; seq_from: first mid of the literal replay
@@ -339,8 +341,10 @@ bool local_patterns(const std::vector<ContigView> &fa, const std::vector<Group> 
     uint64_t n_win = 0; uint32_t tot_l = 0;
     for (size_t ci = 0; ci < fa.size(); ++ci) {
         const Group &g = groups[ci];
-        if (g.n == 0) continue;                               // tot_l is NOT advanced (localPattern.c:218-221)
-        if (g.chr != fa[ci].name) continue;                   // localPattern.c:224-227
+        if (g.n == 0 || g.chr != fa[ci].name) {               // tot_l is NOT advanced in the reference (localPattern.c:218-221, 224-227)
+            if (by_name) tot_l += (uint32_t)fa[ci].len;
+            continue;
+        }
         jobs.push_back(Job{ ci, tot_l, n_win, g.n, true });
         n_win += g.n;
         tot_l += (uint32_t)fa[ci].len;
@@ -630,7 +634,7 @@ bool r_ann_amb(const std::vector<char> &lp, uint64_t l_pac, std::string &ann, st
 // the build proper
 // ---------------------------------------------------------------------------------------------
 int build_core(const std::vector<ContigView> &fa, std::vector<Group> &groups, const std::string &prefix, int l_seed,
-               const salt_idx_backend_t *be, int flags)
+               const salt_idx_backend_t *be, int flags, bool by_name)
 {
     if (!be) be = &CPU_BACKEND;
     if (l_seed < 2 || l_seed > 255) { g_ierr = "seed length out of range"; return -1; }
@@ -718,7 +722,7 @@ int build_core(const std::vector<ContigView> &fa, std::vector<Group> &groups, co
     t0 = now_s();
     LocalPatterns lpat;
     const bool want_lp = !(flags & SALT_IDX_NO_LP), need_lp = want_lp || (flags & SALT_IDX_ALL_FILES);      // (.R.ann / .R.amb are read off the text)
-    if (!local_patterns(fa, groups, l_seed, need_lp, lpat)) return -1;
+    if (!local_patterns(fa, groups, l_seed, need_lp, by_name, lpat)) return -1;
     if (want_lp) ok = ok && write_file(prefix + ".lp", lpat.lp.data(), lpat.lp.size());
     if (!(flags & SALT_IDX_ALL_FILES)) { std::vector<char>().swap(lpat.lp); }
     if (verbose()) fprintf(stderr, "[salt-idx] local patterns: %.2f s (%zu symbols, %zu segments)\n", now_s() - t0, lpat.rtext.size(), lpat.sharp_off.size());
@@ -850,7 +854,174 @@ int build_core(const std::vector<ContigView> &fa, std::vector<Group> &groups, co
     return ok ? 0 : -1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// SNP sites from a VCF.  One object for both paths: the host twin keeps a mask byte per genome position, like the
+// device, and runs the device's own per-line function (salt_vcf_line.h) over the lines; the device path hands the text to libsalt_gpu.so.
+// Either way the result is one Group per contig, by name.
+// ---------------------------------------------------------------------------------------------
+struct VcfIngest {
+    const std::vector<ContigView> *fa = nullptr;
+    std::vector<uint64_t> start;
+    std::vector<std::string> keys; std::vector<int32_t> key_contig;
+    // host twin
+    std::string names; std::vector<uint32_t> key_off, slots; std::vector<uint8_t> mask; std::vector<const uint8_t *> seq;
+    salt::VcfTable T;
+    uint64_t line = 0, bad = 0, cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, first_unknown = 0;
+    // device
+    const salt_vcf_device_t *dev = nullptr; salt_gpu_vcf_t *h = nullptr;
+    // result
+    std::vector<Group> groups; std::vector<std::vector<uint8_t>> al, rf;
+    salt_vcf_counters_t ctr;
+
+    ~VcfIngest() { if (h) dev->close(h); }
+
+    bool open(const std::vector<ContigView> &contigs, const salt_vcf_opt_t *opt, const std::vector<std::pair<std::string, std::string>> &rename)
+    {
+        fa = &contigs; dev = opt ? opt->device : nullptr;
+        memset(&ctr, 0, sizeof ctr);
+        start.assign(contigs.size() + 1, 0);
+        for (size_t i = 0; i < contigs.size(); ++i) start[i + 1] = start[i] + contigs[i].len;
+        if (start.back() == 0 || start.back() >= 0xFFFFFFE0ull) { g_ierr = "genome empty or too long for the 32-bit index"; return false; }
+        // the names a CHROM may carry: the FASTA names (the first of two equal ones), then the map -- `from` now means `to`'s contig, or nothing
+        auto find = [&](const std::string &k) { for (size_t i = 0; i < keys.size(); ++i) if (keys[i] == k) return (int)i; return -1; };
+        std::vector<std::string> fa_name; std::vector<int32_t> fa_contig;
+        for (size_t i = 0; i < contigs.size(); ++i) if (find(contigs[i].name) < 0) { keys.push_back(contigs[i].name); key_contig.push_back((int32_t)i); }
+        fa_name = keys; fa_contig = key_contig;
+        for (const auto &r : rename) {
+            int32_t to = -1;
+            for (size_t i = 0; i < fa_name.size(); ++i) if (fa_name[i] == r.second) to = fa_contig[i];
+            const int at = find(r.first);
+            if (at >= 0) { keys.erase(keys.begin() + at); key_contig.erase(key_contig.begin() + at); }
+            if (to >= 0) { keys.push_back(r.first); key_contig.push_back(to); }
+        }
+        if (dev) {
+            std::vector<const char *> seq, kp; std::vector<uint64_t> len;
+            for (const auto &c : contigs) { seq.push_back(c.seq); len.push_back(c.len); }
+            for (const auto &k : keys) kp.push_back(k.c_str());
+            salt_gpu_vcf_opt_t go; go.pass_only = opt->pass_only; go.reserved = 0; go.chunk_bytes = opt->chunk_bytes;
+            if (dev->open(dev->device, (int32_t)contigs.size(), seq.data(), len.data(), (int32_t)keys.size(), kp.data(), key_contig.data(), &go, &h) != 0) {
+                h = nullptr; g_ierr = std::string("VCF on the device: ") + dev->last_error(); return false;
+            }
+            return true;
+        }
+        key_off.assign(1, 0);
+        for (const auto &k : keys) { names += k; key_off.push_back((uint32_t)names.size()); }
+        uint32_t n_slots = 16;
+        while (n_slots < 2 * keys.size() + 2) n_slots <<= 1;
+        slots.assign(n_slots, 0);
+        for (size_t k = 0; k < keys.size(); ++k) {
+            uint32_t s = salt::vcf_hash((const uint8_t *)keys[k].data(), keys[k].size()) & (n_slots - 1);
+            while (slots[s]) s = (s + 1) & (n_slots - 1);
+            slots[s] = (uint32_t)k + 1;
+        }
+        mask.assign((size_t)start.back(), 0);
+        for (const auto &c : contigs) seq.push_back((const uint8_t *)c.seq);
+        T.names = (const uint8_t *)names.data(); T.key_off = key_off.data(); T.key_contig = key_contig.data(); T.slots = slots.data();
+        T.slot_mask = n_slots - 1; T.pass_only = opt && opt->pass_only ? 1u : 0u; T.start = start.data(); T.seq = seq.data();
+        return true;
+    }
+    // whole lines; only the last line of the last call may lack its '\n'
+    bool add(const char *text, uint64_t n)
+    {
+        if (dev) {
+            if (dev->add(h, text, n) != 0) { g_ierr = std::string("VCF on the device: ") + dev->last_error(); return false; }
+            return true;
+        }
+        for (uint64_t p = 0; p < n;) {
+            const void *q = memchr(text + p, '\n', (size_t)(n - p));
+            const uint64_t e = q ? (uint64_t)((const char *)q - text) : n;
+            ++line;
+            uint64_t g = 0; uint32_t m = 0;
+            const int st = salt::vcf_line((const uint8_t *)text, p, e, T, &g, &m);
+            if (st == salt::VCF_KEPT) mask[(size_t)g] |= (uint8_t)m;
+            else if (st == salt::VCF_MALFORMED) { if (!bad) bad = line; }
+            else if (st == salt::VCF_UNKNOWN && !first_unknown) first_unknown = line;
+            ++cnt[st];
+            p = e + 1;
+        }
+        return true;
+    }
+    bool finish()
+    {
+        const size_t nc = fa->size();
+        groups.assign(nc, Group()); al.assign(nc, {}); rf.assign(nc, {});
+        for (size_t c = 0; c < nc; ++c) groups[c].chr = (*fa)[c].name;
+        if (dev) {
+            std::vector<uint32_t> n_per(nc, 0);
+            if (dev->finish(h, &ctr, n_per.data()) != 0) { g_ierr = dev->last_error(); return false; }
+            for (size_t c = 0; c < nc; ++c) {
+                groups[c].pos.resize(n_per[c]); al[c].resize(n_per[c]); rf[c].resize(n_per[c]);
+                if (dev->fetch(h, (int32_t)c, groups[c].pos.data(), al[c].data(), rf[c].data()) != 0) { g_ierr = std::string("VCF on the device: ") + dev->last_error(); return false; }
+            }
+        } else {
+            if (bad) { g_ierr = "VCF line " + std::to_string(bad) + " is malformed (fewer than 5 fields, or POS is not 1 to 10 digits)"; return false; }
+            for (size_t c = 0; c < nc; ++c)
+                for (uint64_t p = start[c]; p < start[c + 1]; ++p) {
+                    uint64_t w;                                // eight untouched positions at a time
+                    while (p + 8 <= start[c + 1] && (memcpy(&w, &mask[(size_t)p], 8), w == 0)) p += 8;
+                    if (p < start[c + 1] && mask[(size_t)p]) {
+                        groups[c].pos.push_back((uint32_t)(p - start[c])); al[c].push_back(mask[(size_t)p]);
+                        rf[c].push_back((uint8_t)salt::vcf_base((uint8_t)(*fa)[c].seq[p - start[c]]));
+                    }
+                }
+            ctr.kept = cnt[salt::VCF_KEPT]; ctr.unknown_contig = cnt[salt::VCF_UNKNOWN]; ctr.out_of_range = cnt[salt::VCF_RANGE]; ctr.not_snv = cnt[salt::VCF_NOT_SNV];
+            ctr.ref_mismatch = cnt[salt::VCF_REF]; ctr.filtered = cnt[salt::VCF_FILTERED];
+            ctr.lines = ctr.kept + ctr.unknown_contig + ctr.out_of_range + ctr.not_snv + ctr.ref_mismatch + ctr.filtered;
+            ctr.first_unknown_line = first_unknown;
+            ctr.sites = 0;
+            for (size_t c = 0; c < nc; ++c) ctr.sites += groups[c].pos.size();
+            std::vector<uint8_t>().swap(mask);
+        }
+        for (size_t c = 0; c < nc; ++c) {
+            groups[c].type.resize(groups[c].pos.size());
+            for (size_t j = 0; j < groups[c].pos.size(); ++j) groups[c].type[j] = (uint8_t)((al[c][j] & 15u) | ((rf[c][j] & 7u) << 4));
+        }
+        return true;
+    }
+};
+
+// --vcf-contigs: VCF name TAB FASTA name per line, as `bcftools annotate --rename-chrs` takes (it splits at any white space)
+bool read_rename_map(const char *fn, std::vector<std::pair<std::string, std::string>> &out)
+{
+    FILE *f = fopen(fn, "r");
+    if (!f) { g_ierr = std::string("cannot open ") + fn; return false; }
+    char buf[4096]; int ln = 0;
+    while (fgets(buf, sizeof buf, f)) {
+        ++ln;
+        std::string l(buf);
+        while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+        if (l.empty()) continue;
+        const size_t a = l.find_first_of(" \t");
+        const size_t b = a == std::string::npos ? a : l.find_first_not_of(" \t", a);
+        if (a == 0 || b == std::string::npos) { fclose(f); g_ierr = std::string(fn) + " line " + std::to_string(ln) + ": two columns expected (VCF name, FASTA name)"; return false; }
+        const size_t e = l.find_first_of(" \t", b);
+        out.emplace_back(l.substr(0, a), l.substr(b, e == std::string::npos ? e : e - b));
+    }
+    fclose(f);
+    return true;
+}
+
+// the groups as a four-column SNP file: contig, 1-based position, the alleles in ACGT order joined by '/', the reference base
+bool write_snp_file(const char *fn, const std::vector<Group> &groups)
+{
+    FILE *f = fopen(fn, "w");
+    if (!f) { g_ierr = std::string("cannot write ") + fn; return false; }
+    bool ok = true;
+    for (const Group &g : groups)
+        for (size_t j = 0; j < g.pos.size() && ok; ++j) {
+            char al[8]; int k = 0;
+            for (int b = 0; b < 4; ++b) if ((g.type[j] >> b) & 1) { if (k) al[k++] = '/'; al[k++] = "ACGT"[b]; }
+            al[k] = 0;
+            ok = fprintf(f, "%s\t%u\t%s\t%c\n", g.chr.c_str(), g.pos[j] + 1, al, "ACGTN"[std::min(g.type[j] >> 4, 4)]) > 0;
+        }
+    ok = fclose(f) == 0 && ok;
+    if (!ok) g_ierr = std::string("short write on ") + fn;
+    return ok;
+}
+
 } // namespace
+
+struct salt_vcf { VcfIngest in; std::vector<ContigView> fa; };
 
 extern "C" const char *salt_idx_last_error(void) { return g_ierr.c_str(); }
 
@@ -863,7 +1034,7 @@ extern "C" int salt_idx_build_ex(const char *fn_fa, const char *fn_snp, const ch
     for (auto &c : own) fa.push_back(ContigView{ c.name, c.comment, c.seq.data(), c.seq.size() });
     std::vector<Group> groups;
     if (!read_snp_groups(fn_snp, groups)) return -1;
-    return build_core(fa, groups, prefix_c, l_seed, be, flags);
+    return build_core(fa, groups, prefix_c, l_seed, be, flags, false);
 }
 
 extern "C" int salt_idx_build(const char *fn_fa, const char *fn_snp, const char *prefix_c, int l_seed)
@@ -888,7 +1059,7 @@ extern "C" int salt_idx_build_mem(const salt_idx_contig_t *contigs, int n_contig
         g.type.resize(snps[i].n);
         for (uint32_t j = 0; j < snps[i].n; ++j) g.type[j] = (uint8_t)((snps[i].alleles[j] & 15u) | ((snps[i].ref ? snps[i].ref[j] & 7u : 4u) << 4));
     }
-    return build_core(fa, groups, prefix_c, l_seed, be, flags);
+    return build_core(fa, groups, prefix_c, l_seed, be, flags, true);
 }
 
 // the host suffix sorter by itself (tests compare the device sorter with it)
@@ -897,4 +1068,106 @@ extern "C" int salt_idx_suffix_array_cpu(const uint8_t *text, uint64_t n, int bi
     if (!text || !sa_out || (bits != 2 && bits != 3)) { g_ierr = "bad argument"; return -1; }
     cpu_suffix_array(text, n, 1 << bits, sa_out);
     return 0;
+}
+
+// ---- SNP sites from a VCF: the C ABI (include/salt_host.h) ----
+static void vcf_rename_pairs(const salt_vcf_opt_t *opt, std::vector<std::pair<std::string, std::string>> &out)
+{
+    if (opt) for (int32_t i = 0; i < opt->n_rename; ++i) out.emplace_back(opt->rename_from[i], opt->rename_to[i]);
+}
+
+extern "C" salt_vcf_t *salt_vcf_snps(const salt_idx_contig_t *contigs, int n_contigs, const char *vcf, uint64_t n, const salt_vcf_opt_t *opt)
+{
+    if (!contigs || n_contigs <= 0 || (n && !vcf) || (opt && opt->n_rename > 0 && (!opt->rename_from || !opt->rename_to))) { g_ierr = "null argument"; return nullptr; }
+    salt_vcf *v = new salt_vcf;
+    for (int i = 0; i < n_contigs; ++i) {
+        if (!contigs[i].name || (!contigs[i].seq && contigs[i].len)) { g_ierr = "contig without name or bases"; delete v; return nullptr; }
+        v->fa.push_back(ContigView{ contigs[i].name, "", contigs[i].seq, contigs[i].len });
+    }
+    std::vector<std::pair<std::string, std::string>> rename;
+    vcf_rename_pairs(opt, rename);
+    if (!v->in.open(v->fa, opt, rename) || !v->in.add(vcf, n) || !v->in.finish()) { delete v; return nullptr; }
+    return v;
+}
+extern "C" void salt_vcf_counters(const salt_vcf_t *v, salt_vcf_counters_t *out) { if (v && out) *out = v->in.ctr; }
+extern "C" int salt_vcf_group(const salt_vcf_t *v, int c, salt_idx_snps_t *out)
+{
+    if (!v || !out || c < 0 || (size_t)c >= v->in.groups.size()) { g_ierr = "no such contig"; return -1; }
+    out->chr = v->in.groups[(size_t)c].chr.c_str(); out->pos = v->in.groups[(size_t)c].pos.data();
+    out->alleles = v->in.al[(size_t)c].data(); out->ref = v->in.rf[(size_t)c].data(); out->n = (uint32_t)v->in.groups[(size_t)c].pos.size();
+    return 0;
+}
+extern "C" void salt_vcf_free(salt_vcf_t *v) { delete v; }
+
+// CHROM of the 1-based line `want` of a (possibly compressed) text file, cut to cap - 1 bytes
+static void vcf_chrom_of_line(const char *fn, uint64_t want, char *out, uint32_t cap)
+{
+    out[0] = 0;
+    gzFile fp = gzopen(fn, "r");
+    if (!fp) return;
+    std::vector<char> buf(1 << 20);
+    uint64_t line = 1; uint32_t k = 0; int r; bool done = false;
+    while (!done && (r = gzread(fp, buf.data(), (unsigned)buf.size())) > 0) {
+        int i = 0;
+        while (i < r && !done) {
+            if (line < want) {
+                const void *q = memchr(buf.data() + i, '\n', (size_t)(r - i));
+                if (!q) break;
+                i = (int)((const char *)q - buf.data()) + 1; ++line;
+            } else {
+                const char ch = buf[(size_t)i++];
+                if (ch == '\t' || ch == '\n' || k + 1 >= cap) done = true; else out[k++] = ch;
+            }
+        }
+    }
+    out[k] = 0;
+    gzclose(fp);
+}
+
+extern "C" int salt_idx_build_vcf(const char *fn_fa, const char *fn_vcf, const char *prefix_c, int l_seed, const salt_idx_backend_t *be, int flags,
+                                  const salt_vcf_opt_t *opt)
+{
+    if (!fn_fa || !fn_vcf || !prefix_c || (opt && opt->n_rename > 0 && (!opt->rename_from || !opt->rename_to))) { g_ierr = "null argument"; return -1; }
+    std::vector<OwnedContig> own;
+    if (!read_fasta(fn_fa, own)) return -1;
+    std::vector<ContigView> fa;
+    for (auto &c : own) fa.push_back(ContigView{ c.name, c.comment, c.seq.data(), c.seq.size() });
+    std::vector<std::pair<std::string, std::string>> rename;
+    if (opt && opt->rename_file && !read_rename_map(opt->rename_file, rename)) return -1;
+    vcf_rename_pairs(opt, rename);
+    std::vector<Group> groups;
+    {
+        const double t0 = now_s();
+        VcfIngest in;
+        if (!in.open(fa, opt, rename)) return -1;
+        gzFile fp = gzopen(fn_vcf, "r");                       // plain text, gzip and BGZF (a run of gzip members) alike
+        if (!fp) { g_ierr = std::string("cannot open ") + fn_vcf; return -1; }
+        gzbuffer(fp, 1 << 20);
+        const size_t piece = 32u << 20;
+        std::vector<char> buf; size_t have = 0; bool ok = true;
+        for (;;) {
+            if (buf.size() < have + piece) buf.resize(have + piece);
+            const int r = gzread(fp, buf.data() + have, (unsigned)piece);
+            if (r < 0) { int e; g_ierr = std::string(fn_vcf) + ": " + gzerror(fp, &e); ok = false; break; }
+            if (r == 0) break;
+            have += (size_t)r;
+            const void *q = memrchr(buf.data(), '\n', have);   // whole lines go on; a line longer than the buffer makes it grow
+            if (!q) continue;
+            const size_t n = (size_t)((const char *)q - buf.data()) + 1;
+            if (!in.add(buf.data(), n)) { ok = false; break; }
+            memmove(buf.data(), buf.data() + n, have - n); have -= n;
+        }
+        gzclose(fp);
+        if (!ok || (have && !in.add(buf.data(), have)) || !in.finish()) return -1;
+        if (opt && opt->counters) *opt->counters = in.ctr;
+        if (opt && opt->unknown_name && opt->unknown_name_cap) {
+            opt->unknown_name[0] = 0;
+            if (in.ctr.first_unknown_line) vcf_chrom_of_line(fn_vcf, in.ctr.first_unknown_line, opt->unknown_name, opt->unknown_name_cap);
+        }
+        if (verbose()) fprintf(stderr, "[salt-idx] VCF ingest (%s): %.2f s (%llu lines, %llu sites)\n", opt && opt->device ? "device" : "host", now_s() - t0,
+                               (unsigned long long)in.ctr.lines, (unsigned long long)in.ctr.sites);
+        groups.swap(in.groups);
+    }
+    if (opt && opt->snp_out && !write_snp_file(opt->snp_out, groups)) return -1;
+    return build_core(fa, groups, prefix_c, l_seed, be, flags, true);
 }
