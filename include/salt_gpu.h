@@ -625,6 +625,40 @@ int  salt_gpu_ws_set_sam_bam(salt_gpu_ws_t *ws, int on);
  * record is printed with its empty name); an index with two contigs of one name (`polish` resolves the name to the last of them; here a hit
  * keeps the contig it lies in). */
 int  salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode);
+/* Trimming (`salt --trim-*`): after salt_gpu_ws_set_trim(ws, &opt) the text entry points (salt_gpu_align_se_text, _se_text_dev,
+ * salt_gpu_align_pe_text) trim every read of the block on the device, between the parser and the aligner (k_fq_trim), and everything behind
+ * it -- the aligner, the SAM, BAM and polish writers, the tallies -- sees the trimmed read: the block equals the block the same call returns,
+ * trimming off, for a FASTQ trimmed beforehand by salt_host.h's salt_trim_fastq.  The rule, integers only (csrc/salt_trim_rule.h is its one
+ * definition, for the device and the host), on a read of L >= 1 bases, each step on the span [beg, end) the one before left:
+ *   1. front, tail   0 .. 511: beg += front, end -= tail, saturating (end >= beg)
+ *   2. qual          0 off, 1 .. 93: s = best = 0, cut = end; for i = end - 1 down to beg: s += qual - (byte[i] - 33) (a byte below 33
+ *                    counts as quality 0); stop when s < 0; when s > best: best = s, cut = i.  end = cut.  (bwa aln -q, cutadapt -q)
+ *   3. adapter       1 .. 64 letters of ACGTacgt; adapter searches mate 0 (single end: every read), adapter2 mate 1 (without it mate 1 is
+ *                    searched with adapter).  Every start p from beg upward, ov = min(A, end - p); the search ends at the first p with
+ *                    ov < min_overlap (1 .. 64); mm = the j < ov where the read's letter p + j differs from the adapter's letter j (case
+ *                    ignored, a read letter outside ACGTacgt always differs); the leftmost p with 100 mm <= error_pct ov (0 .. 50) wins:
+ *                    end = p.  No indels, no wildcards.
+ *   4. floor         end <= beg: beg = min(beg, L - 1), end = beg + 1 -- no record is dropped and none becomes empty.
+ * SALT_MAX_READ_LEN applies to the trimmed length.  A null pointer or an all-zero struct switches trimming off, and the calls launch what
+ * they launch today.  A value out of range, adapter2 without adapter, min_overlap or error_pct without an adapter: SALT_E_INVAL, and
+ * salt_gpu_last_error() names the field.  The strings are copied.
+ * Counters: uint64 out[16], eight per mate (mate 0 first; single end counts as mate 0): 0 reads, 1 bases in, 2 bases out, 3 reads the
+ * quality step shortened, 4 bases it removed, 5 reads the adapter step shortened, 6 bases it removed, 7 reads the floor applied to.
+ * (Reads the clips shortened: all of them when front or tail is set.)  They add up over the workspace's calls until reset.  A block comes
+ * back with the parser's control words and is added once the parser has accepted it -- a block refused as "not 4-line FASTQ" adds nothing, its
+ * caller reads those records another way -- so salt_gpu_ws_trim_counts waits for nothing; salt_gpu_ws_trim_uncount takes back what the
+ * workspace's last call added (a block the caller aligned and then drops), as the tallies' _uncount calls do.
+ * salt_gpu_trim_spans: the parser and k_fq_trim alone on one block of 4-line FASTQ (at most max_reads records), every record as mate `mate`:
+ * beg_end[2 i], beg_end[2 i + 1] = the span of record i in its untrimmed read.  The block's counters are added too. */
+typedef struct salt_trim_opt {
+    const char *adapter;  uint32_t adapter_len;      /* NULL / 0: no adapter search */
+    const char *adapter2; uint32_t adapter2_len;     /* NULL / 0: mate 1 is searched with `adapter` */
+    uint32_t front, tail, qual, min_overlap, error_pct;
+} salt_trim_opt_t;
+int  salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *opt);
+int  salt_gpu_ws_trim_counts(salt_gpu_ws_t *ws, uint64_t out[16], int reset);
+int  salt_gpu_ws_trim_uncount(salt_gpu_ws_t *ws);
+int  salt_gpu_trim_spans(salt_gpu_ws_t *ws, const char *fastq, uint64_t n_bytes, int mate, uint32_t *beg_end);
 /* The same kernels on their own, host buffers in and out: text[0 .. n_bytes) -> ceil(n_bytes / 32640) BGZF blocks in out, *out_bytes of them
  * (0 for an empty text; no end-of-file block).  The same text gives the same bytes on every run.  SALT_E_CAPACITY when out_cap is too
  * small: n_bytes + 31 bytes per block is the exact bound, 65 536 bytes per block always suffice. */
@@ -720,7 +754,7 @@ int  salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t n, const u
  * (pe given: two blocks, row 2p + m belongs to mate m of pair p) through the same two functions -- the parse stage and the output stage --
  * with the align kernels between them replaced by k_pack and a copy of rows[0 .. n_rows) into the workspace's result rows.  Output as the
  * production entries give it: *out points into the workspace's page-locked buffer, salt_gpu_ws_set_sam_bam and salt_gpu_ws_set_sam_bgzf
- * are honoured, *n_records = the number of parsed records (both mates counted).  With salt_gpu_ws_set_polish on: SALT_E_INVAL.
+ * are honoured, *n_records = the number of parsed records (both mates counted).  With salt_gpu_ws_set_polish or salt_gpu_ws_set_trim on: SALT_E_INVAL.
  * The rows are checked on the host before a kernel reads one, with the read lengths the parse kernels found; SALT_E_INVAL and a message
  * "text rows: ..." (the row is named) for:
  *   n_rows different from the number of parsed records; a read longer than SALT_MAX_READ_LEN;

@@ -310,6 +310,19 @@ const char *salt_idx_last_error(void);
 int salt_isize_infer(const salt_index_t *ix, uint32_t n_pairs, const uint32_t *offs, const salt_result_t *res,
                      uint32_t *min_tlen, uint32_t *max_tlen, uint32_t *n_used);
 
+/* Trimming (`salt --trim-*`): the host twins of the device's k_fq_trim.  They compile the rule's one definition, csrc/salt_trim_rule.h, which the
+ * kernel compiles too (salt_gpu.h states the rule and the options); the independent statement is the Python model of the tests.  They are what
+ * the device is compared with, what `salt` trims with wherever its host pipeline parses the reads, and what gives a user the trimmed reads.
+ *   salt_trim_span    one read: seq and qual are its len >= 1 letters and quality bytes, mate 0 or 1 -> *beg, *end, its span; counts: NULL,
+ *                     or uint64[16] to which the read's counters are added at the mate's eight.  Returns 0.
+ *   salt_trim_fastq   a block of whole 4-line FASTQ records (LF or CR LF), every record as mate `mate` -> the same records trimmed, LF line
+ *                     ends, the header and '+' lines as they were: the block that, aligned without trimming, gives what the untrimmed block
+ *                     gives with it.  Returns the bytes of the trimmed block (never more than n); they are written when out holds them.
+ * Both return -1 with salt_host_last_error() set on failure: an option out of range (the message names the field), a block that is not
+ * 4-line FASTQ. */
+int     salt_trim_span(const salt_trim_opt_t *opt, int mate, const char *seq, const char *qual, uint32_t len, uint32_t *beg, uint32_t *end, uint64_t *counts);
+int64_t salt_trim_fastq(const salt_trim_opt_t *opt, int mate, const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *counts);
+
 /* "<len><op>..." text of a binary CIGAR (ops as in salt_result_t); returns bytes written or -1 */
 int salt_cigar_text(const uint16_t *ops, int n_ops, char *buf, size_t cap);
 

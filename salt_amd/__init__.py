@@ -8,4 +8,5 @@ from .api import (AlnOpt, GpuAligner, Index, SaltError, RESULT_DTYPE, read_fastq
                   BAM_MAX_NAME, Polisher, POLISH_STATS, snp_sites, snp_count_sam, depth_add_sam, depth_text, errprof_add_sam, errprof_text, ERRPROF_SHAPE, stats_add_sam, stats_text, stats_split, STATS_TABLES, STATS_CELLS, STATS_CT_LDS, STATS_CHUNK,
                   gt_add_sam, gt_text, gt_header, gt_table, GT_Q_NONE,
                   disc_add_sam, disc_text, DISC_ALT, DISC_DIFF, DISC_FIELD_BITS, DISC_DEFAULTS,
-                  indel_add_sam, indel_text, indel_header, INDEL_DEFAULTS, INDEL_STATS, INDEL_PROBE, INDEL_MAX_INS, INDEL_MAX_DEL, INDEL_MAX_SHIFT)
+                  indel_add_sam, indel_text, indel_header, INDEL_DEFAULTS, INDEL_STATS, INDEL_PROBE, INDEL_MAX_INS, INDEL_MAX_DEL, INDEL_MAX_SHIFT,
+                  trim_span, trim_fastq, TRIM_COUNTERS)

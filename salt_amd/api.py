@@ -918,6 +918,63 @@ def indel_header(index, min_mapq=20, min_alt=3, min_pct=20, dropped=0):
     return out.raw[:n]
 
 
+TRIM_COUNTERS = ("reads", "bases_in", "bases_out", "reads_qual", "bases_qual", "reads_adapter", "bases_adapter", "reads_floored")
+
+
+class _TrimOpt(ctypes.Structure):
+    _fields_ = [("adapter", ctypes.c_char_p), ("adapter_len", ctypes.c_uint32), ("adapter2", ctypes.c_char_p), ("adapter2_len", ctypes.c_uint32),
+                ("front", ctypes.c_uint32), ("tail", ctypes.c_uint32), ("qual", ctypes.c_uint32), ("min_overlap", ctypes.c_uint32),
+                ("error_pct", ctypes.c_uint32)]
+
+
+def _trim_opt(adapter, adapter2, qual, front, tail, min_overlap, error_pct):
+    """salt_trim_opt_t; min_overlap and error_pct belong to the adapter and are left out without one"""
+    a = adapter.encode() if isinstance(adapter, str) else adapter
+    a2 = adapter2.encode() if isinstance(adapter2, str) else adapter2
+    for v in (qual, front, tail, min_overlap, error_pct):
+        if not 0 <= int(v) < 2 ** 32:
+            raise SaltError("trim: a number outside 0 .. 2^32 - 1")
+    return _TrimOpt(a or None, len(a) if a else 0, a2 or None, len(a2) if a2 else 0, int(front), int(tail), int(qual),
+                    int(min_overlap) if a else 0, int(error_pct) if a else 0)
+
+
+def _host_trim():
+    lib = host_lib()
+    lib.salt_trim_span.argtypes = [ctypes.POINTER(_TrimOpt), ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lib.salt_trim_fastq.restype = ctypes.c_int64
+    lib.salt_trim_fastq.argtypes = [ctypes.POINTER(_TrimOpt), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    return lib
+
+
+def trim_span(seq, qual, mate=0, adapter=None, adapter2=None, qual_min=0, front=0, tail=0, min_overlap=5, error_pct=10, counts=None):
+    """The host twin of k_fq_trim on one read (salt_trim_span): -> (beg, end).  qual_min is set_trim's `qual` (qual here is the read's
+    quality string).  counts: a (2, 8) uint64 array the read's counters are added to."""
+    lib, o = _host_trim(), _trim_opt(adapter, adapter2, qual_min, front, tail, min_overlap, error_pct)
+    seq, qual = bytes(seq), bytes(qual)
+    if len(seq) != len(qual):
+        raise SaltError("trim: sequence and quality lengths differ")
+    if counts is not None and (counts.dtype != np.uint64 or counts.shape != (2, 8) or not counts.flags.c_contiguous):
+        raise SaltError("trim: counts is a C-contiguous (2, 8) uint64 array")
+    b, e = ctypes.c_uint32(), ctypes.c_uint32()
+    if lib.salt_trim_span(ctypes.byref(o), int(mate), seq, qual, len(seq), ctypes.byref(b), ctypes.byref(e), counts.ctypes.data if counts is not None else None) != 0:
+        raise SaltError(lib.salt_host_last_error().decode())
+    return b.value, e.value
+
+
+def trim_fastq(fastq, mate=0, adapter=None, adapter2=None, qual=0, front=0, tail=0, min_overlap=5, error_pct=10, counts=None):
+    """A block of 4-line FASTQ trimmed on the host (salt_trim_fastq): the reads `salt --trim-*` aligns, as FASTQ."""
+    lib, o = _host_trim(), _trim_opt(adapter, adapter2, qual, front, tail, min_overlap, error_pct)
+    fastq = bytes(fastq)
+    if counts is not None and (counts.dtype != np.uint64 or counts.shape != (2, 8) or not counts.flags.c_contiguous):
+        raise SaltError("trim: counts is a C-contiguous (2, 8) uint64 array")
+    out = ctypes.create_string_buffer(len(fastq) + 1)
+    n = lib.salt_trim_fastq(ctypes.byref(o), int(mate), fastq, len(fastq), out, len(fastq), counts.ctypes.data if counts is not None else None)
+    if n < 0:
+        raise SaltError(lib.salt_host_last_error().decode())
+    return out.raw[:n]
+
+
 class _IndelTextOpt(ctypes.Structure):
     _fields_ = [("min_alt", ctypes.c_uint32), ("min_pct", ctypes.c_uint32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
@@ -1121,6 +1178,33 @@ class GpuAligner:
         mode = {"off": 0, "lv": 1, "sw": 2}.get(mode, mode)
         gpu_lib().salt_gpu_ws_set_polish.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _gpu_check(gpu_lib().salt_gpu_ws_set_polish(self._ws, int(mode)))
+
+    def set_trim(self, adapter=None, adapter2=None, qual=0, front=0, tail=0, min_overlap=5, error_pct=10):
+        """The text entry points trim every read on the device (k_fq_trim) in front of the aligner: fixed clips, the 3' quality rule of
+        `bwa aln -q`, a 3' adapter by Hamming overlap (adapter2: mate 2's own), never below one base.  Without arguments: off."""
+        o = _trim_opt(adapter, adapter2, qual, front, tail, min_overlap, error_pct)
+        gpu_lib().salt_gpu_ws_set_trim.argtypes = [ctypes.c_void_p, ctypes.POINTER(_TrimOpt)]
+        _gpu_check(gpu_lib().salt_gpu_ws_set_trim(self._ws, ctypes.byref(o)))
+
+    def trim_counts(self, reset=False):
+        """(2, 8) uint64: per mate TRIM_COUNTERS, summed over this workspace's calls."""
+        out = np.zeros((2, 8), dtype=np.uint64)
+        gpu_lib().salt_gpu_ws_trim_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _gpu_check(gpu_lib().salt_gpu_ws_trim_counts(self._ws, out.ctypes.data, 1 if reset else 0))
+        return out
+
+    def trim_uncount(self):
+        """Takes back what this aligner's last text call (or trim_spans) added to trim_counts."""
+        gpu_lib().salt_gpu_ws_trim_uncount.argtypes = [ctypes.c_void_p]
+        _gpu_check(gpu_lib().salt_gpu_ws_trim_uncount(self._ws))
+
+    def trim_spans(self, fastq, mate=0):
+        """The parser and k_fq_trim alone on one block of 4-line FASTQ: (records, 2) uint32, the span (beg, end) of every record."""
+        fastq = bytes(fastq)
+        out = np.zeros((fastq.count(b"\n") // 4 + 1, 2), dtype=np.uint32)
+        gpu_lib().salt_gpu_trim_spans.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
+        _gpu_check(gpu_lib().salt_gpu_trim_spans(self._ws, fastq, len(fastq), int(mate), out.ctypes.data))
+        return out[:-1]
 
     def align_se_text(self, opt, fastq):
         """One block of whole 4-line FASTQ records -> (the block's SAM lines, or what set_sam_bam / set_sam_bgzf make of them; reads)."""

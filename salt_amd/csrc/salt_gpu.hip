@@ -121,6 +121,13 @@ struct salt_gpu_ws {
     // salt_gpu_ws_set_polish: the text entry points return the polished records of the block (salt_polish.hip) where they returned its SAM
     // lines; the polish buffers and Landau-Vishkin tables are this workspace's (allocated on first use)
     int polish = 0; PolishText *pl = nullptr; DevBuf<uint8_t> d_pl_tabs; uint32_t pl_blocks = 0;
+    // salt_gpu_ws_set_trim: k_fq_trim stands behind k_fq_parse in the text entry points.  d_trim_cnt: the sixteen counters of the block being
+    // parsed; they come back with the parser's control words (no wait of their own) and are added to trim_total once the parser has accepted
+    // the block (a refused block is parsed again by the caller's own reader); trim_last: what the last call added (salt_gpu_ws_trim_uncount)
+    bool trim = false; TrimRule trim_rule{}; DevBuf<unsigned long long> d_trim_cnt; DevBuf<uint32_t> d_trim_spans;
+    uint64_t trim_total[2 * TRIM_N_COUNTS] = {}, trim_last[2 * TRIM_N_COUNTS] = {};
+    // (not part of forget_last: the align stage of a text call forgets the tallies' jobs behind the parse stage that set trim_last)
+    void trim_forget() { memset(trim_last, 0, sizeof trim_last); }
     DevBuf<uint32_t> d_bz_slots, d_bz_sizes; DevBuf<unsigned long long> d_bz_offs; DevBuf<uint8_t> d_bz_out;      // bgzf_bufs_alloc: d_bz_sizes.cap blocks
     PinBuf<char> h_bz;                                                       // only for a compressed block that outgrows h_sam
     // salt_gpu_ws_inflate_bgzf: a chunk's BGZF members, their offsets and status words, and the text they inflate to (allocated on first use, grown on demand)
@@ -930,6 +937,49 @@ extern "C" int salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode)
     return SALT_OK;
 }
 
+extern "C" int salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *o)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    TrimRule r{};
+    if (o) if (const char *what = trim_rule_make(o->adapter, o->adapter_len, o->adapter2, o->adapter2_len, o->front, o->tail, o->qual, o->min_overlap, o->error_pct, &r))
+        return fail(SALT_E_INVAL, what);
+    if (trim_rule_on(r) && !ws->d_trim_cnt) {
+        HIPCHK(hipSetDevice(ws->ix->device));
+        HIPCHK(ws->d_trim_cnt.alloc(2 * TRIM_N_COUNTS));
+    }
+    ws->trim_rule = r; ws->trim = trim_rule_on(r);
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_trim_counts(salt_gpu_ws_t *ws, uint64_t out[16], int reset)
+{
+    if (!ws || !out) return fail(SALT_E_INVAL, "null argument");
+    memcpy(out, ws->trim_total, sizeof ws->trim_total);          // every finished call has added its block already
+    if (reset) memset(ws->trim_total, 0, sizeof ws->trim_total);
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_trim_uncount(salt_gpu_ws_t *ws)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    for (uint32_t k = 0; k < 2 * TRIM_N_COUNTS; ++k) ws->trim_total[k] -= ws->trim_last[k];
+    memset(ws->trim_last, 0, sizeof ws->trim_last);
+    return SALT_OK;
+}
+
+// k_fq_trim behind the parse kernels of a call, its counters zeroed in front of it
+static int ws_trim_launch(salt_gpu_ws_t *ws, uint64_t n_raw, uint32_t n_rec, int pe, uint32_t mate, uint32_t *spans, hipStream_t st)
+{
+    if (!ws->d_trim_cnt) HIPCHK(ws->d_trim_cnt.alloc(2 * TRIM_N_COUNTS));
+    HIPCHK(hipMemsetAsync(ws->d_trim_cnt, 0, 2 * TRIM_N_COUNTS * 8, st));
+    HIPCHK(launch_fq_trim(ws->d_raw, n_raw, ws->d_rec, ws->d_offs, n_rec, pe, mate, ws->trim_rule, ws->d_tctl, ws->d_trim_cnt, spans, st));
+    return SALT_OK;
+}
+static void ws_trim_add(salt_gpu_ws_t *ws, const uint64_t *blk)
+{
+    for (uint32_t k = 0; k < 2 * TRIM_N_COUNTS; ++k) { ws->trim_total[k] += blk[k]; ws->trim_last[k] = blk[k]; }
+}
+
 // The polish stage of a text call, where the SAM kernels run without it: the block's records from its result rows (polish_rows_len: all but
 // the bytes; *total = how many they are), then -- the caller has made room in ws->d_sam -- polish_rows_write.
 static int ws_polish_len(salt_gpu_ws_t *ws, uint32_t n_rec, uint32_t max_len, int paired, hipStream_t st, uint64_t *total)
@@ -1132,18 +1182,20 @@ struct TextTrace {
 // codes.  blocks: "block" or "blocks", as the entry point takes one or two.
 static int text_codes(salt_gpu_ws_t *ws, uint32_t n_rec, const char *blocks, hipStream_t st, uint32_t *max_len)
 {
-    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0;
+    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0; uint64_t trimmed[2 * TRIM_N_COUNTS];
     HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&bases, ws->d_offs + n_rec, 4, hipMemcpyDeviceToHost, st));
+    if (ws->trim) HIPCHK(hipMemcpyAsync(trimmed, ws->d_trim_cnt, sizeof trimmed, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ctl[0]) {
         const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
                          : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
         return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the " + blocks + ": " + what);
     }
+    if (ws->trim) ws_trim_add(ws, trimmed);
     if (int rc = reserve_seqs(ws, bases, st)) return rc;
     HIPCHK(launch_fq_codes(ws->d_raw, ws->d_rec, ws->d_offs, n_rec, ws->d_seqs, st));
-    *max_len = ctl[1];
+    *max_len = ws->trim ? ctl[3] : ctl[1];                         // k_fq_trim leaves the longest trimmed read in ctl[3]
     return SALT_OK;
 }
 
@@ -1241,7 +1293,14 @@ static int text_parse_se(salt_gpu_ws_t *ws, const char *fastq, const uint8_t *d_
     HIPCHK(launch_fq_lines(ws->d_raw, n_bytes, ws->d_tile, ws->d_lines, st));
     // ---- records, offsets, codes ----
     if ((rc = reserve_records(ws))) return rc;
-    HIPCHK(launch_fq_parse(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, ws->d_scan, ws->d_scan.cap, st));
+    if (!ws->trim) HIPCHK(launch_fq_parse(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, ws->d_scan, ws->d_scan.cap, st));
+    else {                                                       // the same, k_fq_trim between the records and the scan of their lengths
+        HIPCHK(launch_fq_ctl_init(ws->d_tctl, st));
+        HIPCHK(hipMemsetAsync(ws->d_offs + n_rec, 0, 4, st));
+        HIPCHK(launch_fq_parse_recs(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, st));
+        if ((rc = ws_trim_launch(ws, n_bytes, n_rec, 0, 0u, nullptr, st))) return rc;
+        HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->d_scan.cap, st));
+    }
     if ((rc = text_codes(ws, n_rec, "block", st, max_len))) return rc;
     ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = n_bytes;      // the error profile reads the qualities where they lie
     *n_rec_out = n_rec;
@@ -1253,7 +1312,7 @@ static int se_text_impl(salt_gpu_ws_t *ws, const salt_aln_opt_t *o, const salt_t
 {
     const uint64_t n_src = n_bytes;
     if (d_src && add_newline) ++n_bytes;
-    ws->forget_last();
+    ws->forget_last(); ws->trim_forget();
     salt_gpu_index *ix = ws->ix;
     if (!ix->d_c_off) return fail(SALT_E_INVAL, "SAM text needs the contig table: call salt_gpu_index_set_contigs first");
     HIPCHK(hipSetDevice(ix->device));
@@ -1312,6 +1371,7 @@ static int text_parse_pe(salt_gpu_ws_t *ws, const char *fastq1, uint64_t n1, con
     HIPCHK(hipMemsetAsync(ws->d_offs + n_rec, 0, 4, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, 0u, lines1, n, 0u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, (uint32_t)b2, lines2, n, 1u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
+    if (ws->trim && (rc = ws_trim_launch(ws, b2 + n2, n_rec, 1, 0u, nullptr, st))) return rc;
     HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->d_scan.cap, st));
     if ((rc = text_codes(ws, n_rec, "blocks", st, max_len))) return rc;
     ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = b2 + n2;      // both blocks; a mate's qual_off counts from d_raw
@@ -1326,7 +1386,7 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
                                       const char **sam, uint64_t *sam_bytes, uint32_t *n_pairs)
 {
     if (!ws || !o || !pe || !to || !fastq1 || !fastq2 || !sam || !sam_bytes || !n_pairs) return fail(SALT_E_INVAL, "null argument");
-    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->forget_last();
+    *sam = nullptr; *sam_bytes = 0; *n_pairs = 0; ws->forget_last(); ws->trim_forget();
     if (n1 == 0 && n2 == 0) return SALT_OK;
     if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
     if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
@@ -1345,6 +1405,51 @@ extern "C" int salt_gpu_align_pe_text(salt_gpu_ws_t *ws, const salt_aln_opt_t *o
     TextTrace tr;                                               // off: the stage clocks are single end's
     if ((rc = text_emit(ws, to, pe, n_rec, max_len, st, tr, sam, sam_bytes))) return rc;
     *n_pairs = n;
+    return SALT_OK;
+}
+
+// The parser and k_fq_trim alone (include/salt_gpu.h): the lines and records of one block as text_parse_se makes them, every record trimmed
+// as mate `mate`, the spans back.  Nothing behind the trim kernel runs: no scan, no codes.
+extern "C" int salt_gpu_trim_spans(salt_gpu_ws_t *ws, const char *fastq, uint64_t n_bytes, int mate, uint32_t *beg_end)
+{
+    if (!ws || !fastq || !beg_end) return fail(SALT_E_INVAL, "null argument");
+    if (mate != 0 && mate != 1) return fail(SALT_E_INVAL, "trim spans: mate is 0 or 1");
+    ws->forget_last(); ws->trim_forget();
+    if (n_bytes == 0) return SALT_OK;
+    if (n_bytes >= 0xFFFFFFF0ull) return fail(SALT_E_CAPACITY, "FASTQ block of 4 GiB or more");
+    if (fastq[n_bytes - 1] != '\n') return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
+    HIPCHK(hipSetDevice(ws->ix->device));
+    hipStream_t st = ws->stream;
+    int rc = reserve_parse(ws, n_bytes, st);
+    if (rc) return rc;
+    const uint64_t n_tiles = (n_bytes + FQ_TILE - 1) / FQ_TILE;
+    HIPCHK(hipMemcpyAsync(ws->d_raw, fastq, n_bytes, hipMemcpyHostToDevice, st));
+    uint32_t n_nl = 0;
+    HIPCHK(launch_fq_count(ws->d_raw, n_bytes, ws->d_tile, ws->d_scan, ws->d_scan.cap, st));
+    HIPCHK(hipMemcpyAsync(&n_nl, ws->d_tile + n_tiles, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_nl % 4 != 0) return fail(SALT_E_INVAL, "FASTQ block does not hold whole 4-line records (" + std::to_string(n_nl) + " lines)");
+    const uint32_t n_rec = n_nl / 4;
+    if (n_rec > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads in the block (" + std::to_string(n_rec) + ") than the workspace holds");
+    if (n_rec == 0) return SALT_OK;
+    if ((rc = ws->d_lines.reserve((uint64_t)n_nl + 8, st))) return rc;
+    HIPCHK(launch_fq_lines(ws->d_raw, n_bytes, ws->d_tile, ws->d_lines, st));
+    if ((rc = reserve_records(ws))) return rc;
+    if (!ws->d_trim_spans) HIPCHK(ws->d_trim_spans.alloc(2 * (uint64_t)ws->max_reads));
+    HIPCHK(launch_fq_ctl_init(ws->d_tctl, st));
+    HIPCHK(launch_fq_parse_recs(ws->d_raw, ws->d_lines, n_rec, ws->d_rec, ws->d_offs, ws->d_tctl, st));
+    if ((rc = ws_trim_launch(ws, n_bytes, n_rec, 0, (uint32_t)mate, ws->d_trim_spans, st))) return rc;
+    uint32_t ctl[4] = { 0, 0, 0, 0 }; uint64_t trimmed[2 * TRIM_N_COUNTS];
+    HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(trimmed, ws->d_trim_cnt, sizeof trimmed, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(beg_end, ws->d_trim_spans, 2 * (uint64_t)n_rec * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ctl[0]) {
+        const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
+                         : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
+        return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the block: " + what);
+    }
+    ws_trim_add(ws, trimmed);
     return SALT_OK;
 }
 
@@ -1381,8 +1486,9 @@ extern "C" int salt_gpu_diag_text_rows(salt_gpu_ws_t *ws, const salt_text_opt_t 
                                        const char **out, uint64_t *out_bytes, uint32_t *n_records)
 {
     if (!ws || !to || !fastq1 || (pe && !fastq2) || (n_rows && !rows) || !out || !out_bytes || !n_records) return fail(SALT_E_INVAL, "null argument");
-    *out = nullptr; *out_bytes = 0; *n_records = 0; ws->forget_last();
+    *out = nullptr; *out_bytes = 0; *n_records = 0; ws->forget_last(); ws->trim_forget();
     if (ws->polish) return fail(SALT_E_INVAL, "text rows: the polish stage is not driven from rows (salt_gpu_ws_set_polish is on)");
+    if (ws->trim) return fail(SALT_E_INVAL, "text rows: the rows are checked against the untrimmed reads (salt_gpu_ws_set_trim is on)");
     if (n1 == 0 || (pe && n2 == 0)) return fail(SALT_E_INVAL, "text rows: an empty FASTQ block");
     if (n1 + (pe ? n2 : 0) >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
     if (fastq1[n1 - 1] != '\n' || (pe && fastq2[n2 - 1] != '\n')) return fail(SALT_E_INVAL, "FASTQ block must end with a newline");

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/salt_gpu.h"
 #include "salt_device.h"
+#include "salt_trim_rule.h"
 
 // Diagnostics that CHANGE results (phase timing by leaving kernels early) exist only in -DSALT_DIAG builds (`make DIAG=1`): the release
 // library has neither the environment switches nor the code paths behind them (tests/test_release_build.py greps for the names).
@@ -211,6 +212,12 @@ hipError_t launch_sam_write(const SamDev &d, uint32_t n, const uint32_t *off, ch
 // the same block as BAM records (salt --bam): same slots, same scan; *err != 0: a read name longer than 254 bytes
 hipError_t launch_bam_len(const SamDev &d, uint32_t n, uint32_t *off, unsigned long long *total64, uint32_t *err, void *tmp, size_t tmp_bytes, hipStream_t st);
 hipError_t launch_bam_write(const SamDev &d, uint32_t n, const uint32_t *off, char *out, hipStream_t st);
+// records and lengths alone, for the caller that puts k_fq_trim between them and the scan (ctl initialised and offs[n_rec] zeroed by the caller)
+hipError_t launch_fq_parse_recs(const uint8_t *raw, const uint32_t *line_start, uint32_t n_rec, FqRec *rec, uint32_t *len, uint32_t *ctl, hipStream_t st);
+// trimming (salt_trim.hip): behind k_fq_parse, in front of the scan of len.  Rewrites seq_off, qual_off and len of rec[i] and len[i],
+// leaves the longest trimmed read in ctl[3], adds to counts[16]; spans (or null): beg, end of every record.  raw[0, n_raw) is what the offsets may reach.
+hipError_t launch_fq_trim(const uint8_t *raw, uint64_t n_raw, FqRec *rec, uint32_t *len, uint32_t n_rec, int pe, uint32_t mate, const TrimRule &rule,
+                          uint32_t *ctl, unsigned long long *counts, uint32_t *spans, hipStream_t st);
 static const uint32_t FQ_TILE = 1024;                                          // bytes per newline-count tile (k_fq_count)
 
 // ---- polish over SAM text (salt_polish.hip) ----

@@ -697,6 +697,11 @@ hipError_t launch_fq_parse(const uint8_t *raw, const uint32_t *line_start, uint3
     hipLaunchKernelGGL(k_fq_parse, dim3(tgrid(n_rec)), dim3(256), 0, st, raw, line_start, n_rec, rec, offs, ctl, 0u, 1u, 0u);
     return rocprim::exclusive_scan(tmp, tmp_bytes, offs, offs, 0u, (size_t)n_rec + 1, rocprim::plus<uint32_t>(), st);
 }
+hipError_t launch_fq_parse_recs(const uint8_t *raw, const uint32_t *line_start, uint32_t n_rec, FqRec *rec, uint32_t *len, uint32_t *ctl, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_fq_parse, dim3(tgrid(n_rec)), dim3(256), 0, st, raw, line_start, n_rec, rec, len, ctl, 0u, 1u, 0u);
+    return hipGetLastError();
+}
 hipError_t launch_fq_parse_mate(const uint8_t *raw, uint32_t base, const uint32_t *line_start, uint32_t n_rec, uint32_t which, FqRec *rec, uint32_t *len,
                                 uint32_t *ctl, hipStream_t st)
 {

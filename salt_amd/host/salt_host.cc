@@ -1496,3 +1496,56 @@ extern "C" int64_t salt_indel_header(const salt_index_t *ix, uint32_t min_mapq, 
     o.puts("\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     return (int64_t)o.n;
 }
+
+// ---- trimming: the rule of csrc/salt_trim_rule.h on the host (include/salt_host.h) ----------------------------------------------------------
+#include "../csrc/salt_trim_rule.h"
+
+static bool trim_rule_of(const salt_trim_opt_t *o, salt::TrimRule *r)
+{
+    *r = salt::TrimRule();
+    if (!o) return true;
+    if (const char *what = salt::trim_rule_make(o->adapter, o->adapter_len, o->adapter2, o->adapter2_len, o->front, o->tail, o->qual, o->min_overlap, o->error_pct, r)) {
+        g_err = what;
+        return false;
+    }
+    return true;
+}
+
+extern "C" int salt_trim_span(const salt_trim_opt_t *opt, int mate, const char *seq, const char *qual, uint32_t len, uint32_t *beg, uint32_t *end, uint64_t *counts)
+{
+    if (!seq || !qual || !beg || !end || len == 0 || (mate != 0 && mate != 1)) { g_err = "trim: null argument, an empty read or a mate other than 0 and 1"; return -1; }
+    salt::TrimRule r;
+    if (!trim_rule_of(opt, &r)) return -1;
+    salt::trim_span(r, (uint32_t)mate, reinterpret_cast<const uint8_t *>(seq), reinterpret_cast<const uint8_t *>(qual), len, beg, end,
+                    counts ? counts + salt::TRIM_N_COUNTS * mate : nullptr);
+    return 0;
+}
+
+extern "C" int64_t salt_trim_fastq(const salt_trim_opt_t *opt, int mate, const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *counts)
+{
+    if ((!in && n) || (!out && cap) || (mate != 0 && mate != 1)) { g_err = "trim: null argument or a mate other than 0 and 1"; return -1; }
+    salt::TrimRule r;
+    if (!trim_rule_of(opt, &r)) return -1;
+    uint64_t w = 0, rec = 0;
+    auto put = [&](const char *p, uint64_t k) { if (w + k <= cap) memcpy(out + w, p, k); w += k; };
+    auto bad = [&](const char *why) -> int64_t { g_err = "trim: input is not 4-line FASTQ at record " + std::to_string(rec) + ": " + why; return -1; };
+    for (uint64_t p = 0; p < n; ++rec) {
+        const char *l[4]; uint64_t len[4];
+        for (int k = 0; k < 4; ++k) {
+            const char *nl = p < n ? static_cast<const char *>(memchr(in + p, '\n', n - p)) : nullptr;
+            if (!nl) return bad("the block does not hold whole 4-line records");
+            l[k] = in + p; len[k] = (uint64_t)(nl - (in + p)); p += len[k] + 1;
+            while (len[k] && l[k][len[k] - 1] == '\r') --len[k];
+        }
+        if (!len[0] || l[0][0] != '@') return bad("a record does not start with '@'");
+        if (!len[2] || l[2][0] != '+') return bad("the third line of a record does not start with '+'");
+        if (len[1] != len[3]) return bad("sequence and quality lengths differ");
+        if (!len[1]) return bad("empty read");
+        if (len[1] > 0xFFFFFFFFull) return bad("a read of 4 Gbases or more");
+        uint32_t beg = 0, end = 0;
+        salt::trim_span(r, (uint32_t)mate, reinterpret_cast<const uint8_t *>(l[1]), reinterpret_cast<const uint8_t *>(l[3]), (uint32_t)len[1], &beg, &end,
+                        counts ? counts + salt::TRIM_N_COUNTS * mate : nullptr);
+        put(l[0], len[0]); put("\n", 1); put(l[1] + beg, end - beg); put("\n", 1); put(l[2], len[2]); put("\n", 1); put(l[3] + beg, end - beg); put("\n", 1);
+    }
+    return (int64_t)w;
+}

@@ -54,6 +54,10 @@ extern "C" int salt_gpu_ws_text_peek(salt_gpu_ws_t *ws, uint64_t off, uint64_t n
 extern "C" int salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_t *opt, const salt_text_opt_t *topt, uint64_t off, uint64_t n_bytes, int add_newline,
                                           const char **sam, uint64_t *sam_bytes, uint32_t *n_reads) __attribute__((weak));
 
+// Likewise the trim kernel in front of the aligner (--trim-*): without it the run trims on the host, through the host pipeline.
+extern "C" int salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *opt) __attribute__((weak));
+extern "C" int salt_gpu_ws_trim_counts(salt_gpu_ws_t *ws, uint64_t out[16], int reset) __attribute__((weak));
+extern "C" int salt_gpu_ws_trim_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
 // Likewise the polish stage behind the aligner (--polish) and the polish handle the host pipeline passes its lines through.
 extern "C" int salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode) __attribute__((weak));
 extern "C" int salt_gpu_polish_open(int device, const uint8_t *pac, uint64_t l_pac, salt_gpu_polish_t **out) __attribute__((weak));
@@ -122,6 +126,39 @@ namespace {
 
 const int N_SEQS = 100000;
 int g_polish = 0;                             // --polish: 0 off, 1 Landau-Vishkin, 2 Smith-Waterman
+
+// --trim-*: the reads are trimmed in front of the aligner -- on the text path by the device's k_fq_trim (salt_gpu_ws_set_trim on every
+// workspace), wherever the host parses the reads (parse_batch: the host pipeline, the continuation behind a hand-over, the first batch of
+// infer_isize) by the host twin salt_trim_span, which compiles the same rule.  The sixteen counters of both sides end in one line on stderr.
+struct TrimRun {
+    bool on = false, device = false;                         // device: the text path's workspaces trim
+    bool instead_of_text_path = false;                       // the host pipeline reads a file the text path would have read: records of any shape, as behind a hand-over
+    salt_trim_opt_t opt{}; bool has_overlap = false, has_error = false;
+    std::atomic<uint64_t> counts[16]; std::atomic<bool> by_device{ false }, by_host{ false };
+    void add(const uint64_t *c, bool dev) { bool any = false; for (int k = 0; k < 16; ++k) if (c[k]) { counts[k] += c[k]; any = true; } if (any) (dev ? by_device : by_host) = true; }
+} g_trim;
+// a workspace of the text path is about to go: its counters join the run's
+void trim_collect(salt_gpu_ws_t *ws)
+{
+    uint64_t c[16];
+    if (ws && g_trim.device && salt_gpu_ws_trim_counts(ws, c, 1) == 0) g_trim.add(c, true);
+}
+void trim_report()
+{
+    if (!g_trim.on) return;
+    const bool clip = g_trim.opt.front || g_trim.opt.tail;
+    std::string line = std::string("[salt] trim: ") + (g_trim.by_device && g_trim.by_host ? "device, and host behind the hand-over" : g_trim.by_host || !g_trim.device ? "host" : "device");
+    for (int m = 0; m < 2; ++m) {
+        uint64_t c[8]; for (int k = 0; k < 8; ++k) c[k] = g_trim.counts[8 * m + k];
+        if (m && !c[0]) break;
+        char buf[400];
+        snprintf(buf, sizeof buf, "%s mate %d: reads %llu bases_in %llu bases_out %llu reads_clipped %llu reads_qual %llu bases_qual %llu reads_adapter %llu bases_adapter %llu reads_floored %llu",
+                 m ? ";" : ":", m + 1, (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)(clip ? c[0] : 0), (unsigned long long)c[3],
+                 (unsigned long long)c[4], (unsigned long long)c[5], (unsigned long long)c[6], (unsigned long long)c[7]);
+        line += buf;
+    }
+    fprintf(stderr, "%s\n", line.c_str());
+}
 
 struct Batch {
     long seq_no = 0;
@@ -292,7 +329,7 @@ public:
     }
 };
 
-void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool);
+void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool, int mate = 0, bool count = true);
 
 void format_batch(const salt_index_t *ix, const salt_sam_opt_t *so, Batch &b, Pool &pool)
 {
@@ -340,7 +377,8 @@ void format_batch_pe(const salt_index_t *ix, const salt_sam_opt_t *so, const sal
     });
 }
 
-void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool)
+// mate: which adapter --trim-* searches the batch's reads with; count: their trim counters join the run's (not for infer_isize's look at the first batch)
+void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool, int mate, bool count)
 {
     const std::vector<uint32_t> &rec = b.rec;                  // record starts, found by the reader
     const int n = (int)rec.size(), n_threads = pool.n;
@@ -349,6 +387,7 @@ void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool)
     std::vector<std::pair<size_t, size_t>> seq_span((size_t)n);
     auto line_end = [&](size_t p) { const char *nl = (const char *)memchr(raw.data() + p, '\n', raw.size() - p); size_t e = nl ? (size_t)(nl - raw.data()) : raw.size(); return e; };
     pool.parallel([&](int t) {
+        uint64_t trimmed[16] = {};
         for (int i = (int)((long)n * t / n_threads); i < (int)((long)n * (t + 1) / n_threads); ++i) {
             size_t p = rec[(size_t)i], e = line_end(p);
             size_t ne = p + 1;
@@ -369,9 +408,16 @@ void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool)
                                 "the head of the file shows them\n", i, raw.data() + p);
                 exit(1);
             }
+            if (g_trim.on && se > s0) {                      // the span of the rule: bases, qualities and length move with it
+                uint32_t tb = 0, te = 0;
+                if (salt_trim_span(&g_trim.opt, mate, raw.data() + s0, raw.data() + q0, (uint32_t)(se - s0), &tb, &te, trimmed)) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); exit(1); }
+                seq_span[(size_t)i] = { s0 + tb, s0 + te }; len[(size_t)i] = te - tb;
+                b.qual[(size_t)i] = (uint32_t)(q0 + tb); q1 = q0 + te;
+            }
             raw[name_end] = 0;                               // terminate in place (after every read of these lines)
             if (q1 < raw.size()) raw[q1] = 0;
         }
+        if (g_trim.on && count) g_trim.add(trimmed, false);
     });
     b.offs.assign((size_t)n + 1, 0);
     for (int i = 0; i < n; ++i) b.offs[(size_t)i + 1] = b.offs[(size_t)i] + len[(size_t)i];
@@ -585,6 +631,7 @@ void drop_block(salt_gpu_ws_t *ws)
 {
     for (const Tally &t : TALLIES)
         if (t.run->on && t.run->device && t.uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());
+    if (g_trim.device && salt_gpu_ws_trim_uncount(ws)) fprintf(stderr, "[salt] %s\n", salt_gpu_last_error());      // (the host parser trims those reads again)
 }
 
 // SAM lines -> BAM records in `out`; false with the reason on stderr (a read name past the format's limit)
@@ -712,6 +759,17 @@ int usage()
             "               --indels-min-pct <int>   --indels: ... that are at least this share of the depth at the anchor, 0 .. 100 [20]\n"
             "               --indels-slots <int>     --indels: slots of the GPU's allele table, a power of two from 64 to 268435456, 16 bytes\n"
             "                                        each; alleles that find no slot are dropped and counted [16777216]\n"
+            "               --trim-adapter  <seq>    trim the reads in front of the aligner (on the GPU, in the FASTQ block as it lies there):\n"
+            "                                        cut a read where this 3' adapter starts, 1 to 64 letters of ACGT; the leftmost start whose\n"
+            "                                        overlap with the adapter (no indels) has few enough mismatches; single end and mate 1 [off]\n"
+            "               --trim-adapter2 <seq>    --trim-adapter: the adapter of mate 2 [the one of mate 1]\n"
+            "               --trim-min-overlap <int> --trim-adapter: an overlap at the read's end counts from this many bases, 1 .. 64 [5]\n"
+            "               --trim-error-pct <int>   --trim-adapter: mismatches allowed, in percent of the overlap, 0 .. 50 [10]\n"
+            "               --trim-qual     <int>    cut the 3' end by base quality, the rule of bwa aln -q and cutadapt -q, 1 .. 93 [off]\n"
+            "               --trim-front    <int>    remove this many bases from every read's 5' end, 0 .. 511 [0]\n"
+            "               --trim-tail     <int>    remove this many bases from every read's 3' end, 0 .. 511 [0]\n"
+            "                                        order: clips, quality, adapter; a read keeps at least one base, no read is dropped;\n"
+            "                                        one line of counters on stderr\n"
             "               --genotype      <file>   write a VCF 4.2 record per SNP site of the index: the genotype, allele depths and\n"
             "                                        likelihoods from the reads' bases and base qualities (summed, called and printed on\n"
             "                                        the GPU); a name ending in .gz is written as BGZF [off]\n"
@@ -994,6 +1052,7 @@ static int open_text_ws(salt_gpu_index_t *gix, uint32_t max_reads, salt_gpu_ws_t
     if (!rc && g_bgzf.device) rc = salt_gpu_ws_set_sam_bgzf(*ws, 1);
     if (!rc && g_bam.device) rc = salt_gpu_ws_set_sam_bam(*ws, 1);
     if (!rc && g_polish) rc = salt_gpu_ws_set_polish(*ws, g_polish);
+    if (!rc && g_trim.device) rc = salt_gpu_ws_set_trim(*ws, &g_trim.opt);
     if (!rc && text_reads && P->head_read_len) rc = salt_gpu_ws_reserve_text(*ws, ao, text_bytes, text_reads, P->head_read_len, P->sam_cap - 64, P->sam_buf[(size_t)wk], P->sam_cap);
     return rc;
 }
@@ -1126,7 +1185,7 @@ int SeWorker::align(uint64_t k, uint64_t beg, uint64_t end, const char **sam, ui
     int grc = call();
     if (grc == SALT_E_CAPACITY && ws_reads < S.P.worst_reads) {                         // shorter records than the file's head promised
         if (getenv("SALT_TEXT_TRACE")) fprintf(stderr, "[salt] worker %d: chunk %llu holds more than %u reads, workspace re-created for %u\n", wk, (unsigned long long)k, ws_reads, S.P.worst_reads);
-        salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = S.P.worst_reads;
+        trim_collect(ws); salt_gpu_ws_destroy(ws); ws = nullptr; ws_reads = S.P.worst_reads;
         grc = open_text_ws(gix(), ws_reads, &ws);
         if (!grc && on_dev) grc = salt_gpu_ws_inflate_bgzf(ws, S.P.in_buf[(size_t)wk], zc.back(), (uint32_t)(zc.size() - 1), zc.data(), zu.data());      // the new workspace's text
         if (!grc) grc = call();
@@ -1176,6 +1235,7 @@ void SeWorker::run()
     }
     if (trace) fprintf(stderr, "[salt] worker %d: started %.3f s after the clock, setup %.3f s, first device call %.3f s, %d later calls %.4f s each, done at %.3f s\n", wk,
                        tw_start - S.t0, t_setup, t_first, n_calls - 1, n_calls > 1 ? t_rest / (n_calls - 1) : 0.0, now() - S.t0);
+    trim_collect(ws);
     salt_gpu_ws_destroy(ws);
 }
 
@@ -1374,6 +1434,7 @@ static int run_pe_text(const char *fn1, const char *fn2, const std::vector<salt_
                 if (!host_twins_add(lines, (size_t)lines_bytes)) { R.fail(); break; }
                 if (!R.write_block(k, sam, sam_bytes, 2 * (long)n_pairs)) break;
             }
+            trim_collect(ws);
             salt_gpu_ws_destroy(ws);
         });
     for (auto &w : workers) w.join();
@@ -1444,7 +1505,9 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "genotype", 1, 0, 1012 }, { "genotype-min-mapq", 1, 0, 1013 }, { "genotype-sample", 1, 0, 1014 },
         { "discover", 1, 0, 1015 }, { "discover-min-mapq", 1, 0, 1016 }, { "discover-min-baseq", 1, 0, 1017 }, { "discover-min-alt", 1, 0, 1018 }, { "discover-min-pct", 1, 0, 1019 },
         { "discover-all", 0, 0, 1020 }, { "stats", 1, 0, 1021 }, { "stats-min-mapq", 1, 0, 1022 },
-        { "indels", 1, 0, 1023 }, { "indels-min-mapq", 1, 0, 1024 }, { "indels-min-alt", 1, 0, 1025 }, { "indels-min-pct", 1, 0, 1026 }, { "indels-slots", 1, 0, 1027 }, { 0, 0, 0, 0 } };
+        { "indels", 1, 0, 1023 }, { "indels-min-mapq", 1, 0, 1024 }, { "indels-min-alt", 1, 0, 1025 }, { "indels-min-pct", 1, 0, 1026 }, { "indels-slots", 1, 0, 1027 },
+        { "trim-adapter", 1, 0, 1028 }, { "trim-adapter2", 1, 0, 1029 }, { "trim-qual", 1, 0, 1030 }, { "trim-front", 1, 0, 1031 }, { "trim-tail", 1, 0, 1032 },
+        { "trim-min-overlap", 1, 0, 1033 }, { "trim-error-pct", 1, 0, 1034 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1515,12 +1578,33 @@ static int parse_options(int argc, char **argv, Opts &o)
             g_indel.log2_slots = lg;
             break;
         }
+        case 1028: case 1029: {
+            const char *name = c == 1028 ? "adapter" : "adapter2";
+            const size_t n = strlen(optarg);
+            if (n < 1 || n > 64 || strspn(optarg, "ACGTacgt") != n) { fprintf(stderr, "[opt_parse]: --trim-%s %s: 1 to 64 letters of ACGT\n", name, optarg); return 1; }
+            if (c == 1028) { g_trim.opt.adapter = optarg; g_trim.opt.adapter_len = (uint32_t)n; } else { g_trim.opt.adapter2 = optarg; g_trim.opt.adapter2_len = (uint32_t)n; }
+            break;
+        }
+        case 1030: case 1031: case 1032: case 1033: case 1034: {
+            static const struct { const char *name; long lo, hi; } F[5] = { { "qual", 1, 93 }, { "front", 0, 511 }, { "tail", 0, 511 }, { "min-overlap", 1, 64 }, { "error-pct", 0, 50 } };
+            char *end = nullptr; errno = 0; const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || errno || v < F[c - 1030].lo || v > F[c - 1030].hi) { fprintf(stderr, "[opt_parse]: --trim-%s %s: a number from %ld to %ld\n", F[c - 1030].name, optarg, F[c - 1030].lo, F[c - 1030].hi); return 1; }
+            (c == 1030 ? g_trim.opt.qual : c == 1031 ? g_trim.opt.front : c == 1032 ? g_trim.opt.tail : c == 1033 ? g_trim.opt.min_overlap : g_trim.opt.error_pct) = (uint32_t)v;
+            if (c == 1033) g_trim.has_overlap = true;
+            if (c == 1034) g_trim.has_error = true;
+            break;
+        }
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
         }
     }
     if (g_polish && g_bam.on) { fprintf(stderr, "[opt_parse]: --polish and --bam cannot be combined: polished records are written as text only (--polish --bgzf compresses them)\n"); return 1; }
+    if (g_trim.opt.adapter2 && !g_trim.opt.adapter) { fprintf(stderr, "[opt_parse]: --trim-adapter2 needs --trim-adapter (the adapter of mate 1; without --trim-adapter2 mate 2 is searched with it too)\n"); return 1; }
+    if ((g_trim.has_overlap || g_trim.has_error) && !g_trim.opt.adapter) { fprintf(stderr, "[opt_parse]: --trim-%s belongs to the adapter search: give --trim-adapter (1 to 64 letters of ACGT)\n", g_trim.has_overlap ? "min-overlap" : "error-pct"); return 1; }
+    if (g_trim.opt.adapter) { if (!g_trim.has_overlap) g_trim.opt.min_overlap = 5; if (!g_trim.has_error) g_trim.opt.error_pct = 10; }
+    g_trim.on = g_trim.opt.adapter || g_trim.opt.qual || g_trim.opt.front || g_trim.opt.tail;
+    g_trim.device = g_trim.on && salt_gpu_ws_set_trim != nullptr && salt_gpu_ws_trim_counts != nullptr && salt_gpu_ws_trim_uncount != nullptr && !(getenv("SALT_TRIM_HOST") && atoi(getenv("SALT_TRIM_HOST")));
     if (optind + 2 + o.pe > argc) { fprintf(stderr, "[opt_parse]: index prefix and read file can't be omited!\n"); return 1; }
     if (o.n_threads < 1) o.n_threads = 1;
     if (o.n_gpus < 1) o.n_gpus = 1;
@@ -1587,7 +1671,7 @@ static bool infer_isize(Opts &o, const salt_index_t *ix, salt_gpu_index_t *gix)
     Batch b1, b2; Pool pool(o.n_threads < 16 ? o.n_threads : 16);
     const int got = r1.take(b1.raw, N_SEQS / 2, b1.rec);
     if (got == 0 || r2.take(b2.raw, got, b2.rec) != got) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); return false; }
-    parse_batch(b1.raw, b1, pool); parse_batch(b2.raw, b2, pool);
+    parse_batch(b1.raw, b1, pool, 0, false); parse_batch(b2.raw, b2, pool, 1, false);
     std::vector<uint8_t> iseq; std::vector<uint32_t> ioff;
     interleave_mates(b1, b2, iseq, ioff);
     gzclose(g1); gzclose(g2);
@@ -1641,8 +1725,9 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
     double t_write = 0, t_read = 0;
     std::thread reader([&]() {
         // (after a hand-over from the text path the head of the file says nothing about what follows: kseq's general reader)
-        RawReader rr(fp, header_out || !sniff_four_line(o.fn_reads));
-        std::unique_ptr<RawReader> rr2(pe ? new RawReader(fp2, header_out || !sniff_four_line(o.fn_mates)) : nullptr);
+        const bool general = header_out || g_trim.instead_of_text_path;
+        RawReader rr(fp, general || !sniff_four_line(o.fn_reads));
+        std::unique_ptr<RawReader> rr2(pe ? new RawReader(fp2, general || !sniff_four_line(o.fn_mates)) : nullptr);
         const int per_batch = pe ? N_SEQS / 2 : N_SEQS;    // pairs per batch: N_SEQS mates (query_read_multiPairedSeqs, query.c:252-268)
         long seq_no = 0;
         for (;;) {
@@ -1694,7 +1779,7 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                 std::vector<uint8_t> iseq; std::vector<uint32_t> ioff;
                 if (pe && b->n()) {                              // interleave the mates: pair i = reads 2i, 2i+1
                     Batch &m = *b->mate;
-                    parse_batch(m.raw, m, pool);
+                    parse_batch(m.raw, m, pool, 1);
                     if (m.n() != b->n()) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); set_failed(); break; }
                     interleave_mates(*b, m, iseq, ioff);
                 }
@@ -2245,6 +2330,10 @@ int main(int argc, char **argv)
         // single end, blocked gzip (BGZF) whose text starts as strict 4-line FASTQ: the text path over the uncompressed byte range
         if (!text_path && !pe && bgzf_index(o.fn_reads, plan.bgzf) && sniff_four_line(o.fn_reads)) text_path = true;
         else if (!text_path) plan.bgzf = Bgzf();
+        if (text_path && g_trim.on && !g_trim.device) {      // no k_fq_trim in this libsalt_gpu: the host parser trims, so the host pipeline reads
+            fprintf(stderr, "[salt] trim: this libsalt_gpu does not trim on the device: the whole run goes through the host pipeline\n");
+            text_path = false; plan.bgzf = Bgzf(); g_trim.instead_of_text_path = true;
+        }
         if (text_path) text_plan(plan, o.fn_reads, n_gpus, o.n_threads, pe);
     }
     const double t0 = now();
@@ -2267,7 +2356,7 @@ int main(int argc, char **argv)
             if (salt_gpu_index_set_pac(gix[(size_t)i], pac, l_pac)) { fprintf(stderr, "[salt] %s\n", salt_gpu_last_error()); return 1; }
     }
     const Contigs contigs(ix);
-    auto leave = [&](int rc) { for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
+    auto leave = [&](int rc) { if (rc == 0) trim_report(); for (int i = n_gpus - 1; i >= 0; --i) salt_gpu_index_detach(gix[(size_t)i]); salt_index_free(ix); return rc; };
     if (pe && o.po.max_tlen == 0 && !infer_isize(o, ix, gix[0])) return 1;
     if (!snp_begin(ix, gix) || !depth_begin(ix, gix) || !errprof_begin(ix, gix) || !gt_begin(ix, gix) || !disc_begin(ix, gix) || !stats_begin(ix, gix, contigs) || !indel_begin(ix, gix, contigs)) return 1;                          // (behind infer_isize: its single-end pass over the first batch is not the run's)
     bool header_out = false; uint64_t resume[2] = { 0, 0 };      // set when the text path hands the rest of the input to the host pipeline
