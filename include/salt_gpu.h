@@ -749,6 +749,18 @@ int  salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t 
  *   [10], [11] 0 */
 int  salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t n, const uint32_t *queries, uint32_t *out);
 
+/* Unit entry of k_pack (tests): the launch the align and text entries make, on the caller's device buffers; it needs no index.  d_seqs:
+ * the reads' codes (0..3, 4 = N, above 4 read as N), at any byte alignment; d_offs: n_reads + 1 uint32 offsets into d_seqs.  With
+ * nw8 = ceil(max_read_len / 8), nw16 = ceil(/ 16), nw32 = ceil(/ 32), read r gets
+ *   d_pm[r * pm_stride ..], pm_stride = (2 nw8 + 1) rounded up to 4 words: one-hot nibble words, LSB first, N = 15, no base = 0:
+ *       [0, nw8) forward, [nw8, 2 nw8) reverse complement, [2 nw8] = L (the read's length, at most 8 nw8: longer reads are truncated);
+ *   d_tb[r * tb_stride ..], tb_stride = (2 nw16 + 2 nw32 + 1) rounded up to 4 words: 2-bit codes, first base in the high bits, N read as
+ *       0: [0, nw16) forward, [nw16, 2 nw16) reverse complement; 'is N' flags, first base highest: [2 nw16, + nw32) forward, then nw32
+ *       words reverse; then L.
+ * Words between a record's L word and its stride are not written.  The launch is queued on hip_stream and not waited for. */
+int  salt_gpu_diag_pack(int device, uint32_t n_reads, uint32_t max_read_len, const void *d_seqs, const void *d_offs,
+                        void *d_pm, void *d_tb, void *hip_stream);
+
 /* Unit entry of the text stage (tests): the FASTQ scan, k_pack's records and k_sam_len / k_sam_write or k_bam_len / k_bam_write, on result rows
  * of the caller's choosing.  It runs the stages of salt_gpu_align_se_text (pe == NULL: one block, fastq2 ignored) or salt_gpu_align_pe_text
  * (pe given: two blocks, row 2p + m belongs to mate m of pair p) through the same two functions -- the parse stage and the output stage --

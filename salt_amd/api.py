@@ -150,6 +150,7 @@ def gpu_lib():
         lib.salt_gpu_diag_verify.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         lib.salt_gpu_diag_occ.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.salt_gpu_diag_pack.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 5
         assert lib.salt_gpu_result_size() == RESULT_DTYPE.itemsize
         _gpu = lib
     return _gpu
@@ -996,6 +997,33 @@ class _TextOpt(ctypes.Structure):
 
 
 KERNELS = ("k_pack", "k_seed", "k_light", "k_heavy", "k_gap", "k_gapfin", "k_cigar", "k_pair", "k_sw", "k_pe_final")
+
+PACK_FILL = 0x5A5A5A5A      # what diag_pack's buffers hold where k_pack wrote nothing
+
+
+def pack_geom(max_read_len):
+    """PackGeom::make (salt_kernels.h): the word counts and strides of k_pack's records for reads of up to max_read_len bases."""
+    m = max(1, int(max_read_len))
+    nw8, nw16, nw32 = (m + 7) // 8, (m + 15) // 16, (m + 31) // 32
+    return {"nw8": nw8, "nw16": nw16, "nw32": nw32, "pm_stride": (2 * nw8 + 1 + 3) & ~3, "tb_stride": (2 * nw16 + 2 * nw32 + 1 + 3) & ~3}
+
+
+def diag_pack(n_reads, max_read_len, d_seqs, d_offs, byte_offset=0, stream=0):
+    """k_pack alone (salt_gpu_diag_pack) on torch tensors of one GPU: the reads' uint8 codes start byte_offset bytes into d_seqs, d_offs
+    n_reads + 1 int32 offsets from there -> (pack_geom(max_read_len), pm (n_reads, pm_stride), tb (n_reads, tb_stride)) as int64 numpy
+    arrays of the uint32 words; words the kernel did not write hold PACK_FILL."""
+    import torch
+    lib = gpu_lib()
+    g = pack_geom(max_read_len)
+    dev = d_seqs.device
+    fill = PACK_FILL - (1 << 32) if PACK_FILL >= 1 << 31 else PACK_FILL
+    pm = torch.full((max(n_reads, 1), g["pm_stride"]), fill, dtype=torch.int32, device=dev)
+    tb = torch.full((max(n_reads, 1), g["tb_stride"]), fill, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    _gpu_check(lib.salt_gpu_diag_pack(dev.index or 0, n_reads, max_read_len, d_seqs.data_ptr() + byte_offset, d_offs.data_ptr(), pm.data_ptr(), tb.data_ptr(), stream))
+    torch.cuda.synchronize(dev)
+    u = lambda t: t[:n_reads].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    return g, u(pm), u(tb)
 
 
 class GpuAligner:

@@ -79,142 +79,160 @@ __device__ __forceinline__ uint32_t read_base(const uint8_t *seq, uint32_t L, in
 
 // ---------------------------------------------------------------------------------------------
 // k_pack: the batch's reads in the two packed, fixed-stride forms the other kernels gather from (PackGeom,
-// salt_kernels.h).  A block of 256 threads takes 256 / (2*nw32) consecutive reads: their bytes are staged in LDS
-// as both strands (coalesced loads; query_seq_reverse / nst_nt4_table semantics, codes > 4 read as N,
-// query.c:46-71,177-183), then one thread per (read, strand, 32 bases) packs with shift-and-mask steps only.
+// salt_kernels.h).  A block is nw32 x rpb threads (rpb = 256 / nw32, at most 64): thread (j, rr) owns bases 32 j .. 32 j + 31 of
+// BOTH strands of read r0 + rr, so the mapping needs no division.  Three steps, each between two barriers:
+//   1. stage: the read's bytes come from global memory as aligned 16-byte units, a row of LDS per read that keeps the read's
+//      byte offset inside its first unit.  On the way every byte is folded to a nibble: codes 0 .. 3 stay, anything above has
+//      bit 2 or bit 3 set (N; nst_nt4_table's "codes > 4 read as N", query.c:177-183).
+//   2. pack: one body for both strands.  A chunk is nine aligned LDS words and eight v_perm_b32, which take the 32 bases from any
+//      byte offset and, for strand 1, from the read's other end with the bytes of a word reversed (query_seq_reverse,
+//      query.c:46-71); the complement is one XOR on the code bits, N keeps its flag bits.  From there both strands run the same
+//      shift-and-mask steps under the same "base exists" masks (base i of either strand exists when i < L).
+//   3. store: the words go to an image of the block's records in LDS (over the staged bytes) and leave as 16-byte stores; a
+//      record's last unit is written word by word up to its L word, so the words behind it stay untouched.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t pk_nibbles(uint32_t x)        // 4 bytes (low nibbles) -> 16 bits, byte 0 lowest
+// words of a read's row of staged bytes: 32 bytes in front (strand 1 of a short read starts before the read), the units of
+// 8 nw8 bytes at any offset in the first unit; odd, so that the rows of neighbouring reads start on different LDS banks
+__host__ __device__ __forceinline__ uint32_t pack_row_words(const PackGeom &pg) { return (8u + 4u * ((8u * pg.nw8 + 30u) >> 4)) | 1u; }
+__host__ __device__ __forceinline__ uint32_t pack_reads_per_block(const PackGeom &pg) { return 256u / pg.nw32 < 64u ? 256u / pg.nw32 : 64u; }
+// CORRECTNESS RESTS ON THE MASKS V (pack_chunk): step 2 reads LDS that step 1 never wrote -- the 32 bytes in front of a row, the
+// units behind a read's last one, and the ninth word of a row's last chunk, which lies in the next row (or in the 16 spare
+// words behind the last row).  Every such byte stands at a base place i >= L of its strand, and places without a base follow
+// the places with one in both strands, so a stray high nibble can only spill into another masked place (e0 / e1 in pack_chunk).
+// Whoever changes V, the chunk size or the row layout has to keep that true.
+// LDS words of a block: the staged rows (+ 16: the ninth word of a chunk that starts in a row's last unit) or the image of the
+// records; at most 16 384 bytes (121 .. 128 bases: 64 reads x (36 + 28) words), so eight blocks a CU take 133 of the 160 KB
+__host__ __device__ __forceinline__ uint32_t pack_lds_words(const PackGeom &pg)
 {
-    uint32_t t = x & 0x0F0F0F0Fu;
-    t = (t | (t >> 4)) & 0x00FF00FFu;
-    return (t | (t >> 8)) & 0xFFFFu;
+    const uint32_t rpb = pack_reads_per_block(pg), a = rpb * pack_row_words(pg) + 16u, b = rpb * (pg.pm_stride + pg.tb_stride);
+    return a > b ? a : b;
 }
+__device__ __forceinline__ uint32_t pk_fold(uint32_t x) { return (x | (x >> 2) | (x >> 4)) & 0x0F0F0F0Fu; }   // byte -> nibble: code, or bit 2 / 3 set
 
-// Phase 1: one thread per (read, 32 forward bases): the bytes come straight from global memory as aligned dwords (never
-// past the ends of seqs[]), are clamped (codes > 4 read as N) and packed with shift-and-mask steps; the forward words go to
-// global memory and to LDS.  Phase 2: one thread per reverse-strand word, derived from the forward WORDS: reversing a
-// read reverses its bit string, complementing a base reverses the bits of its one-hot nibble / inverts its 2-bit code.
-struct PackWords { uint32_t pm[64], tb[32], nm[16]; };               // forward words of one read (up to 512 bases)
+// the words of one strand's 32 bases: 4 one-hot words, 2 words of 2-bit codes, 1 word of N flags
+struct PackChunk { uint32_t pm[4], t2[2], nf; };
+
+// w[0 .. 8]: the aligned LDS words around the chunk's 32 bytes, sh: the first byte's place in w[0]; REV: the bytes are the strand's
+// bases from the last to the first, to be complemented.  V[h]: 15 in every nibble of one-hot word h whose base exists.
+template <bool REV>
+__device__ __forceinline__ PackChunk pack_chunk(const uint32_t (&w)[9], uint32_t sh, const uint32_t (&V)[4])
+{
+    const uint32_t sel = (REV ? 0x00010203u : 0x03020100u) + sh * 0x01010101u, one = 0x11111111u;
+    PackChunk c;
+    uint32_t p16[4], nb = 0;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        // bases 8 h .. 8 h + 7 of the chunk as two words of four folded bytes, first base lowest
+        const uint32_t d0 = REV ? __builtin_amdgcn_perm(w[8 - 2 * h], w[7 - 2 * h], sel) : __builtin_amdgcn_perm(w[2 * h + 1], w[2 * h], sel);
+        const uint32_t d1 = REV ? __builtin_amdgcn_perm(w[7 - 2 * h], w[6 - 2 * h], sel) : __builtin_amdgcn_perm(w[2 * h + 2], w[2 * h + 1], sel);
+        const uint32_t e0 = d0 | (d0 >> 4), e1 = d1 | (d1 >> 4);                               // bytes 0 and 2: two nibbles each
+        uint32_t n8 = __builtin_amdgcn_perm(e1, e0, 0x06040200u);                              // base q of the word in nibble q
+        if (REV) n8 ^= 0x33333333u;                                                            // A <-> T, C <-> G; N keeps bit 2 / 3
+        n8 &= V[h];
+        const uint32_t isn = ((n8 >> 2) | (n8 >> 3)) & one, n3 = isn | (isn << 1), n15 = n3 | (n3 << 2);    // shifts: a multiply by 15 issues at a quarter of the rate
+        const uint32_t a = n8 & one, b = (n8 >> 1) & one, p = a + one, bm = b | (b << 1), t = p & bm;   // p: 1 << (code & 1)
+        c.pm[h] = (((p ^ t) | (t << 2)) | n15) & V[h];                                         // 1 << code; N -> 15, no base -> 0 (nt2bit, editdistance.c:40)
+        uint32_t q = n8 & 0x33333333u & ~n15;                                                  // 2-bit codes (N and 'no base' read 0)
+        q = (q | (q >> 2)) & 0x0F0F0F0Fu; p16[h] = q | (q >> 4);                               // bytes 0 and 2: four codes each
+        uint32_t u = isn;
+        u = (u | (u >> 3)) & 0x03030303u; u = (u | (u >> 6)) & 0x000F000Fu; u = (u | (u >> 12)) & 0xFFu;
+        nb |= u << (8 * h);
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const uint32_t rv = __brev(__builtin_amdgcn_perm(p16[2 * g + 1], p16[2 * g], 0x06040200u));   // first base highest; then put each pair back in order
+        c.t2[g] = ((rv & 0x55555555u) << 1) | ((rv >> 1) & 0x55555555u);
+    }
+    c.nf = __brev(nb);
+    return c;
+}
 
 __global__ void __launch_bounds__(256)
 k_pack(PackGeom pg, uint32_t n_reads, const uint8_t *__restrict__ seqs, const uint32_t *__restrict__ offs,
        uint32_t *__restrict__ pm, uint32_t *__restrict__ tb)
 {
-    extern __shared__ uint32_t pk_lds[];                                    // [rpb][nw8 + nw16 + nw32] forward words
+    extern __shared__ uint4 pk_lds4[];                                      // pack_lds_words(pg) words
+    uint32_t *const lds = reinterpret_cast<uint32_t *>(pk_lds4);
     __shared__ uint32_t so[65];
-    const uint32_t tpr = pg.nw32, rpb = 256 / tpr < 64 ? 256 / tpr : 64;   // threads per read in phase 1, reads per block
-    const uint32_t wpr = pg.nw8 + pg.nw16 + pg.nw32;                       // forward words per read
+    const uint32_t tpr = blockDim.x, rpb = blockDim.y, j = threadIdx.x, rr = threadIdx.y;      // threads per read (nw32), reads per block
     const uint32_t r0 = blockIdx.x * rpb, nr = n_reads - r0 < rpb ? n_reads - r0 : rpb;
-    if (threadIdx.x <= nr) so[threadIdx.x] = offs[r0 + threadIdx.x];
-    __syncthreads();
-    const uint32_t cap = 8 * pg.nw8;                                        // bases the records hold per strand
+    {   // nr + 1 <= 65 offsets; a block has at least 64 threads
+        const uint32_t t = __umul24(rr, tpr) + j, nt = __umul24(tpr, rpb);
+        if (t <= nr) so[t] = offs[r0 + t];
+        if (t + nt <= nr) so[t + nt] = offs[r0 + t + nt];
+    }
+    const uint32_t cap = 8 * pg.nw8, rw = pack_row_words(pg);               // bases the records hold per strand
     const uint64_t total_bases = offs[n_reads];                             // end of the valid bytes of seqs[]
-    {
-        const uint32_t rr = threadIdx.x / tpr, j = threadIdx.x - rr * tpr;
-        if (rr < nr) {
-            uint32_t L = so[rr + 1] - so[rr];
-            if (L > cap) L = cap;                                           // longer than max_read_len says: truncated, never out of bounds
-            // 32 bytes from seqs + so[rr] + 32 j as 9 aligned dwords; dwords outside [seqs, seqs + total_bases) read as 0
-            const uintptr_t a0 = (uintptr_t)seqs + so[rr] + 32u * j, lo = (uintptr_t)seqs & ~(uintptr_t)3, hi = (uintptr_t)seqs + total_bases;
-            const uintptr_t ab = a0 & ~(uintptr_t)3;
-            const uint32_t sh = (uint32_t)(a0 & 3u) * 8u;
-            uint32_t wv[9];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) { const uintptr_t ad = ab + 4u * t; wv[t] = (ad >= lo && ad < hi) ? *reinterpret_cast<const uint32_t *>(ad) : 0u; }
-            uint32_t d[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                uint32_t x = __funnelshift_r(wv[t], wv[t + 1], sh);
-                const uint32_t big = ((((x & 0x7F7F7F7Fu) + 0x7B7B7B7Bu) | x) & 0x80808080u) >> 7;   // 1 in every byte >= 5
-                const uint32_t mb = big * 0xFFu;
-                x = (x & ~mb) | (0x04040404u & mb);                                            // codes > 4 read as N
-                const int nv = (int)L - (int)(32u * j + 4u * t);                               // bases of the read in this dword
-                const uint32_t vm = nv >= 4 ? 0xFFFFFFFFu : nv <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - nv)));
-                d[t] = (x & vm) | (0x08080808u & ~vm);                                         // 8 = no base
-            }
-            uint32_t *pmr = pm + (uint64_t)(r0 + rr) * pg.pm_stride, *tbr = tb + (uint64_t)(r0 + rr) * pg.tb_stride;
-            uint32_t *fw = pk_lds + (size_t)rr * wpr;
-            uint32_t p16[4], nb = 0;
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const uint32_t n8 = pk_nibbles(d[2 * h]) | (pk_nibbles(d[2 * h + 1]) << 16);     // base q of the chunk in nibble q
-                const uint32_t one = 0x11111111u;
-                const uint32_t aa = n8 & one, bb = (n8 >> 1) & one, isn = (n8 >> 2) & one, valid = ~(n8 >> 3) & one;
-                const uint32_t na = aa ^ one, nb_ = bb ^ one;
-                uint32_t oh = (na & nb_) | ((aa & nb_) << 1) | ((na & bb) << 2) | ((aa & bb) << 3);  // 1 << code
-                oh = (oh | isn * 15u) & (valid * 15u);                                          // N -> 15, no base -> 0 (nt2bit, editdistance.c:40)
-                if (4 * j + h < pg.nw8) { pmr[4 * j + h] = oh; fw[4 * j + h] = oh; }
-                uint32_t t = n8 & 0x33333333u;                                                  // 2-bit codes (N and 'no base' read 0)
-                t = (t | (t >> 2)) & 0x0F0F0F0Fu; t = (t | (t >> 4)) & 0x00FF00FFu; p16[h] = (t | (t >> 8)) & 0xFFFFu;
-                uint32_t u = isn;
-                u = (u | (u >> 3)) & 0x03030303u; u = (u | (u >> 6)) & 0x000F000Fu; u = (u | (u >> 12)) & 0xFFu;
-                nb |= u << (8 * h);
-            }
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                const uint32_t rv = __brev(p16[2 * g] | (p16[2 * g + 1] << 16));               // first base highest; then put each pair back in order
-                const uint32_t wd = ((rv & 0x55555555u) << 1) | ((rv >> 1) & 0x55555555u);
-                if (2 * j + g < pg.nw16) { tbr[2 * j + g] = wd; fw[pg.nw8 + 2 * j + g] = wd; }
-            }
-            const uint32_t nmw = __brev(nb);
-            tbr[2 * pg.nw16 + j] = nmw; fw[pg.nw8 + pg.nw16 + j] = nmw;
-            if (j == 0) { pmr[2 * pg.nw8] = L; tbr[2 * pg.nw16 + 2 * pg.nw32] = L; }
+    __syncthreads();
+    const bool live = rr < nr;
+    uint32_t L = 0, mis = 0;
+    // ---- 1. the read's bytes as aligned 16-byte units, folded, into its row ----
+    if (live) {
+        L = so[rr + 1] - so[rr];
+        if (L > cap) L = cap;                                               // longer than max_read_len says: truncated, never out of bounds
+        const uintptr_t a = (uintptr_t)seqs + so[rr], lo = (uintptr_t)seqs, hi = (uintptr_t)seqs + total_bases;
+        mis = (uint32_t)(a & 15u);
+        // Only units that hold a byte of the read are asked for, and of those only units that overlap [seqs, seqs + total_bases): an
+        // aligned 16-byte unit that overlaps the valid bytes lies inside their allocation granule, so the bytes of it that are not
+        // ours can be read; they are never used (the masks V below).  A unit wholly outside reads as 0.
+        const uint32_t nu = L ? (mis + L + 15u) >> 4 : 0u;
+        uint32_t *row = lds + __umul24(rr, rw) + 8u;
+        for (uint32_t u = j; u < nu; u += tpr) {
+            const uintptr_t ad = a - mis + 16u * u;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (ad + 16u > lo && ad < hi) v = *reinterpret_cast<const uint4 *>(ad);
+            row[4 * u] = pk_fold(v.x); row[4 * u + 1] = pk_fold(v.y); row[4 * u + 2] = pk_fold(v.z); row[4 * u + 3] = pk_fold(v.w);
         }
     }
     __syncthreads();
-    // ---- phase 2: the reverse-complement strand, word by word, from the forward words ----
-    for (uint32_t t = threadIdx.x; t < nr * wpr; t += 256) {
-        const uint32_t rr = t / wpr, wi = t - rr * wpr;
-        uint32_t L = so[rr + 1] - so[rr];
-        if (L > cap) L = cap;
-        const uint32_t *fw = pk_lds + (size_t)rr * wpr;
+    // ---- 2. both strands of bases 32 j .. 32 j + 31 ----
+    PackChunk fw, rv;
+    if (live) {
+        uint32_t V[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int nv = (int)L - (int)(32u * j + 8u * h);                                   // bases of either strand in one-hot word 4 j + h
+            const uint32_t s = 16u - 2u * (uint32_t)(nv < 0 ? 0 : nv > 8 ? 8 : nv);
+            V[h] = (0xFFFFFFFFu >> s) >> s;
+        }
+        const uint32_t *row = lds + __umul24(rr, rw);
+        uint32_t w[9];
+        {   // strand 0: the bytes from 32 j on
+            const uint32_t at = 32u + mis + 32u * j;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) w[k] = row[(at >> 2) + k];
+            fw = pack_chunk<false>(w, at & 3u, V);
+        }
+        {   // strand 1: the 32 bytes that end at base L - 1 - 32 j (a chunk that starts before the read begins in the 32 bytes in front of it)
+            const int p0 = (int)L - 32 - 32 * (int)j;
+            const uint32_t at = 32u + mis + (uint32_t)(p0 < -32 ? -32 : p0);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) w[k] = row[(at >> 2) + k];
+            rv = pack_chunk<true>(w, at & 3u, V);
+        }
+    }
+    __syncthreads();
+    // ---- 3. the block's records as an image in LDS, then out in 16-byte units ----
+    uint32_t *const ipm = lds + __umul24(rr, pg.pm_stride), *const itb = lds + rpb * pg.pm_stride + __umul24(rr, pg.tb_stride);
+    if (live) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) if (4 * j + h < pg.nw8) { ipm[4 * j + h] = fw.pm[h]; ipm[pg.nw8 + 4 * j + h] = rv.pm[h]; }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) if (2 * j + g < pg.nw16) { itb[2 * j + g] = fw.t2[g]; itb[pg.nw16 + 2 * j + g] = rv.t2[g]; }
+        itb[2 * pg.nw16 + j] = fw.nf; itb[2 * pg.nw16 + pg.nw32 + j] = rv.nf;
+        if (j == 0) { ipm[2 * pg.nw8] = L; itb[2 * pg.nw16 + 2 * pg.nw32] = L; }
+    }
+    __syncthreads();
+    if (live) {
         uint32_t *pmr = pm + (uint64_t)(r0 + rr) * pg.pm_stride, *tbr = tb + (uint64_t)(r0 + rr) * pg.tb_stride;
-        if (wi < pg.nw8) {
-            // nibbles 8k .. 8k+7 of the reverse strand = forward nibbles L-1-8k down to L-8-8k, each bit-reversed:
-            // take forward nibbles a .. a+7 (a = L-8-8k; nibbles before the read are zero) and reverse all 32 bits
-            const uint32_t k = wi;
-            const int a = (int)L - 8 - 8 * (int)k;
-            uint32_t x = 0;
-            if (a > -8) {
-                if (a >= 0) { const uint32_t j0 = (uint32_t)a >> 3; x = __funnelshift_r(fw[j0], j0 + 1 < pg.nw8 ? fw[j0 + 1] : 0u, 4u * ((uint32_t)a & 7u)); }
-                else x = fw[0] << (4 * -a);
-            }
-            pmr[pg.nw8 + k] = __brev(x);
-        } else if (wi < pg.nw8 + pg.nw16) {
-            // 16 bases of the reverse strand (first base highest) = forward bases a+15 down to a (a = L-16-16k), complemented; N -> 0
-            const uint32_t k = wi - pg.nw8;
-            const int a = (int)L - 16 - 16 * (int)k;
-            const uint32_t *f2 = fw + pg.nw8, *fn = fw + pg.nw8 + pg.nw16;
-            uint32_t y = 0, z = 0;                                          // y: forward bases a..a+15 (a at the top), z: their N flags (a at bit 15)
-            if (a > -16) {
-                if (a >= 0) {
-                    const uint32_t j0 = (uint32_t)a >> 4, s2 = 2u * ((uint32_t)a & 15u);
-                    const uint32_t w0 = f2[j0], w1 = j0 + 1 < pg.nw16 ? f2[j0 + 1] : 0u;
-                    y = s2 ? (w0 << s2) | (w1 >> (32 - s2)) : w0;
-                    const uint32_t n0 = (uint32_t)a >> 5, s1 = (uint32_t)a & 31u;
-                    const uint32_t m0 = fn[n0], m1 = n0 + 1 < pg.nw32 ? fn[n0 + 1] : 0u;
-                    z = (s1 ? (m0 << s1) | (m1 >> (32 - s1)) : m0) >> 16;
-                } else { y = f2[0] >> (2 * -a); z = (fn[0] >> 16) >> (-a); }
-            }
-            const uint32_t ry = __brev(y);                                  // base a+15 first, bits inside every pair swapped
-            uint32_t rev = ~(((ry & 0x55555555u) << 1) | ((ry >> 1) & 0x55555555u));            // pairs back in order, complemented
-            uint32_t zz = __brev(z) >> 16;                                  // N flag of base a+15 at bit 15 ... base a at bit 0
-            zz = (zz | (zz << 8)) & 0x00FF00FFu; zz = (zz | (zz << 4)) & 0x0F0F0F0Fu;           // spread every flag to a pair of bits
-            zz = (zz | (zz << 2)) & 0x33333333u; zz = (zz | (zz << 1)) & 0x55555555u; zz |= zz << 1;
-            const int nv = (int)L - 16 * (int)k;                            // bases of the reverse strand in this word
-            const uint32_t vm = nv >= 16 ? 0xFFFFFFFFu : nv <= 0 ? 0u : ~(0xFFFFFFFFu >> (2 * nv));
-            tbr[pg.nw16 + k] = rev & ~zz & vm;
-        } else {
-            // 32 N flags of the reverse strand (first base highest) = forward flags a+31 down to a (a = L-32-32k)
-            const uint32_t k = wi - pg.nw8 - pg.nw16;
-            const int a = (int)L - 32 - 32 * (int)k;
-            const uint32_t *fn = fw + pg.nw8 + pg.nw16;
-            uint32_t y = 0;
-            if (a > -32) {
-                if (a >= 0) { const uint32_t n0 = (uint32_t)a >> 5, s1 = (uint32_t)a & 31u; const uint32_t m0 = fn[n0], m1 = n0 + 1 < pg.nw32 ? fn[n0 + 1] : 0u; y = s1 ? (m0 << s1) | (m1 >> (32 - s1)) : m0; }
-                else y = fn[0] >> (-a);
-            }
-            tbr[2 * pg.nw16 + pg.nw32 + k] = __brev(y);
+        const uint32_t npm = 2 * pg.nw8 + 1, ntb = 2 * pg.nw16 + 2 * pg.nw32 + 1;            // defined words of a record
+        for (uint32_t u = 4 * j; u < npm; u += 4 * tpr) {
+            if (u + 4 <= npm) *reinterpret_cast<uint4 *>(pmr + u) = *reinterpret_cast<const uint4 *>(ipm + u);
+            else for (uint32_t k = u; k < npm; ++k) pmr[k] = ipm[k];
+        }
+        for (uint32_t u = 4 * j; u < ntb; u += 4 * tpr) {
+            if (u + 4 <= ntb) *reinterpret_cast<uint4 *>(tbr + u) = *reinterpret_cast<const uint4 *>(itb + u);
+            else for (uint32_t k = u; k < ntb; ++k) tbr[k] = itb[k];
         }
     }
 }
@@ -222,9 +240,8 @@ k_pack(PackGeom pg, uint32_t n_reads, const uint8_t *__restrict__ seqs, const ui
 void launch_pack(const PackGeom &pg, uint32_t n_reads, const uint8_t *seqs, const uint32_t *offs, uint32_t *pm, uint32_t *tb, hipStream_t st)
 {
     if (!n_reads) return;
-    const uint32_t rpb = 256 / pg.nw32 < 64 ? 256 / pg.nw32 : 64;
-    const uint32_t lds = rpb * (pg.nw8 + pg.nw16 + pg.nw32) * 4u;
-    hipLaunchKernelGGL(k_pack, dim3((n_reads + rpb - 1) / rpb), dim3(256), lds, st, pg, n_reads, seqs, offs, pm, tb);
+    const uint32_t rpb = pack_reads_per_block(pg);
+    hipLaunchKernelGGL(k_pack, dim3((n_reads + rpb - 1) / rpb), dim3(pg.nw32, rpb), pack_lds_words(pg) * 4u, st, pg, n_reads, seqs, offs, pm, tb);
 }
 
 // ---------------------------------------------------------------------------------------------

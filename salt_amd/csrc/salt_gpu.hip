@@ -1973,6 +1973,20 @@ extern "C" int salt_gpu_diag_occ(const salt_gpu_index_t *ix, int mode, uint32_t 
     return done(SALT_OK);
 }
 
+// Unit entry of k_pack (tests): the production launch on the caller's device buffers, no index and no workspace: see include/salt_gpu.h
+extern "C" int salt_gpu_diag_pack(int device, uint32_t n_reads, uint32_t max_read_len, const void *d_seqs, const void *d_offs,
+                                  void *d_pm, void *d_tb, void *hip_stream)
+{
+    if (!d_seqs || !d_offs || !d_pm || !d_tb) return fail(SALT_E_INVAL, "null argument");
+    if (max_read_len > SALT_MAX_READ_LEN) return fail(SALT_E_INVAL, "max_read_len above " + std::to_string(SALT_MAX_READ_LEN));      // 0 reads as 1 (PackGeom::make)
+    if (n_reads == 0) return SALT_OK;
+    HIPCHK(hipSetDevice(device));
+    launch_pack(PackGeom::make(max_read_len), n_reads, static_cast<const uint8_t *>(d_seqs), static_cast<const uint32_t *>(d_offs),
+                static_cast<uint32_t *>(d_pm), static_cast<uint32_t *>(d_tb), static_cast<hipStream_t>(hip_stream));
+    HIPCHK(hipGetLastError());
+    return SALT_OK;
+}
+
 // Unit entry of the candidate verifiers on a caller-supplied mixRef (see k_diag_verify): fault-free check of the guards that keep a
 // wrapped locate from being used as an address.
 extern "C" int salt_gpu_diag_verify(const uint32_t *ref_words, uint32_t ref_len, uint32_t n_cases, const uint8_t *seqs, const uint32_t *offs,
