@@ -659,6 +659,26 @@ int  salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *opt);
 int  salt_gpu_ws_trim_counts(salt_gpu_ws_t *ws, uint64_t out[16], int reset);
 int  salt_gpu_ws_trim_uncount(salt_gpu_ws_t *ws);
 int  salt_gpu_trim_spans(salt_gpu_ws_t *ws, const char *fastq, uint64_t n_bytes, int mate, uint32_t *beg_end);
+/* The pair rule (`salt --trim-pair-overlap`): after salt_gpu_ws_set_trim_pair(ws, &opt) salt_gpu_align_pe_text finds each
+ * pair's adapters from the mates' overlap, as step 2p between steps 2 and 3 above (k_fq_trim_pair, a wave a pair, in k_fq_trim's place).  It
+ * works with or without salt_gpu_ws_set_trim; the single-end entry points ignore it.  All positions are in the untrimmed reads of L1 and L2
+ * letters; [b1, e1) and [b2, e2) are what steps 1 and 2 left:
+ *   2p. for a candidate insert length I >= 1, column j of mate 1 faces letter I - 1 - j of mate 2, complemented.  Compared are the columns
+ *       max(b1, I - e2) <= j < min(e1, I - b2): ov(I) of them, mm(I) of those where the two letters are no complementary pair (case ignored,
+ *       a letter outside ACGTacgt on either side always differs).  I is accepted when ov >= min_overlap (1 .. 512) and
+ *       100 mm <= error_pct ov (0 .. 50).  The LARGEST accepted I in 1 .. e1 + e2 - min_overlap wins: e1 = min(e1, I), e2 = min(e2, I).
+ *       A pair with a mate longer than SALT_MAX_READ_LEN skips the step.  Mates are not merged and no base is corrected.
+ * A null pointer or an all-zero struct switches the rule off, and the call launches what it launches today; a value out of range:
+ * SALT_E_INVAL, the field named.  Pair counters, uint64 out[8]: 0 pairs, 1 pairs with an accepted layout, 2 pairs in which a mate was
+ * shortened, 3 mate-1 reads shortened, 4 bases taken from mate 1, 5 mate-2 reads shortened, 6 bases taken from mate 2, 7 pairs that skipped the
+ * step for a mate's length.  The sixteen above keep their meaning: 5 and 6 count what step 3 took from what step 2p left, 2 is the final span.
+ * The pair counters travel and add up with the sixteen, and salt_gpu_ws_trim_uncount takes both back.
+ * salt_gpu_trim_pair_spans: the parser and k_fq_trim_pair alone on two blocks (at most max_reads records together): beg_end[4 p ..] =
+ * b1, e1, b2, e2 of pair p.  The blocks' counters of both kinds are added too. */
+typedef struct salt_trim_pair_opt { uint32_t min_overlap, error_pct; } salt_trim_pair_opt_t;
+int  salt_gpu_ws_set_trim_pair(salt_gpu_ws_t *ws, const salt_trim_pair_opt_t *opt);
+int  salt_gpu_ws_trim_pair_counts(salt_gpu_ws_t *ws, uint64_t out[8], int reset);
+int  salt_gpu_trim_pair_spans(salt_gpu_ws_t *ws, const char *fastq1, uint64_t n1, const char *fastq2, uint64_t n2, uint32_t *beg_end);
 /* The same kernels on their own, host buffers in and out: text[0 .. n_bytes) -> ceil(n_bytes / 32640) BGZF blocks in out, *out_bytes of them
  * (0 for an empty text; no end-of-file block).  The same text gives the same bytes on every run.  SALT_E_CAPACITY when out_cap is too
  * small: n_bytes + 31 bytes per block is the exact bound, 65 536 bytes per block always suffice. */

@@ -322,6 +322,15 @@ int salt_isize_infer(const salt_index_t *ix, uint32_t n_pairs, const uint32_t *o
  * 4-line FASTQ. */
 int     salt_trim_span(const salt_trim_opt_t *opt, int mate, const char *seq, const char *qual, uint32_t len, uint32_t *beg, uint32_t *end, uint64_t *counts);
 int64_t salt_trim_fastq(const salt_trim_opt_t *opt, int mate, const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *counts);
+/* The pair forms (`salt --trim-pair-overlap`; salt_gpu.h states step 2p): the host twins of k_fq_trim_pair, compiled from the header's
+ * one-thread trim_pair_span.  opt and pair: NULL or all zero = that part of the rule is off.
+ *   salt_trim_pair_span    one pair -> span[4] = b1, e1, b2, e2; counts: NULL or uint64[16]; pair_counts: NULL or uint64[8].  Returns 0.
+ *   salt_trim_fastq_pair   two blocks of whole 4-line FASTQ records, as many in each -> the two trimmed blocks (as salt_trim_fastq writes
+ *                          them); *w1 and *w2 = their bytes, written when out1 / out2 hold them (never more than n1 / n2).  Returns 0. */
+int salt_trim_pair_span(const salt_trim_opt_t *opt, const salt_trim_pair_opt_t *pair, const char *seq1, const char *qual1, uint32_t len1,
+                        const char *seq2, const char *qual2, uint32_t len2, uint32_t span[4], uint64_t *counts, uint64_t *pair_counts);
+int salt_trim_fastq_pair(const salt_trim_opt_t *opt, const salt_trim_pair_opt_t *pair, const char *in1, uint64_t n1, const char *in2, uint64_t n2,
+                         char *out1, uint64_t cap1, uint64_t *w1, char *out2, uint64_t cap2, uint64_t *w2, uint64_t *counts, uint64_t *pair_counts);
 
 /* "<len><op>..." text of a binary CIGAR (ops as in salt_result_t); returns bytes written or -1 */
 int salt_cigar_text(const uint16_t *ops, int n_ops, char *buf, size_t cap);

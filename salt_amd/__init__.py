@@ -9,5 +9,5 @@ from .api import (AlnOpt, GpuAligner, Index, SaltError, RESULT_DTYPE, read_fastq
                   gt_add_sam, gt_text, gt_header, gt_table, GT_Q_NONE,
                   disc_add_sam, disc_text, DISC_ALT, DISC_DIFF, DISC_FIELD_BITS, DISC_DEFAULTS,
                   indel_add_sam, indel_text, indel_header, INDEL_DEFAULTS, INDEL_STATS, INDEL_PROBE, INDEL_MAX_INS, INDEL_MAX_DEL, INDEL_MAX_SHIFT,
-                  trim_span, trim_fastq, TRIM_COUNTERS,
+                  trim_span, trim_fastq, TRIM_COUNTERS, trim_pair_span, trim_fastq_pair, TRIM_PAIR_COUNTERS,
                   diag_pack, pack_geom, PACK_FILL)

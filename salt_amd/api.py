@@ -976,6 +976,68 @@ def trim_fastq(fastq, mate=0, adapter=None, adapter2=None, qual=0, front=0, tail
     return out.raw[:n]
 
 
+TRIM_PAIR_COUNTERS = ("pairs", "overlapping", "trimmed", "reads1", "bases1", "reads2", "bases2", "skipped_long")
+
+
+class _TrimPairOpt(ctypes.Structure):
+    _fields_ = [("min_overlap", ctypes.c_uint32), ("error_pct", ctypes.c_uint32)]
+
+
+def _trim_pair_opt(min_overlap, error_pct):
+    """salt_trim_pair_opt_t of a rule that is on (all zero would switch it off, so a min_overlap of 0 is refused here)"""
+    for v in (min_overlap, error_pct):
+        if not 0 <= int(v) < 2 ** 32:
+            raise SaltError("trim pair: a number outside 0 .. 2^32 - 1")
+    if int(min_overlap) == 0:
+        raise SaltError("trim pair: min_overlap outside 1 .. 512")
+    return _TrimPairOpt(int(min_overlap), int(error_pct))
+
+
+def _pair_args(pair, min_overlap, error_pct, adapter, adapter2, qual, front, tail, a_min_overlap, a_error_pct, counts, pair_counts):
+    lib = _host_trim()
+    o = _trim_opt(adapter, adapter2, qual, front, tail, a_min_overlap, a_error_pct)
+    po = _trim_pair_opt(min_overlap, error_pct) if pair else _TrimPairOpt(0, 0)
+    if counts is not None and (counts.dtype != np.uint64 or counts.shape != (2, 8) or not counts.flags.c_contiguous):
+        raise SaltError("trim: counts is a C-contiguous (2, 8) uint64 array")
+    if pair_counts is not None and (pair_counts.dtype != np.uint64 or pair_counts.shape != (8,) or not pair_counts.flags.c_contiguous):
+        raise SaltError("trim pair: pair_counts is a C-contiguous (8,) uint64 array")
+    return lib, o, po, counts.ctypes.data if counts is not None else None, pair_counts.ctypes.data if pair_counts is not None else None
+
+
+def trim_pair_span(seq1, qual1, seq2, qual2, pair=True, min_overlap=20, error_pct=10, adapter=None, adapter2=None, qual_min=0, front=0, tail=0,
+                   adapter_min_overlap=5, adapter_error_pct=10, counts=None, pair_counts=None):
+    """The host twin of k_fq_trim_pair on one pair (salt_trim_pair_span): -> (b1, e1, b2, e2).  min_overlap and error_pct are the pair
+    rule's (pair=False: the rule off); the adapter step's are adapter_min_overlap and adapter_error_pct.  counts: a (2, 8) uint64 array,
+    pair_counts: an (8,) one, to which the pair's counters are added."""
+    lib, o, po, c, pc = _pair_args(pair, min_overlap, error_pct, adapter, adapter2, qual_min, front, tail, adapter_min_overlap, adapter_error_pct, counts, pair_counts)
+    seq1, qual1, seq2, qual2 = bytes(seq1), bytes(qual1), bytes(seq2), bytes(qual2)
+    if len(seq1) != len(qual1) or len(seq2) != len(qual2):
+        raise SaltError("trim pair: sequence and quality lengths differ")
+    span = (ctypes.c_uint32 * 4)()
+    lib.salt_trim_pair_span.argtypes = [ctypes.POINTER(_TrimOpt), ctypes.POINTER(_TrimPairOpt), ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                                        ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    if lib.salt_trim_pair_span(ctypes.byref(o), ctypes.byref(po), seq1, qual1, len(seq1), seq2, qual2, len(seq2), span, c, pc) != 0:
+        raise SaltError(lib.salt_host_last_error().decode())
+    return tuple(span)
+
+
+def trim_fastq_pair(fastq1, fastq2, pair=True, min_overlap=20, error_pct=10, adapter=None, adapter2=None, qual=0, front=0, tail=0,
+                    adapter_min_overlap=5, adapter_error_pct=10, counts=None, pair_counts=None):
+    """Two blocks of 4-line FASTQ trimmed on the host as pairs (salt_trim_fastq_pair): -> (block1, block2), the reads
+    `salt --trim-pair-overlap` aligns, as FASTQ."""
+    lib, o, po, c, pc = _pair_args(pair, min_overlap, error_pct, adapter, adapter2, qual, front, tail, adapter_min_overlap, adapter_error_pct, counts, pair_counts)
+    fastq1, fastq2 = bytes(fastq1), bytes(fastq2)
+    out1, out2 = ctypes.create_string_buffer(len(fastq1) + 1), ctypes.create_string_buffer(len(fastq2) + 1)
+    w1, w2 = ctypes.c_uint64(), ctypes.c_uint64()
+    lib.salt_trim_fastq_pair.argtypes = [ctypes.POINTER(_TrimOpt), ctypes.POINTER(_TrimPairOpt), ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64,
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_void_p]
+    if lib.salt_trim_fastq_pair(ctypes.byref(o), ctypes.byref(po), fastq1, len(fastq1), fastq2, len(fastq2), out1, len(fastq1), ctypes.byref(w1),
+                                out2, len(fastq2), ctypes.byref(w2), c, pc) != 0:
+        raise SaltError(lib.salt_host_last_error().decode())
+    return out1.raw[:w1.value], out2.raw[:w2.value]
+
+
 class _IndelTextOpt(ctypes.Structure):
     _fields_ = [("min_alt", ctypes.c_uint32), ("min_pct", ctypes.c_uint32), ("tile_positions", ctypes.c_uint32), ("bgzf", ctypes.c_int32)]
 
@@ -1232,6 +1294,28 @@ class GpuAligner:
         out = np.zeros((fastq.count(b"\n") // 4 + 1, 2), dtype=np.uint32)
         gpu_lib().salt_gpu_trim_spans.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
         _gpu_check(gpu_lib().salt_gpu_trim_spans(self._ws, fastq, len(fastq), int(mate), out.ctypes.data))
+        return out[:-1]
+
+    def set_trim_pair(self, min_overlap=20, error_pct=10):
+        """align_pe_text finds each pair's adapters from the mates' overlap (step 2p of the trimming rule, k_fq_trim_pair) and cuts both
+        mates at the insert's end.  Without arguments: on with the defaults; set_trim_pair(None): off."""
+        o = _TrimPairOpt(0, 0) if min_overlap is None else _trim_pair_opt(min_overlap, error_pct)
+        gpu_lib().salt_gpu_ws_set_trim_pair.argtypes = [ctypes.c_void_p, ctypes.POINTER(_TrimPairOpt)]
+        _gpu_check(gpu_lib().salt_gpu_ws_set_trim_pair(self._ws, ctypes.byref(o)))
+
+    def trim_pair_counts(self, reset=False):
+        """(8,) uint64: TRIM_PAIR_COUNTERS, summed over this workspace's calls."""
+        out = np.zeros(8, dtype=np.uint64)
+        gpu_lib().salt_gpu_ws_trim_pair_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _gpu_check(gpu_lib().salt_gpu_ws_trim_pair_counts(self._ws, out.ctypes.data, 1 if reset else 0))
+        return out
+
+    def trim_pair_spans(self, fastq1, fastq2):
+        """The parser and k_fq_trim_pair alone on two blocks of 4-line FASTQ: (pairs, 4) uint32, (b1, e1, b2, e2) of every pair."""
+        fastq1, fastq2 = bytes(fastq1), bytes(fastq2)
+        out = np.zeros((max(fastq1.count(b"\n"), fastq2.count(b"\n")) // 4 + 1, 4), dtype=np.uint32)
+        gpu_lib().salt_gpu_trim_pair_spans.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p]
+        _gpu_check(gpu_lib().salt_gpu_trim_pair_spans(self._ws, fastq1, len(fastq1), fastq2, len(fastq2), out.ctypes.data))
         return out[:-1]
 
     def align_se_text(self, opt, fastq):

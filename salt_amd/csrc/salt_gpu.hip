@@ -127,7 +127,11 @@ struct salt_gpu_ws {
     bool trim = false; TrimRule trim_rule{}; DevBuf<unsigned long long> d_trim_cnt; DevBuf<uint32_t> d_trim_spans;
     uint64_t trim_total[2 * TRIM_N_COUNTS] = {}, trim_last[2 * TRIM_N_COUNTS] = {};
     // (not part of forget_last: the align stage of a text call forgets the tallies' jobs behind the parse stage that set trim_last)
-    void trim_forget() { memset(trim_last, 0, sizeof trim_last); }
+    // salt_gpu_ws_set_trim_pair: the paired-end text entry point launches k_fq_trim_pair in k_fq_trim's place (step 2p of the rule); its eight
+    // pair counters lie behind the sixteen in d_trim_cnt and travel with them.
+    TrimPairRule trim_pair{};
+    uint64_t trim_pair_total[TRIM_PAIR_N_COUNTS] = {}, trim_pair_last[TRIM_PAIR_N_COUNTS] = {};
+    void trim_forget() { memset(trim_last, 0, sizeof trim_last); memset(trim_pair_last, 0, sizeof trim_pair_last); }
     DevBuf<uint32_t> d_bz_slots, d_bz_sizes; DevBuf<unsigned long long> d_bz_offs; DevBuf<uint8_t> d_bz_out;      // bgzf_bufs_alloc: d_bz_sizes.cap blocks
     PinBuf<char> h_bz;                                                       // only for a compressed block that outgrows h_sam
     // salt_gpu_ws_inflate_bgzf: a chunk's BGZF members, their offsets and status words, and the text they inflate to (allocated on first use, grown on demand)
@@ -937,6 +941,8 @@ extern "C" int salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode)
     return SALT_OK;
 }
 
+static constexpr uint32_t TRIM_CNT_WORDS = 2 * TRIM_N_COUNTS + TRIM_PAIR_N_COUNTS;      // d_trim_cnt: the sixteen, then the eight of the pairs
+
 extern "C" int salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *o)
 {
     if (!ws) return fail(SALT_E_INVAL, "null argument");
@@ -945,9 +951,30 @@ extern "C" int salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *o)
         return fail(SALT_E_INVAL, what);
     if (trim_rule_on(r) && !ws->d_trim_cnt) {
         HIPCHK(hipSetDevice(ws->ix->device));
-        HIPCHK(ws->d_trim_cnt.alloc(2 * TRIM_N_COUNTS));
+        HIPCHK(ws->d_trim_cnt.alloc(TRIM_CNT_WORDS));
     }
     ws->trim_rule = r; ws->trim = trim_rule_on(r);
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_set_trim_pair(salt_gpu_ws_t *ws, const salt_trim_pair_opt_t *o)
+{
+    if (!ws) return fail(SALT_E_INVAL, "null argument");
+    TrimPairRule p{};
+    if (o) if (const char *what = trim_pair_rule_make(o->min_overlap, o->error_pct, &p)) return fail(SALT_E_INVAL, what);
+    if (trim_pair_on(p) && !ws->d_trim_cnt) {
+        HIPCHK(hipSetDevice(ws->ix->device));
+        HIPCHK(ws->d_trim_cnt.alloc(TRIM_CNT_WORDS));
+    }
+    ws->trim_pair = p;
+    return SALT_OK;
+}
+
+extern "C" int salt_gpu_ws_trim_pair_counts(salt_gpu_ws_t *ws, uint64_t out[8], int reset)
+{
+    if (!ws || !out) return fail(SALT_E_INVAL, "null argument");
+    memcpy(out, ws->trim_pair_total, sizeof ws->trim_pair_total);
+    if (reset) memset(ws->trim_pair_total, 0, sizeof ws->trim_pair_total);
     return SALT_OK;
 }
 
@@ -964,20 +991,33 @@ extern "C" int salt_gpu_ws_trim_uncount(salt_gpu_ws_t *ws)
     if (!ws) return fail(SALT_E_INVAL, "null argument");
     for (uint32_t k = 0; k < 2 * TRIM_N_COUNTS; ++k) ws->trim_total[k] -= ws->trim_last[k];
     memset(ws->trim_last, 0, sizeof ws->trim_last);
+    for (uint32_t k = 0; k < TRIM_PAIR_N_COUNTS; ++k) ws->trim_pair_total[k] -= ws->trim_pair_last[k];
+    memset(ws->trim_pair_last, 0, sizeof ws->trim_pair_last);
     return SALT_OK;
 }
 
 // k_fq_trim behind the parse kernels of a call, its counters zeroed in front of it
 static int ws_trim_launch(salt_gpu_ws_t *ws, uint64_t n_raw, uint32_t n_rec, int pe, uint32_t mate, uint32_t *spans, hipStream_t st)
 {
-    if (!ws->d_trim_cnt) HIPCHK(ws->d_trim_cnt.alloc(2 * TRIM_N_COUNTS));
+    if (!ws->d_trim_cnt) HIPCHK(ws->d_trim_cnt.alloc(TRIM_CNT_WORDS));
     HIPCHK(hipMemsetAsync(ws->d_trim_cnt, 0, 2 * TRIM_N_COUNTS * 8, st));
     HIPCHK(launch_fq_trim(ws->d_raw, n_raw, ws->d_rec, ws->d_offs, n_rec, pe, mate, ws->trim_rule, ws->d_tctl, ws->d_trim_cnt, spans, st));
     return SALT_OK;
 }
-static void ws_trim_add(salt_gpu_ws_t *ws, const uint64_t *blk)
+// k_fq_trim_pair in its place: the pair rule is on.  n_rec = both mates of every pair.
+static int ws_trim_pair_launch(salt_gpu_ws_t *ws, uint64_t n_raw, uint32_t n_rec, uint32_t *spans, hipStream_t st)
+{
+    if (!ws->d_trim_cnt) HIPCHK(ws->d_trim_cnt.alloc(TRIM_CNT_WORDS));
+    HIPCHK(hipMemsetAsync(ws->d_trim_cnt, 0, TRIM_CNT_WORDS * 8, st));
+    HIPCHK(launch_fq_trim_pair(ws->d_raw, n_raw, ws->d_rec, ws->d_offs, n_rec / 2, ws->trim_rule, ws->trim_pair, ws->d_tctl, ws->d_trim_cnt,
+                               ws->d_trim_cnt + 2 * TRIM_N_COUNTS, spans, st));
+    return SALT_OK;
+}
+// blk: the sixteen, and with pair the eight behind them
+static void ws_trim_add(salt_gpu_ws_t *ws, const uint64_t *blk, bool pair = false)
 {
     for (uint32_t k = 0; k < 2 * TRIM_N_COUNTS; ++k) { ws->trim_total[k] += blk[k]; ws->trim_last[k] = blk[k]; }
+    if (pair) for (uint32_t k = 0; k < TRIM_PAIR_N_COUNTS; ++k) { ws->trim_pair_total[k] += blk[2 * TRIM_N_COUNTS + k]; ws->trim_pair_last[k] = blk[2 * TRIM_N_COUNTS + k]; }
 }
 
 // The polish stage of a text call, where the SAM kernels run without it: the block's records from its result rows (polish_rows_len: all but
@@ -1180,22 +1220,23 @@ struct TextTrace {
 
 // Behind the parse kernels: their control words back (ctl[0] what is wrong, ctl[2] where; ctl[1] = *max_len, the longest read), then the reads'
 // codes.  blocks: "block" or "blocks", as the entry point takes one or two.
-static int text_codes(salt_gpu_ws_t *ws, uint32_t n_rec, const char *blocks, hipStream_t st, uint32_t *max_len)
+static int text_codes(salt_gpu_ws_t *ws, uint32_t n_rec, const char *blocks, hipStream_t st, uint32_t *max_len, bool pair = false)
 {
-    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0; uint64_t trimmed[2 * TRIM_N_COUNTS];
+    uint32_t ctl[4] = { 0, 0, 0, 0 }, bases = 0; uint64_t trimmed[TRIM_CNT_WORDS];
+    const bool trim = ws->trim || pair;                            // pair: k_fq_trim_pair ran, its eight counters lie behind the sixteen
     HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&bases, ws->d_offs + n_rec, 4, hipMemcpyDeviceToHost, st));
-    if (ws->trim) HIPCHK(hipMemcpyAsync(trimmed, ws->d_trim_cnt, sizeof trimmed, hipMemcpyDeviceToHost, st));
+    if (trim) HIPCHK(hipMemcpyAsync(trimmed, ws->d_trim_cnt, (pair ? TRIM_CNT_WORDS : 2 * TRIM_N_COUNTS) * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ctl[0]) {
         const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
                          : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
         return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the " + blocks + ": " + what);
     }
-    if (ws->trim) ws_trim_add(ws, trimmed);
+    if (trim) ws_trim_add(ws, trimmed, pair);
     if (int rc = reserve_seqs(ws, bases, st)) return rc;
     HIPCHK(launch_fq_codes(ws->d_raw, ws->d_rec, ws->d_offs, n_rec, ws->d_seqs, st));
-    *max_len = ws->trim ? ctl[3] : ctl[1];                         // k_fq_trim leaves the longest trimmed read in ctl[3]
+    *max_len = trim ? ctl[3] : ctl[1];                             // k_fq_trim leaves the longest trimmed read in ctl[3]
     return SALT_OK;
 }
 
@@ -1371,9 +1412,11 @@ static int text_parse_pe(salt_gpu_ws_t *ws, const char *fastq1, uint64_t n1, con
     HIPCHK(hipMemsetAsync(ws->d_offs + n_rec, 0, 4, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, 0u, lines1, n, 0u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
     HIPCHK(launch_fq_parse_mate(ws->d_raw, (uint32_t)b2, lines2, n, 1u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
-    if (ws->trim && (rc = ws_trim_launch(ws, b2 + n2, n_rec, 1, 0u, nullptr, st))) return rc;
+    const bool pair = trim_pair_on(ws->trim_pair);
+    if (pair) { if ((rc = ws_trim_pair_launch(ws, b2 + n2, n_rec, nullptr, st))) return rc; }
+    else if (ws->trim && (rc = ws_trim_launch(ws, b2 + n2, n_rec, 1, 0u, nullptr, st))) return rc;
     HIPCHK(launch_text_scan(ws->d_offs, n_rec + 1, ws->d_scan, ws->d_scan.cap, st));
-    if ((rc = text_codes(ws, n_rec, "blocks", st, max_len))) return rc;
+    if ((rc = text_codes(ws, n_rec, "blocks", st, max_len, pair))) return rc;
     ws->q_cur.quals = ws->d_raw; ws->q_cur.rec = ws->d_rec; ws->q_cur.bytes = b2 + n2;      // both blocks; a mate's qual_off counts from d_raw
     *n_pairs = n;
     return SALT_OK;
@@ -1453,6 +1496,60 @@ extern "C" int salt_gpu_trim_spans(salt_gpu_ws_t *ws, const char *fastq, uint64_
     return SALT_OK;
 }
 
+// The pair form of salt_gpu_trim_spans: both blocks through the parser as text_parse_pe takes them, then k_fq_trim_pair alone (the pair rule
+// on or off), b1, e1, b2, e2 of every pair back.  No scan, no codes.
+extern "C" int salt_gpu_trim_pair_spans(salt_gpu_ws_t *ws, const char *fastq1, uint64_t n1, const char *fastq2, uint64_t n2, uint32_t *beg_end)
+{
+    if (!ws || !fastq1 || !fastq2 || !beg_end) return fail(SALT_E_INVAL, "null argument");
+    ws->forget_last(); ws->trim_forget();
+    if (n1 == 0 && n2 == 0) return SALT_OK;
+    if (n1 == 0 || n2 == 0) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads");
+    if (n1 + n2 >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
+    if (fastq1[n1 - 1] != '\n' || fastq2[n2 - 1] != '\n') return fail(SALT_E_INVAL, "FASTQ block must end with a newline");
+    HIPCHK(hipSetDevice(ws->ix->device));
+    hipStream_t st = ws->stream;
+    const uint64_t b2 = (n1 + 3) & ~3ull;
+    int rc = reserve_parse(ws, b2 + n2, st);
+    if (rc) return rc;
+    const uint64_t t1 = (n1 + FQ_TILE - 1) / FQ_TILE, t2 = (n2 + FQ_TILE - 1) / FQ_TILE;
+    uint32_t *tile1 = ws->d_tile, *tile2 = ws->d_tile + t1 + 4;
+    HIPCHK(hipMemcpyAsync(ws->d_raw, fastq1, n1, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ws->d_raw + b2, fastq2, n2, hipMemcpyHostToDevice, st));
+    uint32_t nl[2] = { 0, 0 };
+    HIPCHK(launch_fq_count(ws->d_raw, n1, tile1, ws->d_scan, ws->d_scan.cap, st));
+    HIPCHK(launch_fq_count(ws->d_raw + b2, n2, tile2, ws->d_scan, ws->d_scan.cap, st));
+    HIPCHK(hipMemcpyAsync(&nl[0], tile1 + t1, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&nl[1], tile2 + t2, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nl[0] % 4 != 0 || nl[1] % 4 != 0) return fail(SALT_E_INVAL, "FASTQ block does not hold whole 4-line records (" + std::to_string(nl[0]) + " / " + std::to_string(nl[1]) + " lines)");
+    if (nl[0] != nl[1]) return fail(SALT_E_INVAL, "the two FASTQ blocks hold different numbers of reads (" + std::to_string(nl[0] / 4) + " / " + std::to_string(nl[1] / 4) + ")");
+    const uint32_t n = nl[0] / 4, n_rec = 2 * n;
+    if (n_rec > ws->max_reads) return fail(SALT_E_CAPACITY, "more reads in the blocks (" + std::to_string(n_rec) + ") than the workspace holds");
+    if (n == 0) return SALT_OK;
+    if ((rc = ws->d_lines.reserve((uint64_t)nl[0] + nl[1] + 24, st))) return rc;
+    uint32_t *lines1 = ws->d_lines, *lines2 = ws->d_lines + nl[0] + 8;
+    HIPCHK(launch_fq_lines(ws->d_raw, n1, tile1, lines1, st));
+    HIPCHK(launch_fq_lines(ws->d_raw + b2, n2, tile2, lines2, st));
+    if ((rc = reserve_records(ws))) return rc;
+    if (!ws->d_trim_spans) HIPCHK(ws->d_trim_spans.alloc(2 * (uint64_t)ws->max_reads));
+    HIPCHK(launch_fq_ctl_init(ws->d_tctl, st));
+    HIPCHK(launch_fq_parse_mate(ws->d_raw, 0u, lines1, n, 0u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
+    HIPCHK(launch_fq_parse_mate(ws->d_raw, (uint32_t)b2, lines2, n, 1u, ws->d_rec, ws->d_offs, ws->d_tctl, st));
+    if ((rc = ws_trim_pair_launch(ws, b2 + n2, n_rec, ws->d_trim_spans, st))) return rc;
+    uint32_t ctl[4] = { 0, 0, 0, 0 }; uint64_t trimmed[TRIM_CNT_WORDS];
+    HIPCHK(hipMemcpyAsync(ctl, ws->d_tctl, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(trimmed, ws->d_trim_cnt, sizeof trimmed, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(beg_end, ws->d_trim_spans, 2 * (uint64_t)n_rec * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ctl[0]) {
+        const char *what = ctl[0] & 1 ? "a record does not start with '@'" : ctl[0] & 2 ? "the third line of a record does not start with '+'"
+                         : ctl[0] & 4 ? "sequence and quality lengths differ" : "empty read";
+        return fail(SALT_E_INVAL, std::string("input is not 4-line FASTQ at record ") + std::to_string(ctl[2]) + " of the blocks: " + what);
+    }
+    ws_trim_add(ws, trimmed, true);
+    return SALT_OK;
+}
+
 // One row of salt_gpu_diag_text_rows against what the record kernels index with it: empty = the row is in range.  L: the read's length.
 // pe: the paired-end kernels never read `skipped` (mapped is pos alone there), so only a single-end row is excused by it.
 static std::string text_row_fault(const salt_result_t &q, uint32_t L, uint32_t ref_len, bool pe)
@@ -1489,6 +1586,7 @@ extern "C" int salt_gpu_diag_text_rows(salt_gpu_ws_t *ws, const salt_text_opt_t 
     *out = nullptr; *out_bytes = 0; *n_records = 0; ws->forget_last(); ws->trim_forget();
     if (ws->polish) return fail(SALT_E_INVAL, "text rows: the polish stage is not driven from rows (salt_gpu_ws_set_polish is on)");
     if (ws->trim) return fail(SALT_E_INVAL, "text rows: the rows are checked against the untrimmed reads (salt_gpu_ws_set_trim is on)");
+    if (trim_pair_on(ws->trim_pair)) return fail(SALT_E_INVAL, "text rows: the rows are checked against the untrimmed reads (salt_gpu_ws_set_trim_pair is on)");
     if (n1 == 0 || (pe && n2 == 0)) return fail(SALT_E_INVAL, "text rows: an empty FASTQ block");
     if (n1 + (pe ? n2 : 0) >= 0xFFFFFFE0ull) return fail(SALT_E_CAPACITY, "FASTQ blocks of 4 GiB or more");
     if (fastq1[n1 - 1] != '\n' || (pe && fastq2[n2 - 1] != '\n')) return fail(SALT_E_INVAL, "FASTQ block must end with a newline");

@@ -218,6 +218,10 @@ hipError_t launch_fq_parse_recs(const uint8_t *raw, const uint32_t *line_start, 
 // leaves the longest trimmed read in ctl[3], adds to counts[16]; spans (or null): beg, end of every record.  raw[0, n_raw) is what the offsets may reach.
 hipError_t launch_fq_trim(const uint8_t *raw, uint64_t n_raw, FqRec *rec, uint32_t *len, uint32_t n_rec, int pe, uint32_t mate, const TrimRule &rule,
                           uint32_t *ctl, unsigned long long *counts, uint32_t *spans, hipStream_t st);
+// the same for the interleaved mates of n_pairs pairs with the pair rule (step 2p) on: k_fq_trim_pair, a wave a pair; adds to pair_counts[8] too;
+// spans (or null): b1, e1, b2, e2 of every pair
+hipError_t launch_fq_trim_pair(const uint8_t *raw, uint64_t n_raw, FqRec *rec, uint32_t *len, uint32_t n_pairs, const TrimRule &rule, const TrimPairRule &pair,
+                               uint32_t *ctl, unsigned long long *counts, unsigned long long *pair_counts, uint32_t *spans, hipStream_t st);
 static const uint32_t FQ_TILE = 1024;                                          // bytes per newline-count tile (k_fq_count)
 
 // ---- polish over SAM text (salt_polish.hip) ----

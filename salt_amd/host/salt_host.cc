@@ -1549,3 +1549,69 @@ extern "C" int64_t salt_trim_fastq(const salt_trim_opt_t *opt, int mate, const c
     }
     return (int64_t)w;
 }
+
+static bool trim_pair_rule_of(const salt_trim_pair_opt_t *o, salt::TrimPairRule *p)
+{
+    *p = salt::TrimPairRule();
+    if (!o) return true;
+    if (const char *what = salt::trim_pair_rule_make(o->min_overlap, o->error_pct, p)) { g_err = what; return false; }
+    return true;
+}
+
+extern "C" int salt_trim_pair_span(const salt_trim_opt_t *opt, const salt_trim_pair_opt_t *pair, const char *seq1, const char *qual1, uint32_t len1,
+                                   const char *seq2, const char *qual2, uint32_t len2, uint32_t span[4], uint64_t *counts, uint64_t *pair_counts)
+{
+    if (!seq1 || !qual1 || !seq2 || !qual2 || !span || len1 == 0 || len2 == 0) { g_err = "trim pair: null argument or an empty read"; return -1; }
+    salt::TrimRule r; salt::TrimPairRule p;
+    if (!trim_rule_of(opt, &r) || !trim_pair_rule_of(pair, &p)) return -1;
+    salt::trim_pair_span(r, p, reinterpret_cast<const uint8_t *>(seq1), reinterpret_cast<const uint8_t *>(qual1), len1, reinterpret_cast<const uint8_t *>(seq2),
+                         reinterpret_cast<const uint8_t *>(qual2), len2, span, counts, pair_counts);
+    return 0;
+}
+
+// one 4-line record of in[*p, n) -> its lines without line ends; null, or what is wrong with it
+static const char *trim_next_record(const char *in, uint64_t n, uint64_t *p, const char *l[4], uint64_t len[4])
+{
+    for (int k = 0; k < 4; ++k) {
+        const char *nl = *p < n ? static_cast<const char *>(memchr(in + *p, '\n', n - *p)) : nullptr;
+        if (!nl) return "the block does not hold whole 4-line records";
+        l[k] = in + *p; len[k] = (uint64_t)(nl - (in + *p)); *p += len[k] + 1;
+        while (len[k] && l[k][len[k] - 1] == '\r') --len[k];
+    }
+    if (!len[0] || l[0][0] != '@') return "a record does not start with '@'";
+    if (!len[2] || l[2][0] != '+') return "the third line of a record does not start with '+'";
+    if (len[1] != len[3]) return "sequence and quality lengths differ";
+    if (!len[1]) return "empty read";
+    if (len[1] > 0xFFFFFFFFull) return "a read of 4 Gbases or more";
+    return nullptr;
+}
+
+extern "C" int salt_trim_fastq_pair(const salt_trim_opt_t *opt, const salt_trim_pair_opt_t *pair, const char *in1, uint64_t n1, const char *in2, uint64_t n2,
+                                    char *out1, uint64_t cap1, uint64_t *w1, char *out2, uint64_t cap2, uint64_t *w2, uint64_t *counts, uint64_t *pair_counts)
+{
+    if ((!in1 && n1) || (!in2 && n2) || (!out1 && cap1) || (!out2 && cap2) || !w1 || !w2) { g_err = "trim pair: null argument"; return -1; }
+    salt::TrimRule r; salt::TrimPairRule pr;
+    if (!trim_rule_of(opt, &r) || !trim_pair_rule_of(pair, &pr)) return -1;
+    const char *in[2] = { in1, in2 }; const uint64_t n[2] = { n1, n2 }, cap[2] = { cap1, cap2 };
+    char *out[2] = { out1, out2 };
+    uint64_t w[2] = { 0, 0 }, p[2] = { 0, 0 }, rec = 0;
+    for (; p[0] < n1 && p[1] < n2; ++rec) {
+        const char *l[2][4]; uint64_t len[2][4];
+        for (int m = 0; m < 2; ++m)
+            if (const char *why = trim_next_record(in[m], n[m], &p[m], l[m], len[m])) {
+                g_err = "trim pair: input is not 4-line FASTQ at record " + std::to_string(rec) + " of block " + std::to_string(m + 1) + ": " + why;
+                return -1;
+            }
+        uint32_t span[4];
+        salt::trim_pair_span(r, pr, reinterpret_cast<const uint8_t *>(l[0][1]), reinterpret_cast<const uint8_t *>(l[0][3]), (uint32_t)len[0][1],
+                             reinterpret_cast<const uint8_t *>(l[1][1]), reinterpret_cast<const uint8_t *>(l[1][3]), (uint32_t)len[1][1], span, counts, pair_counts);
+        for (int m = 0; m < 2; ++m) {
+            auto put = [&](const char *s, uint64_t k) { if (w[m] + k <= cap[m]) memcpy(out[m] + w[m], s, k); w[m] += k; };
+            const uint32_t beg = span[2 * m], k = span[2 * m + 1] - beg;
+            put(l[m][0], len[m][0]); put("\n", 1); put(l[m][1] + beg, k); put("\n", 1); put(l[m][2], len[m][2]); put("\n", 1); put(l[m][3] + beg, k); put("\n", 1);
+        }
+    }
+    if (p[0] < n1 || p[1] < n2) { g_err = "trim pair: the two FASTQ blocks hold different numbers of reads"; return -1; }
+    *w1 = w[0]; *w2 = w[1];
+    return 0;
+}

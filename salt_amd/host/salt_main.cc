@@ -58,6 +58,9 @@ extern "C" int salt_gpu_align_se_text_dev(salt_gpu_ws_t *ws, const salt_aln_opt_
 extern "C" int salt_gpu_ws_set_trim(salt_gpu_ws_t *ws, const salt_trim_opt_t *opt) __attribute__((weak));
 extern "C" int salt_gpu_ws_trim_counts(salt_gpu_ws_t *ws, uint64_t out[16], int reset) __attribute__((weak));
 extern "C" int salt_gpu_ws_trim_uncount(salt_gpu_ws_t *ws) __attribute__((weak));
+// And the pair rule's kernel (--trim-pair-overlap): without it the run finds the overlaps on the host, through the host pipeline.
+extern "C" int salt_gpu_ws_set_trim_pair(salt_gpu_ws_t *ws, const salt_trim_pair_opt_t *opt) __attribute__((weak));
+extern "C" int salt_gpu_ws_trim_pair_counts(salt_gpu_ws_t *ws, uint64_t out[8], int reset) __attribute__((weak));
 // Likewise the polish stage behind the aligner (--polish) and the polish handle the host pipeline passes its lines through.
 extern "C" int salt_gpu_ws_set_polish(salt_gpu_ws_t *ws, int mode) __attribute__((weak));
 extern "C" int salt_gpu_polish_open(int device, const uint8_t *pac, uint64_t l_pac, salt_gpu_polish_t **out) __attribute__((weak));
@@ -130,22 +133,30 @@ int g_polish = 0;                             // --polish: 0 off, 1 Landau-Vishk
 // --trim-*: the reads are trimmed in front of the aligner -- on the text path by the device's k_fq_trim (salt_gpu_ws_set_trim on every
 // workspace), wherever the host parses the reads (parse_batch: the host pipeline, the continuation behind a hand-over, the first batch of
 // infer_isize) by the host twin salt_trim_span, which compiles the same rule.  The sixteen counters of both sides end in one line on stderr.
+// With --trim-pair-overlap the pairs go through k_fq_trim_pair there and salt_trim_pair_span here (parse_batch_pe); a second line follows.
 struct TrimRun {
     bool on = false, device = false;                         // device: the text path's workspaces trim
     bool instead_of_text_path = false;                       // the host pipeline reads a file the text path would have read: records of any shape, as behind a hand-over
     salt_trim_opt_t opt{}; bool has_overlap = false, has_error = false;
     std::atomic<uint64_t> counts[16]; std::atomic<bool> by_device{ false }, by_host{ false };
     void add(const uint64_t *c, bool dev) { bool any = false; for (int k = 0; k < 16; ++k) if (c[k]) { counts[k] += c[k]; any = true; } if (any) (dev ? by_device : by_host) = true; }
+    // --trim-pair-overlap: step 2p of the rule, for pairs (k_fq_trim_pair on the text path, salt_trim_pair_span in parse_batch_pe); `on` stays
+    // the per-read steps' switch, any() says whether the run trims at all; eight counters of their own, a second line on stderr
+    bool pair_on = false, has_pair_overlap = false, has_pair_error = false; salt_trim_pair_opt_t pair_opt{};
+    std::atomic<uint64_t> pair_counts[8];
+    bool any() const { return on || pair_on; }
+    void add_pairs(const uint64_t *c, bool dev) { bool some = false; for (int k = 0; k < 8; ++k) if (c[k]) { pair_counts[k] += c[k]; some = true; } if (some) (dev ? by_device : by_host) = true; }
 } g_trim;
 // a workspace of the text path is about to go: its counters join the run's
 void trim_collect(salt_gpu_ws_t *ws)
 {
     uint64_t c[16];
     if (ws && g_trim.device && salt_gpu_ws_trim_counts(ws, c, 1) == 0) g_trim.add(c, true);
+    if (ws && g_trim.device && g_trim.pair_on && salt_gpu_ws_trim_pair_counts(ws, c, 1) == 0) g_trim.add_pairs(c, true);
 }
 void trim_report()
 {
-    if (!g_trim.on) return;
+    if (!g_trim.any()) return;
     const bool clip = g_trim.opt.front || g_trim.opt.tail;
     std::string line = std::string("[salt] trim: ") + (g_trim.by_device && g_trim.by_host ? "device, and host behind the hand-over" : g_trim.by_host || !g_trim.device ? "host" : "device");
     for (int m = 0; m < 2; ++m) {
@@ -158,6 +169,11 @@ void trim_report()
         line += buf;
     }
     fprintf(stderr, "%s\n", line.c_str());
+    if (!g_trim.pair_on) return;
+    uint64_t c[8]; for (int k = 0; k < 8; ++k) c[k] = g_trim.pair_counts[k];
+    fprintf(stderr, "[salt] trim: pairs: pairs %llu overlapping %llu trimmed %llu mate 1: reads %llu bases %llu mate 2: reads %llu bases %llu skipped_long %llu\n",
+            (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
+            (unsigned long long)c[6], (unsigned long long)c[7]);
 }
 
 struct Batch {
@@ -330,6 +346,7 @@ public:
 };
 
 void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool, int mate = 0, bool count = true);
+void parse_batch_pe(Batch &b1, Batch &b2, Pool &pool, bool count = true);
 
 void format_batch(const salt_index_t *ix, const salt_sam_opt_t *so, Batch &b, Pool &pool)
 {
@@ -378,16 +395,17 @@ void format_batch_pe(const salt_index_t *ix, const salt_sam_opt_t *so, const sal
 }
 
 // mate: which adapter --trim-* searches the batch's reads with; count: their trim counters join the run's (not for infer_isize's look at the first batch)
-void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool, int mate, bool count)
+// The three steps of parse_batch, apart for --trim-pair-overlap, which needs both mates' records before either is trimmed:
+// batch_locate (the records' lines; names terminated), the trimming of the spans, batch_finish (qualities terminated, offsets, codes).
+struct RecSpan { size_t s0, se, q0; };                         // bases [s0, se), qualities from q0
+void batch_locate(std::vector<char> &raw, Batch &b, Pool &pool, std::vector<RecSpan> &span)
 {
     const std::vector<uint32_t> &rec = b.rec;                  // record starts, found by the reader
     const int n = (int)rec.size(), n_threads = pool.n;
     b.name.assign((size_t)n, 0u); b.qual.assign((size_t)n, 0u);
-    std::vector<uint32_t> len((size_t)n, 0);
-    std::vector<std::pair<size_t, size_t>> seq_span((size_t)n);
+    span.assign((size_t)n, RecSpan{ 0, 0, 0 });
     auto line_end = [&](size_t p) { const char *nl = (const char *)memchr(raw.data() + p, '\n', raw.size() - p); size_t e = nl ? (size_t)(nl - raw.data()) : raw.size(); return e; };
     pool.parallel([&](int t) {
-        uint64_t trimmed[16] = {};
         for (int i = (int)((long)n * t / n_threads); i < (int)((long)n * (t + 1) / n_threads); ++i) {
             size_t p = rec[(size_t)i], e = line_end(p);
             size_t ne = p + 1;
@@ -398,37 +416,80 @@ void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool, int mate, bool co
             const size_t name_end = ne;
             size_t s0 = e + 1, s1 = line_end(s0);
             size_t se = s1; while (se > s0 && raw[se - 1] == '\r') --se;
-            seq_span[(size_t)i] = { s0, se }; len[(size_t)i] = (uint32_t)(se - s0);
             size_t p2 = s1 + 1, e2 = line_end(p2);           // '+' line
             size_t q0 = e2 + 1, q1 = line_end(q0);
             while (q1 > q0 && raw[q1 - 1] == '\r') --q1;
-            b.qual[(size_t)i] = (uint32_t)q0;
             if (raw[p] != '@' || p2 >= raw.size() || raw[p2] != '+' || q1 - q0 != se - s0) {
                 fprintf(stderr, "[salt] input is not 4-line FASTQ at record %d of a batch ('%.60s'): multi-line records are only read when "
                                 "the head of the file shows them\n", i, raw.data() + p);
                 exit(1);
             }
-            if (g_trim.on && se > s0) {                      // the span of the rule: bases, qualities and length move with it
-                uint32_t tb = 0, te = 0;
-                if (salt_trim_span(&g_trim.opt, mate, raw.data() + s0, raw.data() + q0, (uint32_t)(se - s0), &tb, &te, trimmed)) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); exit(1); }
-                seq_span[(size_t)i] = { s0 + tb, s0 + te }; len[(size_t)i] = te - tb;
-                b.qual[(size_t)i] = (uint32_t)(q0 + tb); q1 = q0 + te;
-            }
+            span[(size_t)i] = RecSpan{ s0, se, q0 };
             raw[name_end] = 0;                               // terminate in place (after every read of these lines)
-            if (q1 < raw.size()) raw[q1] = 0;
         }
-        if (g_trim.on && count) g_trim.add(trimmed, false);
     });
+}
+void batch_finish(std::vector<char> &raw, Batch &b, Pool &pool, const std::vector<RecSpan> &span)
+{
+    const int n = (int)span.size(), n_threads = pool.n;
     b.offs.assign((size_t)n + 1, 0);
-    for (int i = 0; i < n; ++i) b.offs[(size_t)i + 1] = b.offs[(size_t)i] + len[(size_t)i];
+    for (int i = 0; i < n; ++i) {
+        const RecSpan &r = span[(size_t)i];
+        b.qual[(size_t)i] = (uint32_t)r.q0;
+        if (r.q0 + (r.se - r.s0) < raw.size()) raw[r.q0 + (r.se - r.s0)] = 0;
+        b.offs[(size_t)i + 1] = b.offs[(size_t)i] + (uint32_t)(r.se - r.s0);
+    }
     b.seqs.resize(b.offs[(size_t)n]);
     pool.parallel([&](int t) {
         for (int i = (int)((long)n * t / n_threads); i < (int)((long)n * (t + 1) / n_threads); ++i) {
             uint8_t *d = b.seqs.data() + b.offs[(size_t)i];
-            const char *sp = raw.data() + seq_span[(size_t)i].first;
-            for (uint32_t j = 0; j < len[(size_t)i]; ++j) d[j] = nt4((unsigned char)sp[j]);
+            const char *sp = raw.data() + span[(size_t)i].s0;
+            for (size_t j = 0, L = span[(size_t)i].se - span[(size_t)i].s0; j < L; ++j) d[j] = nt4((unsigned char)sp[j]);
         }
     });
+}
+void parse_batch(std::vector<char> &raw, Batch &b, Pool &pool, int mate, bool count)
+{
+    std::vector<RecSpan> span;
+    batch_locate(raw, b, pool, span);
+    const int n = (int)span.size(), n_threads = pool.n;
+    if (g_trim.on) pool.parallel([&](int t) {
+        uint64_t trimmed[16] = {};
+        for (int i = (int)((long)n * t / n_threads); i < (int)((long)n * (t + 1) / n_threads); ++i) {
+            RecSpan &r = span[(size_t)i];
+            if (r.se == r.s0) continue;
+            uint32_t tb = 0, te = 0;                         // the span of the rule: bases, qualities and length move with it
+            if (salt_trim_span(&g_trim.opt, mate, raw.data() + r.s0, raw.data() + r.q0, (uint32_t)(r.se - r.s0), &tb, &te, trimmed)) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); exit(1); }
+            r = RecSpan{ r.s0 + tb, r.s0 + te, r.q0 + tb };
+        }
+        if (count) g_trim.add(trimmed, false);
+    });
+    batch_finish(raw, b, pool, span);
+}
+// Both mates' batches of a paired-end run (b2's reads are mate 2).  With --trim-pair-overlap every pair is trimmed as one (salt_trim_pair_span).
+void parse_batch_pe(Batch &b1, Batch &b2, Pool &pool, bool count)
+{
+    if (!g_trim.pair_on || b1.rec.size() != b2.rec.size()) {   // (unequal numbers: the caller refuses the batches)
+        parse_batch(b1.raw, b1, pool, 0, count); parse_batch(b2.raw, b2, pool, 1, count);
+        return;
+    }
+    std::vector<RecSpan> s1, s2;
+    batch_locate(b1.raw, b1, pool, s1); batch_locate(b2.raw, b2, pool, s2);
+    const int n = (int)s1.size(), n_threads = pool.n;
+    pool.parallel([&](int t) {
+        uint64_t trimmed[16] = {}, pairs[8] = {};
+        for (int i = (int)((long)n * t / n_threads); i < (int)((long)n * (t + 1) / n_threads); ++i) {
+            RecSpan &r1 = s1[(size_t)i], &r2 = s2[(size_t)i];
+            if (r1.se == r1.s0 || r2.se == r2.s0) continue;
+            uint32_t sp[4];
+            if (salt_trim_pair_span(g_trim.on ? &g_trim.opt : nullptr, &g_trim.pair_opt, b1.raw.data() + r1.s0, b1.raw.data() + r1.q0, (uint32_t)(r1.se - r1.s0),
+                                    b2.raw.data() + r2.s0, b2.raw.data() + r2.q0, (uint32_t)(r2.se - r2.s0), sp, trimmed, pairs)) { fprintf(stderr, "[salt] %s\n", salt_host_last_error()); exit(1); }
+            r1 = RecSpan{ r1.s0 + sp[0], r1.s0 + sp[1], r1.q0 + sp[0] };
+            r2 = RecSpan{ r2.s0 + sp[2], r2.s0 + sp[3], r2.q0 + sp[2] };
+        }
+        if (count) { g_trim.add(trimmed, false); g_trim.add_pairs(pairs, false); }
+    });
+    batch_finish(b1.raw, b1, pool, s1); batch_finish(b2.raw, b2, pool, s2);
 }
 
 // The calling thread (and the threads it creates) onto the host NUMA node its GPU is attached to: the chunk a worker preads, the page-locked
@@ -770,6 +831,12 @@ int usage()
             "               --trim-tail     <int>    remove this many bases from every read's 3' end, 0 .. 511 [0]\n"
             "                                        order: clips, quality, adapter; a read keeps at least one base, no read is dropped;\n"
             "                                        one line of counters on stderr\n"
+            "               --trim-pair-overlap      paired end: find each pair's adapters from the mates' overlap, whatever the adapter is (on the\n"
+            "                                        GPU): the largest insert length at which the mates agree, both cut there; between the\n"
+            "                                        quality and the adapter step; mates of up to 512 bases; nothing is merged or corrected;\n"
+            "                                        a second line of counters on stderr [off]\n"
+            "               --trim-pair-min-overlap <int>  --trim-pair-overlap: the mates agree over at least this many bases, 1 .. 512 [20]\n"
+            "               --trim-pair-error-pct <int>    --trim-pair-overlap: mismatches allowed, in percent of the overlap, 0 .. 50 [10]\n"
             "               --genotype      <file>   write a VCF 4.2 record per SNP site of the index: the genotype, allele depths and\n"
             "                                        likelihoods from the reads' bases and base qualities (summed, called and printed on\n"
             "                                        the GPU); a name ending in .gz is written as BGZF [off]\n"
@@ -1052,7 +1119,8 @@ static int open_text_ws(salt_gpu_index_t *gix, uint32_t max_reads, salt_gpu_ws_t
     if (!rc && g_bgzf.device) rc = salt_gpu_ws_set_sam_bgzf(*ws, 1);
     if (!rc && g_bam.device) rc = salt_gpu_ws_set_sam_bam(*ws, 1);
     if (!rc && g_polish) rc = salt_gpu_ws_set_polish(*ws, g_polish);
-    if (!rc && g_trim.device) rc = salt_gpu_ws_set_trim(*ws, &g_trim.opt);
+    if (!rc && g_trim.device && g_trim.on) rc = salt_gpu_ws_set_trim(*ws, &g_trim.opt);
+    if (!rc && g_trim.device && g_trim.pair_on) rc = salt_gpu_ws_set_trim_pair(*ws, &g_trim.pair_opt);
     if (!rc && text_reads && P->head_read_len) rc = salt_gpu_ws_reserve_text(*ws, ao, text_bytes, text_reads, P->head_read_len, P->sam_cap - 64, P->sam_buf[(size_t)wk], P->sam_cap);
     return rc;
 }
@@ -1507,7 +1575,8 @@ static int parse_options(int argc, char **argv, Opts &o)
         { "discover-all", 0, 0, 1020 }, { "stats", 1, 0, 1021 }, { "stats-min-mapq", 1, 0, 1022 },
         { "indels", 1, 0, 1023 }, { "indels-min-mapq", 1, 0, 1024 }, { "indels-min-alt", 1, 0, 1025 }, { "indels-min-pct", 1, 0, 1026 }, { "indels-slots", 1, 0, 1027 },
         { "trim-adapter", 1, 0, 1028 }, { "trim-adapter2", 1, 0, 1029 }, { "trim-qual", 1, 0, 1030 }, { "trim-front", 1, 0, 1031 }, { "trim-tail", 1, 0, 1032 },
-        { "trim-min-overlap", 1, 0, 1033 }, { "trim-error-pct", 1, 0, 1034 }, { 0, 0, 0, 0 } };
+        { "trim-min-overlap", 1, 0, 1033 }, { "trim-error-pct", 1, 0, 1034 },
+        { "trim-pair-overlap", 0, 0, 1035 }, { "trim-pair-min-overlap", 1, 0, 1036 }, { "trim-pair-error-pct", 1, 0, 1037 }, { 0, 0, 0, 0 } };
     for (int c; (c = getopt_long(argc, argv, "t:n:hpa:b:g:em:s:l:cdr:vM:O:E:X:", lo, nullptr)) >= 0; ) {
         switch (c) {
         case 't': o.n_threads = atoi(optarg); break;
@@ -1594,6 +1663,14 @@ static int parse_options(int argc, char **argv, Opts &o)
             if (c == 1034) g_trim.has_error = true;
             break;
         }
+        case 1035: g_trim.pair_on = true; break;
+        case 1036: case 1037: {
+            const char *name = c == 1036 ? "min-overlap" : "error-pct"; const long lo = c == 1036 ? 1 : 0, hi = c == 1036 ? 512 : 50;
+            char *end = nullptr; errno = 0; const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || errno || v < lo || v > hi) { fprintf(stderr, "[opt_parse]: --trim-pair-%s %s: a number from %ld to %ld\n", name, optarg, lo, hi); return 1; }
+            if (c == 1036) { g_trim.pair_opt.min_overlap = (uint32_t)v; g_trim.has_pair_overlap = true; } else { g_trim.pair_opt.error_pct = (uint32_t)v; g_trim.has_pair_error = true; }
+            break;
+        }
         case 'h': return usage();
         case '?': fprintf(stderr, "[ERROR]: no arg %c\n", optopt); return 1;
         default: break;
@@ -1603,8 +1680,12 @@ static int parse_options(int argc, char **argv, Opts &o)
     if (g_trim.opt.adapter2 && !g_trim.opt.adapter) { fprintf(stderr, "[opt_parse]: --trim-adapter2 needs --trim-adapter (the adapter of mate 1; without --trim-adapter2 mate 2 is searched with it too)\n"); return 1; }
     if ((g_trim.has_overlap || g_trim.has_error) && !g_trim.opt.adapter) { fprintf(stderr, "[opt_parse]: --trim-%s belongs to the adapter search: give --trim-adapter (1 to 64 letters of ACGT)\n", g_trim.has_overlap ? "min-overlap" : "error-pct"); return 1; }
     if (g_trim.opt.adapter) { if (!g_trim.has_overlap) g_trim.opt.min_overlap = 5; if (!g_trim.has_error) g_trim.opt.error_pct = 10; }
+    if ((g_trim.has_pair_overlap || g_trim.has_pair_error) && !g_trim.pair_on) { fprintf(stderr, "[opt_parse]: --trim-pair-%s belongs to the search for the mates' overlap: give --trim-pair-overlap\n", g_trim.has_pair_overlap ? "min-overlap" : "error-pct"); return 1; }
+    if (g_trim.pair_on && !o.pe) { fprintf(stderr, "[opt_parse]: --trim-pair-overlap needs the mates: paired end (-p) and a second read file\n"); return 1; }
+    if (g_trim.pair_on) { if (!g_trim.has_pair_overlap) g_trim.pair_opt.min_overlap = 20; if (!g_trim.has_pair_error) g_trim.pair_opt.error_pct = 10; }
     g_trim.on = g_trim.opt.adapter || g_trim.opt.qual || g_trim.opt.front || g_trim.opt.tail;
-    g_trim.device = g_trim.on && salt_gpu_ws_set_trim != nullptr && salt_gpu_ws_trim_counts != nullptr && salt_gpu_ws_trim_uncount != nullptr && !(getenv("SALT_TRIM_HOST") && atoi(getenv("SALT_TRIM_HOST")));
+    g_trim.device = g_trim.any() && salt_gpu_ws_set_trim != nullptr && salt_gpu_ws_trim_counts != nullptr && salt_gpu_ws_trim_uncount != nullptr &&
+                    (!g_trim.pair_on || (salt_gpu_ws_set_trim_pair != nullptr && salt_gpu_ws_trim_pair_counts != nullptr)) && !(getenv("SALT_TRIM_HOST") && atoi(getenv("SALT_TRIM_HOST")));
     if (optind + 2 + o.pe > argc) { fprintf(stderr, "[opt_parse]: index prefix and read file can't be omited!\n"); return 1; }
     if (o.n_threads < 1) o.n_threads = 1;
     if (o.n_gpus < 1) o.n_gpus = 1;
@@ -1671,7 +1752,7 @@ static bool infer_isize(Opts &o, const salt_index_t *ix, salt_gpu_index_t *gix)
     Batch b1, b2; Pool pool(o.n_threads < 16 ? o.n_threads : 16);
     const int got = r1.take(b1.raw, N_SEQS / 2, b1.rec);
     if (got == 0 || r2.take(b2.raw, got, b2.rec) != got) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); return false; }
-    parse_batch(b1.raw, b1, pool, 0, false); parse_batch(b2.raw, b2, pool, 1, false);
+    parse_batch_pe(b1, b2, pool, false);
     std::vector<uint8_t> iseq; std::vector<uint32_t> ioff;
     interleave_mates(b1, b2, iseq, ioff);
     gzclose(g1); gzclose(g2);
@@ -1775,11 +1856,10 @@ static int run_host_pipeline(const Opts &o, const salt_index_t *ix, const std::v
                     b = std::move(todo.front()); todo.pop_front();
                 }
                 double tp0 = now();
-                parse_batch(b->raw, *b, pool);
+                if (pe && !b->rec.empty()) parse_batch_pe(*b, *b->mate, pool); else parse_batch(b->raw, *b, pool);
                 std::vector<uint8_t> iseq; std::vector<uint32_t> ioff;
                 if (pe && b->n()) {                              // interleave the mates: pair i = reads 2i, 2i+1
                     Batch &m = *b->mate;
-                    parse_batch(m.raw, m, pool, 1);
                     if (m.n() != b->n()) { fprintf(stderr, "[salt] the two read files hold different numbers of reads\n"); set_failed(); break; }
                     interleave_mates(*b, m, iseq, ioff);
                 }
@@ -2330,7 +2410,7 @@ int main(int argc, char **argv)
         // single end, blocked gzip (BGZF) whose text starts as strict 4-line FASTQ: the text path over the uncompressed byte range
         if (!text_path && !pe && bgzf_index(o.fn_reads, plan.bgzf) && sniff_four_line(o.fn_reads)) text_path = true;
         else if (!text_path) plan.bgzf = Bgzf();
-        if (text_path && g_trim.on && !g_trim.device) {      // no k_fq_trim in this libsalt_gpu: the host parser trims, so the host pipeline reads
+        if (text_path && g_trim.any() && !g_trim.device) {   // no k_fq_trim (or no k_fq_trim_pair) in this libsalt_gpu: the host parser trims, so the host pipeline reads
             fprintf(stderr, "[salt] trim: this libsalt_gpu does not trim on the device: the whole run goes through the host pipeline\n");
             text_path = false; plan.bgzf = Bgzf(); g_trim.instead_of_text_path = true;
         }
